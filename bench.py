@@ -6,7 +6,7 @@ A "step" is one pass of the hot path over one batch of synthetic episodes: ONE l
 (basis contraction on MFMA + ProDMP boundary conditions + PD tracking-controller actions) for BASELINE config 2:
 ProDMP, 7 DoF, 5 basis (+goal) per DoF, 100 steps, batch 4096 per GPU, inputs resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--eager] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--eager] [--no-cpu] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -18,6 +18,11 @@ trajectories over RCCL/xGMI (north_star) is timed separately and reported under 
 single GPU call -- runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same args>` as a
 CHILD process and exits with its code (never an exec of a process that touched the GPU).  A WORLD_SIZE that disagrees
 with `--gpus` is an error (exit 2), not a warning.
+
+`--dump-outputs DIR` writes what the timed path computed in its LAST timed step -- the (pos, vel, act) arrays a caller of
+TrajectoryEngine.trajectory_actions receives, float32 [B, 100, 7] -- to DIR/pos.npy, DIR/vel.npy, DIR/act.npy (rank 0's
+shard).  The inputs are seeded, so two builds run with the same arguments can be compared output for output.  Above
+DUMP_MAX_BYTES the files hold a fixed, seeded sample of episodes, whose indices go to DIR/episode.npy (float64).
 """
 from __future__ import annotations
 
@@ -42,7 +47,8 @@ D_GAINS = 0.01 * np.array([10., 10., 10., 10., 6., 5., 3.])
 T_STEPS, D, P = 100, 7, 42
 # algorithmic bytes per trajectory: 224 B in + 2*T*D*4 B (pos, vel) + T*D*4 B (torques)
 BYTES_PER_TRAJ = 224 + 2 * T_STEPS * D * 4 + T_STEPS * D * 4
-HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E: 8 TB/s spec
+DUMP_MAX_BYTES = 64 * 10**6   # --dump-outputs: all files together stay below this
 
 
 def parse():
@@ -62,7 +68,36 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-streaming", action="store_true", help="skip the HBM-streaming roofline row (B = 262144)")
     ap.add_argument("--streaming-batch", type=int, default=262144)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (see the module docstring)")
     return ap.parse_args()
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """
+    arrays: name -> [B, ...] tensor, one row per episode.  Writes DIR/<name>.npy in float32 (float64 stays float64); when
+    all of them together exceed DUMP_MAX_BYTES, only a seeded sample of episodes (the same rows in every array, indices
+    sorted, DIR/episode.npy) -- the sample depends on B alone, so runs with the same arguments write the same rows.
+    """
+    os.makedirs(path, exist_ok=True)
+    B = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(t[0].numel() * (8 if t.dtype == torch.float64 else 4) for t in arrays.values())
+    keep = None
+    if B * row_bytes > DUMP_MAX_BYTES:
+        n = (DUMP_MAX_BYTES - 4096) // (row_bytes + 8)          # 4096: the .npy headers
+        keep = np.sort(np.random.default_rng(20240607).choice(B, size=n, replace=False))
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if keep is not None:
+            a = a[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+    if keep is not None:
+        np.save(os.path.join(path, "episode.npy"), keep.astype(np.float64))
+        written["episode"] = [len(keep)]
+    return {"dir": os.path.abspath(path), "arrays": written, "sampled": keep is not None}
 
 
 def pmc_traffic(batch: int):
@@ -413,6 +448,9 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     barrier()
+    # --dump-outputs: what the last timed step wrote, copied on the device now (outside the clock) before any later leg
+    # launches into the same buffers; written to files at the end
+    last_outputs = {"pos": pos.clone(), "vel": vel.clone(), "act": act.clone()} if args.dump_outputs and rank == 0 else None
     # the kernel's average launch duration for the roofline line: the same K steps once more, bracketed by HIP events on
     # the launch stream (kept out of the wall-clock region above: two event records cost a short run several percent)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -658,6 +696,9 @@ def main():
             out["roofline_streaming"] = streaming
         if allgather is not None:
             out["allgather"] = allgather
+        if last_outputs is not None:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, last_outputs)
+            del last_outputs
         if not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, B)
         elif not args.no_cpu:

@@ -173,6 +173,35 @@ def test_bench_reads_the_gpu_state_without_a_child_process(monkeypatch):
     assert "rocm-smi\"" not in src and "'rocm-smi'" not in src
 
 
+def test_bench_dump_outputs_writes_every_array_and_samples_the_same_episodes_above_the_cap(tmp_path):
+    """bench.py --dump-outputs: every array as DIR/<name>.npy (float32; float64 stays float64), all of them when they fit in
+    DUMP_MAX_BYTES; above it the same seeded episodes of every array, their indices in episode.npy, the files within the cap"""
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(3)
+    small = {"pos": torch.randn((16, 100, 7), generator=g), "q": torch.randn((16, 7), generator=g, dtype=torch.float64)}
+    rep = bench.dump_outputs(str(tmp_path / "small"), small)
+    assert rep["sampled"] is False and rep["arrays"] == {"pos": [16, 100, 7], "q": [16, 7]}
+    for name, t in small.items():
+        a = np.load(tmp_path / "small" / f"{name}.npy")
+        assert a.dtype == (np.float64 if name == "q" else np.float32) and np.array_equal(a, t.numpy())
+    assert not (tmp_path / "small" / "episode.npy").exists()
+
+    B = bench.DUMP_MAX_BYTES // (3 * 100 * 7 * 4) + 1000
+    big = {k: torch.randn((B, 100, 7), generator=g) for k in ("pos", "vel", "act")}
+    reps = [bench.dump_outputs(str(tmp_path / d), big) for d in ("a", "b")]
+    assert all(r["sampled"] for r in reps) and reps[0]["arrays"] == reps[1]["arrays"]
+    files = sorted((tmp_path / "a").iterdir())
+    assert [f.name for f in files] == ["act.npy", "episode.npy", "pos.npy", "vel.npy"]
+    assert sum(f.stat().st_size for f in files) <= bench.DUMP_MAX_BYTES
+    ep = np.load(tmp_path / "a" / "episode.npy")
+    assert ep.dtype == np.float64 and np.array_equal(ep, np.load(tmp_path / "b" / "episode.npy"))
+    idx = ep.astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < B
+    for name, t in big.items():
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), t.numpy()[idx])
+
+
 def test_trajectory_shard_single_process_views_and_episode_lookup():
     """TrajectoryShard / GatheredTrajectories without a process group (world = 1): the gather is the identity, views alias"""
     from fancy_gym_amd.distributed import GatheredTrajectories, TrajectoryShard, gather_trajectories, shard_bounds

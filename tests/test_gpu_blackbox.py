@@ -1593,6 +1593,36 @@ def test_bench_prints_the_contract_line_last():
     assert "allgather" in d            # the forced one-rank RCCL path ran the collective section
 
 
+def test_bench_dump_outputs_are_the_timed_steps_outputs(tmp_path):
+    """bench.py --dump-outputs DIR: `--steps` timed steps, then pos / vel / act of the last one as float32 .npy, equal bit for bit
+    to what TrajectoryEngine.trajectory_actions returns for the same seeded inputs; a second run writes the same files"""
+    import bench
+    from fancy_gym_amd import RolloutSpec, TrajectoryEngine
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MPK_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    B = 512
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--batch", str(B), "--no-cpu", "--no-streaming", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads(r.stdout.strip().splitlines()[-1])
+        assert d["steps"] == 7 and d["ms_per_step"] > 0
+        assert d["dump_outputs"]["sampled"] is False
+        assert d["dump_outputs"]["arrays"] == {k: [B, 100, 7] for k in ("pos", "vel", "act")}
+    eng = TrajectoryEngine("prodmp", "exp", "prodmp", device=0, **bench.CFG)
+    spec = RolloutSpec("motor", 7, bench.P_GAINS, bench.D_GAINS, -1.0, 1.0, plant="static")
+    params, ip, iv = bench.synth_inputs(B, 0)
+    want = eng.trajectory_actions(params, ip, iv, spec, ip.double(), iv.double())
+    torch.cuda.synchronize()
+    for name, w in zip(("pos", "vel", "act"), want):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+        assert np.array_equal(a, w.cpu().numpy()), name
+
+
 @pytest.mark.gpu
 def test_bench_gpus_2_starts_two_ranks_itself_and_gathers_both_shards():
     """
