@@ -210,6 +210,23 @@ __device__ __forceinline__ int replan_rule(const ReplanDev& rp, int b, int T, bo
     return v.seg;
 }
 
+// The validity gate's scalar pieces, the reference's expressions (TableTennisEnv.check_traj_validity / _get_traj_invalid_penalty,
+// table_tennis_env.py:282-309) shared by every route: the time check is the reference's `>` / `<` on the RAW tau / delay (a NaN never
+// trips it), and an excess term is np.maximum(x, 0) -- NaN stays NaN (fmax(x, 0.0) would drop it).
+__device__ __forceinline__ double gate_excess(double x) { return x <= 0.0 ? 0.0 : x; }
+__device__ __forceinline__ bool gate_time_invalid(double tau, double delay, const double (&tb)[2], const double (&db)[2]) {
+    return tau > tb[1] || tau < tb[0] || delay > db[1] || delay < db[0];
+}
+__device__ __forceinline__ double gate_time_excess(double tau, double delay, const double (&tb)[2], const double (&db)[2]) {
+    return 3.0 * (gate_excess(tau - tb[1]) + gate_excess(tb[0] - tau)) + 3.0 * (gate_excess(delay - db[1]) + gate_excess(db[0] - delay));
+}
+// the penalty of a plan: 0 when it is valid (the reference never asks for one), NaN when it is invalid and a position or a limit it
+// was held to is NaN (np.mean over a NaN), else -(time excess + mean excess above + mean excess below)
+__device__ __forceinline__ double gate_penalty(bool invalid, bool pos_nan, double tpen, double over, double under, double n) {
+    if (!invalid) return 0.0;
+    return pos_nan ? __builtin_nan("") : -(tpen + over / n + under / n);
+}
+
 // Basis tables -> LDS, once per workgroup of 256 threads: every thread issues ALL its loads (up to four chunks of the
 // rows, one of the aux row) before its first LDS write -- one memory round trip instead of one per loop iteration,
 // which matters for launches that give a wave a single work unit.  Longer tables take plain loops after that.

@@ -134,9 +134,8 @@ __global__ void __launch_bounds__(512) k_episode_return(const TrajArgs a, const 
             if (a.rp.traj_steps) { rv = replan_eval(a.rp, bq, T); nst_ = rv.seg; }
             if (a.gate_check_td) {
                 const double tau = (double)a.gate_raw[(size_t)bq * c.P], delay = (double)a.gate_raw[(size_t)bq * c.P + 1];
-                t_bad = !(tau >= a.gate_tb[0] && tau <= a.gate_tb[1] && delay >= a.gate_db[0] && delay <= a.gate_db[1]);
-                tpen = 3.0 * (fmax(0.0, tau - a.gate_tb[1]) + fmax(0.0, a.gate_tb[0] - tau)) +
-                       3.0 * (fmax(0.0, delay - a.gate_db[1]) + fmax(0.0, a.gate_db[0] - delay));
+                t_bad = gate_time_invalid(tau, delay, a.gate_tb, a.gate_db);
+                tpen = gate_time_excess(tau, delay, a.gate_tb, a.gate_db);
             }
         }
         asm volatile("" : "+v"(qs), "+v"(qds), "+v"(nst_), "+v"(s0_));
@@ -274,7 +273,8 @@ __global__ void __launch_bounds__(512) k_episode_return(const TrajArgs a, const 
 #pragma unroll
                 for (int m = 0; m < KM; ++m) xz[j][m] = g0 + j < a.G ? xb[j][m] : 0.0f;
             double over, under;
-            const bool p_bad = gate_verdict<KM, NQ>(a, L, gs, ap, TS, km, xz, g0, glim, over, under);
+            bool pnan;
+            const bool p_bad = gate_verdict<KM, NQ>(a, L, gs, ap, TS, km, xz, g0, glim, over, under, pnan);
             invalid = serial && (p_bad || t_bad);
             if (serial) {
                 const size_t si = (size_t)bq * D + L.d;
@@ -282,7 +282,7 @@ __global__ void __launch_bounds__(512) k_episode_return(const TrajArgs a, const 
                 if (L.d == 0) {
                     a.gate_valid[bq] = invalid ? 0 : 1;
                     const double n = (double)(T * D);
-                    if (a.gate_penalty) a.gate_penalty[bq] = -(tpen + over / n + under / n);
+                    if (a.gate_penalty) a.gate_penalty[bq] = gate_penalty(invalid, pnan, tpen, over, under, n);
                     if (a.rp.traj_steps) replan_write(a.rp, bq, rv, !invalid);
                     if (ep.seg_out) ep.seg_out[bq] = invalid ? 0 : nst;
                 }

@@ -84,6 +84,19 @@ struct ReplanDev {
     int every = 1, max_planning_times = 0, horizon = 0;
 };
 
+// fp32 thresholds of a float64 interval: an fp32 position x satisfies !(x > high || x < low) exactly when it satisfies
+// !(x > f32_at_most(high) || x < f32_at_least(low)) -- NaN limits stay NaN (never trip), limits beyond the fp32 range become +-FLT_MAX
+inline float f32_at_least(double x) {
+    float f = (float)x;
+    if ((double)f < x) f = __builtin_nextafterf(f, __builtin_inff());
+    return f;
+}
+inline float f32_at_most(double x) {
+    float f = (float)x;
+    if ((double)f > x) f = __builtin_nextafterf(f, -__builtin_inff());
+    return f;
+}
+
 // validity gate of the fused closed-loop entry points (mpk_validity_gate of include/mpk.h with the limits copied in)
 struct GateDev {
     double lo[kMaxD], hi[kMaxD];     // joint limits

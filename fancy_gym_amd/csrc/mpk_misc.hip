@@ -132,16 +132,16 @@ __global__ void __launch_bounds__(256) k_validity(const ValidArgs v, const float
     for (int e = lane; e < n; e += 64) {
         const int d = e % v.D;
         const double x = (double)p[e];
-        ok = ok && (x >= s_lo[d]) && (x <= s_hi[d]);
-        over += fmax(x - s_hi[d], 0.0);
-        under += fmax(s_lo[d] - x, 0.0);
+        // table_tennis_env.py:307: np.any(pos > high) / np.any(pos < low) -- a NaN position or limit never trips
+        ok = ok && !(x > s_hi[d] || x < s_lo[d]);
+        over += gate_excess(x - s_hi[d]);
+        under += gate_excess(s_lo[d] - x);
     }
     double tpen = 0.0;
     if (v.check_td) {
         const double tau = (double)params[(size_t)b * v.P], delay = (double)params[(size_t)b * v.P + 1];
-        if (lane == 0) ok = ok && tau >= v.tb[0] && tau <= v.tb[1] && delay >= v.db[0] && delay <= v.db[1];
-        tpen = 3.0 * (fmax(0.0, tau - v.tb[1]) + fmax(0.0, v.tb[0] - tau)) +
-               3.0 * (fmax(0.0, delay - v.db[1]) + fmax(0.0, v.db[0] - delay));
+        if (lane == 0) ok = ok && !gate_time_invalid(tau, delay, v.tb, v.db);
+        tpen = gate_time_excess(tau, delay, v.tb, v.db);
     }
     const bool all_ok = __all(ok);
     if (lane == 0) valid[b] = all_ok ? 1 : 0;
@@ -150,8 +150,9 @@ __global__ void __launch_bounds__(256) k_validity(const ValidArgs v, const float
             over += __shfl_xor(over, m);
             under += __shfl_xor(under, m);
         }
-        // table_tennis_env.py:282-289: -(3*tau excess + 3*delay excess + mean(max(pos - high, 0)) + mean(max(low - pos, 0)))
-        if (lane == 0) penalty[b] = -(tpen + over / (double)n + under / (double)n);
+        // table_tennis_env.py:282-289: -(3*tau excess + 3*delay excess + mean(max(pos - high, 0)) + mean(max(low - pos, 0))) for an
+        // invalid plan (NaN propagating as in numpy), 0 for a valid one
+        if (lane == 0) penalty[b] = all_ok ? 0.0 : -(tpen + over / (double)n + under / (double)n);
     }
 }
 

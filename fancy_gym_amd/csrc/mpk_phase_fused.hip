@@ -356,9 +356,8 @@ __global__ void __launch_bounds__(PIPE ? 64 * (1 + kPipeProducers) : (TL ? MPK_P
                 }
                 if (a.gate && a.check_td) {
                     const double tau = (double)a.raw_params[(size_t)b * P], delay = (double)a.raw_params[(size_t)b * P + 1];
-                    t_bad = !(tau >= a.tau_b[0] && tau <= a.tau_b[1] && delay >= a.delay_b[0] && delay <= a.delay_b[1]);
-                    tpen = 3.0 * (fmax(0.0, tau - a.tau_b[1]) + fmax(0.0, a.tau_b[0] - tau)) +
-                           3.0 * (fmax(0.0, delay - a.delay_b[1]) + fmax(0.0, a.delay_b[0] - delay));
+                    t_bad = gate_time_invalid(tau, delay, a.tau_b, a.delay_b);
+                    tpen = gate_time_excess(tau, delay, a.tau_b, a.delay_b);
                 }
             }
         }
@@ -368,7 +367,7 @@ __global__ void __launch_bounds__(PIPE ? 64 * (1 + kPipeProducers) : (TL ? MPK_P
         const int she = (vec && on) ? (int)((((unsigned)b & 3u) * (unsigned)a.td3) & 3u) : 0;     // 16-byte phase of the episode's outputs
         const int oq = le * pitch + she + ld;           // (step 0 of the tile, this column) in the chunk's images
         float row0p = 0.0f, row0v = 0.0f;               // gate: the desired state of step 0 (condition of an episode that executes nothing)
-        bool p_bad = false;
+        bool p_bad = false, p_nan = false;       // gate: a position outside the limits / a NaN position or limit
         double over = 0.0, under = 0.0;
         __builtin_amdgcn_wave_barrier();
         // promp: the carry in front of a tile that starts at step t_begin: p[t_begin] of every (episode, DoF) -- one partial round, lane <->
@@ -559,7 +558,8 @@ __global__ void __launch_bounds__(PIPE ? 64 * (1 + kPipeProducers) : (TL ? MPK_P
                                                                        nullptr, nullptr, nrows);
                     }
                 }
-                if (tb) p_bad = true;
+                if (tb & 1) p_bad = true;
+                if (tb & 2) p_nan = true;
                 over = gsum[0]; under = gsum[1];
             }
         };
@@ -630,6 +630,7 @@ __global__ void __launch_bounds__(PIPE ? 64 * (1 + kPipeProducers) : (TL ? MPK_P
             if (a.gate) {
                 const unsigned long long m = __ballot(on && p_bad);
                 const unsigned long long mine = (m >> (le * D)) & ((1ull << D) - 1ull);
+                const bool pnan = ((__ballot(on && p_nan) >> (le * D)) & ((1ull << D) - 1ull)) != 0ull;
                 invalid = on && (mine != 0ull || t_bad);
                 if (m != 0ull) {                        // (wave-uniform) excess of the episode = its columns left to right
                     double so = 0.0, su = 0.0;
@@ -643,7 +644,7 @@ __global__ void __launch_bounds__(PIPE ? 64 * (1 + kPipeProducers) : (TL ? MPK_P
                     a.valid[b] = invalid ? 0 : 1;
                     const double n = (double)(T * D);
                     // table_tennis_env.py:282-289: -(3 tau excess + 3 delay excess + mean(max(pos - high, 0)) + mean(max(low - pos, 0)))
-                    if (a.penalty) a.penalty[b] = -(tpen + over / n + under / n);
+                    if (a.penalty) a.penalty[b] = gate_penalty(invalid, pnan, tpen, over, under, n);
                 }
             }
             if (on) {
@@ -684,17 +685,6 @@ __global__ void __launch_bounds__(PIPE ? 64 * (1 + kPipeProducers) : (TL ? MPK_P
 }
 
 #ifndef MPK_DEVICE_ONLY
-// fp32 thresholds of a float64 interval: pos (fp32) lies in [low, high] exactly when it lies in [up(low), down(high)]
-static float f32_at_least(double x) {
-    float f = (float)x;
-    if ((double)f < x) f = nextafterf(f, INFINITY);
-    return f;
-}
-static float f32_at_most(double x) {
-    float f = (float)x;
-    if ((double)f > x) f = nextafterf(f, -INFINITY);
-    return f;
-}
 
 bool phase_fused_capable(const DevCfg& c) {
     if (c.mp_type != MPK_MP_PROMP && c.mp_type != MPK_MP_PRODMP) return false;

@@ -290,18 +290,25 @@ __device__ __forceinline__ GateLim kernarg_gate(int d) {
 //   ap: the lane's A-fragment base (sA + L.q * TS + L.col), position rows first (o = 0); km: MFMAs per tile actually needed
 // the running state of a unit's scan: maximum / minimum of every position seen per group (this lane's rows and column), and which row
 // tiles hold a violation anywhere in the wave
+// NaN-propagating maximum / minimum (v_maximum3_f32 / v_minimum3_f32): the scans run on these, and a NaN they carry -- rare, tested
+// wave-uniformly -- sends the wave through the NaN-dropping form (v_max3_f32 / v_min3_f32) and marks the lane
+__device__ __forceinline__ float fmax_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+__device__ __forceinline__ float fmin_nan(float a, float b) { return __builtin_elementwise_minimum(a, b); }
 template <int NQ>
 struct GateScan {
     float mx[NQ], mn[NQ];
     unsigned long long tiles;
+    unsigned nan;                                       // bit j: group j's plan holds a NaN position, or this lane's limits are NaN
     __device__ __forceinline__ void init(const GateLim& gl) {
 #pragma unroll
         for (int j = 0; j < NQ; ++j) { mx[j] = gl.lo32; mn[j] = gl.hi32; }
         tiles = 0ull;
+        nan = (gl.lo != gl.lo || gl.hi != gl.hi) ? ~0u : 0u;
     }
 };
-// one position C tile of group j, row tile rt, into the scan (v_max3_f32 / v_min3_f32; NaN positions pass, as in the reference's
-// `np.any(pos > high)`, table_tennis_env.py:307); returns the lane's "this tile violates" for the caller's wave-level test
+// one position C tile of group j, row tile rt, into the scan (NaN positions pass, as in the reference's `np.any(pos > high)`,
+// table_tennis_env.py:307, but mark the plan: its penalty is NaN if it is invalid); returns the lane's "this tile violates" for the
+// caller's wave-level test
 template <int NQ>
 __device__ __forceinline__ bool gate_scan_tile(GateScan<NQ>& g, const int j, f32x4 acc, const int rt, const int lq, const bool dvalid,
                                                const GateLim& gl, const int T) {
@@ -310,29 +317,37 @@ __device__ __forceinline__ bool gate_scan_tile(GateScan<NQ>& g, const int j, f32
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[r] = row0 + r < T ? acc[r] : gl.lo32;
     }
-    const float hi4 = __builtin_fmaxf(__builtin_fmaxf(acc[0], acc[1]), __builtin_fmaxf(acc[2], acc[3]));
-    const float lo4 = __builtin_fminf(__builtin_fminf(acc[0], acc[1]), __builtin_fminf(acc[2], acc[3]));
+    float hi4 = fmax_nan(fmax_nan(acc[0], acc[1]), fmax_nan(acc[2], acc[3]));
+    float lo4 = fmin_nan(fmin_nan(acc[0], acc[1]), fmin_nan(acc[2], acc[3]));
+    if (__any(hi4 != hi4) != 0) {                       // (wave-uniform, rare) a NaN position
+        if (hi4 != hi4) g.nan |= 1u << j;
+        hi4 = __builtin_fmaxf(__builtin_fmaxf(acc[0], acc[1]), __builtin_fmaxf(acc[2], acc[3]));
+        lo4 = __builtin_fminf(__builtin_fminf(acc[0], acc[1]), __builtin_fminf(acc[2], acc[3]));
+    }
     g.mx[j] = __builtin_fmaxf(g.mx[j], hi4); g.mn[j] = __builtin_fminf(g.mn[j], lo4);
     return dvalid && (hi4 > gl.hi32 || lo4 < gl.lo32);
 }
-// the verdict for the SERIAL lane of (group L.q, episode L.bl) after every row tile went through the scan, and -- only in a unit that
-// holds a violation -- the penalty's excess sums: the flagged row tiles again, float64, reduced over the rows of a lane, the four lane
+// the verdict for the SERIAL lane of (group L.q, episode L.bl) after every row tile went through the scan (pnan: the plan holds a NaN
+// position or a NaN limit), and -- only in a unit that holds a violation -- the penalty's excess sums: the flagged row tiles again, float64, reduced over the rows of a lane, the four lane
 // quarters and the DoF lanes of an episode (a fixed order)
 template <int KM, int NQ>
 __device__ __forceinline__ bool gate_verdict(const TrajArgs& a, const LaneMap<KM>& L, const GateScan<NQ>& g, const float* __restrict__ ap,
                                              const int TS, const int km, const float (&xz)[NQ][KM], const int g0, const GateLim& gl,
-                                             double& over, double& under) {
+                                             double& over, double& under, bool& pnan) {
     const int T = a.c.T, NRT = (T + 15) >> 4;
     // the lanes that hold episode bl's columns of a C tile: its DP columns, in all four lane quarters
     const int DP = 1 << a.sh;
     const unsigned long long em = (unsigned long long)(((1u << DP) - 1u) << (L.bl * DP)) * 0x0001000100010001ull;
     unsigned long long any = 0ull;
     bool mine = false;
+    pnan = false;
 #pragma unroll
     for (int j = 0; j < NQ; ++j) {
-        const unsigned long long mj = __ballot(L.dvalid && (g.mx[j] > gl.hi32 || g.mn[j] < gl.lo32) && (g0 + j) * L.NTW + L.bl < a.B);
+        const bool ep = L.dvalid && (g0 + j) * L.NTW + L.bl < a.B;
+        const unsigned long long mj = __ballot(ep && (g.mx[j] > gl.hi32 || g.mn[j] < gl.lo32));
+        const unsigned long long nj = __ballot(ep && ((g.nan >> j) & 1u));
         any |= mj;
-        if (L.q == j) mine = (mj & em) != 0ull;
+        if (L.q == j) { mine = (mj & em) != 0ull; pnan = (nj & em) != 0ull; }
     }
     over = 0.0; under = 0.0;
     if (any != 0ull) {                                  // (wave-uniform)
@@ -355,8 +370,8 @@ __device__ __forceinline__ bool gate_verdict(const TrajArgs& a, const LaneMap<KM
                 for (int r = 0; r < 4; ++r) {
                     const double x = (double)acc[r];
                     const bool in = row0 + r < T && L.dvalid;
-                    ov[j] += in ? fmax(x - gl.hi, 0.0) : 0.0;
-                    un[j] += in ? fmax(gl.lo - x, 0.0) : 0.0;
+                    ov[j] += in ? gate_excess(x - gl.hi) : 0.0;
+                    un[j] += in ? gate_excess(gl.lo - x) : 0.0;
                 }
             }
         }
@@ -374,7 +389,8 @@ __device__ __forceinline__ bool gate_verdict(const TrajArgs& a, const LaneMap<KM
 // episodes pays latencies, not instructions)
 template <int KM, int NQ>
 __device__ __forceinline__ bool gate_pass(const TrajArgs& a, const LaneMap<KM>& L, const float* __restrict__ ap, const int TS, const int km,
-                                          const float (&xb)[NQ][KM], const int g0, const GateLim& gl, double& over, double& under) {
+                                          const float (&xb)[NQ][KM], const int g0, const GateLim& gl, double& over, double& under,
+                                          bool& pnan) {
     const int T = a.c.T, NRT = (T + 15) >> 4;
     // (a group past the launch's last one contracts zeros: no test per group inside the loop)
     float xz[NQ][KM];
@@ -405,7 +421,7 @@ __device__ __forceinline__ bool gate_pass(const TrajArgs& a, const LaneMap<KM>& 
             if (rt0 + u < 64 && rt0 + u < NRT && __any(tv) != 0) g.tiles |= 1ull << (rt0 + u);
         }
     }
-    return gate_verdict<KM, NQ>(a, L, g, ap, TS, km, xz, g0, gl, over, under);
+    return gate_verdict<KM, NQ>(a, L, g, ap, TS, km, xz, g0, gl, over, under, pnan);
 }
 
 // The step loop of black_box_wrapper.py:175-203 on the reference's torque double integrator (base_reacher_torque.py:25-26)
@@ -426,8 +442,9 @@ __device__ __forceinline__ bool gate_pass(const TrajArgs& a, const LaneMap<KM>& 
 // of every step: ~40 cycles of LDS latency exposed per step).  PRE = 1: all 32 reads issued, ONE wait, all conversions, then the
 // chain with nothing but its own operations, the action conversion and the LDS write in between.
 // GATE (round 6, k_phase_fused): the desired positions the chain pulls into registers anyway are also tested against the joint limits
-// [glo32, ghi32] (exact fp32 thresholds of the validity gate); *gate_bad |= any of the tile's `rows` positions outside -- no LDS read, no
-// wait of its own; a wave that holds a violation adds the tile's float64 excess above / below [gate_lo, gate_hi] to gate_sum[0] / [1].
+// [glo32, ghi32] (exact fp32 thresholds of the validity gate); *gate_bad |= 1 if any of the tile's `rows` positions lies above / below,
+// |= 2 if one of them (or a limit) is NaN -- no LDS read, no wait of its own; a wave that holds a violation adds the tile's float64
+// excess above / below [gate_lo, gate_hi] to gate_sum[0] / [1].
 template <int CTRL, bool MASKED, bool INTEGRATE = true, int KEEP64 = 0, int PRE = 0, bool WRITE_A = true, bool GATE = false>
 __device__ __forceinline__ void pd_tile_steps(const float* __restrict__ sP, const float* __restrict__ sV,
                                               float* __restrict__ sA, const int stride, const int t0, const int nst,
@@ -444,15 +461,27 @@ __device__ __forceinline__ void pd_tile_steps(const float* __restrict__ sP, cons
 #pragma unroll
     for (int tl = 0; tl < 16; ++tl) { pr[tl] = sP[tl * stride]; vr[tl] = sV[tl * stride]; }
     if (GATE) {
-        // running maximum / minimum of the tile's positions: two v_max3_f32 / v_min3_f32 per four values, compared once (rows past the
-        // horizon replaced by a value inside the limits -- a select, no control flow).  NaN positions pass, as they do in the reference's
-        // `np.any(pos > high)` (table_tennis_env.py:307)
+        // running maximum / minimum of the tile's positions: one v_maximum3_f32 / v_minimum3_f32 per two values, compared once (rows
+        // past the horizon replaced by a value inside the limits -- a select, no control flow).  NaN positions pass, as they do in the
+        // reference's `np.any(pos > high)` (table_tennis_env.py:307): the NaN-propagating scan sees them, and only a wave that holds
+        // one (or NaN limits) repeats it in the NaN-dropping form
         float mx = glo32, mn = ghi32;
 #pragma unroll
         for (int tl = 0; tl < 16; tl += 2) {
             const float p0 = (!MASKED || tl < rows) ? pr[tl] : glo32, p1 = (!MASKED || tl + 1 < rows) ? pr[tl + 1] : glo32;
-            mx = __builtin_fmaxf(mx, __builtin_fmaxf(p0, p1));
-            mn = __builtin_fminf(mn, __builtin_fminf(p0, p1));
+            mx = fmax_nan(mx, fmax_nan(p0, p1));
+            mn = fmin_nan(mn, fmin_nan(p0, p1));
+        }
+        const bool has_nan = mx != mx || mn != mn;
+        if (__any(has_nan) != 0) {
+            gate_bad[0] |= has_nan ? 2 : 0;
+            mx = glo32; mn = ghi32;
+#pragma unroll
+            for (int tl = 0; tl < 16; tl += 2) {
+                const float p0 = (!MASKED || tl < rows) ? pr[tl] : glo32, p1 = (!MASKED || tl + 1 < rows) ? pr[tl + 1] : glo32;
+                mx = __builtin_fmaxf(mx, __builtin_fmaxf(p0, p1));
+                mn = __builtin_fminf(mn, __builtin_fminf(p0, p1));
+            }
         }
         const bool bh = mx > ghi32, bl_ = mn < glo32;
         gate_bad[0] |= (int)(bh || bl_);
@@ -463,7 +492,7 @@ __device__ __forceinline__ void pd_tile_steps(const float* __restrict__ sP, cons
 #pragma unroll
             for (int tl = 0; tl < 16; ++tl) {
                 if (MASKED && tl >= rows) break;
-                ov += fmax((double)pr[tl] - gate_hi, 0.0);
+                ov += gate_excess((double)pr[tl] - gate_hi);
             }
             gate_sum[0] += ov;
         }
@@ -472,7 +501,7 @@ __device__ __forceinline__ void pd_tile_steps(const float* __restrict__ sP, cons
 #pragma unroll
             for (int tl = 0; tl < 16; ++tl) {
                 if (MASKED && tl >= rows) break;
-                un += fmax(gate_lo - (double)pr[tl], 0.0);
+                un += gate_excess(gate_lo - (double)pr[tl]);
             }
             gate_sum[1] += un;
         }

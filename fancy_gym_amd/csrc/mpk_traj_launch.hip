@@ -211,17 +211,6 @@ extern template int launch_episode_kernel<MPK_MP_PRODMP>(const TrajArgs&, const 
 
 // mpk_episode_return: plan + controller + plant + reward + aggregation of a `verbose < 2` step in one launch (k_episode_return).
 // MPK_ENOTIMPL where the tables do not fit beside the images (long horizons): the caller's separate launches take those.
-// fp32 thresholds of a float64 interval: an fp32 position lies in [low, high] exactly when it lies in [up(low), down(high)]
-static float f32_at_least(double x) {
-    float f = (float)x;
-    if ((double)f < x) f = nextafterf(f, INFINITY);
-    return f;
-}
-static float f32_at_most(double x) {
-    float f = (float)x;
-    if ((double)f > x) f = nextafterf(f, -INFINITY);
-    return f;
-}
 static void fill_gate_args(const GateDev* gate, const float* params, int D, TrajArgs& ta, ActArgs& aa) {
     ta.gate_valid = nullptr; ta.gate_penalty = nullptr; ta.gate_raw = nullptr; ta.gate_check_td = 0;
     ta.gate_tb[0] = ta.gate_tb[1] = ta.gate_db[0] = ta.gate_db[1] = 0.0;

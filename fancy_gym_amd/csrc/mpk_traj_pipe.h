@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(320) MPK_PIPE_WAVES_ATTR k_traj_pipe(const Tra
             double qs = 0.0, qds = 0.0;
             int nst = 0;
             ReplanVals rv{T, 0, 0, false};
-            bool t_bad = false, p_bad = false;
+            bool t_bad = false, p_bad = false, p_nan = false;
             double tpen = 0.0, over = 0.0, under = 0.0;
             float row0p = 0.0f, row0v = 0.0f;
             if (serial) {
@@ -108,9 +108,8 @@ __global__ void __launch_bounds__(320) MPK_PIPE_WAVES_ATTR k_traj_pipe(const Tra
                 } else if (a.n_steps) nst = min(a.n_steps[bq], T);
                 if (gated && a.gate_check_td) {
                     const double tau = (double)a.gate_raw[(size_t)bq * c.P], delay = (double)a.gate_raw[(size_t)bq * c.P + 1];
-                    t_bad = !(tau >= a.gate_tb[0] && tau <= a.gate_tb[1] && delay >= a.gate_db[0] && delay <= a.gate_db[1]);
-                    tpen = 3.0 * (fmax(0.0, tau - a.gate_tb[1]) + fmax(0.0, a.gate_tb[0] - tau)) +
-                           3.0 * (fmax(0.0, delay - a.gate_db[1]) + fmax(0.0, a.gate_db[0] - delay));
+                    t_bad = gate_time_invalid(tau, delay, a.gate_tb, a.gate_db);
+                    tpen = gate_time_excess(tau, delay, a.gate_tb, a.gate_db);
                 }
             }
             const int tcond = (serial && a.rp.cond_pos) ? min(max(nst - 1, 0), T - 1) : -1;
@@ -139,7 +138,8 @@ __global__ void __launch_bounds__(320) MPK_PIPE_WAVES_ATTR k_traj_pipe(const Tra
                             pd_tile_steps<CT - 3, true, true, 0, 0, true, true>(sQ + oq, sQ + kStageStride + oq, sQ + 2 * kStageStride + oq, D, rt * 16, nst,
                                                                               pgd, dgd, lod, hid, a.plant_dt, qs, qds, nullptr, nullptr, min(16, T - rt * 16),
                                                                               glim.lo32, glim.hi32, &tb, glim.lo, glim.hi, gsum);
-                        if (tb) p_bad = true;
+                        if (tb & 1) p_bad = true;
+                        if (tb & 2) p_nan = true;
                         over = gsum[0]; under = gsum[1];
                     } else if (full_tile)
                         pd_tile_steps<CT - 3, false, true, false, MPK_PIPE_PRE>(sQ + oq, sQ + kStageStride + oq, sQ + 2 * kStageStride + oq, D, rt * 16, nst,
@@ -156,8 +156,9 @@ __global__ void __launch_bounds__(320) MPK_PIPE_WAVES_ATTR k_traj_pipe(const Tra
             if constexpr (gated) {
                 // the episode's D lanes sit side by side in lane quarter q: its verdict, and its excess sums left to right
                 const int base = L.q * 16 + (L.bl << a.sh);
-                const unsigned long long m = __ballot(serial && p_bad);
+                const unsigned long long m = __ballot(serial && p_bad), mn = __ballot(serial && p_nan);
                 invalid = serial && ((((m >> base) & ((1ull << D) - 1ull)) != 0ull) || t_bad);
+                const bool pnan = ((mn >> base) & ((1ull << D) - 1ull)) != 0ull;
                 if (m != 0ull) {
                     double so = 0.0, su = 0.0;
                     for (int d = 0; d < D; ++d) { so += __shfl(over, base + d); su += __shfl(under, base + d); }
@@ -169,7 +170,7 @@ __global__ void __launch_bounds__(320) MPK_PIPE_WAVES_ATTR k_traj_pipe(const Tra
                     if (L.d == 0) {
                         a.gate_valid[bq] = invalid ? 0 : 1;
                         const double n = (double)(T * D);
-                        if (a.gate_penalty) a.gate_penalty[bq] = -(tpen + over / n + under / n);
+                        if (a.gate_penalty) a.gate_penalty[bq] = gate_penalty(invalid, pnan, tpen, over, under, n);
                         if (a.rp.traj_steps) replan_write(a.rp, bq, rv, !invalid);
                     }
                 }

@@ -146,13 +146,13 @@ __global__ void __launch_bounds__(256, (NQ == 4 ? MPK_QUAD_WPE4 : NQ == 2 ? MPK_
                 if (a.rp.traj_steps) rv = replan_eval(a.rp, bq, T);
                 if (a.gate_check_td) {
                     const double tau = (double)a.gate_raw[(size_t)bq * P], delay = (double)a.gate_raw[(size_t)bq * P + 1];
-                    t_bad = !(tau >= a.gate_tb[0] && tau <= a.gate_tb[1] && delay >= a.gate_db[0] && delay <= a.gate_db[1]);
-                    tpen = 3.0 * (fmax(0.0, tau - a.gate_tb[1]) + fmax(0.0, a.gate_tb[0] - tau)) +
-                           3.0 * (fmax(0.0, delay - a.gate_db[1]) + fmax(0.0, a.gate_db[0] - delay));
+                    t_bad = gate_time_invalid(tau, delay, a.gate_tb, a.gate_db);
+                    tpen = gate_time_excess(tau, delay, a.gate_tb, a.gate_db);
                 }
             }
             double over, under;
-            const bool p_bad = gate_pass<KM, NQ>(a, L, ap, TS, KM, xb, g0, glim, over, under);
+            bool pnan;
+            const bool p_bad = gate_pass<KM, NQ>(a, L, ap, TS, KM, xb, g0, glim, over, under, pnan);
             const bool invalid = serial && (p_bad || t_bad);
             // An invalid plan executes nothing -- but its lanes run the chain like their neighbours' and DROP the result (plant state not
             // written, actions clipped to [0, 0]): with nst = 0 beside lanes that execute the whole plan, every tile of the wave was a
@@ -163,7 +163,7 @@ __global__ void __launch_bounds__(256, (NQ == 4 ? MPK_QUAD_WPE4 : NQ == 2 ? MPK_
             if (serial && L.d == 0) {
                 a.gate_valid[bq] = invalid ? 0 : 1;
                 const double n = (double)(T * D);
-                if (a.gate_penalty) a.gate_penalty[bq] = -(tpen + over / n + under / n);
+                if (a.gate_penalty) a.gate_penalty[bq] = gate_penalty(invalid, pnan, tpen, over, under, n);
                 if (a.rp.traj_steps) replan_write(a.rp, bq, rv, !invalid);
             }
         }

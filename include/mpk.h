@@ -454,8 +454,13 @@ int mpk_episode_return(mpk_handle h, const float* params, const float* init_pos,
  * envs/mujoco/table_tennis/table_tennis_env.py:303-309) and returns invalid_traj_callback's penalty instead of executing a step when
  * it may not (black_box_wrapper.py:169-172; _get_traj_invalid_penalty, table_tennis_env.py:282-289).  With the gate a launch of
  * mpk_replan_step_gated / mpk_episode_return_gated does what mpk_traj_validity_penalty does to the plan it has just produced --
- *   valid[b]   = all_t,d(pos_low[d] <= pos[b,t,d] <= pos_high[d]) and (check_tau_delay == 0 or tau, delay within their bounds)
- *   penalty[b] = -(3 (tau excess) + 3 (delay excess) + mean_t,d max(pos - pos_high, 0) + mean_t,d max(pos_low - pos, 0))   float64
+ *   valid[b]   = not (any_t,d(pos[b,t,d] > pos_high[d] or pos[b,t,d] < pos_low[d])
+ *                     or (check_tau_delay and (tau > tau_hi or tau < tau_lo or delay > delay_hi or delay < delay_lo)))
+ *   penalty[b] = 0 for a valid plan (the reference never asks for one), else
+ *                -(3 (tau excess) + 3 (delay excess) + mean_t,d max(pos - pos_high, 0) + mean_t,d max(pos_low - pos, 0))   float64
+ * in the reference's own form (comparisons in float64 on the fp32 positions): a NaN position, tau, delay or limit never makes a plan
+ * invalid, +-inf positions do against finite limits, and the penalty of an invalid plan is NaN where numpy's is (a NaN position, tau,
+ * delay or limit)
  * with tau = raw_params[b,0], delay = raw_params[b,1] as the caller's policy produced them (NOT clipped, NOT the values an episode
  * froze; NULL: `params`) -- while the positions are still on the CU, and an INVALID plan finishes its episode without a step:
  * done[b] = 1, seg_len[b] = 0, traj_steps / plan_steps / q / qd untouched, actions[b] = 0, cond_pos / cond_vel = the plan's row 0
@@ -547,8 +552,10 @@ int mpk_condition_gather(mpk_handle h, const float* pos, const float* vel, const
 
 /*
  * Batched validity check (raw_interface_wrapper.py:55-72; envs/mujoco/table_tennis/table_tennis_env.py:303-309):
- *   valid[b] = all_t,d( pos_low[d] <= pos[b,t,d] <= pos_high[d] )
- *              and (check_tau_delay == 0 or (tau_lo <= params[b,0] <= tau_hi and delay_lo <= params[b,1] <= delay_hi))
+ *   valid[b] = not ( any_t,d(pos[b,t,d] > pos_high[d] or pos[b,t,d] < pos_low[d])
+ *                    or (check_tau_delay and (params[b,0] > tau_hi or params[b,0] < tau_lo or params[b,1] > delay_hi
+ *                                              or params[b,1] < delay_lo)) )
+ * -- the reference's comparisons: NaN positions, tau / delay or limits never make a plan invalid.
  * pos dev float [B,T,D]; params dev float [B,P]; pos_low/high host double [D]; valid dev uint8 [B].
  */
 int mpk_traj_validity(mpk_handle h, const float* pos, const float* params, const double* pos_low,
@@ -562,7 +569,8 @@ int mpk_traj_validity(mpk_handle h, const float* pos, const float* params, const
  *   penalty[b] = -( 3*(max(0, tau - tau_hi) + max(0, tau_lo - tau)) + 3*(max(0, delay - delay_hi) + max(0, delay_lo - delay))
  *                   + mean_t,d max(pos - pos_high, 0) + mean_t,d max(pos_low - pos, 0) )
  * with tau = params[b,0], delay = params[b,1] as passed (NOT clipped; terms dropped when check_tau_delay == 0).
- * penalty dev double [B], written for every episode (0 or -0 for a valid one).
+ * penalty dev double [B], written for every episode: 0 for a valid one; NaN propagates as in numpy (a NaN position, tau, delay or
+ * limit makes an invalid plan's penalty NaN).
  */
 int mpk_traj_validity_penalty(mpk_handle h, const float* pos, const float* params, const double* pos_low,
                               const double* pos_high, int32_t check_tau_delay, const double tau_bound[2],

@@ -695,6 +695,26 @@ def reacher_rollout(des_pos: Array, des_vel: Array, controller: str, p_gains, d_
     return actions, rewards, q, qd
 
 
+def traj_validity(action: Array, pos_traj: Array, pos_low: Array, pos_high: Array, tau_bound=None,
+                  delay_bound=None) -> Array:
+    """
+    The validity check of a plan (BlackBoxWrapper.step -> preprocessing_and_validity_callback, black_box_wrapper.py:155-156;
+    TableTennisEnv.check_traj_validity, envs/mujoco/table_tennis/table_tennis_env.py:303-309), batched -> bool [B]:
+      valid = not (tau > tb[1] or tau < tb[0] or delay > db[1] or delay < db[0] or any(pos > high) or any(pos < low))
+    action [B, P] raw (tau = action[:, 0], delay = action[:, 1]); pos_traj [B, T, D] compared in float64.  The comparisons are
+    the reference's `>` / `<`: a NaN position, tau, delay or limit never makes a plan invalid; +-inf positions do against finite
+    limits.  tau_bound / delay_bound None drops the time check.
+    """
+    pos = np.asarray(pos_traj, np.float64)
+    lo, hi = np.asarray(pos_low, np.float64), np.asarray(pos_high, np.float64)
+    bad = np.any(pos > hi, axis=(1, 2)) | np.any(pos < lo, axis=(1, 2))
+    if tau_bound is not None and delay_bound is not None:
+        action = np.asarray(action, np.float64)
+        tau, delay = action[:, 0], action[:, 1]
+        bad = bad | (tau > tau_bound[1]) | (tau < tau_bound[0]) | (delay > delay_bound[1]) | (delay < delay_bound[0])
+    return ~bad
+
+
 def traj_invalid_penalty(action: Array, pos_traj: Array, pos_low: Array, pos_high: Array, tau_bound=None,
                          delay_bound=None) -> Array:
     """

@@ -248,6 +248,48 @@ def test_reference_controller_fixture_provenance():
         assert re.search(re.escape(f) + r" sha256 [0-9a-f]{64}\b", meta), f
 
 
+REF_VALID = os.path.join(GOLD, "ref_validity.npz")
+REF_VALID_CASES = tuple(str(c) for c in np.load(REF_VALID)["cases"])
+
+
+def test_reference_validity_fixture_provenance():
+    """tests/golden/ref_validity.npz holds the verdicts / penalties of the reference's check_traj_validity and
+    _get_traj_invalid_penalty compiled alone (tests/golden/make_ref_validity_golden.py); it is the committed generator's product
+    and records the sha256 of both reference files it read"""
+    import hashlib
+    import re
+    z = np.load(REF_VALID)
+    meta = str(z["meta"])
+    assert "check_traj_validity and _get_traj_invalid_penalty compiled alone with ast" in meta
+    gen = hashlib.sha256(open(os.path.join(GOLD, "make_ref_validity_golden.py"), "rb").read()).hexdigest()
+    assert "generator sha256 " + gen in meta, "ref_validity.npz predates the committed generator: re-run it"
+    for f in ("table_tennis_env.py", "table_tennis_utils.py"):
+        assert re.search(re.escape(f) + r" sha256 [0-9a-f]{64}\b", meta), f
+    # what the fixture has to cover: NaN / +-inf positions and tau / delay, both verdicts, NaN and infinite penalties
+    act = np.concatenate([z[c + "_action"] for c in REF_VALID_CASES])
+    pos_nan = np.concatenate([np.isnan(z[c + "_pos"]).any(axis=(1, 2)) for c in REF_VALID_CASES])
+    valid = np.concatenate([z[c + "_valid"] for c in REF_VALID_CASES])
+    pen = np.concatenate([z[c + "_penalty"] for c in REF_VALID_CASES])
+    assert np.isnan(act).any() and np.isinf(act).any() and (pos_nan & valid).any() and (pos_nan & ~valid).any()
+    assert np.isnan(pen[~valid]).any() and np.isinf(pen[~valid]).any() and valid.sum() > 100 and (~valid).sum() > 100
+
+
+@pytest.mark.parametrize("case", REF_VALID_CASES)
+def test_oracle_validity_equals_the_reference(case):
+    """O.traj_validity == check_traj_validity bit for bit, O.traj_invalid_penalty == _get_traj_invalid_penalty with NaN where
+    the reference's is NaN -- on positions exactly on / one float32 beside the limits, NaN / +-inf positions, raw tau / delay
+    and limits, lo > hi and limits beyond the float32 range"""
+    z = np.load(REF_VALID)
+    g = lambda n: z[f"{case}_{n}"]
+    pos, act, lo, hi, tb, db = g("pos"), g("action"), g("lo"), g("hi"), g("tb"), g("db")
+    with np.errstate(invalid="ignore"):
+        valid = O.traj_validity(act, pos, lo, hi, tb, db)
+        pen = O.traj_invalid_penalty(act, pos, lo, hi, tb, db)
+    np.testing.assert_array_equal(valid, g("valid"))
+    np.testing.assert_array_equal(pen, g("penalty"))            # (NaN == NaN here)
+    np.testing.assert_array_equal(pen[~valid], g("penalty")[~valid])
+
+
 @pytest.mark.parametrize("cfg", REF_CFGS)
 def test_oracle_controllers_equal_the_reference_controllers(cfg):
     """oracle pd / pos / vel actions == what the reference's classes returned on the same inputs, bit for bit; the
