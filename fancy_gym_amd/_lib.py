@@ -16,7 +16,7 @@ MP_TYPES = {"promp": 0, "dmp": 1, "prodmp": 2}
 PHASE_TYPES = {"linear": 0, "exp": 1}
 BASIS_TYPES = {"rbf": 0, "zero_rbf": 1, "prodmp": 2}
 CTRL_TYPES = {"motor": 0, "velocity": 1, "position": 2}
-PLANT_TYPES = {"static": 0, "double_integrator": 1}
+PLANT_TYPES = {"static": 0, "double_integrator": 1, "velocity_direct": 2}
 
 MPK_EINVAL, MPK_ENOTIMPL, MPK_EHIP, MPK_ERANGE, MPK_ENODEV, MPK_ECOMM = -1, -2, -3, -4, -5, -6
 MPK_COMM_ID_BYTES = 128
@@ -29,7 +29,7 @@ DMP_FIRST_SAMPLE_MODES = {"init": 0, "step": 1}
 REWARD_TYPES = {None: 0, "none": 0, "simple_reacher": 1}       # MPK_REWARD_*
 AGG_MODES = {"sum": 0, "mean": 1, "last": 2}                   # MPK_AGG_*
 OPTION_KEYS = ("mapping", "bulk", "quad", "pd_quad", "write_through", "ipw", "phase", "phase_table", "phase_chunk",
-               "pd_simple", "split", "lds_pad", "pipe", "flat", "phase_flat", "ring", "ring_np", "ring_ns", "ring_m", "ring_dbg", "ring_parts", "tiles_wpb", "serial_order", "ring_nc", "pd_generic", "dmp_response", "ablations", "ring_tb", "pd_helper", "phase_waves", "phase_split", "phase_pipe", "pd_pipe")
+               "pd_simple", "split", "lds_pad", "pipe", "flat", "phase_flat", "ring", "ring_np", "ring_ns", "ring_m", "ring_dbg", "ring_parts", "tiles_wpb", "serial_order", "ring_nc", "pd_generic", "dmp_response", "ablations", "ring_tb", "pd_helper", "phase_waves", "phase_split", "phase_pipe", "pd_pipe", "hole_sampled")
 
 
 class MPKLibraryError(RuntimeError):
@@ -70,6 +70,13 @@ class mpk_validity_gate(C.Structure):
         ("check_tau_delay", C.c_int32), ("reserved0", C.c_int32),
         ("tau_bound", C.c_double * 2), ("delay_bound", C.c_double * 2),
         ("raw_params", C.c_void_p), ("valid", C.c_void_p), ("penalty", C.c_void_p),
+    ]
+
+
+class mpk_hole_task(C.Structure):
+    _fields_ = [
+        ("collision_penalty", C.c_double), ("allow_self_collision", C.c_int32), ("allow_wall_collision", C.c_int32),
+        ("steps_before_reward", C.c_int32), ("reserved0", C.c_int32),
     ]
 
 
@@ -122,6 +129,8 @@ SIGNATURES = {
     "mpk_gate_flags": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mpk_reacher_rollout": (C.c_int, [_vp, C.POINTER(mpk_rollout_cfg), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
                                       _vp, _i32, _i32, _vp]),
+    "mpk_hole_reacher_rollout": (C.c_int, [_vp, C.POINTER(mpk_rollout_cfg), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(mpk_hole_task),
+                                           _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, C.POINTER(mpk_replan_state), _i32, _i32, _vp]),
     "mpk_replan_advance": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mpk_traj_validity": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
     "mpk_traj_validity_penalty": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
@@ -147,7 +156,7 @@ _lib: Optional[C.CDLL] = None
 # the files libmpk.so is built from, in the order mpk_source_hash() is defined over (include/mpk.h)
 _ROOT = os.path.dirname(_HERE)
 KERNEL_UNITS = ("mpk_traj_family.hip", "mpk_traj_ring.hip", "mpk_episode.hip", "mpk_traj_launch.hip", "mpk_traj_wide.hip", "mpk_traj_phase.hip",
-                "mpk_phase_fused.hip", "mpk_rollout.hip", "mpk_misc.hip")          # translation units of the device code (mpk_traj_family.hip: once per MP type)
+                "mpk_phase_fused.hip", "mpk_rollout.hip", "mpk_hole.hip", "mpk_misc.hip")          # translation units of the device code (mpk_traj_family.hip: once per MP type)
 KERNEL_HEADERS = ("mpk_dev.h", "mpk_tile.h", "mpk_traj_tiles.h", "mpk_traj_stream.h", "mpk_traj_flat.h", "mpk_traj_ring.h", "mpk_traj_quad.h",
                   "mpk_traj_pipe.h", "mpk_reward.h", "mpk_phase.h", "mpk_trace_reader.h")
 SOURCE_FILES = (os.path.join(_ROOT, "include", "mpk.h"), os.path.join(_HERE, "csrc", "mpk_internal.h"),

@@ -31,7 +31,8 @@ class BatchedBlackBox:
                  max_planning_times: Union[int, float] = math.inf, condition_on_desired: bool = False,
                  max_episode_steps: Optional[int] = None, pos_limits: Optional[Sequence] = None,
                  check_tau_delay: bool = False, reward: Optional[str] = None, steps_before_reward: int = 199,
-                 device=None, learn_sub_trajectories: bool = False, reward_aggregation="sum", verbose: int = 2):
+                 device=None, learn_sub_trajectories: bool = False, reward_aggregation="sum", verbose: int = 2,
+                 collision_penalty: float = 100.0, allow_self_collision: bool = False, allow_wall_collision: bool = False):
         """
         trajectory_generator / tracking_controller: the objects the factories return (``get_trajectory_generator``,
         ``get_controller``).  ``replanning_every = n`` is the schedule ``lambda pos, vel, obs, action, t: t % n == 0``
@@ -41,6 +42,13 @@ class BatchedBlackBox:
         to the device rollout: ``step`` then also returns ``step_rewards [B, T]`` and their sum ``rewards [B]``
         (``reward_aggregation``: "sum" / "mean" / "last" or np.sum / np.mean -- black_box_wrapper.py:24,216 -- over the EXECUTED
         steps of each episode, on the device); goals are given to ``reset``.
+
+        ``reward = "hole_reacher"`` with ``plant = "velocity_direct"`` runs the reference's HoleReacher (envs/classic_control/
+        hole_reacher, rew_fct "simple"; ``collision_penalty`` / ``allow_self_collision`` / ``allow_wall_collision`` as its kwargs) on
+        the device: a collision ends the episode in the middle of a plan (terminated, black_box_wrapper.py:197-203), so
+        ``trajectory_length`` is the executed steps and ``rewards`` aggregates only those.  Holes [B, 3] = (x, width, depth) are given
+        to ``reset`` (``sample_hole_reacher_starts`` draws starts and holes as the reference does).  ``step`` also returns
+        ``is_collided`` / ``is_success``.  Collided episodes are done, so the live ones keep lockstep under replanning.
 
         ``learn_sub_trajectories`` (black_box_wrapper.py:98-102, utils/make_env_helpers.py:89-117): every ``step`` plans a new
         sub-trajectory of ``round(tau / dt)`` steps from the current state -- tau is the first parameter (``learn_tau``), read
@@ -92,10 +100,15 @@ class BatchedBlackBox:
         self.plant = plant
         self.pos_limits = pos_limits
         self.check_tau_delay = bool(check_tau_delay)
-        if reward not in (None, "simple_reacher"):
+        if reward not in (None, "simple_reacher", "hole_reacher"):
             raise ValueError(f"unknown device reward {reward!r}")
-        if reward is not None and plant != "double_integrator":
+        if reward == "simple_reacher" and plant != "double_integrator":
             raise ValueError("the simple_reacher reward needs plant='double_integrator'")
+        if (reward == "hole_reacher") != (plant == "velocity_direct"):
+            raise ValueError("the hole_reacher reward and plant='velocity_direct' go together")
+        self.hole_task = dict(collision_penalty=float(collision_penalty), allow_self_collision=bool(allow_self_collision),
+                              allow_wall_collision=bool(allow_wall_collision))
+        self.hole = None
         self.reward = reward
         self.steps_before_reward = int(steps_before_reward)
         self.goal = None
@@ -149,16 +162,20 @@ class BatchedBlackBox:
         cfg = self.engine.config
         return self.engine.mp_type == "prodmp" and bool(cfg.learn_tau or cfg.learn_delay or self._lockstep is None)
 
-    def reset(self, init_pos=None, init_vel=None, goal=None):
+    def reset(self, init_pos=None, init_vel=None, goal=None, hole=None):
         """start B new episodes from plant state (init_pos, init_vel) [B, D] (default zeros); goal [B, 2] for the
-        simple_reacher reward"""
+        simple_reacher reward, hole [B, 3] = (x, width, depth) for the hole_reacher reward"""
         if self._plans_since_reset and self._range_can_overflow() and not torch.cuda.is_current_stream_capturing():
             self.check_range()
         elif self._plans_since_reset:
             # the episodes just finished: whoever read their results has synchronised; a ring kernel that gave up waiting in their LAST
             # plan would otherwise be reported by the next launch only (costs nothing: the fault word lives in host memory)
             self.engine.poll_fault()
-        if self.reward is not None:
+        if self.reward == "hole_reacher":
+            if hole is None:
+                raise ValueError("reward='hole_reacher' needs hole [B, 3] at reset")
+            self.hole = torch.as_tensor(hole, dtype=torch.float64, device=self.device).expand(self.B, 3).contiguous()
+        elif self.reward is not None:
             if goal is None:
                 raise ValueError("reward='simple_reacher' needs goal [B, 2] at reset")
             self.goal = torch.as_tensor(goal, dtype=torch.float64, device=self.device).expand(self.B, 2).contiguous()
@@ -386,6 +403,8 @@ class BatchedBlackBox:
 
     def step(self, params, fuse: bool = True) -> Dict[str, torch.Tensor]:
         self._plans_since_reset += 1
+        if self.reward == "hole_reacher":
+            return self._step_hole(params)
         if fuse and self._can_episode_return():
             out = self._step_lean(params)
             if out is not None:
@@ -428,6 +447,36 @@ class BatchedBlackBox:
             out["step_actions"] = self.engine.pd_rollout(self.spec, pos, vel, self.q, self.qd, n_steps=seg)
         return self._finish(out, seg, valid, was_done)
 
+
+    def _step_hole(self, params) -> Dict[str, torch.Tensor]:
+        """HoleReacher: the plan, then ONE rollout launch that advances the integer state, executes until the plan ends or the
+        arm collides, and commits the break (mpk_hole_reacher_rollout); at verbose < 2 it stores nothing per step"""
+        params = self._plan_params(params)
+        first = self._start32 is not None and self._plans_since_reset == 1
+        cond_pos = self.condition_pos if self.condition_pos is not None else (self._start32[0] if first else self.q.float())
+        cond_vel = self.condition_vel if self.condition_vel is not None else (self._start32[1] if first else self.qd.float())
+        init_time = float(self._lockstep * self.dt) if self.do_replanning else 0.0
+        pos, vel = self.engine.trajectory(params, cond_pos, cond_vel, init_time)
+        mpt = self.max_planning_times if math.isfinite(self.max_planning_times) else 2 ** 31 - 1
+        full = self.verbose >= 2
+        r = self.engine.hole_reacher_rollout(
+            self.spec, pos, vel, self.q, self.qd, self.hole, steps_before_reward=self.steps_before_reward,
+            replan=(self.traj_steps, self.plan_steps, self.done, self.every, int(mpt), self.horizon),
+            condition=self.condition_on_desired, want_actions=full, want_rewards=full, aggregation=self.reward_aggregation,
+            **self.hole_task)
+        if self.condition_on_desired:
+            self.condition_pos, self.condition_vel = r["cond_pos"], r["cond_vel"]
+        if self.do_replanning:
+            # a collision finishes its episode: every live episode executed the segment of the integer rule
+            self._lockstep += self._host_segment()
+        self._prev_done, self._prev_done_known = r["done"], True
+        collided = r["collided"].view(torch.bool)
+        out = dict(params=params, trajectory_length=r["n_exec"], done=r["done"].view(torch.bool), terminated=collided,
+                   truncated=self.traj_steps >= self.horizon, rewards=r["ret"], is_collided=collided,
+                   is_success=r["success"].view(torch.bool), current_pos=self.q, current_vel=self.qd)
+        if full:
+            out.update(des_pos=pos, des_vel=vel, step_actions=r["actions"], step_rewards=r["rewards"])
+        return out
 
     def _sub_trajectory_advance(self, params: torch.Tensor) -> torch.Tensor:
         """
@@ -478,13 +527,16 @@ class EpisodeGraph:
         dev = bb.device
         self.init_pos = torch.zeros((bb.B, bb.D), dtype=torch.float64, device=dev)
         self.init_vel = torch.zeros((bb.B, bb.D), dtype=torch.float64, device=dev)
-        self.goal = torch.zeros((bb.B, 2), dtype=torch.float64, device=dev) if (with_goal or bb.reward) else None
+        self.goal = torch.zeros((bb.B, 2), dtype=torch.float64, device=dev) if (with_goal or bb.reward == "simple_reacher") else None
+        self.hole = torch.zeros((bb.B, 3), dtype=torch.float64, device=dev) if bb.reward == "hole_reacher" else None
         self.params = [torch.zeros((bb.B, bb.engine.num_params), dtype=torch.float32, device=dev)
                        for _ in range(n_plans)]
         self.outs = []
 
         def episode():
             kw = {"goal": self.goal} if self.goal is not None else {}
+            if self.hole is not None:
+                kw["hole"] = self.hole
             bb.reset(self.init_pos, self.init_vel, **kw)
             return [bb.step(p) for p in self.params]
 

@@ -1,0 +1,311 @@
+// k_hole_rollout: the step loop of BlackBoxWrapper.step (black_box_wrapper.py:175-203) around the reference's HoleReacher
+// (envs/classic_control/hole_reacher/hole_reacher.py, base_reacher/base_reacher_direct.py:20-38, hr_simple_reward.py:19-53):
+// controller + clip, the direct-velocity plant, self / wall collision, reward, and the break on collision.  One lane per episode,
+// serial in time; a wave leaves the loop once none of its lanes is live.  float64 without FMA contraction, except where the
+// reference's own numpy flow is float32 (see hole_step).
+#include "mpk_dev.h"
+#include "mpk_reward.h"
+
+namespace mpk {
+
+struct HoleArgs {
+    RolloutDev rc;
+    const float* des_pos;
+    const float* des_vel;
+    double* Q;
+    double* QD;
+    const int32_t* n_steps;
+    const int32_t* step0;
+    const double* hole;              // [B, 3] (x, width, depth)
+    float* actions;                  // [B, T, D] or nullptr
+    double* rewards;                 // [B, T] or nullptr
+    double* ret;                     // [B] or nullptr
+    int32_t* n_exec;                 // [B] or nullptr
+    uint8_t* collided;               // [B] or nullptr
+    uint8_t* success;                // [B] or nullptr
+    ReplanDev rp;                    // traj_steps == nullptr: off
+    double penalty;
+    int allow_self, allow_wall, steps_before_reward, agg;
+    int D, B, T;
+};
+
+constexpr int kHolePoints = 100;     // np.linspace(0, 1, 100) points per link (hole_reacher.py:149)
+constexpr int kHoleWpb = 4;          // waves per workgroup
+
+// np.linspace(0, 1, 100)[j]: j * (1 / 99), the last point exactly 1
+__device__ __forceinline__ double hole_t(int j) { return j == kHolePoints - 1 ? 1.0 : (double)j * (1.0 / 99.0); }
+
+// ccw / intersect of envs/classic_control/utils.py:1-9
+__device__ __forceinline__ bool hole_ccw(double ax, double ay, double bx, double by, double cx, double cy) {
+    return (cy - ay) * (bx - ax) - (by - ay) * (cx - ax) > 1e-12;
+}
+__device__ __forceinline__ bool hole_intersect(double ax, double ay, double bx, double by, double cx, double cy, double dx, double dy) {
+    return hole_ccw(ax, ay, cx, cy, dx, dy) != hole_ccw(bx, by, cx, cy, dx, dy) &&
+           hole_ccw(ax, ay, bx, by, cx, cy) != hole_ccw(ax, ay, bx, by, dx, dy);
+}
+
+// The point coordinates of a link are v_j = fl(fl(a * t_j) + b), monotone in j (t_j increases, rounding is monotone), so
+// {j : v_j < h} (LESS) and {j : v_j > h} are a prefix or a suffix of [0, 100).  The crossing index comes from one division; the
+// exact predicate at the neighbouring indices then moves it to the true boundary (a step or two; any start would do).
+template <bool LESS>
+__device__ __forceinline__ void hole_interval(double a, double b, double h, int& lo, int& hi) {
+    auto pred = [&](int j) {
+        const double v = a * hole_t(j) + b;
+        return LESS ? v < h : v > h;
+    };
+    if (!(a > 0.0) && !(a < 0.0)) {                  // a constant coordinate, or NaN (no comparison holds)
+        const bool all = pred(0);
+        lo = 0; hi = all ? kHolePoints : 0;
+        return;
+    }
+    const double x = fmin(fmax((h - b) / a * 99.0, 0.0), (double)kHolePoints);   // NaN -> 0
+    int g = (int)ceil(x);
+    if ((a > 0.0) == LESS) {                        // true, then false: [0, g)
+        while (g > 0 && !pred(g - 1)) --g;
+        while (g < kHolePoints && pred(g)) ++g;
+        lo = 0; hi = g;
+    } else {                                        // false, then true: [g, 100)
+        while (g > 0 && pred(g - 1)) --g;
+        while (g < kHolePoints && !pred(g)) ++g;
+        lo = g; hi = kHolePoints;
+    }
+}
+
+// check_wall_collision (hole_reacher.py:151-179) for the link from (x0, y0) along (c, s): any point left of the hole and below 0,
+// right of the hole and below 0, or over the hole and below -depth
+template <bool SAMPLED>
+__device__ __forceinline__ bool hole_link_hits_wall(double c, double s, double x0, double y0, double hl, double hr, double floor_y) {
+    if constexpr (SAMPLED) {
+        bool hit = false;
+        for (int j = 0; j < kHolePoints; ++j) {
+            const double t = hole_t(j);
+            const double px = c * t + x0, py = s * t + y0;
+            hit |= (px < hl && py < 0.0) || (px > hr && py < 0.0) || (px > hl && px < hr && py < floor_y);
+        }
+        return hit;
+    } else {
+        int l0, l1, r0, r1, a0, a1, b0, b1, y0l, y0h, yd0, yd1;
+        hole_interval<true>(s, y0, 0.0, y0l, y0h);
+        hole_interval<true>(c, x0, hl, l0, l1);
+        if (max(l0, y0l) < min(l1, y0h)) return true;
+        hole_interval<false>(c, x0, hr, r0, r1);
+        if (max(r0, y0l) < min(r1, y0h)) return true;
+        hole_interval<true>(s, y0, floor_y, yd0, yd1);
+        hole_interval<false>(c, x0, hl, a0, a1);
+        hole_interval<true>(c, x0, hr, b0, b1);
+        return max(max(a0, b0), yd0) < min(min(a1, b1), yd1);
+    }
+}
+
+// DC: link count compiled in (0: run time, <= kMaxD)
+template <int DC, bool SAMPLED>
+__global__ void __launch_bounds__(64 * kHoleWpb) k_hole_rollout(const HoleArgs a) {
+    constexpr int MD = DC > 0 ? DC : kMaxD;
+    __shared__ double s_g[4 * kMaxD];
+    __shared__ double s_slot[16 * 64 * kHoleWpb];     // ret: per step slot t mod 16, the order of k_reward_aggregate
+    const int D = DC > 0 ? DC : a.D;
+    if (threadIdx.x < (unsigned)D) {
+        const double *pg = a.rc.pg, *dg = a.rc.dg, *lo = a.rc.lo, *hi = a.rc.hi;
+        s_g[threadIdx.x] = pg[threadIdx.x];
+        s_g[kMaxD + threadIdx.x] = dg[threadIdx.x];
+        s_g[2 * kMaxD + threadIdx.x] = lo[threadIdx.x];
+        s_g[3 * kMaxD + threadIdx.x] = hi[threadIdx.x];
+    }
+    __syncthreads();
+    const long bl = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool on = bl < a.B;
+    if (!__any(on)) return;
+    const int b = on ? (int)bl : 0;
+    const int T = a.T;
+    const int ctrl = a.rc.controller_type;
+    const bool with_rp = a.rp.traj_steps != nullptr;
+
+    int n = 0, s0 = 0;
+    ReplanVals rv{0, 0, 0, true};
+    if (on) {
+        if (with_rp) {
+            rv = replan_eval(a.rp, b, T);
+            n = rv.seg;
+            s0 = rv.cur;
+        } else {
+            n = a.n_steps ? a.n_steps[b] : T;
+            n = n < T ? (n < 0 ? 0 : n) : T;
+            s0 = a.step0 ? a.step0[b] : 0;
+        }
+    }
+    double q[MD], qd[MD];
+#pragma unroll
+    for (int d = 0; d < MD; ++d) {
+        q[d] = (on && d < D) ? a.Q[(size_t)b * D + d] : 0.0;
+        qd[d] = (on && d < D) ? a.QD[(size_t)b * D + d] : 0.0;
+    }
+    const double hx = on ? a.hole[3 * (size_t)b] : 0.0, hw = on ? a.hole[3 * (size_t)b + 1] : 0.0;
+    const double hdepth = on ? a.hole[3 * (size_t)b + 2] : 0.0;
+    const double hl = hx - hw / 2.0, hr = hx + hw / 2.0, floor_y = -hdepth;     // hole_reacher.py:156,165,174
+    const double dt = a.rc.dt;
+    const float dt32 = (float)dt;
+    double* slot = s_slot + threadIdx.x;
+    if (a.ret) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) slot[i * 64 * kHoleWpb] = 0.0;
+    }
+    double last_r = 0.0;
+    bool coll = false, succ = false;
+    int t = 0;
+    const size_t row0 = (size_t)b * T;
+    for (;; ++t) {
+        const bool live = t < n && !coll;
+        if (!__any(live)) break;                      // wave-uniform exit
+        if (!live) continue;
+        const size_t row = (row0 + t) * D;
+        // controller + clip (black_box_wrapper.py:176-179)
+        double u[MD];
+#pragma unroll
+        for (int d = 0; d < MD; ++d) {
+            if (d >= D) { u[d] = 0.0; continue; }
+            double v;
+            if (ctrl == MPK_CTRL_VELOCITY) v = (double)a.des_vel[row + d];
+            else if (ctrl == MPK_CTRL_POSITION) v = (double)a.des_pos[row + d];
+            else v = s_g[d] * ((double)a.des_pos[row + d] - q[d]) + s_g[kMaxD + d] * ((double)a.des_vel[row + d] - qd[d]);
+            u[d] = fmin(fmax(v, s_g[2 * kMaxD + d]), s_g[3 * kMaxD + d]);
+        }
+        // the direct-velocity plant (base_reacher_direct.py:26-28) and its control cost, in numpy's dtypes: the velocity / position
+        // controllers hand over a float32 action, which becomes the state qd -- from the episode's second step on acc = (a - qd) / dt
+        // and dt * qd are float32 operations (numpy casts the Python float dt to float32), and np.sum(acc ** 2) adds in float32; the
+        // first step subtracts from the float64 start velocity.  The motor controller's action is float64 throughout.
+        const bool f32 = ctrl != MPK_CTRL_MOTOR && s0 + t > 0;
+        double acc_cost;
+        if (f32) {
+            float c32 = 0.0f;
+#pragma unroll
+            for (int d = 0; d < MD; ++d) {
+                if (d >= D) continue;
+                const float a32 = (float)u[d];
+                const float acc = (a32 - (float)qd[d]) / dt32;
+                c32 = c32 + acc * acc;
+                qd[d] = (double)a32;
+                q[d] = q[d] + (double)(dt32 * a32);
+            }
+            acc_cost = (double)c32;
+        } else {
+            acc_cost = 0.0;
+#pragma unroll
+            for (int d = 0; d < MD; ++d) {
+                if (d >= D) continue;
+                const double acc = (u[d] - qd[d]) / dt;
+                acc_cost = acc_cost + acc * acc;
+                qd[d] = u[d];
+                q[d] = ctrl == MPK_CTRL_MOTOR ? q[d] + dt * qd[d] : q[d] + (double)(dt32 * (float)u[d]);
+            }
+        }
+        // kinematics (base_reacher.py:95-103): unit links, cumulative angles, joints from the origin
+        double jx[MD + 1], jy[MD + 1], cs[MD], sn[MD];
+        jx[0] = 0.0; jy[0] = 0.0;
+        double ang = 0.0;
+#pragma unroll
+        for (int d = 0; d < MD; ++d) {
+            if (d >= D) { cs[d] = sn[d] = 0.0; jx[d + 1] = jx[d]; jy[d + 1] = jy[d]; continue; }
+            ang = d == 0 ? q[0] : ang + q[d];
+            sincos_lean(ang, &sn[d], &cs[d]);
+            jx[d + 1] = jx[d] + cs[d];
+            jy[d + 1] = jy[d] + sn[d];
+        }
+        // self collision (base_reacher.py:105-119): joint limits, then non-adjacent links
+        bool hit = false;
+        if (!a.allow_self) {
+#pragma unroll
+            for (int d = 0; d < MD; ++d)
+                if (d < D) hit |= q[d] > M_PI || q[d] < -M_PI;
+            if (!hit) {
+                for (int i = 0; i < D && !hit; ++i)
+                    for (int k = i + 2; k < D && !hit; ++k)
+                        hit = hole_intersect(jx[i], jy[i], jx[i + 1], jy[i + 1], jx[k], jy[k], jx[k + 1], jy[k + 1]);
+            }
+        }
+        if (!a.allow_wall && !hit) {
+            for (int i = 0; i < D && !hit; ++i) hit = hole_link_hits_wall<SAMPLED>(cs[i], sn[i], jx[i], jy[i], hl, hr, floor_y);
+        }
+        // reward (hr_simple_reward.py:36-53): the distance term at step steps_before_reward or on collision
+        double dist_cost = 0.0;
+        if (s0 + t == a.steps_before_reward || hit) {
+            const double dx = jx[D] - hx, dy = jy[D] - floor_y;
+            const double dist = sqrt(dx * dx + dy * dy);
+            dist_cost = dist * dist;
+            succ = dist < 0.005 && !hit;
+        }
+        const double r = (dist_cost * -1.0 + acc_cost * -5e-8) + (hit ? 1.0 : 0.0) * -a.penalty;
+        if (a.actions) {
+#pragma unroll
+            for (int d = 0; d < MD; ++d)
+                if (d < D) a.actions[row + d] = (float)u[d];
+        }
+        if (a.rewards) a.rewards[row0 + t] = r;
+        if (a.ret) slot[(t & 15) * 64 * kHoleWpb] += r;
+        last_r = r;
+        if (hit) { coll = true; n = t + 1; }      // terminated: the wrapper breaks (black_box_wrapper.py:197-203)
+    }
+    if (!on) return;
+    // steps after the break
+    for (int tt = n; tt < T; ++tt) {
+        if (a.actions)
+            for (int d = 0; d < D; ++d) a.actions[(row0 + tt) * D + d] = 0.0f;
+        if (a.rewards) a.rewards[row0 + tt] = 0.0;
+    }
+#pragma unroll
+    for (int d = 0; d < MD; ++d)
+        if (d < D) { a.Q[(size_t)b * D + d] = q[d]; a.QD[(size_t)b * D + d] = qd[d]; }
+    if (a.ret) {
+        double sum = slot[0];
+#pragma unroll
+        for (int i = 1; i < 16; ++i) sum = sum + slot[i * 64 * kHoleWpb];
+        a.ret[b] = a.agg == MPK_AGG_LAST ? (n > 0 ? last_r : 0.0) : (a.agg == MPK_AGG_MEAN ? (n > 0 ? sum / (double)n : 0.0) : sum);
+    }
+    if (a.n_exec) a.n_exec[b] = n;
+    if (a.collided) a.collided[b] = coll ? 1 : 0;
+    if (a.success) a.success[b] = succ ? 1 : 0;
+    if (with_rp) {
+        // the break committed: the executed steps, the clock, and a collision finishes the episode
+        const ReplanDev& rp = a.rp;
+        rp.seg_len[b] = n;
+        if (!rv.was_done) {
+            const uint8_t dn = (coll || rv.cur + n >= rp.horizon) ? 1 : 0;
+            rp.plan_steps[b] = rv.plan;
+            rp.traj_steps[b] = rv.cur + n;
+            rp.done[b] = dn;
+            if (rp.done_out) rp.done_out[b] = dn;
+        } else if (rp.done_out) {
+            rp.done_out[b] = 1;
+        }
+        if (rp.cond_pos) {
+            int tc = n - 1;
+            tc = tc < 0 ? 0 : (tc > T - 1 ? T - 1 : tc);
+            for (int d = 0; d < D; ++d) {
+                rp.cond_pos[(size_t)b * D + d] = a.des_pos[(row0 + tc) * D + d];
+                rp.cond_vel[(size_t)b * D + d] = a.des_vel[(row0 + tc) * D + d];
+            }
+        }
+    }
+}
+
+#ifndef MPK_DEVICE_ONLY
+int launch_hole_rollout(const HoleLaunch& h, int B, int T, int D, void* stream, const Tuning& tune) {
+    HoleArgs a;
+    a.rc = h.rc; a.des_pos = h.des_pos; a.des_vel = h.des_vel; a.Q = h.q; a.QD = h.qd; a.n_steps = h.n_steps; a.step0 = h.step0;
+    a.hole = h.hole; a.actions = h.actions; a.rewards = h.rewards; a.ret = h.ret; a.n_exec = h.n_exec; a.collided = h.collided;
+    a.success = h.success; a.rp = h.rp; a.penalty = h.penalty; a.allow_self = h.allow_self; a.allow_wall = h.allow_wall;
+    a.steps_before_reward = h.steps_before_reward; a.agg = h.agg; a.D = D; a.B = B; a.T = T;
+    const bool sampled = tune.hole_sampled == 1;
+    const dim3 grid((unsigned)((B + 64 * kHoleWpb - 1) / (64 * kHoleWpb))), block(64 * kHoleWpb);
+    if (D == 5) {
+        if (sampled) hipLaunchKernelGGL((k_hole_rollout<5, true>), grid, block, 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((k_hole_rollout<5, false>), grid, block, 0, (hipStream_t)stream, a);
+    } else {
+        if (sampled) hipLaunchKernelGGL((k_hole_rollout<0, true>), grid, block, 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((k_hole_rollout<0, false>), grid, block, 0, (hipStream_t)stream, a);
+    }
+    MPK_LAUNCH_CHECK();
+    return MPK_OK;
+}
+#endif  // MPK_DEVICE_ONLY
+
+}  // namespace mpk

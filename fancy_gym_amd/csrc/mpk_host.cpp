@@ -540,12 +540,18 @@ static int get_shared(Handle* h, float init_time, void* stream, SharedTables* ou
     return MPK_OK;
 }
 
-static int fill_rollout(const Handle* h, const mpk_rollout_cfg* rc, RolloutDev* out) {
+// direct: the caller integrates MPK_PLANT_VELOCITY_DIRECT (mpk_hole_reacher_rollout); every other entry point refuses that plant
+static int fill_rollout(const Handle* h, const mpk_rollout_cfg* rc, RolloutDev* out, bool direct = false) {
     if (!rc) { set_error("rollout cfg is NULL"); return MPK_EINVAL; }
     const int D = h->dev.D;
     if (D > kMaxDofArgs) { set_error("num_dof too large for the rollout kernels"); return MPK_EINVAL; }
     if (rc->controller_type < 0 || rc->controller_type > 2) { set_error("unknown controller_type"); return MPK_EINVAL; }
-    if (rc->plant_type < 0 || rc->plant_type > 1) { set_error("unknown plant_type"); return MPK_EINVAL; }
+    if (rc->plant_type < 0 || rc->plant_type > 2) { set_error("unknown plant_type"); return MPK_EINVAL; }
+    if ((rc->plant_type == MPK_PLANT_VELOCITY_DIRECT) != direct) {
+        set_error(direct ? "mpk_hole_reacher_rollout integrates MPK_PLANT_VELOCITY_DIRECT only"
+                         : "MPK_PLANT_VELOCITY_DIRECT is integrated by mpk_hole_reacher_rollout only");
+        return MPK_EINVAL;
+    }
     if (!rc->act_low || !rc->act_high) { set_error("act_low/act_high are required"); return MPK_EINVAL; }
     if (rc->controller_type == MPK_CTRL_MOTOR && (!rc->p_gains || !rc->d_gains)) {
         set_error("motor controller needs p_gains and d_gains");
@@ -751,7 +757,7 @@ const OptKey kOptKeys[] = {
     {"ablations", &Tuning::ablations, 0, 1},     {"ring_tb", &Tuning::ring_tb, 1, 64},
     {"pd_helper", &Tuning::pd_helper, 0, 1},     {"phase_waves", &Tuning::phase_waves, 1, 32},
     {"phase_split", &Tuning::phase_split, 1, 64},   {"phase_pipe", &Tuning::phase_pipe, 0, 1},
-    {"pd_pipe", &Tuning::pd_pipe, 0, 1},
+    {"pd_pipe", &Tuning::pd_pipe, 0, 1},         {"hole_sampled", &Tuning::hole_sampled, 0, 1},
 };
 const OptKey* find_opt(const char* key) {
     if (!key) return nullptr;
@@ -1259,6 +1265,41 @@ int mpk_reacher_rollout(mpk_handle hh, const mpk_rollout_cfg* rc, const float* d
     }
     return launch_reacher_rollout(rd, h->dev.D, des_pos, des_vel, q, qd, n_steps, step0, goal, steps_before_reward,
                                   actions, rewards, B, T, stream, effective_tuning(h), h->d_fault);
+}
+
+int mpk_hole_reacher_rollout(mpk_handle hh, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel, double* q,
+                             double* qd, const int32_t* n_steps, const int32_t* step0, const mpk_hole_task* task, const double* hole,
+                             float* actions, double* rewards, double* ret, int32_t agg, int32_t* n_exec, uint8_t* collided,
+                             uint8_t* success, const mpk_replan_state* st, int32_t B, int32_t T, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (B < 0 || T < 0) { set_error("B and T must be >= 0"); return MPK_EINVAL; }
+    HoleLaunch hl;
+    int r = fill_rollout(h, rc, &hl.rc, true);
+    if (r != MPK_OK) return r;
+    const int D = h->dev.D;
+    if (D < 1 || D > kMaxD) { set_error("mpk_hole_reacher_rollout takes 1 .. 16 links"); return MPK_EINVAL; }
+    if (!task) { set_error("task is NULL"); return MPK_EINVAL; }
+    if (agg < MPK_AGG_SUM || agg > MPK_AGG_LAST) { set_error("unknown reward aggregation"); return MPK_EINVAL; }
+    if (st && (n_steps || step0)) { set_error("with a replanning state the steps and the step counter come from it: n_steps and step0 must be NULL"); return MPK_EINVAL; }
+    if (B == 0 || T == 0) return MPK_OK;
+    const bool need_pos = rc->controller_type != MPK_CTRL_VELOCITY || (st && st->cond_pos);
+    const bool need_vel = rc->controller_type != MPK_CTRL_POSITION || (st && st->cond_pos);
+    if ((need_pos && !des_pos) || (need_vel && !des_vel) || !q || !qd || !hole) { set_error("NULL buffer"); return MPK_EINVAL; }
+    if (st) {
+        if (!st->traj_steps || !st->plan_steps || !st->done || !st->seg_len) { set_error("NULL replanning state buffer"); return MPK_EINVAL; }
+        if ((st->cond_pos == nullptr) != (st->cond_vel == nullptr)) { set_error("cond_pos and cond_vel go together"); return MPK_EINVAL; }
+        if (st->every < 1 || st->horizon < 1) { set_error("every and horizon must be >= 1"); return MPK_EINVAL; }
+        hl.rp.traj_steps = st->traj_steps; hl.rp.plan_steps = st->plan_steps; hl.rp.done = st->done; hl.rp.seg_len = st->seg_len;
+        hl.rp.done_out = st->done_out; hl.rp.cond_pos = st->cond_pos; hl.rp.cond_vel = st->cond_vel;
+        hl.rp.every = st->every; hl.rp.max_planning_times = st->max_planning_times; hl.rp.horizon = st->horizon;
+    }
+    hl.des_pos = des_pos; hl.des_vel = des_vel; hl.q = q; hl.qd = qd; hl.n_steps = n_steps; hl.step0 = step0; hl.hole = hole;
+    hl.actions = actions; hl.rewards = rewards; hl.ret = ret; hl.n_exec = n_exec; hl.collided = collided; hl.success = success;
+    hl.penalty = task->collision_penalty; hl.allow_self = task->allow_self_collision != 0; hl.allow_wall = task->allow_wall_collision != 0;
+    hl.steps_before_reward = task->steps_before_reward; hl.agg = agg;
+    MPK_ON_DEVICE(h->cfg.device);
+    return launch_hole_rollout(hl, B, T, D, stream, effective_tuning(h));
 }
 
 int mpk_episode_reset(mpk_handle hh, const double* init_q, const double* init_qd, double* q, double* qd,

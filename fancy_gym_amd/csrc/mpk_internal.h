@@ -35,7 +35,8 @@ struct Tuning {
     int mapping = -1, bulk = -1, quad = -1, pd_quad = -1, write_through = -1, ipw = -1, phase = -1, phase_table = -1,
         phase_chunk = -1, pd_simple = -1, split = -1, lds_pad = -1, pipe = -1, flat = -1, phase_flat = -1,
         ring = -1, ring_np = -1, ring_ns = -1, ring_m = -1, ring_dbg = -1, ring_parts = -1, tiles_wpb = -1, serial_order = -1, ring_nc = -1,
-        pd_generic = -1, dmp_response = -1, ablations = -1, ring_tb = -1, pd_helper = -1, phase_waves = -1, phase_split = -1, phase_pipe = -1, pd_pipe = -1;
+        pd_generic = -1, dmp_response = -1, ablations = -1, ring_tb = -1, pd_helper = -1, phase_waves = -1, phase_split = -1, phase_pipe = -1, pd_pipe = -1,
+        hole_sampled = -1;
 };
 
 // ---- device-side configuration (kernel argument, by value) --------------------------------------------------
@@ -162,6 +163,27 @@ int launch_reacher_rollout(const RolloutDev& rc, int D, const float* des_pos, co
                            double* qd, const int32_t* n_steps, const int32_t* step0, const double* goal,
                            int steps_before_reward, float* actions, double* rewards, int B, int T, void* stream,
                            const Tuning& tune, int* fault);
+// mpk_hole_reacher_rollout (mpk_hole.hip): the HoleReacher step loop with its break on collision
+struct HoleLaunch {
+    RolloutDev rc;
+    const float* des_pos = nullptr;
+    const float* des_vel = nullptr;
+    double* q = nullptr;
+    double* qd = nullptr;
+    const int32_t* n_steps = nullptr;
+    const int32_t* step0 = nullptr;
+    const double* hole = nullptr;
+    float* actions = nullptr;
+    double* rewards = nullptr;
+    double* ret = nullptr;
+    int32_t* n_exec = nullptr;
+    uint8_t* collided = nullptr;
+    uint8_t* success = nullptr;
+    ReplanDev rp;
+    double penalty = 0.0;
+    int allow_self = 0, allow_wall = 0, steps_before_reward = 0, agg = 0;
+};
+int launch_hole_rollout(const HoleLaunch& h, int B, int T, int D, void* stream, const Tuning& tune);
 int launch_episode_reset(const double* init_q, const double* init_qd, double* q, double* qd, float* cond_pos,
                          float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done, int B, int D,
                          void* stream);

@@ -556,6 +556,59 @@ class TrajectoryEngine:
                                                  rew.data_ptr(), B, T, self._stream()))
         return act, rew
 
+    def hole_reacher_rollout(self, spec: RolloutSpec, des_pos: Optional[torch.Tensor], des_vel: torch.Tensor, q: torch.Tensor,
+                             qd: torch.Tensor, hole: torch.Tensor, *, collision_penalty: float = 100.0,
+                             allow_self_collision: bool = False, allow_wall_collision: bool = False, steps_before_reward: int = 199,
+                             n_steps: Optional[torch.Tensor] = None, step0: Optional[torch.Tensor] = None, replan=None,
+                             condition: bool = False, want_actions: bool = True, want_rewards: bool = True,
+                             aggregation: Optional[str] = "sum"):
+        """
+        The HoleReacher step loop on the device (mpk.h: mpk_hole_reacher_rollout; spec.plant 'velocity_direct'): controller, clip,
+        direct-velocity plant, collisions, reward, and the break on collision.  q, qd are updated in place.  ``replan`` =
+        (traj_steps, plan_steps, done, every, max_planning_times, horizon) lets the launch advance the integer state itself and commit
+        the break (then n_steps / step0 must be None).  Returns a dict: actions [B, T, D] / rewards [B, T] (or None), ret [B] (or None
+        when aggregation is None), n_exec [B] int32, collided / success [B] uint8, and with ``replan`` done (snapshot after the plan)
+        plus cond_pos / cond_vel when ``condition``.
+        """
+        if spec.plant != "velocity_direct":
+            raise ValueError("hole_reacher_rollout integrates plant='velocity_direct'")
+        B, T, D = des_vel.shape
+        assert des_vel.dtype == torch.float32 and (des_pos is None or des_pos.dtype == torch.float32)
+        assert q.dtype == torch.float64 and qd.dtype == torch.float64 and q.is_contiguous() and qd.is_contiguous()
+        des_vel = des_vel.contiguous()
+        des_pos = des_pos.contiguous() if des_pos is not None else None
+        hole = torch.as_tensor(hole, dtype=torch.float64, device=self.device).expand(B, 3).contiguous()
+        f = dict(device=self.device)
+        act = torch.empty((B, T, D), dtype=torch.float32, **f) if want_actions else None
+        rew = torch.empty((B, T), dtype=torch.float64, **f) if want_rewards else None
+        ret = torch.empty(B, dtype=torch.float64, **f) if aggregation is not None else None
+        n_exec = torch.empty(B, dtype=torch.int32, **f)
+        coll = torch.empty(B, dtype=torch.uint8, **f)
+        succ = torch.empty(B, dtype=torch.uint8, **f)
+        task = _lib.mpk_hole_task(float(collision_penalty), int(bool(allow_self_collision)), int(bool(allow_wall_collision)),
+                                  int(steps_before_reward), 0)
+        st = done_out = cp = cv = None
+        if replan is not None:
+            traj_steps, plan_steps, done, every, max_planning_times, horizon = replan
+            assert traj_steps.dtype == torch.int32 and plan_steps.dtype == torch.int32 and done.dtype == torch.uint8
+            done_out = torch.empty(B, dtype=torch.uint8, **f)
+            if condition:
+                cp, cv = (torch.empty((B, D), dtype=torch.float32, **f) for _ in range(2))
+            st = _lib.mpk_replan_state(traj_steps.data_ptr(), plan_steps.data_ptr(), done.data_ptr(), n_exec.data_ptr(),
+                                       done_out.data_ptr(), _dptr(cp), _dptr(cv), int(every),
+                                       int(min(max_planning_times, 2 ** 31 - 1)), int(horizon), 0)
+        if n_steps is not None:
+            n_steps = n_steps.to(device=self.device, dtype=torch.int32).contiguous()
+        if step0 is not None:
+            step0 = step0.to(device=self.device, dtype=torch.int32).contiguous()
+        agg = _lib.AGG_MODES[aggregation] if aggregation is not None else 0
+        _lib.check(self._lib.mpk_hole_reacher_rollout(
+            self._h, C.byref(spec.c), _dptr(des_pos), des_vel.data_ptr(), q.data_ptr(), qd.data_ptr(), _dptr(n_steps), _dptr(step0),
+            C.byref(task), hole.data_ptr(), _dptr(act), _dptr(rew), _dptr(ret), agg, n_exec.data_ptr(), coll.data_ptr(),
+            succ.data_ptr(), C.byref(st) if st is not None else None, B, T, self._stream()))
+        return dict(actions=act, rewards=rew, ret=ret, n_exec=n_exec, collided=coll, success=succ, done=done_out, cond_pos=cp,
+                    cond_vel=cv)
+
     def condition_gather(self, pos: torch.Tensor, vel: torch.Tensor, seg_len: torch.Tensor,
                          out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
         """desired (pos, vel) [B, D] at the last executed step of each episode (condition_on_desired)"""

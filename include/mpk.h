@@ -56,6 +56,8 @@ extern "C" {
 /* plants the rollout kernel can integrate on device */
 #define MPK_PLANT_STATIC             0  /* state never changes (test/test_black_box.py:50-56 ToyWrapper)            */
 #define MPK_PLANT_DOUBLE_INTEGRATOR  1  /* envs/classic_control/base_reacher/base_reacher_torque.py:25-26           */
+#define MPK_PLANT_VELOCITY_DIRECT    2  /* base_reacher/base_reacher_direct.py:20-38 (HoleReacher): integrated by
+                                           mpk_hole_reacher_rollout only; every other entry point answers MPK_EINVAL */
 
 /*
  * mp_pytorch semantics that cannot be checked against the package in this build (it is not vendored by the reference:
@@ -263,6 +265,8 @@ int mpk_set_duration(mpk_handle h, double duration, double dt);
  *                   recurrence either), 2 no stores, 8 (open loop) no input loads, 128 every workgroup's second batch is never
  *                   published (the roles that wait for it give up after ~0.3 s and raise the handle's fault word: below).
  *   "ablations"     1 lets the ablation bits of "ring_dbg" take effect (default: they are masked out)
+ *   "hole_sampled"  1 mpk_hole_reacher_rollout tests the wall on the reference's 100 points per link instead of the index intervals
+ *                   (A/B runs and tests: the same verdicts bit for bit)
  * Unknown key or value out of range: MPK_EINVAL.  mpk_get_option returns the effective value (MPK_OPT_AUTO if automatic).
  */
 #define MPK_OPT_AUTO (-1)
@@ -516,6 +520,47 @@ int mpk_reacher_rollout(mpk_handle h, const mpk_rollout_cfg* rc, const float* de
                         double* q, double* qd, const int32_t* n_steps, const int32_t* step0, const double* goal,
                         int32_t steps_before_reward, float* actions, double* rewards, int32_t B, int32_t T,
                         void* stream);
+
+/*
+ * The step loop of BlackBoxWrapper.step (black_box_wrapper.py:175-203) around the reference's HoleReacher (ABI 4, appended):
+ * envs/classic_control/hole_reacher/hole_reacher.py with rew_fct "simple" (hr_simple_reward.py:19-53) on the direct-velocity plant
+ * (base_reacher/base_reacher_direct.py:20-38, rc->plant_type MPK_PLANT_VELOCITY_DIRECT).  Per executed step t, a = the clipped
+ * controller output (motor / velocity / position; the velocity controller reads des_vel only, des_pos may then be NULL):
+ *   acc = (a - qd) / dt ; qd = a ; q = q + dt * qd          in numpy's dtypes: with the velocity / position controller the action is
+ *                                                           float32, so from an episode's second step on (step0 + t > 0) acc, its
+ *                                                           square sum and dt * qd are float32 operations; motor: float64 throughout
+ *   joints = unit links from the origin, cumulative angles (base_reacher.py:95-103)
+ *   collided = (!allow_self_collision and (a joint outside [-pi, pi] or two non-adjacent links intersect: utils.py:1-9))
+ *              or (!allow_wall_collision and a point of np.linspace(0, 1, 100) on a link lies left / right of the hole below 0 or
+ *                  over it below -depth: hole_reacher.py:151-179 -- evaluated as exact index intervals, option "hole_sampled" 1: the
+ *                  100 points themselves; the verdicts are the same)
+ *   rewards[b,t] = -dist^2 * paid - 5e-8 * sum(acc^2) - collision_penalty * collided,  paid = (step0 + t == steps_before_reward or
+ *                  collided), dist = |end effector - (x, -depth)|
+ * and the loop BREAKS after a colliding step (terminated = collided, :197-203).
+ *   hole      dev double [B, 3]  (x, width, depth) of each episode
+ *   n_steps   dev int32 [B] or NULL (= T): steps the plan may execute; step0 dev int32 [B] or NULL (= 0): the env step counter at the
+ *             plan's first step.  Both must be NULL when st is given.
+ *   actions   dev float [B, T, D] or NULL; rewards dev double [B, T] or NULL: steps after the break are written as 0
+ *   ret       dev double [B] or NULL: reward_aggregation (agg: MPK_AGG_*) over the executed steps, equal bit for bit to
+ *             mpk_reward_aggregate of the stored rewards -- a verbose < 2 step need not store them
+ *   n_exec    dev int32 [B] or NULL: executed steps (infos['trajectory_length']); collided / success dev uint8 [B] or NULL: the episode
+ *             collided in this plan / is_success of its paid step (dist < 0.005 and no collision)
+ *   st        NULL, or the replanning state of mpk_replan_step: the launch advances it itself (n_steps = the rule's seg_len, step0 =
+ *             traj_steps before the plan) and commits the break: seg_len = n_exec, traj_steps += n_exec, done |= collided, done_out,
+ *             and cond_pos / cond_vel gathered at the corrected seg_len (des_pos and des_vel are then both needed)
+ * q, qd dev double [B, D] as mpk_pd_rollout; D <= 16.  One lane per episode.
+ */
+typedef struct mpk_hole_task {
+    double  collision_penalty;       /* hole_reacher.py:20 (fancy/HoleReacher-v0 registers 100) */
+    int32_t allow_self_collision;
+    int32_t allow_wall_collision;
+    int32_t steps_before_reward;     /* the step that pays the distance: 199 (hr_simple_reward.py:36) */
+    int32_t reserved0;
+} mpk_hole_task;
+int mpk_hole_reacher_rollout(mpk_handle h, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel, double* q,
+                             double* qd, const int32_t* n_steps, const int32_t* step0, const mpk_hole_task* task, const double* hole,
+                             float* actions, double* rewards, double* ret, int32_t agg, int32_t* n_exec, uint8_t* collided,
+                             uint8_t* success, const mpk_replan_state* st, int32_t B, int32_t T, void* stream);
 
 /*
  * BlackBoxWrapper.reset (black_box_wrapper.py:222-229) for B device-resident episodes, one launch: the integer state

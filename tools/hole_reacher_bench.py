@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""
+HoleReacher rollout (mpk_hole_reacher_rollout, 5 links, 200 steps, velocity controller) on random smooth plans from random starts
+with sampled holes: verbose = 2 (actions + step rewards stored) against the return only, the index-interval wall test against the
+reference's 100 sampled points ("hole_sampled" 1), and mpk_reacher_rollout at LongSimpleReacher's shape (5 x 200, reward) as the
+yardstick; a one-core NumPy loop over the host env as the CPU baseline.  Every timed call first restores the start state (two
+[B, 5] float64 copies), so that every launch runs the same episodes.  Captured graphs of 20 calls, median of rounds.
+    python tools/hole_reacher_bench.py [B ...] [--cpu N]
+"""
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from fancy_gym_amd import RolloutSpec, TrajectoryEngine  # noqa: E402
+from fancy_gym_amd.envs.classic_control.hole_reacher import HoleReacherEnv  # noqa: E402
+from tools.closed_bench import graph_time  # noqa: E402
+
+D, T = 5, 200
+LIM = float(np.float32(2 * np.pi))
+
+
+def plans(B, seed=0):
+    rng = np.random.default_rng(seed)
+    q0 = np.zeros((B, D)); q0[:, 0] = rng.uniform(np.pi / 4, 3 * np.pi / 4, B)
+    t = np.arange(T)[None, :, None] * 0.01
+    vel = np.zeros((B, T, D), np.float32)
+    for _ in range(2):
+        vel += (rng.uniform(-1.5, 1.5, (B, 1, D)) * np.sin(rng.uniform(0.2, 2, (B, 1, D)) * 2 * np.pi * t
+                                                           + rng.uniform(0, 7, (B, 1, D)))).astype(np.float32)
+    w = rng.uniform(0.15, 0.5, B)
+    hole = np.stack([rng.choice([-1, 1], B) * rng.uniform(w / 2, 3.5), w, np.ones(B)], axis=1)
+    return q0, vel, hole
+
+
+def cpu_loop(n):
+    q0, vel, hole = plans(n, 1)
+    env = HoleReacherEnv(D, collision_penalty=100)
+    t0 = time.perf_counter()
+    steps = 0
+    for b in range(n):
+        env.hole, env.q, env.qd, env.steps = hole[b], q0[b].copy(), np.zeros(D), 0
+        env._update_joints()
+        for t in range(T):
+            steps += 1
+            if env.step(np.clip(vel[b, t], -LIM, LIM))[2]:
+                break
+    dt = time.perf_counter() - t0
+    return n / dt, steps / n
+
+
+def main():
+    args = sys.argv[1:]
+    if "--cpu" in args:
+        del args[args.index("--cpu"):args.index("--cpu") + 2]
+    batches = [int(a) for a in args if a.isdigit()] or [1024, 4096, 65536, 262144]
+    torch.cuda.set_device(0)
+    eng = TrajectoryEngine("promp", "linear", "zero_rbf", D, 5, dt=0.01, duration=2.0, tau=2.0, num_basis_zero_start=1, device=0)
+    vspec = RolloutSpec("velocity", D, 1.0, 0.1, -LIM, LIM, plant="velocity_direct", dt=0.01)
+    rspec = RolloutSpec("motor", D, 0.6, 0.075, -1000.0, 1000.0, plant="double_integrator", dt=0.01)
+    print("| rollout | B | us | episodes/s | mean executed steps | collided |")
+    print("|---|---|---|---|---|---|")
+    for B in batches:
+        q0, vel, hole = plans(B)
+        q0 = torch.as_tensor(q0, device="cuda")
+        vel_d = torch.as_tensor(vel, device="cuda")
+        hole_d = torch.as_tensor(hole, device="cuda")
+        q, qd = torch.empty_like(q0), torch.empty_like(q0)
+        goal = torch.zeros((B, 2), dtype=torch.float64, device="cuda")
+        stats = {}
+        for name, sampled, full in (("hole, interval, verbose 2", 0, True), ("hole, interval, ret only", 0, False),
+                                    ("hole, sampled, verbose 2", 1, True), ("hole, sampled, ret only", 1, False)):
+            eng.set_option("hole_sampled", sampled)
+
+            def fn():
+                q.copy_(q0); qd.zero_()
+                r = eng.hole_reacher_rollout(vspec, None, vel_d, q, qd, hole_d, want_actions=full, want_rewards=full)
+                stats["n"], stats["c"] = r["n_exec"], r["collided"]
+            us = graph_time(fn) * 1e6
+            fn(); torch.cuda.synchronize()
+            print(f"| {name} | {B} | {us:.1f} | {B / us * 1e6:.3g} | {stats['n'].float().mean().item():.1f} | "
+                  f"{stats['c'].float().mean().item():.2f} |", flush=True)
+        eng.set_option("hole_sampled")
+
+        def fr():
+            q.copy_(q0); qd.zero_()
+            eng.reacher_rollout(rspec, vel_d, vel_d, q, qd, goal)
+        us = graph_time(fr) * 1e6
+        print(f"| LongSimpleReacher reacher_rollout (yardstick) | {B} | {us:.1f} | {B / us * 1e6:.3g} | 200 | - |", flush=True)
+    n = int(sys.argv[sys.argv.index("--cpu") + 1]) if "--cpu" in sys.argv else 256
+    eps, mean_steps = cpu_loop(n)
+    print(f"| NumPy host env, one core | {n} | - | {eps:.3g} | {mean_steps:.1f} | - |", flush=True)
+
+
+if __name__ == "__main__":
+    main()
