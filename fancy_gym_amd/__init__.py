@@ -7,7 +7,7 @@ this package is the Python host mirror of the reference's interfaces for that pa
 ``fancy_gym/__init__.py:1-20`` where they exist there).
 """
 from ._lib import MPKLibraryError  # noqa: F401
-from .engine import RolloutSpec, TrajectoryEngine  # noqa: F401
+from .engine import RolloutSpec, TrajectoryEngine, nprng_state  # noqa: F401
 from .black_box.black_box_wrapper import BlackBoxWrapper  # noqa: F401
 from .black_box.raw_interface_wrapper import RawInterfaceWrapper  # noqa: F401
 from .batched import BatchedBlackBox  # noqa: F401

@@ -80,6 +80,17 @@ class mpk_hole_task(C.Structure):
     ]
 
 
+RESET_ENVS = {"simple_reacher": 0, "hole_reacher": 1}          # MPK_RESET_*
+
+
+class mpk_reacher_reset_task(C.Structure):
+    _fields_ = [
+        ("env", C.c_int32), ("random_start", C.c_int32), ("target", C.c_double * 2),
+        ("hole_width", C.c_double), ("hole_x", C.c_double), ("hole_depth", C.c_double),
+        ("seed_base", C.c_uint64), ("seed_base_given", C.c_int32), ("reserved0", C.c_int32), ("reserved1", C.c_int64 * 2),
+    ]
+
+
 class mpk_replan_state(C.Structure):
     _fields_ = [
         ("traj_steps", C.c_void_p), ("plan_steps", C.c_void_p), ("done", C.c_void_p), ("seg_len", C.c_void_p),
@@ -131,6 +142,8 @@ SIGNATURES = {
                                       _vp, _i32, _i32, _vp]),
     "mpk_hole_reacher_rollout": (C.c_int, [_vp, C.POINTER(mpk_rollout_cfg), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(mpk_hole_task),
                                            _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, C.POINTER(mpk_replan_state), _i32, _i32, _vp]),
+    "mpk_reacher_reset": (C.c_int, [_vp, C.POINTER(mpk_reacher_reset_task), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _i32, _vp]),
     "mpk_replan_advance": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mpk_traj_validity": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
     "mpk_traj_validity_penalty": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
@@ -156,9 +169,9 @@ _lib: Optional[C.CDLL] = None
 # the files libmpk.so is built from, in the order mpk_source_hash() is defined over (include/mpk.h)
 _ROOT = os.path.dirname(_HERE)
 KERNEL_UNITS = ("mpk_traj_family.hip", "mpk_traj_ring.hip", "mpk_episode.hip", "mpk_traj_launch.hip", "mpk_traj_wide.hip", "mpk_traj_phase.hip",
-                "mpk_phase_fused.hip", "mpk_rollout.hip", "mpk_hole.hip", "mpk_misc.hip")          # translation units of the device code (mpk_traj_family.hip: once per MP type)
+                "mpk_phase_fused.hip", "mpk_rollout.hip", "mpk_hole.hip", "mpk_reset.hip", "mpk_misc.hip")          # translation units of the device code (mpk_traj_family.hip: once per MP type)
 KERNEL_HEADERS = ("mpk_dev.h", "mpk_tile.h", "mpk_traj_tiles.h", "mpk_traj_stream.h", "mpk_traj_flat.h", "mpk_traj_ring.h", "mpk_traj_quad.h",
-                  "mpk_traj_pipe.h", "mpk_reward.h", "mpk_phase.h", "mpk_trace_reader.h")
+                  "mpk_traj_pipe.h", "mpk_reward.h", "mpk_phase.h", "mpk_trace_reader.h", "mpk_nprng.h")
 SOURCE_FILES = (os.path.join(_ROOT, "include", "mpk.h"), os.path.join(_HERE, "csrc", "mpk_internal.h"),
                 os.path.join(_HERE, "csrc", "mpk_host.cpp")) + \
     tuple(os.path.join(_HERE, "csrc", f) for f in KERNEL_HEADERS + KERNEL_UNITS)

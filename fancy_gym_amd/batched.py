@@ -32,7 +32,8 @@ class BatchedBlackBox:
                  max_episode_steps: Optional[int] = None, pos_limits: Optional[Sequence] = None,
                  check_tau_delay: bool = False, reward: Optional[str] = None, steps_before_reward: int = 199,
                  device=None, learn_sub_trajectories: bool = False, reward_aggregation="sum", verbose: int = 2,
-                 collision_penalty: float = 100.0, allow_self_collision: bool = False, allow_wall_collision: bool = False):
+                 collision_penalty: float = 100.0, allow_self_collision: bool = False, allow_wall_collision: bool = False,
+                 env_kwargs: Optional[dict] = None):
         """
         trajectory_generator / tracking_controller: the objects the factories return (``get_trajectory_generator``,
         ``get_controller``).  ``replanning_every = n`` is the schedule ``lambda pos, vel, obs, action, t: t % n == 0``
@@ -49,6 +50,11 @@ class BatchedBlackBox:
         ``trajectory_length`` is the executed steps and ``rewards`` aggregates only those.  Holes [B, 3] = (x, width, depth) are given
         to ``reset`` (``sample_hole_reacher_starts`` draws starts and holes as the reference does).  ``step`` also returns
         ``is_collided`` / ``is_success``.  Collided episodes are done, so the live ones keep lockstep under replanning.
+
+        ``reset(seed=...)`` draws the episodes on the device the way the registered env's ``reset(seed=...)`` does (one launch,
+        mpk_reacher_reset): ``env_kwargs`` holds the env's reset constants -- SimpleReacher ``random_start``, ``target``; HoleReacher
+        ``random_start``, ``hole_width``, ``hole_x``, ``hole_depth`` (None = drawn) -- and defaults to the registered ids' kwargs
+        (fancy/(Long)SimpleReacher-v0: random start, goal drawn; fancy/HoleReacher-v0: random start, width and x drawn, depth 1).
 
         ``learn_sub_trajectories`` (black_box_wrapper.py:98-102, utils/make_env_helpers.py:89-117): every ``step`` plans a new
         sub-trajectory of ``round(tau / dt)`` steps from the current state -- tau is the first parameter (``learn_tau``), read
@@ -110,6 +116,18 @@ class BatchedBlackBox:
                               allow_wall_collision=bool(allow_wall_collision))
         self.hole = None
         self.reward = reward
+        defaults = {"simple_reacher": dict(random_start=True, target=None),
+                    "hole_reacher": dict(random_start=True, hole_width=None, hole_x=None, hole_depth=1.0)}.get(reward)
+        if env_kwargs is not None:
+            if defaults is None:
+                raise ValueError("env_kwargs are the reset constants of a reacher reward (reward='simple_reacher' / 'hole_reacher')")
+            unknown = set(env_kwargs) - set(defaults)
+            if unknown:
+                raise ValueError(f"env_kwargs of {reward!r} take {sorted(defaults)}, got {sorted(unknown)}")
+            defaults = {**defaults, **env_kwargs}
+        self.env_kwargs = defaults
+        self._rng = None                    # int64 [B, 5]: every episode's numpy generator (mpk_nprng_state), after a seeded reset
+        self._task_buf = None               # the goal / hole buffer the device resets write
         self.steps_before_reward = int(steps_before_reward)
         self.goal = None
         ctype = getattr(tracking_controller, "device_type", None)
@@ -162,16 +180,53 @@ class BatchedBlackBox:
         cfg = self.engine.config
         return self.engine.mp_type == "prodmp" and bool(cfg.learn_tau or cfg.learn_delay or self._lockstep is None)
 
-    def reset(self, init_pos=None, init_vel=None, goal=None, hole=None):
+    def _seed_args(self, seed, sample: bool, explicit: bool) -> dict:
+        """the seeding of a device-drawn reset: dict(seed_base=...) / dict(seeds=...) / {} (continue), validated"""
+        if explicit:
+            raise ValueError("reset(seed=...) / reset(sample=True) draw init_pos / goal / hole on the device: do not pass them")
+        if self.reward not in ("simple_reacher", "hole_reacher"):
+            raise ValueError("reset(seed=...) / reset(sample=True) draw a reacher's episodes: they need reward='simple_reacher' or "
+                             "'hole_reacher'")
+        if sample:
+            if seed is not None:
+                raise ValueError("reset: seed=... reseeds, sample=True continues the streams -- not both")
+            if self._rng is None:
+                raise ValueError("reset(sample=True) continues the streams of a seeded reset: call reset(seed=...) first")
+            return {}
+        if isinstance(seed, (bool, np.bool_)):
+            raise ValueError(f"seed must be an int or a sequence of {self.B} ints, got {seed!r}")
+        if isinstance(seed, (int, np.integer)):
+            seed = int(seed)
+            if seed < 0 or seed + self.B - 1 >= 2 ** 64:
+                raise ValueError(f"seeds seed + b must lie in [0, 2^64), got seed={seed} for {self.B} episodes")
+            return dict(seed_base=seed)
+        seeds = [int(s) for s in seed]
+        if len(seeds) != self.B:
+            raise ValueError(f"reset(seed=...) takes an int or {self.B} seeds, got {len(seeds)}")
+        if any(s < 0 or s >= 2 ** 64 for s in seeds):
+            raise ValueError("seeds must lie in [0, 2^64)")
+        host = torch.from_numpy(np.array(seeds, dtype=np.uint64).view(np.int64))
+        return dict(seeds=host.to(self.device, non_blocking=False))
+
+    def reset(self, init_pos=None, init_vel=None, goal=None, hole=None, *, seed=None, sample: bool = False):
         """start B new episodes from plant state (init_pos, init_vel) [B, D] (default zeros); goal [B, 2] for the
-        simple_reacher reward, hole [B, 3] = (x, width, depth) for the hole_reacher reward"""
+        simple_reacher reward, hole [B, 3] = (x, width, depth) for the hole_reacher reward.
+
+        With a reacher reward the episodes can be drawn on the device instead (one launch, mpk_reacher_reset): ``seed`` = an int
+        starts episode b as ``env.reset(seed=seed + b)`` starts the registered env (gymnasium's vector-env rule), a sequence of B
+        ints seeds each episode; ``sample=True`` continues every episode's stream as ``env.reset()`` would.  The start pose, goal /
+        hole and generators stay on the device (``goal`` / ``hole`` attributes, ``rng_state()``)."""
+        drawn = seed is not None or bool(sample)
+        seeding = self._seed_args(seed, bool(sample), any(x is not None for x in (init_pos, init_vel, goal, hole))) if drawn else None
         if self._plans_since_reset and self._range_can_overflow() and not torch.cuda.is_current_stream_capturing():
             self.check_range()
         elif self._plans_since_reset:
             # the episodes just finished: whoever read their results has synchronised; a ring kernel that gave up waiting in their LAST
             # plan would otherwise be reported by the next launch only (costs nothing: the fault word lives in host memory)
             self.engine.poll_fault()
-        if self.reward == "hole_reacher":
+        if drawn:
+            self._device_draw(seeding)
+        elif self.reward == "hole_reacher":
             if hole is None:
                 raise ValueError("reward='hole_reacher' needs hole [B, 3] at reset")
             self.hole = torch.as_tensor(hole, dtype=torch.float64, device=self.device).expand(self.B, 3).contiguous()
@@ -188,8 +243,9 @@ class BatchedBlackBox:
         if self._start32 is None:
             self._start32 = tuple(torch.empty((self.B, self.D), dtype=torch.float32, device=self.device)
                                   for _ in range(2))
-        self.engine.episode_reset(self.q, self.qd, self.traj_steps, self.plan_steps, self.done, state(init_pos),
-                                  state(init_vel), cond=self._start32)
+        if not drawn:
+            self.engine.episode_reset(self.q, self.qd, self.traj_steps, self.plan_steps, self.done, state(init_pos),
+                                      state(init_vel), cond=self._start32)
         self.condition_pos = self.condition_vel = None
         self._frozen_phase = None
         self._lockstep = None if (self.device_time and self.do_replanning) else 0
@@ -199,6 +255,30 @@ class BatchedBlackBox:
         self._prev_done_known = True
         self.traj_gen.reset()
         return self.q, self.qd
+
+    def _device_draw(self, seeding: dict):
+        """the one launch of a device-drawn reset (mpk_reacher_reset): state, start pose and its fp32 image, goal / hole, generators"""
+        if self._start32 is None:
+            self._start32 = tuple(torch.empty((self.B, self.D), dtype=torch.float32, device=self.device)
+                                  for _ in range(2))
+        if self._rng is None:
+            self._rng = torch.zeros((self.B, 5), dtype=torch.int64, device=self.device)
+        if self._task_buf is None:
+            self._task_buf = torch.empty((self.B, 2 if self.reward == "simple_reacher" else 3), dtype=torch.float64,
+                                         device=self.device)
+        self.engine.reacher_reset(self.reward, self.q, self.qd, self.traj_steps, self.plan_steps, self.done, self._rng,
+                                  self._task_buf, cond=self._start32, **seeding, **self.env_kwargs)
+        if self.reward == "hole_reacher":
+            self.hole = self._task_buf
+        else:
+            self.goal = self._task_buf
+
+    def rng_state(self, episodes=None) -> list:
+        """numpy's ``bit_generator.state`` of the chosen episodes' generators after the last device-drawn reset (synchronises)"""
+        if self._rng is None:
+            raise ValueError("no device-drawn reset yet: call reset(seed=...)")
+        from .engine import nprng_state
+        return nprng_state(self._rng, episodes)
 
     @property
     def current_pos(self) -> torch.Tensor:
@@ -501,7 +581,7 @@ class BatchedBlackBox:
         return self.engine.reward_aggregate(rew, seg, self.reward_aggregation)
 
     # ---- whole episodes as one hipGraph ----------------------------------------------------------------------------------
-    def capture_episode(self, n_plans: int, with_goal: bool = False) -> "EpisodeGraph":
+    def capture_episode(self, n_plans: int, with_goal: bool = False, sample: bool = False) -> "EpisodeGraph":
         """
         Capture ``reset`` + ``n_plans`` calls of ``step`` into one hipGraph.  At B of a few thousand a plan costs ~100 us of
         Python / ctypes / allocator work around ~20 us of kernels; a replay pays one graph launch for the whole
@@ -512,17 +592,23 @@ class BatchedBlackBox:
         Write the inputs into the returned object's static buffers (``init_pos``, ``init_vel``, ``params[k]``, ``goal``),
         call ``replay()``, read ``outs[k]`` (the dicts ``step`` returned during capture; their tensors are rewritten by
         every replay).
+
+        ``sample=True`` (a reacher reward, after a seeded ``reset``): the captured reset is ``reset(sample=True)``, so every replay
+        draws a new generation of episodes from the streams -- replay k draws what the k-th eager ``reset(sample=True)`` would have
+        (the eager warm-up pass restores the generators it advanced).  ``init_pos`` / ``goal`` / ``hole`` are then not inputs.
         """
+        if sample:
+            self._seed_args(None, True, False)
         if self.spec is None:
             raise ValueError("capture_episode needs a device plant (host environments cannot be captured)")
         if self.pos_limits is not None and not (self.plant == "double_integrator" and self.reward is None
                                                 and not self.learn_sub_trajectories):
             self.device_time = True         # (the fused, gated step keeps the host's lockstep mirror: nothing to read back)
-        return EpisodeGraph(self, int(n_plans), with_goal)
+        return EpisodeGraph(self, int(n_plans), with_goal, sample)
 
 
 class EpisodeGraph:
-    def __init__(self, bb: BatchedBlackBox, n_plans: int, with_goal: bool):
+    def __init__(self, bb: BatchedBlackBox, n_plans: int, with_goal: bool, sample: bool = False):
         self.bb = bb
         dev = bb.device
         self.init_pos = torch.zeros((bb.B, bb.D), dtype=torch.float64, device=dev)
@@ -533,20 +619,31 @@ class EpisodeGraph:
                        for _ in range(n_plans)]
         self.outs = []
 
+        if sample:
+            self.init_pos = self.init_vel = self.goal = self.hole = None
+
         def episode():
+            if sample:
+                bb.reset(sample=True)
+                return [bb.step(p) for p in self.params]
             kw = {"goal": self.goal} if self.goal is not None else {}
             if self.hole is not None:
                 kw["hole"] = self.hole
             bb.reset(self.init_pos, self.init_vel, **kw)
             return [bb.step(p) for p in self.params]
 
-        # one eager pass on a side stream first (allocator warm-up, lazy initialisation), then the capture
+        # one eager pass on a side stream first (allocator warm-up, lazy initialisation), then the capture; the warm-up's draws are
+        # undone, so that the first replay continues the streams where the eager resets left them
+        snapshot = bb._rng.clone() if sample else None
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             episode()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
+        if sample:
+            bb._rng.copy_(snapshot)
+            torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.outs = episode()

@@ -883,7 +883,7 @@ static int pending_ring_fault(Handle* h) {
     if (!(f & 2)) { if (f) __atomic_fetch_or(h->h_fault, f & ~2, __ATOMIC_RELAXED); return MPK_OK; }
     char msg[512];      // (256 until round 6: the text is ~310 characters, and what got cut was "outputs ... are incomplete")
     std::snprintf(msg, sizeof msg, "k_traj_ring: a wave of an earlier launch on this handle gave up waiting for its partner (role mask 0x%x: "
-                  "1 producer / buffer, 2 ticket, 4 store engine / batch, 8 action writer, 16 consumer / tile, 32 consumer / writer, 64 reward helper, 128 k_phase_fused pipeline, 256 rollout pipeline): "
+                  "1 producer / buffer, 2 ticket, 4 store engine / batch, 8 action writer, 16 consumer / tile, 32 consumer / writer, 64 reward helper, 128 k_phase_fused pipeline, 256 rollout pipeline, 512 k_reacher_reset goal draw at its rejection cap): "
                   "outputs (closed loop: plant and replanning state too) of that launch are incomplete", (unsigned)f >> 8);
     set_error(msg);
     return MPK_EHIP;
@@ -1314,6 +1314,40 @@ int mpk_episode_reset(mpk_handle hh, const double* init_q, const double* init_qd
     MPK_ON_DEVICE(h->cfg.device);
     return launch_episode_reset(init_q, init_qd, q, qd, cond_pos, cond_vel, traj_steps, plan_steps, done, B, h->dev.D,
                                 stream);
+}
+
+int mpk_reacher_reset(mpk_handle hh, const mpk_reacher_reset_task* task, const uint64_t* seeds, mpk_nprng_state* rng, double* q,
+                      double* qd, float* cond_pos, float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done,
+                      double* task_out, int32_t B, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!task) { set_error("task is NULL"); return MPK_EINVAL; }
+    if (B < 0) { set_error("B must be >= 0"); return MPK_EINVAL; }
+    if (task->env != MPK_RESET_SIMPLE_REACHER && task->env != MPK_RESET_HOLE_REACHER) { set_error("unknown reset env"); return MPK_EINVAL; }
+    if (task->env == MPK_RESET_SIMPLE_REACHER && std::isnan(task->target[0]) != std::isnan(task->target[1])) {
+        set_error("target: both coordinates given, or both NaN (drawn)");
+        return MPK_EINVAL;
+    }
+    if (task->env == MPK_RESET_HOLE_REACHER && std::isnan(task->hole_x) && !std::isnan(task->hole_width) && !(3.5 - task->hole_width / 2.0 >= 0.0)) {
+        set_error("hole_width: x ~ U(width / 2, 3.5) needs width <= 7 (numpy: high - low < 0)");
+        return MPK_EINVAL;
+    }
+    if (seeds && task->seed_base_given) { set_error("seeds and seed_base_given exclude each other"); return MPK_EINVAL; }
+    if (task->seed_base_given && B > 0 && task->seed_base + (uint64_t)(B - 1) < task->seed_base) {
+        set_error("seed_base + B - 1 must be < 2^64");
+        return MPK_EINVAL;
+    }
+    if (B == 0) return MPK_OK;
+    if (!rng || !q || !qd || !traj_steps || !plan_steps || !done || !task_out) { set_error("NULL buffer"); return MPK_EINVAL; }
+    if ((cond_pos == nullptr) != (cond_vel == nullptr)) { set_error("cond_pos and cond_vel go together"); return MPK_EINVAL; }
+    ResetLaunch l;
+    l.seeds = seeds; l.seed_base = task->seed_base; l.seeded_base = task->seed_base_given != 0; l.rng = rng;
+    l.q = q; l.qd = qd; l.cond_pos = cond_pos; l.cond_vel = cond_vel; l.traj_steps = traj_steps; l.plan_steps = plan_steps; l.done = done;
+    l.task_out = task_out; l.target[0] = task->target[0]; l.target[1] = task->target[1];
+    l.hole_width = task->hole_width; l.hole_x = task->hole_x; l.hole_depth = task->hole_depth;
+    l.env = task->env; l.random_start = task->random_start != 0;
+    MPK_ON_DEVICE(h->cfg.device);
+    return launch_reacher_reset(l, B, h->dev.D, stream, h->d_fault);
 }
 
 int mpk_replan_advance(mpk_handle hh, int32_t* traj_steps, int32_t* plan_steps, int32_t* seg_len, uint8_t* done,

@@ -187,6 +187,25 @@ int launch_hole_rollout(const HoleLaunch& h, int B, int T, int D, void* stream, 
 int launch_episode_reset(const double* init_q, const double* init_qd, double* q, double* qd, float* cond_pos,
                          float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done, int B, int D,
                          void* stream);
+// mpk_reacher_reset (mpk_reset.hip): seeded / continued reacher resets on numpy's generator
+struct ResetLaunch {
+    const uint64_t* seeds = nullptr;
+    uint64_t seed_base = 0;
+    int seeded_base = 0;
+    void* rng = nullptr;
+    double* q = nullptr;
+    double* qd = nullptr;
+    float* cond_pos = nullptr;
+    float* cond_vel = nullptr;
+    int32_t* traj_steps = nullptr;
+    int32_t* plan_steps = nullptr;
+    uint8_t* done = nullptr;
+    double* task_out = nullptr;
+    double target[2] = {0.0, 0.0};
+    double hole_width = 0.0, hole_x = 0.0, hole_depth = 0.0;
+    int env = 0, random_start = 0;
+};
+int launch_reacher_reset(const ResetLaunch& l, int B, int D, void* stream, int* fault);
 int launch_gate_flags(const uint8_t* valid, const uint8_t* was_done, const uint8_t* done, uint8_t* terminated, uint8_t* truncated, int B,
                       void* stream);
 int launch_replan_advance(int32_t* traj_steps, int32_t* plan_steps, int32_t* seg_len, uint8_t* done, int every,

@@ -14,6 +14,7 @@
 //   mpk_phase_fused.hip  per-episode phase: the fused entry points (actions, closed loop, replanning step, verbose < 2 step, validity gate)
 //   mpk_rollout.hip      rollout kernels
 //   mpk_hole.hip         HoleReacher: direct-velocity plant, collisions, reward, break on collision
+//   mpk_reset.hip        reacher resets: numpy's generator per episode (mpk_nprng.h), seeded / continued draws
 //   mpk_misc.hip         integer state, reset, gather, validity, self-tests, trace readout
 #define MPK_AMALGAMATED 1
 #include "mpk_traj_family.hip"
@@ -25,4 +26,5 @@
 #include "mpk_phase_fused.hip"
 #include "mpk_rollout.hip"
 #include "mpk_hole.hip"
+#include "mpk_reset.hip"
 #include "mpk_misc.hip"

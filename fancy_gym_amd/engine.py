@@ -30,6 +30,19 @@ def _dvec(x, n: int):
     return a.ctypes.data_as(C.POINTER(C.c_double)), a
 
 
+def nprng_state(rng: torch.Tensor, episodes=None) -> list:
+    """numpy's ``bit_generator.state`` dicts of the chosen episodes of a reacher reset's generator (int64 [B, 5], mpk_nprng_state):
+    ``np.random.default_rng(); rng.bit_generator.state = d`` continues that episode's stream on the host.  Synchronises."""
+    words = rng.detach().cpu().numpy().view(np.uint64)
+    idx = range(words.shape[0]) if episodes is None else np.atleast_1d(np.asarray(episodes)).tolist()
+    out = []
+    for b in idx:
+        w = [int(v) for v in words[b]]
+        out.append({"bit_generator": "PCG64", "state": {"state": (w[0] << 64) | w[1], "inc": (w[2] << 64) | w[3]},
+                    "has_uint32": w[4] & 0xFFFFFFFF, "uinteger": w[4] >> 32})
+    return out
+
+
 class RolloutSpec:
     """Controller + plant description for the device rollout (mpk_rollout_cfg)."""
 
@@ -608,6 +621,38 @@ class TrajectoryEngine:
             succ.data_ptr(), C.byref(st) if st is not None else None, B, T, self._stream()))
         return dict(actions=act, rewards=rew, ret=ret, n_exec=n_exec, collided=coll, success=succ, done=done_out, cond_pos=cp,
                     cond_vel=cv)
+
+    def reacher_reset(self, env: str, q: torch.Tensor, qd: torch.Tensor, traj_steps: torch.Tensor, plan_steps: torch.Tensor,
+                      done: torch.Tensor, rng: torch.Tensor, task_out: torch.Tensor, *, seeds=None, seed_base: Optional[int] = None,
+                      random_start: bool = True, target=None, hole_width=None, hole_x=None, hole_depth=None,
+                      cond: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """
+        The seeded resets of SimpleReacher (``env`` "simple_reacher") / HoleReacher ("hole_reacher") for B device-resident episodes in
+        one launch (mpk.h: mpk_reacher_reset): what ``episode_reset`` writes, plus the goal [B, 2] / hole [B, 3] into ``task_out`` and
+        each episode's numpy generator into ``rng`` (int64 [B, 5], the words of mpk_nprng_state; ``nprng_state`` reads it).
+        ``seed_base`` seeds episode b with seed_base + b, ``seeds`` (uint64 [B] on the device, as int64) one seed per episode; neither
+        continues every episode's stream.  The kwargs are the env's: None = drawn.  Everything in place; allocates nothing.
+        """
+        B, D = q.shape
+        for t, dt_ in ((q, torch.float64), (qd, torch.float64), (traj_steps, torch.int32), (plan_steps, torch.int32),
+                       (done, torch.uint8), (rng, torch.int64), (task_out, torch.float64)):
+            assert t.dtype == dt_ and t.is_contiguous() and t.shape[0] == B
+        assert tuple(rng.shape) == (B, 5) and tuple(task_out.shape) == (B, 2 if env == "simple_reacher" else 3)
+        if seeds is not None:
+            assert seeds.dtype == torch.int64 and seeds.is_contiguous() and tuple(seeds.shape) == (B,)
+        nan = float("nan")
+        opt = lambda v: nan if v is None else float(v)        # noqa: E731
+        t = _lib.mpk_reacher_reset_task()
+        t.env = _lib.RESET_ENVS[env]
+        t.random_start = int(bool(random_start))
+        t.target[0], t.target[1] = (nan, nan) if target is None else (float(target[0]), float(target[1]))
+        t.hole_width, t.hole_x, t.hole_depth = opt(hole_width), opt(hole_x), opt(hole_depth)
+        t.seed_base_given = int(seed_base is not None)
+        t.seed_base = int(seed_base) if seed_base is not None else 0
+        cp, cv = cond if cond is not None else (None, None)
+        _lib.check(self._lib.mpk_reacher_reset(self._h, C.byref(t), _dptr(seeds), rng.data_ptr(), q.data_ptr(), qd.data_ptr(),
+                                               _dptr(cp), _dptr(cv), traj_steps.data_ptr(), plan_steps.data_ptr(), done.data_ptr(),
+                                               task_out.data_ptr(), B, self._stream()))
 
     def condition_gather(self, pos: torch.Tensor, vel: torch.Tensor, seg_len: torch.Tensor,
                          out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):

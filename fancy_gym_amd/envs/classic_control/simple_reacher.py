@@ -31,6 +31,20 @@ def end_effector(joint_angles: np.ndarray) -> np.ndarray:
                     axis=-1)
 
 
+def sample_simple_reacher_starts(seeds, n_links: int = 2, random_start: bool = True, target=None):
+    """(init_pos [B, n_links], goal [B, 2]) for BatchedBlackBox.reset: episode b is what SimpleReacherEnv.reset(seed=seeds[b]) starts
+    from (the defaults are fancy/SimpleReacher-v0's).  Seeded resets only: the reference reseeds twice (simple_reacher.py:46-54), so
+    its seeded stream gives the first-joint angle, then the goal -- this env and the reference agree there.
+    ``BatchedBlackBox.reset(seed=...)`` draws the same on the device."""
+    pos, goals = [], []
+    for s in seeds:
+        env = SimpleReacherEnv(n_links, target=target, random_start=random_start)
+        env.reset(seed=int(s))
+        pos.append(env.q)
+        goals.append(env.goal)
+    return np.stack(pos), np.stack(goals)
+
+
 class SimpleReacherEnv(_gym.Env):
     dt = 0.01
 

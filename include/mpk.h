@@ -573,6 +573,60 @@ int mpk_episode_reset(mpk_handle h, const double* init_q, const double* init_qd,
                       int32_t B, void* stream);
 
 /*
+ * Seeded resets of the reference's reacher envs for B device-resident episodes, one launch (ABI 4, appended): episode b starts
+ * the way env.reset(seed=seeds[b]) starts the registered env (gymnasium seeds env.np_random with np.random.default_rng(seed)),
+ * and keeps its own numpy-identical generator in rng[b], so a later launch without seeds continues every stream the way
+ * env.reset() does.  The launch writes what mpk_episode_reset writes -- traj_steps, plan_steps, done = 0; q = the start pose,
+ * qd = 0; (cond_pos, cond_vel) = their fp32 image if given (both or neither) -- plus the goal / hole and the advanced generator.
+ * It allocates nothing and synchronises nothing (it can be captured in a graph).
+ *
+ * The generator, per episode (mpk_nprng_state, 40 bytes; what rng.bit_generator.state shows): numpy's PCG64 -- the 128-bit LCG
+ * state = state * 0x2360ED051FC65DA44385DF649FCCF645 + inc with XSL-RR output, stepped before output -- and the 32-bit buffer
+ * of next_uint32 (has_uint32, uinteger: the high half of a 64-bit draw kept for the next 32-bit draw).  Seeding is
+ * SeedSequence(seed) (pool size 4; one 32-bit entropy word for seeds < 2^32, two otherwise) -> generate_state(4, uint64) -> PCG64's
+ * srandom (state = 0, inc = initseq << 1 | 1, step, state += initstate, step), has_uint32 = uinteger = 0.  Draws:
+ * next_double = (next_uint64 >> 11) * 2^-53; uniform(lo, hi) = lo + (hi - lo) * next_double (each operation rounded);
+ * choice([-1, 1]) = Lemire's bounded draw on next_uint32 (numpy's integers(0, 2)).
+ *
+ * The draw programs, with "[reseed]" only when the launch seeds:
+ *   MPK_RESET_HOLE_REACHER   (hole_reacher.py:60-71,79-101; base_reacher.py:73-93)
+ *       [reseed]; width ~ U(0.15, 0.5) unless hole_width is given; unless hole_x is given: direction = choice([-1, 1]), then
+ *       x = direction * U(width / 2, 3.5); depth ~ U(1, 1) unless hole_depth is given (the draw is consumed); the first joint
+ *       ~ U(pi/4, 3pi/4) if random_start, else pi/2; other joints 0.  task_out [B, 3] = (x, width, depth) -- the hole of
+ *       mpk_hole_reacher_rollout.
+ *   MPK_RESET_SIMPLE_REACHER (simple_reacher.py:46-54,85-96; base_reacher.py:73-93)
+ *       a goal from the current stream, discarded (skipped when seeding: the reseed erases it); [reseed]; the first joint if
+ *       random_start; the goal; [reseed]; the first joint again if random_start (else 0: SimpleReacher's _start_pos); other joints
+ *       0.  A goal is U(-L, L, size=2) until sqrt(x*x + y*y) < L, L = num_dof, unless target is given.  task_out [B, 2] = goal.
+ *       The rejection loop takes 1.27 rounds on average; at 4 096 rounds the goal is NaN and the launch raises the handle's fault
+ *       word (role 512), reported as the ring kernels' faults are (mpk_check_range, mpk_poll_fault).
+ *   seeds  dev uint64 [B] or NULL: NULL and task->seed_base_given: episode b is seeded with seed_base + b (gymnasium's vector-env
+ *          rule; the caller keeps seed_base + B - 1 < 2^64); NULL otherwise: every episode continues its stream in rng.
+ *   rng    dev mpk_nprng_state [B], read (when continuing) and written.
+ * q, qd dev double [B, D] (D = the handle's num_dof = the env's n_links); traj_steps, plan_steps dev int32 [B], done dev uint8 [B].
+ */
+#define MPK_RESET_SIMPLE_REACHER 0
+#define MPK_RESET_HOLE_REACHER   1
+typedef struct mpk_nprng_state {
+    uint64_t state_hi, state_lo;     /* PCG64 state */
+    uint64_t inc_hi, inc_lo;         /* PCG64 increment (odd) */
+    uint32_t has_uint32, uinteger;   /* the buffered high half of the last 64-bit draw behind a 32-bit draw */
+} mpk_nprng_state;
+typedef struct mpk_reacher_reset_task {
+    int32_t  env;                    /* MPK_RESET_* */
+    int32_t  random_start;           /* base_reacher.py:80-86 (both registered ids: 1) */
+    double   target[2];              /* SimpleReacher's fixed goal; NaN = drawn (the registered ids) */
+    double   hole_width, hole_x, hole_depth;   /* HoleReacher's fixed hole; NaN = drawn (fancy/HoleReacher-v0: NaN, NaN, 1) */
+    uint64_t seed_base;              /* seeds == NULL and seed_base_given: episode b is seeded with seed_base + b */
+    int32_t  seed_base_given;
+    int32_t  reserved0;
+    int64_t  reserved1[2];
+} mpk_reacher_reset_task;
+int mpk_reacher_reset(mpk_handle h, const mpk_reacher_reset_task* task, const uint64_t* seeds, mpk_nprng_state* rng, double* q,
+                      double* qd, float* cond_pos, float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done,
+                      double* task_out, int32_t B, void* stream);
+
+/*
  * Integer replanning bookkeeping of BlackBoxWrapper.step for the schedule `t % every == 0`
  * (envs/mujoco/box_pushing/mp_wrapper.py:89; black_box_wrapper.py:174,197,206):
  *   plan_steps[b] += 1
