@@ -91,6 +91,12 @@ class mpk_reacher_reset_task(C.Structure):
     ]
 
 
+class mpk_obs_cfg(C.Structure):
+    _fields_ = [
+        ("env", C.c_int32), ("n_links", C.c_int32), ("col_mask", C.c_uint64), ("time_div", C.c_double), ("reserved", C.c_int64 * 2),
+    ]
+
+
 class mpk_replan_state(C.Structure):
     _fields_ = [
         ("traj_steps", C.c_void_p), ("plan_steps", C.c_void_p), ("done", C.c_void_p), ("seg_len", C.c_void_p),
@@ -144,6 +150,9 @@ SIGNATURES = {
                                            _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, C.POINTER(mpk_replan_state), _i32, _i32, _vp]),
     "mpk_reacher_reset": (C.c_int, [_vp, C.POINTER(mpk_reacher_reset_task), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _i32, _vp]),
+    "mpk_reacher_observation": (C.c_int, [_vp, C.POINTER(mpk_obs_cfg), _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "mpk_reacher_step_observations": (C.c_int, [_vp, C.POINTER(mpk_obs_cfg), C.POINTER(mpk_rollout_cfg), _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "mpk_replan_advance": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "mpk_traj_validity": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
     "mpk_traj_validity_penalty": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
@@ -169,9 +178,9 @@ _lib: Optional[C.CDLL] = None
 # the files libmpk.so is built from, in the order mpk_source_hash() is defined over (include/mpk.h)
 _ROOT = os.path.dirname(_HERE)
 KERNEL_UNITS = ("mpk_traj_family.hip", "mpk_traj_ring.hip", "mpk_episode.hip", "mpk_traj_launch.hip", "mpk_traj_wide.hip", "mpk_traj_phase.hip",
-                "mpk_phase_fused.hip", "mpk_rollout.hip", "mpk_hole.hip", "mpk_reset.hip", "mpk_misc.hip")          # translation units of the device code (mpk_traj_family.hip: once per MP type)
+                "mpk_phase_fused.hip", "mpk_rollout.hip", "mpk_hole.hip", "mpk_reset.hip", "mpk_obs.hip", "mpk_misc.hip")          # translation units of the device code (mpk_traj_family.hip: once per MP type)
 KERNEL_HEADERS = ("mpk_dev.h", "mpk_tile.h", "mpk_traj_tiles.h", "mpk_traj_stream.h", "mpk_traj_flat.h", "mpk_traj_ring.h", "mpk_traj_quad.h",
-                  "mpk_traj_pipe.h", "mpk_reward.h", "mpk_phase.h", "mpk_trace_reader.h", "mpk_nprng.h")
+                  "mpk_traj_pipe.h", "mpk_reward.h", "mpk_phase.h", "mpk_trace_reader.h", "mpk_nprng.h", "mpk_plant.h")
 SOURCE_FILES = (os.path.join(_ROOT, "include", "mpk.h"), os.path.join(_HERE, "csrc", "mpk_internal.h"),
                 os.path.join(_HERE, "csrc", "mpk_host.cpp")) + \
     tuple(os.path.join(_HERE, "csrc", f) for f in KERNEL_HEADERS + KERNEL_UNITS)

@@ -23,6 +23,30 @@ from .engine import RolloutSpec, TrajectoryEngine
 from .mp.traj import MPInterface
 
 
+def reacher_observation_layout(reward: str, n_links: int, random_start: bool = True, hole_width=None, context: bool = True,
+                               time_aware: bool = False):
+    """
+    The observation a BlackBoxWrapper over a reacher env hands out, as (col_mask, space): ``col_mask`` bit c = column c of the env's
+    full _get_obs() row is part of it (mpk.h: mpk_obs_cfg), ``space`` the wrapper's observation_space.  Full row and bounds as the
+    envs build them (base_reacher.py:40-48, simple_reacher.py:32-39; HoleReacher adds the hole width before the goal offset);
+    ``context`` masks it with the MP wrapper's context_mask (simple_reacher/mp_wrapper.py, hole_reacher/mp_wrapper.py;
+    black_box_wrapper.py:141-148), ``time_aware`` appends TimeAwareObservation's [0, 1] column (utils/wrappers.py:33-38).
+    """
+    from . import _gym
+    n = int(n_links)
+    hole = reward == "hole_reacher"
+    if reward not in ("simple_reacher", "hole_reacher"):
+        raise ValueError(f"no env observation for reward {reward!r}")
+    bound = np.hstack([[np.pi] * n, [np.pi] * n, [np.inf] * n] + ([[np.inf]] if hole else []) + [[np.inf] * 2, [np.inf]])
+    mask = np.hstack([[bool(random_start)] * (3 * n)] + ([[hole_width is None]] if hole else []) + [[True, True], [False]])
+    keep = mask.astype(bool) if context else np.ones(bound.shape, bool)
+    col_mask = sum(1 << int(c) for c in np.flatnonzero(keep))
+    low, high = -bound[keep], bound[keep]
+    if time_aware:
+        low, high = np.append(low, 0.0), np.append(high, 1.0)
+    return col_mask, _gym.spaces.Box(low=low, high=high, dtype=np.float32)
+
+
 class BatchedBlackBox:
 
     def __init__(self, trajectory_generator: MPInterface, tracking_controller: BaseController, num_envs: int,
@@ -33,7 +57,7 @@ class BatchedBlackBox:
                  check_tau_delay: bool = False, reward: Optional[str] = None, steps_before_reward: int = 199,
                  device=None, learn_sub_trajectories: bool = False, reward_aggregation="sum", verbose: int = 2,
                  collision_penalty: float = 100.0, allow_self_collision: bool = False, allow_wall_collision: bool = False,
-                 env_kwargs: Optional[dict] = None):
+                 env_kwargs: Optional[dict] = None, observations: bool = False):
         """
         trajectory_generator / tracking_controller: the objects the factories return (``get_trajectory_generator``,
         ``get_controller``).  ``replanning_every = n`` is the schedule ``lambda pos, vel, obs, action, t: t % n == 0``
@@ -55,6 +79,13 @@ class BatchedBlackBox:
         mpk_reacher_reset): ``env_kwargs`` holds the env's reset constants -- SimpleReacher ``random_start``, ``target``; HoleReacher
         ``random_start``, ``hole_width``, ``hole_x``, ``hole_depth`` (None = drawn) -- and defaults to the registered ids' kwargs
         (fancy/(Long)SimpleReacher-v0: random start, goal drawn; fancy/HoleReacher-v0: random start, width and x drawn, depth 1).
+
+        ``observations=True`` (a reacher reward, no ``pos_limits``) returns what BlackBoxWrapper returns as its observation, computed on
+        the device (mpk_reacher_observation): ``observe()`` gives the current one [B, n_obs] float32 -- the context rows of the MP
+        wrapper's context_mask, or with replanning / sub-trajectories the full rows plus TimeAwareObservation's t / max_episode_steps
+        --, ``step`` adds it as ``obs`` and at verbose >= 2 ``step_observations`` [B, T, n_full] (the full rows the env returned
+        per step, 0 behind ``trajectory_length``; one launch that replays the executed steps, mpk_reacher_step_observations).
+        ``observation_space`` is the host wrapper's.  Off (the default), nothing is launched for it.
 
         ``learn_sub_trajectories`` (black_box_wrapper.py:98-102, utils/make_env_helpers.py:89-117): every ``step`` plans a new
         sub-trajectory of ``round(tau / dt)`` steps from the current state -- tau is the first parameter (``learn_tau``), read
@@ -126,6 +157,18 @@ class BatchedBlackBox:
                 raise ValueError(f"env_kwargs of {reward!r} take {sorted(defaults)}, got {sorted(unknown)}")
             defaults = {**defaults, **env_kwargs}
         self.env_kwargs = defaults
+        self.observations = bool(observations)
+        self.observation_space = None
+        if self.observations:
+            if reward not in ("simple_reacher", "hole_reacher"):
+                raise ValueError("observations=True needs reward='simple_reacher' or 'hole_reacher': the other device plants have no env "
+                                 "observation")
+            if pos_limits is not None:
+                raise ValueError("observations=True does not take pos_limits: the observation of the invalid-plan callback is not built")
+            context = not (self.learn_sub_trajectories or self.do_replanning)
+            self._obs_time_div = 0.0 if context else float(self.horizon)     # t / max_episode_steps (the TimeLimit's steps)
+            self._obs_mask, self.observation_space = reacher_observation_layout(
+                reward, self.D, self.env_kwargs["random_start"], self.env_kwargs.get("hole_width"), context, not context)
         self._rng = None                    # int64 [B, 5]: every episode's numpy generator (mpk_nprng_state), after a seeded reset
         self._task_buf = None               # the goal / hole buffer the device resets write
         self.steps_before_reward = int(steps_before_reward)
@@ -279,6 +322,28 @@ class BatchedBlackBox:
             raise ValueError("no device-drawn reset yet: call reset(seed=...)")
         from .engine import nprng_state
         return nprng_state(self._rng, episodes)
+
+    def observe(self) -> torch.Tensor:
+        """the current observation [B, n_obs] float32 on the device (``observations=True``), one launch: after ``reset`` the reset
+        observation, after a step that step's ``obs`` (BlackBoxWrapper.observation of the env's _get_obs(), black_box_wrapper.py:89-94)"""
+        if not self.observations:
+            raise ValueError("observe() needs BatchedBlackBox(..., observations=True)")
+        task = self.hole if self.reward == "hole_reacher" else self.goal
+        if task is None:
+            raise ValueError("observe(): no episode yet -- call reset first")
+        return self.engine.reacher_observation(self.reward, self.q, self.qd, task, self.traj_steps, col_mask=self._obs_mask,
+                                               time_div=self._obs_time_div)
+
+    def _add_observations(self, out: Dict[str, torch.Tensor], start) -> Dict[str, torch.Tensor]:
+        """``obs`` and, given the plan-start state, ``step_observations`` (the replay of the executed steps) of a finished step"""
+        if start is not None and "des_pos" in out:
+            seg = out["trajectory_length"]
+            task = self.hole if self.reward == "hole_reacher" else self.goal
+            out["step_observations"] = self.engine.reacher_step_observations(
+                self.reward, self.spec, out["des_pos"], out["des_vel"], start[0], start[1], task, seg, self.traj_steps - seg,
+                time_div=self._obs_time_div)
+        out["obs"] = self.observe()
+        return out
 
     @property
     def current_pos(self) -> torch.Tensor:
@@ -482,7 +547,13 @@ class BatchedBlackBox:
     _PER_STEP = ("des_pos", "des_vel", "step_actions", "step_rewards")
 
     def step(self, params, fuse: bool = True) -> Dict[str, torch.Tensor]:
+        out = self._step(params, fuse)
+        # (the plan-start state for the replay of step_observations: a copy taken by _step before the plan)
+        return self._add_observations(out, self._obs_start) if self.observations else out
+
+    def _step(self, params, fuse: bool) -> Dict[str, torch.Tensor]:
         self._plans_since_reset += 1
+        self._obs_start = (self.q.clone(), self.qd.clone()) if self.observations and self.verbose >= 2 else None
         if self.reward == "hole_reacher":
             return self._step_hole(params)
         if fuse and self._can_episode_return():
@@ -618,6 +689,7 @@ class EpisodeGraph:
         self.params = [torch.zeros((bb.B, bb.engine.num_params), dtype=torch.float32, device=dev)
                        for _ in range(n_plans)]
         self.outs = []
+        self.reset_obs = None           # observations=True: the captured reset observation [B, n_obs], rewritten by every replay
 
         if sample:
             self.init_pos = self.init_vel = self.goal = self.hole = None
@@ -625,12 +697,13 @@ class EpisodeGraph:
         def episode():
             if sample:
                 bb.reset(sample=True)
-                return [bb.step(p) for p in self.params]
-            kw = {"goal": self.goal} if self.goal is not None else {}
-            if self.hole is not None:
-                kw["hole"] = self.hole
-            bb.reset(self.init_pos, self.init_vel, **kw)
-            return [bb.step(p) for p in self.params]
+            else:
+                kw = {"goal": self.goal} if self.goal is not None else {}
+                if self.hole is not None:
+                    kw["hole"] = self.hole
+                bb.reset(self.init_pos, self.init_vel, **kw)
+            reset_obs = bb.observe() if bb.observations else None
+            return reset_obs, [bb.step(p) for p in self.params]
 
         # one eager pass on a side stream first (allocator warm-up, lazy initialisation), then the capture; the warm-up's draws are
         # undone, so that the first replay continues the streams where the eager resets left them
@@ -646,7 +719,7 @@ class EpisodeGraph:
             torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.outs = episode()
+            self.reset_obs, self.outs = episode()
         torch.cuda.synchronize(dev)
 
     def replay(self):

@@ -2,8 +2,9 @@
 // (envs/classic_control/hole_reacher/hole_reacher.py, base_reacher/base_reacher_direct.py:20-38, hr_simple_reward.py:19-53):
 // controller + clip, the direct-velocity plant, self / wall collision, reward, and the break on collision.  One lane per episode,
 // serial in time; a wave leaves the loop once none of its lanes is live.  float64 without FMA contraction, except where the
-// reference's own numpy flow is float32 (see hole_step).
+// reference's own numpy flow is float32 (hole_plant_step, mpk_plant.h).
 #include "mpk_dev.h"
+#include "mpk_plant.h"
 #include "mpk_reward.h"
 
 namespace mpk {
@@ -158,46 +159,10 @@ __global__ void __launch_bounds__(64 * kHoleWpb) k_hole_rollout(const HoleArgs a
         if (!__any(live)) break;                      // wave-uniform exit
         if (!live) continue;
         const size_t row = (row0 + t) * D;
-        // controller + clip (black_box_wrapper.py:176-179)
+        // controller + clip (black_box_wrapper.py:176-179), then the direct-velocity plant in numpy's dtypes (mpk_plant.h)
         double u[MD];
-#pragma unroll
-        for (int d = 0; d < MD; ++d) {
-            if (d >= D) { u[d] = 0.0; continue; }
-            double v;
-            if (ctrl == MPK_CTRL_VELOCITY) v = (double)a.des_vel[row + d];
-            else if (ctrl == MPK_CTRL_POSITION) v = (double)a.des_pos[row + d];
-            else v = s_g[d] * ((double)a.des_pos[row + d] - q[d]) + s_g[kMaxD + d] * ((double)a.des_vel[row + d] - qd[d]);
-            u[d] = fmin(fmax(v, s_g[2 * kMaxD + d]), s_g[3 * kMaxD + d]);
-        }
-        // the direct-velocity plant (base_reacher_direct.py:26-28) and its control cost, in numpy's dtypes: the velocity / position
-        // controllers hand over a float32 action, which becomes the state qd -- from the episode's second step on acc = (a - qd) / dt
-        // and dt * qd are float32 operations (numpy casts the Python float dt to float32), and np.sum(acc ** 2) adds in float32; the
-        // first step subtracts from the float64 start velocity.  The motor controller's action is float64 throughout.
-        const bool f32 = ctrl != MPK_CTRL_MOTOR && s0 + t > 0;
-        double acc_cost;
-        if (f32) {
-            float c32 = 0.0f;
-#pragma unroll
-            for (int d = 0; d < MD; ++d) {
-                if (d >= D) continue;
-                const float a32 = (float)u[d];
-                const float acc = (a32 - (float)qd[d]) / dt32;
-                c32 = c32 + acc * acc;
-                qd[d] = (double)a32;
-                q[d] = q[d] + (double)(dt32 * a32);
-            }
-            acc_cost = (double)c32;
-        } else {
-            acc_cost = 0.0;
-#pragma unroll
-            for (int d = 0; d < MD; ++d) {
-                if (d >= D) continue;
-                const double acc = (u[d] - qd[d]) / dt;
-                acc_cost = acc_cost + acc * acc;
-                qd[d] = u[d];
-                q[d] = ctrl == MPK_CTRL_MOTOR ? q[d] + dt * qd[d] : q[d] + (double)(dt32 * (float)u[d]);
-            }
-        }
+        hole_control<MD>(ctrl, D, s_g, a.des_pos ? a.des_pos + row : nullptr, a.des_vel ? a.des_vel + row : nullptr, q, qd, u);
+        const double acc_cost = hole_plant_step<MD>(ctrl, ctrl != MPK_CTRL_MOTOR && s0 + t > 0, D, dt, dt32, u, q, qd);
         // kinematics (base_reacher.py:95-103): unit links, cumulative angles, joints from the origin
         double jx[MD + 1], jy[MD + 1], cs[MD], sn[MD];
         jx[0] = 0.0; jy[0] = 0.0;

@@ -1350,6 +1350,71 @@ int mpk_reacher_reset(mpk_handle hh, const mpk_reacher_reset_task* task, const u
     return launch_reacher_reset(l, B, h->dev.D, stream, h->d_fault);
 }
 
+// the column layout of an observation launch (mpk.h: mpk_obs_cfg); "what" names the entry point in the messages
+static int obs_layout(const Handle* h, const mpk_obs_cfg* cfg, const char* what, ObsLaunch* l) {
+    if (!cfg) { set_error(std::string(what) + ": cfg is NULL"); return MPK_EINVAL; }
+    if (cfg->env != MPK_RESET_SIMPLE_REACHER && cfg->env != MPK_RESET_HOLE_REACHER) {
+        set_error(std::string(what) + ": unknown env");
+        return MPK_EINVAL;
+    }
+    if (cfg->n_links < 1 || cfg->n_links > kMaxD) { set_error(std::string(what) + ": n_links must be 1 .. 16"); return MPK_EINVAL; }
+    if (cfg->n_links != h->dev.D) { set_error(std::string(what) + ": n_links must be the handle's num_dof"); return MPK_EINVAL; }
+    if (!(cfg->time_div >= 0.0)) { set_error(std::string(what) + ": time_div must be >= 0 (0 = no time awareness)"); return MPK_EINVAL; }
+    const int n_full = 3 * cfg->n_links + (cfg->env == MPK_RESET_HOLE_REACHER ? 4 : 3);
+    const uint64_t all = (n_full >= 64) ? ~0ull : ((1ull << n_full) - 1ull);
+    if (cfg->col_mask & ~all) {
+        set_error(std::string(what) + ": a column index of col_mask lies outside the full row (" + std::to_string(n_full) + " columns)");
+        return MPK_EINVAL;
+    }
+    l->env = cfg->env; l->D = cfg->n_links; l->n_full = n_full;
+    l->mask = cfg->col_mask ? cfg->col_mask : all;
+    l->time_div = cfg->time_div;
+    l->n_out = __builtin_popcountll(l->mask) + (cfg->time_div > 0.0 ? 1 : 0);
+    return MPK_OK;
+}
+
+int mpk_reacher_observation(mpk_handle hh, const mpk_obs_cfg* cfg, const double* q, const double* qd, const double* task,
+                            const int32_t* steps, float* out, int32_t B, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    ObsLaunch l;
+    int r = obs_layout(h, cfg, "mpk_reacher_observation", &l);
+    if (r != MPK_OK) return r;
+    if (B < 0) { set_error("B must be >= 0"); return MPK_EINVAL; }
+    if (B == 0) return MPK_OK;
+    if (!q || !qd || !task || !steps || !out) { set_error("mpk_reacher_observation: NULL buffer"); return MPK_EINVAL; }
+    MPK_ON_DEVICE(h->cfg.device);
+    return launch_reacher_obs(l, q, qd, task, steps, out, B, stream);
+}
+
+int mpk_reacher_step_observations(mpk_handle hh, const mpk_obs_cfg* cfg, const mpk_rollout_cfg* rc, const float* des_pos,
+                                  const float* des_vel, const double* q0, const double* qd0, const double* task, const int32_t* n_exec,
+                                  const int32_t* step0, float* out, double* q_end, double* qd_end, int32_t B, int32_t T, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    ObsLaunch l;
+    int r = obs_layout(h, cfg, "mpk_reacher_step_observations", &l);
+    if (r != MPK_OK) return r;
+    RolloutDev rd;
+    r = fill_rollout(h, rc, &rd, cfg->env == MPK_RESET_HOLE_REACHER);
+    if (r != MPK_OK) return r;
+    if (cfg->env == MPK_RESET_SIMPLE_REACHER && rd.plant_type != MPK_PLANT_DOUBLE_INTEGRATOR) {
+        set_error("mpk_reacher_step_observations: SimpleReacher replays the torque double-integrator plant");
+        return MPK_EINVAL;
+    }
+    if (B < 0 || T < 0) { set_error("B and T must be >= 0"); return MPK_EINVAL; }
+    if (B == 0 || T == 0) return MPK_OK;
+    const bool need_pos = cfg->env == MPK_RESET_SIMPLE_REACHER || rc->controller_type != MPK_CTRL_VELOCITY;
+    const bool need_vel = cfg->env == MPK_RESET_SIMPLE_REACHER || rc->controller_type != MPK_CTRL_POSITION;
+    if ((need_pos && !des_pos) || (need_vel && !des_vel) || !q0 || !qd0 || !task || !n_exec || !step0 || !out) {
+        set_error("mpk_reacher_step_observations: NULL buffer");
+        return MPK_EINVAL;
+    }
+    if ((q_end == nullptr) != (qd_end == nullptr)) { set_error("q_end and qd_end go together"); return MPK_EINVAL; }
+    MPK_ON_DEVICE(h->cfg.device);
+    return launch_reacher_step_obs(l, rd, des_pos, des_vel, q0, qd0, task, n_exec, step0, out, q_end, qd_end, B, T, stream);
+}
+
 int mpk_replan_advance(mpk_handle hh, int32_t* traj_steps, int32_t* plan_steps, int32_t* seg_len, uint8_t* done,
                        int32_t every, int32_t max_planning_times, int32_t horizon, int32_t T, int32_t B,
                        void* stream) {

@@ -206,6 +206,17 @@ struct ResetLaunch {
     int env = 0, random_start = 0;
 };
 int launch_reacher_reset(const ResetLaunch& l, int B, int D, void* stream, int* fault);
+// mpk_reacher_observation / mpk_reacher_step_observations (mpk_obs.hip): reacher observation rows, current and replayed per step
+struct ObsLaunch {
+    uint64_t mask = 0;                  // full columns written, in order (never 0: the host expands "every column")
+    double time_div = 0.0;              // > 0: a last column steps / time_div
+    int env = 0, D = 0, n_full = 0, n_out = 0;
+};
+int launch_reacher_obs(const ObsLaunch& l, const double* q, const double* qd, const double* task, const int32_t* steps, float* out,
+                       int B, void* stream);
+int launch_reacher_step_obs(const ObsLaunch& l, const RolloutDev& rc, const float* des_pos, const float* des_vel, const double* q0,
+                            const double* qd0, const double* task, const int32_t* n_exec, const int32_t* step0, float* out,
+                            double* q_end, double* qd_end, int B, int T, void* stream);
 int launch_gate_flags(const uint8_t* valid, const uint8_t* was_done, const uint8_t* done, uint8_t* terminated, uint8_t* truncated, int B,
                       void* stream);
 int launch_replan_advance(int32_t* traj_steps, int32_t* plan_steps, int32_t* seg_len, uint8_t* done, int every,

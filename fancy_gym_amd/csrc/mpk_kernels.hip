@@ -15,6 +15,7 @@
 //   mpk_rollout.hip      rollout kernels
 //   mpk_hole.hip         HoleReacher: direct-velocity plant, collisions, reward, break on collision
 //   mpk_reset.hip        reacher resets: numpy's generator per episode (mpk_nprng.h), seeded / continued draws
+//   mpk_obs.hip          reacher observations: current rows, per-step rows replayed on the stored plan (mpk_plant.h)
 //   mpk_misc.hip         integer state, reset, gather, validity, self-tests, trace readout
 #define MPK_AMALGAMATED 1
 #include "mpk_traj_family.hip"
@@ -27,4 +28,5 @@
 #include "mpk_rollout.hip"
 #include "mpk_hole.hip"
 #include "mpk_reset.hip"
+#include "mpk_obs.hip"
 #include "mpk_misc.hip"

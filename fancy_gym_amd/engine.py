@@ -654,6 +654,59 @@ class TrajectoryEngine:
                                                _dptr(cp), _dptr(cv), traj_steps.data_ptr(), plan_steps.data_ptr(), done.data_ptr(),
                                                task_out.data_ptr(), B, self._stream()))
 
+    def _obs_cfg(self, env: str, col_mask: int, time_div: float):
+        c = _lib.mpk_obs_cfg()
+        c.env = _lib.RESET_ENVS[env]
+        c.n_links = self.num_dof
+        c.col_mask = int(col_mask)
+        c.time_div = float(time_div)
+        n_full = 3 * self.num_dof + (4 if env == "hole_reacher" else 3)
+        n_out = bin(int(col_mask)).count("1") if col_mask else n_full
+        return c, n_out + int(time_div > 0)
+
+    def reacher_observation(self, env: str, q: torch.Tensor, qd: torch.Tensor, task: torch.Tensor, steps: torch.Tensor, *,
+                            col_mask: int = 0, time_div: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """
+        The current observation of B reacher episodes (``env`` "simple_reacher" / "hole_reacher"; mpk.h: mpk_reacher_observation) as
+        float32 [B, n_out] on the device, in one launch: the env's _get_obs() row from q, qd (float64 [B, D]), the goal [B, 2] / hole
+        [B, 3] ``task`` and the step counter ``steps`` (int32 [B]); ``col_mask`` bit c keeps column c of the full row (0 = all),
+        ``time_div`` > 0 appends steps / time_div.  Allocates ``out`` unless given.
+        """
+        B = q.shape[0]
+        for t, dt_ in ((q, torch.float64), (qd, torch.float64), (task, torch.float64), (steps, torch.int32)):
+            assert t.dtype == dt_ and t.is_contiguous() and t.shape[0] == B
+        c, n_out = self._obs_cfg(env, col_mask, time_div)
+        if out is None:
+            out = torch.empty((B, n_out), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, n_out)
+        _lib.check(self._lib.mpk_reacher_observation(self._h, C.byref(c), q.data_ptr(), qd.data_ptr(), task.data_ptr(),
+                                                     steps.data_ptr(), out.data_ptr(), B, self._stream()))
+        return out
+
+    def reacher_step_observations(self, env: str, spec: RolloutSpec, des_pos: Optional[torch.Tensor], des_vel: Optional[torch.Tensor],
+                                  q0: torch.Tensor, qd0: torch.Tensor, task: torch.Tensor, n_exec: torch.Tensor, step0: torch.Tensor, *,
+                                  col_mask: int = 0, time_div: float = 0.0, end_state: bool = False):
+        """
+        ``infos['step_observations']`` of a verbose >= 2 step for B reacher episodes (mpk.h: mpk_reacher_step_observations): one launch
+        replays the ``n_exec`` executed steps of the plan (des_pos, des_vel) [B, T, D] from the plan-start state (q0, qd0) with the
+        rollout's controller and plant (``spec``: the double integrator for "simple_reacher", 'velocity_direct' for "hole_reacher"),
+        starting at env step ``step0``, and writes the observation after every step: float32 [B, T, n_out], 0 behind n_exec.
+        ``end_state`` also returns the replayed (q, qd) -- the state the rollout left.
+        """
+        ref = des_vel if des_vel is not None else des_pos
+        B, T, D = ref.shape
+        for t, dt_ in ((q0, torch.float64), (qd0, torch.float64), (task, torch.float64), (n_exec, torch.int32), (step0, torch.int32)):
+            assert t.dtype == dt_ and t.is_contiguous() and t.shape[0] == B
+        des_pos = des_pos.contiguous() if des_pos is not None else None
+        des_vel = des_vel.contiguous() if des_vel is not None else None
+        c, n_out = self._obs_cfg(env, col_mask, time_div)
+        out = torch.empty((B, T, n_out), dtype=torch.float32, device=self.device)
+        qe, qde = (torch.empty((B, D), dtype=torch.float64, device=self.device) for _ in range(2)) if end_state else (None, None)
+        _lib.check(self._lib.mpk_reacher_step_observations(
+            self._h, C.byref(c), C.byref(spec.c), _dptr(des_pos), _dptr(des_vel), q0.data_ptr(), qd0.data_ptr(), task.data_ptr(),
+            n_exec.data_ptr(), step0.data_ptr(), out.data_ptr(), _dptr(qe), _dptr(qde), B, T, self._stream()))
+        return (out, qe, qde) if end_state else out
+
     def condition_gather(self, pos: torch.Tensor, vel: torch.Tensor, seg_len: torch.Tensor,
                          out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
         """desired (pos, vel) [B, D] at the last executed step of each episode (condition_on_desired)"""

@@ -627,6 +627,45 @@ int mpk_reacher_reset(mpk_handle h, const mpk_reacher_reset_task* task, const ui
                       double* task_out, int32_t B, void* stream);
 
 /*
+ * Observations of the reference's reacher envs for B device-resident episodes (ABI 4, appended): what env._get_obs() returns,
+ * masked by the MP wrapper's context_mask and extended by TimeAwareObservation as BlackBoxWrapper.observation hands it out
+ * (black_box_wrapper.py:89-94; utils/wrappers.py:49-63; utils/make_env_helpers.py:95-97).  The full row, float64 cast to float32 once:
+ *   MPK_RESET_SIMPLE_REACHER (simple_reacher.py:75-83)  [cos q (D), sin q (D), qd (D), ee - goal (2), steps]          3 D + 3
+ *   MPK_RESET_HOLE_REACHER   (hole_reacher.py:114-124)   [cos q (D), sin q (D), qd (D), width, ee - (x, -depth) (2), steps]   3 D + 4
+ * ee: the joints as _update_joints builds them (base_reacher.py:95-103) -- cumulative angles and joint coordinates as sequential sums.
+ * cfg->col_mask selects the written columns of the full row, in order (0 = all of them; context rows: bit c = context_mask[c],
+ * simple_reacher/mp_wrapper.py and hole_reacher/mp_wrapper.py); cfg->time_div > 0 appends a last column steps / time_div
+ * (t / max_episode_steps, computed in float64).  n_out = popcount(mask) + (time_div > 0) floats per row.
+ *   task   dev double [B, 2] goal (SimpleReacher) or [B, 3] (x, width, depth) (HoleReacher): what mpk_reacher_reset writes
+ * Both launches allocate nothing and synchronise nothing (they can be captured in a graph).  n_links must be the handle's num_dof
+ * (<= 16); a column outside the full row, a negative or NaN time_div, an unknown env or a NULL buffer is MPK_EINVAL.
+ *
+ * mpk_reacher_observation: the current observation, out dev float [B, n_out], from q, qd dev double [B, D] and the env step counter
+ * steps dev int32 [B] (traj_steps): after a reset the reset observation, after a step the step's obs.
+ *
+ * mpk_reacher_step_observations: infos['step_observations'] of a verbose >= 2 step (black_box_wrapper.py:160-164,184-186,212),
+ * out dev float [B, T, n_out]; rows at and after n_exec[b] are 0.  The rollouts keep no per-step states, so the launch replays the
+ * executed steps from the plan-start state (q0, qd0) dev double [B, D] on the stored plan (des_pos, des_vel) dev float [B, T, D] with
+ * the rollout's controller, clip and plant code (bits identical): rc as for mpk_reacher_rollout (double integrator) or
+ * mpk_hole_reacher_rollout (MPK_PLANT_VELOCITY_DIRECT, its float32 / float64 rule keyed on step0 + t > 0).  n_exec dev int32 [B]
+ * (trajectory_length), step0 dev int32 [B] (the env step counter at the plan's first step); row t holds the observation after env
+ * step step0 + t + 1.  q_end, qd_end dev double [B, D] or NULL (both or neither): the replayed end state, equal to the state the
+ * rollout left.
+ */
+typedef struct mpk_obs_cfg {
+    int32_t  env;                    /* MPK_RESET_* */
+    int32_t  n_links;                /* D: the handle's num_dof */
+    uint64_t col_mask;               /* bit c: column c of the full row is written; 0 = every column */
+    double   time_div;               /* > 0: last column steps / time_div (TimeAwareObservation); 0 = none */
+    int64_t  reserved[2];
+} mpk_obs_cfg;
+int mpk_reacher_observation(mpk_handle h, const mpk_obs_cfg* cfg, const double* q, const double* qd, const double* task,
+                            const int32_t* steps, float* out, int32_t B, void* stream);
+int mpk_reacher_step_observations(mpk_handle h, const mpk_obs_cfg* cfg, const mpk_rollout_cfg* rc, const float* des_pos,
+                                  const float* des_vel, const double* q0, const double* qd0, const double* task, const int32_t* n_exec,
+                                  const int32_t* step0, float* out, double* q_end, double* qd_end, int32_t B, int32_t T, void* stream);
+
+/*
  * Integer replanning bookkeeping of BlackBoxWrapper.step for the schedule `t % every == 0`
  * (envs/mujoco/box_pushing/mp_wrapper.py:89; black_box_wrapper.py:174,197,206):
  *   plan_steps[b] += 1
