@@ -6,13 +6,18 @@ A "step" is one pass of the hot path over one batch of synthetic episodes: ONE l
 (basis contraction on MFMA + ProDMP boundary conditions + PD tracking-controller actions) for BASELINE config 2:
 ProDMP, 7 DoF, 5 basis (+goal) per DoF, 100 steps, batch 4096 per GPU, inputs resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--eager] [--no-cpu] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--eager] [--dump-outputs DIR] [--full [--no-cpu] ...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  Multi-GPU: episodes shard across ranks (independent units, no data-path collective):
-"scaling": "weak", value = all ranks' trajectories / max-over-ranks time.  The optional all-gather of the generated
-trajectories over RCCL/xGMI (north_star) is timed separately and reported under "allgather".
+"scaling": "weak", value = all ranks' trajectories / max-over-ranks time.
+
+A plain run does only what the headline needs: set up, W warm-up steps, the K timed steps, the outputs of
+`--dump-outputs`, the line.  `--full` adds everything else, each after the timed steps: the event-timed pass of the same
+K steps ("roofline"), the HBM-streaming row ("roofline_streaming", unless --no-streaming), the CPU baselines
+("cpu_baseline", unless --no-cpu), the two-stream leg ("two_stream", with --overlap), and for N > 1 the per-rank figures
+and the all-gather of the generated trajectories over RCCL/xGMI ("allgather", unless --no-allgather).
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself: the parent -- before it makes a
 single GPU call -- runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same args>` as a
@@ -58,7 +63,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--batch", type=int, default=4096, help="episodes per GPU per step")
     ap.add_argument("--eager", action="store_true", help="one host launch per step instead of one hipGraph of K steps")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs below (roofline pass, streaming row, CPU baselines, "
+                         "all-gather, two-stream); a plain run skips them all")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--no-allgather", action="store_true")
     ap.add_argument("--no-overlap", action="store_true", help="(accepted for older scripts: the two-stream leg is off by default since round 6)")
     ap.add_argument("--overlap", action="store_true",
@@ -66,11 +74,14 @@ def parse():
                          "plain line in round 5 (4.29 vs 4.44 x 10^8 trajectories/s) -- two launches of one kernel that each fill the chip "
                          "share its write path, they do not hide each other's ramp")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-streaming", action="store_true", help="skip the HBM-streaming roofline row (B = 262144)")
+    ap.add_argument("--no-streaming", action="store_true", help="--full without the HBM-streaming roofline row (B = 262144)")
     ap.add_argument("--streaming-batch", type=int, default=262144)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the outputs of the last timed step as DIR/<name>.npy (see the module docstring)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.overlap and not args.full:
+        ap.error("--overlap is a leg of --full")
+    return args
 
 
 def dump_outputs(path: str, arrays: dict) -> dict:
@@ -451,16 +462,18 @@ def main():
     # --dump-outputs: what the last timed step wrote, copied on the device now (outside the clock) before any later leg
     # launches into the same buffers; written to files at the end
     last_outputs = {"pos": pos.clone(), "vel": vel.clone(), "act": act.clone()} if args.dump_outputs and rank == 0 else None
-    # the kernel's average launch duration for the roofline line: the same K steps once more, bracketed by HIP events on
-    # the launch stream (kept out of the wall-clock region above: two event records cost a short run several percent)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record(stream)
-    k_steps()
-    ev1.record(stream)
-    torch.cuda.synchronize()
-    kern_avg = ev0.elapsed_time(ev1) * 1e-3 / K
+    kern_avg = None
+    if args.full:
+        # the kernel's average launch duration for the roofline line: the same K steps once more, bracketed by HIP events
+        # on the launch stream (kept out of the wall-clock region above: two event records cost a short run several percent)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record(stream)
+        k_steps()
+        ev1.record(stream)
+        torch.cuda.synchronize()
+        kern_avg = ev0.elapsed_time(ev1) * 1e-3 / K
     per_rank = None
-    if dist is not None:
+    if dist is not None and args.full:
         # outside the timed region, no new collective inside it: every rank's own wall-clock sample and its event-timed kernel
         # average, so that a reader of the N-rank line can tell host jitter (one rank's wall sample off, its kernel time not)
         # from imbalance (a rank's kernel time off) without a re-run
@@ -471,6 +484,7 @@ def main():
                     "per_rank_kernel_avg_us": [float(x[1].item()) * 1e6 for x in every]}
         per_rank["kernel_avg_us_max"] = max(per_rank["per_rank_kernel_avg_us"])
         per_rank["event_timed_value"] = world * B / (per_rank["kernel_avg_us_max"] * 1e-6)
+    if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
@@ -481,7 +495,7 @@ def main():
     # first collective of the leg and is agreed on with a MIN all-reduce, so a rank never leaves its peers blocked in a
     # collective; a failure after the collectives have started ends the rank non-zero (the launcher then ends the job).
     allgather = None
-    if dist is not None and not args.no_allgather:
+    if dist is not None and args.full and not args.no_allgather:
         from fancy_gym_amd.distributed import TrajectoryShard
         Kg = max(10, min(K, 200))
         local_err = None
@@ -560,7 +574,7 @@ def main():
             if rccl is not None and rank == 0:
                 allgather["rccl"] = rccl
 
-    headline_kernel = eng.last_kernel()
+    headline_kernel = eng.last_kernel() if args.full else None
     # ---- the same K steps with consecutive launches allowed to OVERLAP: two capture streams, alternating output sets ----
     # Every step is still a full B-episode launch writing all three arrays (to set i % 2); step i + 1 no longer waits for
     # step i's last store, so its dispatch ramp and input loads (time-to-first-store, ~1.8 us of the 8.2: profiles/
@@ -610,7 +624,7 @@ def main():
             print(f"[bench] two-stream leg failed: {e}", file=sys.stderr)
     # ---- the same kernel family where the outputs really stream to HBM (B = 262144: 2.2 GB written per launch) ---------
     streaming = None
-    if rank == 0 and world == 1 and not args.no_streaming:
+    if args.full and rank == 0 and world == 1 and not args.no_streaming:
         try:
             Bs = args.streaming_batch
             gs = torch.Generator(device="cpu").manual_seed(1)
@@ -670,7 +684,6 @@ def main():
 
     line = None
     if rank == 0:
-        achieved = BYTES_PER_TRAJ * B / kern_avg / 1e9
         out = {
             "metric": "MP trajectories/sec (7-DoF, 5 basis, 100 steps) at 1/2/4/8 GPUs; % roofline",
             "value": value, "unit": "trajectories/s", "n_gpus": world, "steps": K, "warmup": W,
@@ -680,13 +693,15 @@ def main():
                                    "trajectory (pos, vel) + PD tracking-controller actions, fused",
                        "batch_per_gpu": B, "global_batch": world * B, "launch": launch, "untimed_graph_replays": untimed_replays,
                        "sharding": f"dp{world} (independent episodes, no data-path collective)"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(B),
-                         "traffic_source": "profiles/pmc_traffic.json: rocprofv3 --pmc passes of this command on an earlier "
-                                           "call (tools/pmc_traffic.sh), committed; not re-measured in this run",
-                         "kernel": headline_kernel, "kernel_avg_us": kern_avg * 1e6,
-                         "algorithmic_bytes_per_launch": BYTES_PER_TRAJ * B},
         }
+        if kern_avg is not None:
+            achieved = BYTES_PER_TRAJ * B / kern_avg / 1e9
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(B),
+                               "traffic_source": "profiles/pmc_traffic.json: rocprofv3 --pmc passes of this command on an "
+                                                 "earlier call (tools/pmc_traffic.sh), committed; not re-measured in this run",
+                               "kernel": headline_kernel, "kernel_avg_us": kern_avg * 1e6,
+                               "algorithmic_bytes_per_launch": BYTES_PER_TRAJ * B}
         if per_rank is not None:
             # N > 1 only: `value` = world * B * K / max(per_rank_ms); event_timed_value = world * B / kernel_avg_us_max
             out.update(per_rank)
@@ -699,9 +714,9 @@ def main():
         if last_outputs is not None:
             out["dump_outputs"] = dump_outputs(args.dump_outputs, last_outputs)
             del last_outputs
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, B)
-        elif not args.no_cpu:
+        elif args.full and not args.no_cpu:
             out["cpu_baseline"] = None
         line = json.dumps(out)
     if dist is not None:

@@ -112,6 +112,22 @@ def test_bench_refuses_a_world_size_that_disagrees_with_gpus():
     assert r.returncode == 2 and "WORLD_SIZE" in r.stderr and not r.stdout.strip()
 
 
+def test_bench_legs_beyond_the_headline_need_full(monkeypatch):
+    """a plain bench.py run is the headline alone (`--full` off by default); --overlap names a leg of --full, so without it
+    the run is a usage error (exit 2) decided before anything touches a GPU, not a line that silently lacks the leg"""
+    import subprocess
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full", "--overlap"])
+    a = bench.parse()
+    assert a.full is True and a.overlap is True
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--overlap"],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 2 and "--full" in r.stderr and not r.stdout.strip()
+
+
 def test_bench_gpus_n_spawns_a_torch_distributed_run_child(monkeypatch):
     """--gpus N without WORLD_SIZE: the parent builds the torch.distributed.run command line for N ranks on 127.0.0.1 and
     returns the child's exit code (the child is faked here: no GPU in this container)"""

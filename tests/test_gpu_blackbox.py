@@ -1572,14 +1572,14 @@ def test_captured_episode_with_learned_phase_and_device_reward():
 @pytest.mark.timing
 @pytest.mark.gpu
 def test_bench_prints_the_contract_line_last():
-    """bench.py: the LAST stdout line is the JSON contract line, with the roofline and cpu_baseline objects"""
+    """bench.py --full: the LAST stdout line is the JSON contract line, with the roofline and cpu_baseline objects"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MPK_BENCH_FORCE_DIST="1")          # also walks the RCCL code path with one rank
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("MASTER_ADDR", None); env.pop("MASTER_PORT", None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "40", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "40", "--warmup", "5", "--full",
                         "--cpu-seconds", "1"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -1629,7 +1629,7 @@ def test_bench_dump_outputs_are_the_timed_steps_outputs(tmp_path):
 @pytest.mark.gpu
 def test_bench_gpus_2_starts_two_ranks_itself_and_gathers_both_shards():
     """
-    `python bench.py --gpus 2` with no WORLD_SIZE: the parent spawns the two ranks (torch.distributed.run child, before it
+    `python bench.py --gpus 2 --full` with no WORLD_SIZE: the parent spawns the two ranks (torch.distributed.run child, before it
     touches the GPU).  On a 1-GPU box the ranks share the device, which RCCL refuses ("duplicate GPU"), so the rehearsal
     uses gloo (MPK_BENCH_BACKEND); the driver's runs use one rank per GPU and RCCL.  Checks: n_gpus == 2, global batch
     2 B, the all-gather leg ran, every gathered slice equals its rank's shard, and the shards ARE what a single-rank
@@ -1643,7 +1643,7 @@ def test_bench_gpus_2_starts_two_ranks_itself_and_gathers_both_shards():
         env.pop(k, None)
     B = 512
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3",
-                        "--batch", str(B), "--no-cpu"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                        "--batch", str(B), "--full", "--no-cpu"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 2 * B and d["config"]["batch_per_gpu"] == B
@@ -1670,7 +1670,7 @@ def test_bench_gpus_2_starts_two_ranks_itself_and_gathers_both_shards():
 @pytest.mark.gpu
 def test_forced_one_rank_rccl_line_pays_nothing_the_plain_line_does_not():
     """
-    The N-rank code path of bench.py (init_process_group("nccl"), barrier -> synchronize -> t0 -> K steps -> synchronize ->
+    The N-rank code path of bench.py --full (init_process_group("nccl"), barrier -> synchronize -> t0 -> K steps -> synchronize ->
     t1, closing barrier OUTSIDE the clock, MAX all-reduce of the elapsed time) against the plain one-process line, same
     box, the driver's `--steps 20 --warmup 5`, runs alternated, best of three each: `value` within 3 %.  Round 2's line
     had the closing RCCL barrier inside the 0.19 ms region.
@@ -1682,8 +1682,8 @@ def test_forced_one_rank_rccl_line_pays_nothing_the_plain_line_does_not():
 
     def run(forced):
         env = dict(base, MPK_BENCH_FORCE_DIST="1") if forced else base
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu",
-                            "--no-streaming"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--full",
+                            "--no-cpu", "--no-streaming"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
         assert r.returncode == 0, r.stderr[-2000:]
         return json.loads(r.stdout.strip().splitlines()[-1])
     plain, forced = [], []
@@ -1698,7 +1698,7 @@ def test_forced_one_rank_rccl_line_pays_nothing_the_plain_line_does_not():
 
 @pytest.mark.timing
 def test_bench_line_carries_the_whole_contract():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` (the driver's form): ONE JSON line on stdout, last, with every key
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full`: ONE JSON line on stdout, last, with every key
     the measurement contract names -- metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better /
     scaling / vs_baseline / dtype / data / config.workload, roofline {bound, achieved, peak, unit, frac, traffic} for the
     dominant kernel, cpu_baseline {value, unit, cores, kind, sample} -- and numbers that are consistent with each other"""
@@ -1706,8 +1706,8 @@ def test_bench_line_carries_the_whole_contract():
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
-                       capture_output=True, text=True, timeout=900, env=env, cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                        "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and r.stdout.strip().splitlines()[-1] == lines[0]
@@ -1736,6 +1736,38 @@ def test_bench_line_carries_the_whole_contract():
     assert cb["kind"] == "port" and cb["cores"] == 1 and cb["unit"] == d["unit"] and cb["value"] > 0
     assert cb["all_cores"]["cores"] >= 1 and cb["all_cores"]["value"] > 0
     assert 1e3 < d["value"] / cb["value"] < 1e6
+
+
+@pytest.mark.timing
+def test_plain_bench_line_is_the_headline_alone():
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` (the driver's form) does only what its headline needs: ONE JSON line
+    on stdout, last, with metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling /
+    vs_baseline / dtype / data / config and none of the legs of --full; the whole run, from process start to exit, spends
+    less than 30 s outside its W + K steps.  The N-rank code path (MPK_BENCH_FORCE_DIST=1) runs no all-gather leg either."""
+    import time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MPK_BENCH_FORCE_DIST"):
+        base.pop(k, None)
+    for forced in (False, True):
+        env = dict(base, MPK_BENCH_FORCE_DIST="1") if forced else base
+        t0 = time.perf_counter()
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
+                           capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        wall = time.perf_counter() - t0
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1 and r.stdout.strip().splitlines()[-1] == lines[0]
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                  "vs_baseline", "dtype", "data", "config"):
+            assert k in d, k
+        assert not set(d) & {"roofline", "roofline_streaming", "cpu_baseline", "two_stream", "allgather", "per_rank_ms"}, sorted(d)
+        assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["higher_is_better"] is True
+        assert d["unit"] == "trajectories/s" and d["dtype"] == "f32" and d["config"]["launch"] == "hipgraph"
+        assert abs(d["value"] - d["config"]["batch_per_gpu"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        outside = wall - (20 + 5) * d["ms_per_step"] * 1e-3
+        assert outside < 30.0, (forced, wall)
 
 
 def test_rccl_calls_of_the_bench_with_one_rank():

@@ -9,9 +9,9 @@ O=gpurun_out/$TAG
 mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|FAILED|Error" | tail -8 > $O/pytest.log
 python -c "import __graft_entry__ as e; e.smoke(); print('smoke ok')" 2>&1 | grep -v amdgpu | tail -2 > $O/smoke.log
-python bench.py --steps 20 --warmup 5 > $O/bench_k20.json 2> $O/bench_k20.err
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_bench -o bench -- python3 $R/bench.py --no-cpu --no-streaming --no-overlap > $R/$O/bench_under_rocprof.json 2> $R/$O/bench_under_rocprof.err)
+python bench.py --steps 20 --warmup 5 --full > $O/bench_k20.json 2> $O/bench_k20.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_bench -o bench -- python3 $R/bench.py --full --no-cpu --no-streaming --no-overlap > $R/$O/bench_under_rocprof.json 2> $R/$O/bench_under_rocprof.err)
 python tools/trace_timed_region.py $O/prof_bench/bench_kernel_trace.csv > $O/timed_region.txt 2>&1
 gzip -9 -f $O/prof_bench/bench_kernel_trace.csv
 bash tools/pmc_traffic.sh 4096 262144 > $O/pmc_traffic.txt 2>&1
@@ -36,6 +36,6 @@ python tools/rollout_bench.py 24576 65536 262144 --waves 2>/dev/null | grep Long
 (for c in 2 4 8; do echo "== phase_chunk=$c"; python tools/learned_phase_bench.py 8192 65536 TT-ProDMP BeerPong-ProMP phase_chunk=$c 2>/dev/null | grep -v "separate launches\|gated\|trajectory |\|^lib\|^| config\|^|---"; done) > $O/phase_fused_chunks.md
 (for cfg in "TT-ProDMP" "cfg5 TT-ProMP"; do for B in 8192 65536; do n=40; [ $B -gt 10000 ] && n=10; python3 tools/gate_probe.py "$cfg" $B $n scale=0.2; python3 tools/gate_probe.py "$cfg" $B $n; done; done) 2>&1 | grep -v amdgpu > $O/gate_cost.txt
 bash tools/gpu/phase_wpb_sweep.sh 2>&1 | grep -v amdgpu > $O/phase_wpb.md
-MPK_BENCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5 --no-cpu --no-streaming > $O/bench_k20_rccl1.json 2> $O/bench_k20_rccl1.err
-MPK_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 50 --warmup 5 --no-cpu > $O/bench_g2.json 2> $O/bench_g2.err
+MPK_BENCH_FORCE_DIST=1 python bench.py --steps 20 --warmup 5 --full --no-cpu --no-streaming > $O/bench_k20_rccl1.json 2> $O/bench_k20_rccl1.err
+MPK_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 50 --warmup 5 --full --no-cpu > $O/bench_g2.json 2> $O/bench_g2.err
 cat $O/pytest.log $O/smoke.log; tail -c 700 $O/bench_k20.json; echo; cat $O/timed_region.txt; tail -c 900 $O/bench_k20_rccl1.json

@@ -5,7 +5,7 @@ TAG=${1:-r03_spread}
 cd $GRAFT_REPO_ROOT
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG; mkdir -p $O
-python bench.py --steps 20 --warmup 5 --no-cpu > $O/bench_k20.json 2> $O/bench_k20.err
+python bench.py --steps 20 --warmup 5 --full --no-cpu > $O/bench_k20.json 2> $O/bench_k20.err
 python tools/skew_probe.py 262144 3 > $O/skew.md 2> $O/skew.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L > $O/counters_list.txt 2>&1

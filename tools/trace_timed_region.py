@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """
-Split a rocprofv3 kernel trace of `bench.py` into its phases.  The bench launches the headline kernel W times eagerly
+Split a rocprofv3 kernel trace of `bench.py --full` into its phases.  The bench launches the headline kernel W times eagerly
 (warm-up), replays the captured graph of K launches untimed until the GPU has been busy ~30 ms, replays it once between
 barrier + synchronize (the wall-clock-timed region: `value`, `ms_per_step`) and once more between two HIP events
 (`roofline.kernel_avg_us`); the streaming row and everything else come afterwards under other kernel names.  `--stats`
