@@ -76,8 +76,22 @@ class mpk_validity_gate(C.Structure):
 class mpk_hole_task(C.Structure):
     _fields_ = [
         ("collision_penalty", C.c_double), ("allow_self_collision", C.c_int32), ("allow_wall_collision", C.c_int32),
-        ("steps_before_reward", C.c_int32), ("reserved0", C.c_int32),
+        ("steps_before_reward", C.c_int32), ("rew_fct", C.c_int32),
     ]
+
+
+HOLE_REW_FCTS = {"simple": 0, "vel_acc": 1, "unbounded": 2}     # MPK_HOLE_REW_*
+
+
+def hole_rew_fct(rew_fct: str, steps_before_reward: int) -> int:
+    """MPK_HOLE_REW_* of HoleReacher's ``rew_fct`` (hole_reacher.py:48-58); vel_acc / unbounded pay at the reference's literal
+    step 199 (and unbounded stores the end effector at 180), so they take steps_before_reward = 199 only"""
+    if rew_fct not in HOLE_REW_FCTS:
+        raise ValueError("Unknown reward function {}".format(rew_fct))
+    if rew_fct != "simple" and int(steps_before_reward) != 199:
+        raise ValueError(f"rew_fct {rew_fct!r} pays at the reference's step 199: steps_before_reward must be 199, "
+                         f"got {steps_before_reward}")
+    return HOLE_REW_FCTS[rew_fct]
 
 
 RESET_ENVS = {"simple_reacher": 0, "hole_reacher": 1}          # MPK_RESET_*
@@ -148,6 +162,9 @@ SIGNATURES = {
                                       _vp, _i32, _i32, _vp]),
     "mpk_hole_reacher_rollout": (C.c_int, [_vp, C.POINTER(mpk_rollout_cfg), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(mpk_hole_task),
                                            _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, C.POINTER(mpk_replan_state), _i32, _i32, _vp]),
+    "mpk_hole_reacher_rollout2": (C.c_int, [_vp, C.POINTER(mpk_rollout_cfg), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(mpk_hole_task),
+                                            _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, C.POINTER(mpk_replan_state), _vp, _i32, _i32,
+                                            _vp]),
     "mpk_reacher_reset": (C.c_int, [_vp, C.POINTER(mpk_reacher_reset_task), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _i32, _vp]),
     "mpk_reacher_observation": (C.c_int, [_vp, C.POINTER(mpk_obs_cfg), _vp, _vp, _vp, _vp, _vp, _i32, _vp]),

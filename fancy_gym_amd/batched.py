@@ -18,6 +18,7 @@ from typing import Dict, Optional, Sequence, Union
 import numpy as np
 import torch
 
+from . import _lib
 from .black_box.controller.base_controller import BaseController
 from .engine import RolloutSpec, TrajectoryEngine
 from .mp.traj import MPInterface
@@ -57,7 +58,7 @@ class BatchedBlackBox:
                  check_tau_delay: bool = False, reward: Optional[str] = None, steps_before_reward: int = 199,
                  device=None, learn_sub_trajectories: bool = False, reward_aggregation="sum", verbose: int = 2,
                  collision_penalty: float = 100.0, allow_self_collision: bool = False, allow_wall_collision: bool = False,
-                 env_kwargs: Optional[dict] = None, observations: bool = False):
+                 env_kwargs: Optional[dict] = None, observations: bool = False, rew_fct: str = "simple"):
         """
         trajectory_generator / tracking_controller: the objects the factories return (``get_trajectory_generator``,
         ``get_controller``).  ``replanning_every = n`` is the schedule ``lambda pos, vel, obs, action, t: t % n == 0``
@@ -73,7 +74,9 @@ class BatchedBlackBox:
         the device: a collision ends the episode in the middle of a plan (terminated, black_box_wrapper.py:197-203), so
         ``trajectory_length`` is the executed steps and ``rewards`` aggregates only those.  Holes [B, 3] = (x, width, depth) are given
         to ``reset`` (``sample_hole_reacher_starts`` draws starts and holes as the reference does).  ``step`` also returns
-        ``is_collided`` / ``is_success``.  Collided episodes are done, so the live ones keep lockstep under replanning.
+        ``is_collided`` / ``is_success``.  Collided episodes are done, so the live ones keep lockstep under replanning.  ``rew_fct``
+        is the env's reward function (hole_reacher.py:48-58): "simple" (the default), "vel_acc" or "unbounded" -- the last two with
+        steps_before_reward = 199; "unbounded" keeps its end effector of step 180 in a device buffer of the object, across plans.
 
         ``reset(seed=...)`` draws the episodes on the device the way the registered env's ``reset(seed=...)`` does (one launch,
         mpk_reacher_reset): ``env_kwargs`` holds the env's reset constants -- SimpleReacher ``random_start``, ``target``; HoleReacher
@@ -109,6 +112,10 @@ class BatchedBlackBox:
         relative -- mpk.h, mpk_episode_return).  Falls back to the verbose = 2 launches (and drops their arrays)
         where the fused kernel does not apply: sub-trajectories, a device reward together with a learned phase, drifted episodes.
         """
+        if rew_fct != "simple" and reward != "hole_reacher":
+            raise ValueError(f"rew_fct={rew_fct!r} is HoleReacher's reward function: it needs reward='hole_reacher'")
+        _lib.hole_rew_fct(rew_fct, steps_before_reward)        # (refused before anything is built)
+        self.rew_fct = rew_fct
         self.verbose = int(verbose)
         self._lean_ok = True
         self.traj_gen = trajectory_generator
@@ -146,6 +153,9 @@ class BatchedBlackBox:
         self.hole_task = dict(collision_penalty=float(collision_penalty), allow_self_collision=bool(allow_self_collision),
                               allow_wall_collision=bool(allow_wall_collision))
         self.hole = None
+        # unbounded's stored end effector [B, 2], allocated once: captured episodes keep pointing at it
+        self._reward_state = (torch.zeros((self.B, 2), dtype=torch.float64, device=self.device) if rew_fct == "unbounded"
+                              else None)
         self.reward = reward
         defaults = {"simple_reacher": dict(random_start=True, target=None),
                     "hole_reacher": dict(random_start=True, hole_width=None, hole_x=None, hole_depth=1.0)}.get(reward)
@@ -614,7 +624,7 @@ class BatchedBlackBox:
             self.spec, pos, vel, self.q, self.qd, self.hole, steps_before_reward=self.steps_before_reward,
             replan=(self.traj_steps, self.plan_steps, self.done, self.every, int(mpt), self.horizon),
             condition=self.condition_on_desired, want_actions=full, want_rewards=full, aggregation=self.reward_aggregation,
-            **self.hole_task)
+            rew_fct=self.rew_fct, reward_state=self._reward_state, **self.hole_task)
         if self.condition_on_desired:
             self.condition_pos, self.condition_vel = r["cond_pos"], r["cond_vel"]
         if self.do_replanning:

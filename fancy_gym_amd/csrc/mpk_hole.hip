@@ -1,5 +1,6 @@
 // k_hole_rollout: the step loop of BlackBoxWrapper.step (black_box_wrapper.py:175-203) around the reference's HoleReacher
-// (envs/classic_control/hole_reacher/hole_reacher.py, base_reacher/base_reacher_direct.py:20-38, hr_simple_reward.py:19-53):
+// (envs/classic_control/hole_reacher/hole_reacher.py, base_reacher/base_reacher_direct.py:20-38, and the reward function of rew_fct:
+// hr_simple_reward.py:19-53, hr_dist_vel_acc_reward.py:20-60, hr_unbounded_reward.py:17-60, one instantiation each):
 // controller + clip, the direct-velocity plant, self / wall collision, reward, and the break on collision.  One lane per episode,
 // serial in time; a wave leaves the loop once none of its lanes is live.  float64 without FMA contraction, except where the
 // reference's own numpy flow is float32 (hole_plant_step, mpk_plant.h).
@@ -24,6 +25,7 @@ struct HoleArgs {
     int32_t* n_exec;                 // [B] or nullptr
     uint8_t* collided;               // [B] or nullptr
     uint8_t* success;                // [B] or nullptr
+    double* reward_state;            // [B, 2] unbounded's stored end effector (REW == MPK_HOLE_REW_UNBOUNDED only)
     ReplanDev rp;                    // traj_steps == nullptr: off
     double penalty;
     int allow_self, allow_wall, steps_before_reward, agg;
@@ -98,8 +100,33 @@ __device__ __forceinline__ bool hole_link_hits_wall(double c, double s, double x
     }
 }
 
-// DC: link count compiled in (0: run time, <= kMaxD)
-template <int DC, bool SAMPLED>
+// vel_acc's sum(qd^2) (hr_dist_vel_acc_reward.py:54) in numpy's dtypes: qd is the action, float32 for the velocity / position
+// controllers from the first step on (f32), float64 for the motor controller; np.sum adds in order
+template <int MD>
+__device__ __forceinline__ double hole_vel_cost(bool f32, int D, const double* qd) {
+    if (f32) {
+        float c32 = 0.0f;
+#pragma unroll
+        for (int d = 0; d < MD; ++d) {
+            if (d >= D) continue;
+            const float v = (float)qd[d];
+            c32 = c32 + v * v;
+        }
+        return (double)c32;
+    }
+    double c = 0.0;
+#pragma unroll
+    for (int d = 0; d < MD; ++d)
+        if (d < D) c = c + qd[d] * qd[d];
+    return c;
+}
+
+__device__ __noinline__ double hole_unbounded_dist_reward(double dist, bool hit, bool up, double ey) {
+    return hit ? 0.25 * exp(-dist) : (up ? exp(-dist) : 1.0 - ey);
+}
+
+// DC: link count compiled in (0: run time, <= kMaxD); REW: the reward function, MPK_HOLE_REW_*
+template <int DC, bool SAMPLED, int REW>
 __global__ void __launch_bounds__(64 * kHoleWpb) k_hole_rollout(const HoleArgs a) {
     constexpr int MD = DC > 0 ? DC : kMaxD;
     __shared__ double s_g[4 * kMaxD];
@@ -190,15 +217,48 @@ __global__ void __launch_bounds__(64 * kHoleWpb) k_hole_rollout(const HoleArgs a
         if (!a.allow_wall && !hit) {
             for (int i = 0; i < D && !hit; ++i) hit = hole_link_hits_wall<SAMPLED>(cs[i], sn[i], jx[i], jy[i], hl, hr, floor_y);
         }
-        // reward (hr_simple_reward.py:36-53): the distance term at step steps_before_reward or on collision
-        double dist_cost = 0.0;
-        if (s0 + t == a.steps_before_reward || hit) {
-            const double dx = jx[D] - hx, dy = jy[D] - floor_y;
-            const double dist = sqrt(dx * dx + dy * dy);
-            dist_cost = dist * dist;
-            succ = dist < 0.005 && !hit;
+        double r;
+        if constexpr (REW == MPK_HOLE_REW_VEL_ACC) {
+            // hr_dist_vel_acc_reward.py:40-58: the distance terms at step 199 only -- also after a collision, which ended the episode
+            // before (the latch of :29-38 never sees a second step), so a collision before 199 pays velocity and acceleration alone
+            const double vel_cost = hole_vel_cost<MD>(ctrl != MPK_CTRL_MOTOR, D, qd);
+            double dist_cost = 0.0, coll_cost = 0.0;
+            if (s0 + t == 199) {
+                const double dx = jx[D] - hx, dy = jy[D] - floor_y;
+                const double dist = sqrt(dx * dx + dy * dy);
+                dist_cost = dist * dist;
+                coll_cost = hit ? dist_cost : 0.0;          // collided * collision_dist^2, collision_dist = this step's dist
+                succ = dist < 0.005 && !hit;
+            }
+            // (the fifth feature, time_cost, has factor 0)
+            r = ((dist_cost * -1.0 + vel_cost * -1e-4) + acc_cost * -1e-6) + coll_cost * -a.penalty;
+        } else if constexpr (REW == MPK_HOLE_REW_UNBOUNDED) {
+            // hr_unbounded_reward.py:32-58: store the end effector at step 180 or on collision, pay at step 199 or on collision.  The
+            // stored one lives in reward_state, not in registers (the kernel is at the occupancy-2 limit): step 180 and step 199 may
+            // fall into different plans; a collision pays on its own end effector
+            double* e = a.reward_state + 2 * (size_t)b;
+            const double cx = jx[D], cy = jy[D];
+            if (s0 + t == 180 || hit) { e[0] = cx; e[1] = cy; }
+            double dist_reward = 0.0;
+            if (s0 + t == 199 || hit) {
+                const double ex = hit ? cx : e[0], ey = hit ? cy : e[1];
+                const double dx = ex - hx, dy = ey - floor_y;
+                const double dist = sqrt(dx * dx + dy * dy);
+                dist_reward = hole_unbounded_dist_reward(dist, hit, cy > 0.0, ey);
+                succ = !hit;
+            }
+            r = dist_reward * 1.0 + acc_cost * -5e-6;
+        } else {
+            // reward (hr_simple_reward.py:36-53): the distance term at step steps_before_reward or on collision
+            double dist_cost = 0.0;
+            if (s0 + t == a.steps_before_reward || hit) {
+                const double dx = jx[D] - hx, dy = jy[D] - floor_y;
+                const double dist = sqrt(dx * dx + dy * dy);
+                dist_cost = dist * dist;
+                succ = dist < 0.005 && !hit;
+            }
+            r = (dist_cost * -1.0 + acc_cost * -5e-8) + (hit ? 1.0 : 0.0) * -a.penalty;
         }
-        const double r = (dist_cost * -1.0 + acc_cost * -5e-8) + (hit ? 1.0 : 0.0) * -a.penalty;
         if (a.actions) {
 #pragma unroll
             for (int d = 0; d < MD; ++d)
@@ -253,20 +313,29 @@ __global__ void __launch_bounds__(64 * kHoleWpb) k_hole_rollout(const HoleArgs a
 }
 
 #ifndef MPK_DEVICE_ONLY
+template <int DC, bool SAMPLED>
+static void launch_hole_rew(int rew_fct, dim3 grid, dim3 block, hipStream_t stream, const HoleArgs& a) {
+    if (rew_fct == MPK_HOLE_REW_VEL_ACC) hipLaunchKernelGGL((k_hole_rollout<DC, SAMPLED, MPK_HOLE_REW_VEL_ACC>), grid, block, 0, stream, a);
+    else if (rew_fct == MPK_HOLE_REW_UNBOUNDED)
+        hipLaunchKernelGGL((k_hole_rollout<DC, SAMPLED, MPK_HOLE_REW_UNBOUNDED>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((k_hole_rollout<DC, SAMPLED, MPK_HOLE_REW_SIMPLE>), grid, block, 0, stream, a);
+}
+
 int launch_hole_rollout(const HoleLaunch& h, int B, int T, int D, void* stream, const Tuning& tune) {
     HoleArgs a;
     a.rc = h.rc; a.des_pos = h.des_pos; a.des_vel = h.des_vel; a.Q = h.q; a.QD = h.qd; a.n_steps = h.n_steps; a.step0 = h.step0;
     a.hole = h.hole; a.actions = h.actions; a.rewards = h.rewards; a.ret = h.ret; a.n_exec = h.n_exec; a.collided = h.collided;
-    a.success = h.success; a.rp = h.rp; a.penalty = h.penalty; a.allow_self = h.allow_self; a.allow_wall = h.allow_wall;
+    a.success = h.success; a.reward_state = h.reward_state; a.rp = h.rp; a.penalty = h.penalty; a.allow_self = h.allow_self; a.allow_wall = h.allow_wall;
     a.steps_before_reward = h.steps_before_reward; a.agg = h.agg; a.D = D; a.B = B; a.T = T;
     const bool sampled = tune.hole_sampled == 1;
     const dim3 grid((unsigned)((B + 64 * kHoleWpb - 1) / (64 * kHoleWpb))), block(64 * kHoleWpb);
+    const hipStream_t s = (hipStream_t)stream;
     if (D == 5) {
-        if (sampled) hipLaunchKernelGGL((k_hole_rollout<5, true>), grid, block, 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((k_hole_rollout<5, false>), grid, block, 0, (hipStream_t)stream, a);
+        if (sampled) launch_hole_rew<5, true>(h.rew_fct, grid, block, s, a);
+        else launch_hole_rew<5, false>(h.rew_fct, grid, block, s, a);
     } else {
-        if (sampled) hipLaunchKernelGGL((k_hole_rollout<0, true>), grid, block, 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL((k_hole_rollout<0, false>), grid, block, 0, (hipStream_t)stream, a);
+        if (sampled) launch_hole_rew<0, true>(h.rew_fct, grid, block, s, a);
+        else launch_hole_rew<0, false>(h.rew_fct, grid, block, s, a);
     }
     MPK_LAUNCH_CHECK();
     return MPK_OK;

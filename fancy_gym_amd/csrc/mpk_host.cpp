@@ -1271,6 +1271,15 @@ int mpk_hole_reacher_rollout(mpk_handle hh, const mpk_rollout_cfg* rc, const flo
                              double* qd, const int32_t* n_steps, const int32_t* step0, const mpk_hole_task* task, const double* hole,
                              float* actions, double* rewards, double* ret, int32_t agg, int32_t* n_exec, uint8_t* collided,
                              uint8_t* success, const mpk_replan_state* st, int32_t B, int32_t T, void* stream) {
+    return mpk_hole_reacher_rollout2(hh, rc, des_pos, des_vel, q, qd, n_steps, step0, task, hole, actions, rewards, ret, agg, n_exec,
+                                     collided, success, st, nullptr, B, T, stream);
+}
+
+int mpk_hole_reacher_rollout2(mpk_handle hh, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel, double* q,
+                              double* qd, const int32_t* n_steps, const int32_t* step0, const mpk_hole_task* task, const double* hole,
+                              float* actions, double* rewards, double* ret, int32_t agg, int32_t* n_exec, uint8_t* collided,
+                              uint8_t* success, const mpk_replan_state* st, double* reward_state, int32_t B, int32_t T,
+                              void* stream) {
     if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
     Handle* h = reinterpret_cast<Handle*>(hh);
     if (B < 0 || T < 0) { set_error("B and T must be >= 0"); return MPK_EINVAL; }
@@ -1280,6 +1289,16 @@ int mpk_hole_reacher_rollout(mpk_handle hh, const mpk_rollout_cfg* rc, const flo
     const int D = h->dev.D;
     if (D < 1 || D > kMaxD) { set_error("mpk_hole_reacher_rollout takes 1 .. 16 links"); return MPK_EINVAL; }
     if (!task) { set_error("task is NULL"); return MPK_EINVAL; }
+    if (task->rew_fct < MPK_HOLE_REW_SIMPLE || task->rew_fct > MPK_HOLE_REW_UNBOUNDED) { set_error("unknown rew_fct (MPK_HOLE_REW_*)"); return MPK_EINVAL; }
+    if (task->rew_fct != MPK_HOLE_REW_SIMPLE && task->steps_before_reward != 199) {
+        set_error("rew_fct vel_acc / unbounded pay at the reference's step 199: steps_before_reward must be 199");
+        return MPK_EINVAL;
+    }
+    if (task->rew_fct == MPK_HOLE_REW_UNBOUNDED && !reward_state) {
+        set_error("rew_fct unbounded keeps the end effector of step 180 across plans: it needs reward_state [B, 2] "
+                  "(mpk_hole_reacher_rollout2)");
+        return MPK_EINVAL;
+    }
     if (agg < MPK_AGG_SUM || agg > MPK_AGG_LAST) { set_error("unknown reward aggregation"); return MPK_EINVAL; }
     if (st && (n_steps || step0)) { set_error("with a replanning state the steps and the step counter come from it: n_steps and step0 must be NULL"); return MPK_EINVAL; }
     if (B == 0 || T == 0) return MPK_OK;
@@ -1298,6 +1317,7 @@ int mpk_hole_reacher_rollout(mpk_handle hh, const mpk_rollout_cfg* rc, const flo
     hl.actions = actions; hl.rewards = rewards; hl.ret = ret; hl.n_exec = n_exec; hl.collided = collided; hl.success = success;
     hl.penalty = task->collision_penalty; hl.allow_self = task->allow_self_collision != 0; hl.allow_wall = task->allow_wall_collision != 0;
     hl.steps_before_reward = task->steps_before_reward; hl.agg = agg;
+    hl.rew_fct = task->rew_fct; hl.reward_state = task->rew_fct == MPK_HOLE_REW_UNBOUNDED ? reward_state : nullptr;
     MPK_ON_DEVICE(h->cfg.device);
     return launch_hole_rollout(hl, B, T, D, stream, effective_tuning(h));
 }

@@ -182,6 +182,8 @@ struct HoleLaunch {
     ReplanDev rp;
     double penalty = 0.0;
     int allow_self = 0, allow_wall = 0, steps_before_reward = 0, agg = 0;
+    int rew_fct = 0;                        // MPK_HOLE_REW_*
+    double* reward_state = nullptr;         // [B, 2] unbounded's stored end effector (MPK_HOLE_REW_UNBOUNDED only)
 };
 int launch_hole_rollout(const HoleLaunch& h, int B, int T, int D, void* stream, const Tuning& tune);
 int launch_episode_reset(const double* init_q, const double* init_qd, double* q, double* qd, float* cond_pos,

@@ -574,10 +574,14 @@ class TrajectoryEngine:
                              allow_self_collision: bool = False, allow_wall_collision: bool = False, steps_before_reward: int = 199,
                              n_steps: Optional[torch.Tensor] = None, step0: Optional[torch.Tensor] = None, replan=None,
                              condition: bool = False, want_actions: bool = True, want_rewards: bool = True,
-                             aggregation: Optional[str] = "sum"):
+                             aggregation: Optional[str] = "sum", rew_fct: str = "simple",
+                             reward_state: Optional[torch.Tensor] = None):
         """
-        The HoleReacher step loop on the device (mpk.h: mpk_hole_reacher_rollout; spec.plant 'velocity_direct'): controller, clip,
-        direct-velocity plant, collisions, reward, and the break on collision.  q, qd are updated in place.  ``replan`` =
+        The HoleReacher step loop on the device (mpk.h: mpk_hole_reacher_rollout2; spec.plant 'velocity_direct'): controller, clip,
+        direct-velocity plant, collisions, reward, and the break on collision.  q, qd are updated in place.  ``rew_fct`` is the
+        env's reward function ("simple", "vel_acc", "unbounded"; the last two need steps_before_reward = 199); "unbounded" keeps the
+        end effector of step 180 in ``reward_state`` float64 [B, 2] on the device, read and written -- pass the same tensor to every
+        plan of an episode (a reset need not clear it).  ``replan`` =
         (traj_steps, plan_steps, done, every, max_planning_times, horizon) lets the launch advance the integer state itself and commit
         the break (then n_steps / step0 must be None).  Returns a dict: actions [B, T, D] / rewards [B, T] (or None), ret [B] (or None
         when aggregation is None), n_exec [B] int32, collided / success [B] uint8, and with ``replan`` done (snapshot after the plan)
@@ -593,13 +597,19 @@ class TrajectoryEngine:
         hole = torch.as_tensor(hole, dtype=torch.float64, device=self.device).expand(B, 3).contiguous()
         f = dict(device=self.device)
         act = torch.empty((B, T, D), dtype=torch.float32, **f) if want_actions else None
-        rew = torch.empty((B, T), dtype=torch.float64, **f) if want_rewards else None
+        rews = torch.empty((B, T), dtype=torch.float64, **f) if want_rewards else None
         ret = torch.empty(B, dtype=torch.float64, **f) if aggregation is not None else None
         n_exec = torch.empty(B, dtype=torch.int32, **f)
         coll = torch.empty(B, dtype=torch.uint8, **f)
         succ = torch.empty(B, dtype=torch.uint8, **f)
+        rew = _lib.hole_rew_fct(rew_fct, steps_before_reward)
+        if rew_fct == "unbounded":
+            if reward_state is None:
+                raise ValueError("rew_fct='unbounded' keeps the end effector of step 180 across plans: pass reward_state "
+                                 "(float64 [B, 2] on the device)")
+            assert reward_state.dtype == torch.float64 and reward_state.shape == (B, 2) and reward_state.is_contiguous()
         task = _lib.mpk_hole_task(float(collision_penalty), int(bool(allow_self_collision)), int(bool(allow_wall_collision)),
-                                  int(steps_before_reward), 0)
+                                  int(steps_before_reward), rew)
         st = done_out = cp = cv = None
         if replan is not None:
             traj_steps, plan_steps, done, every, max_planning_times, horizon = replan
@@ -615,11 +625,12 @@ class TrajectoryEngine:
         if step0 is not None:
             step0 = step0.to(device=self.device, dtype=torch.int32).contiguous()
         agg = _lib.AGG_MODES[aggregation] if aggregation is not None else 0
-        _lib.check(self._lib.mpk_hole_reacher_rollout(
+        _lib.check(self._lib.mpk_hole_reacher_rollout2(
             self._h, C.byref(spec.c), _dptr(des_pos), des_vel.data_ptr(), q.data_ptr(), qd.data_ptr(), _dptr(n_steps), _dptr(step0),
-            C.byref(task), hole.data_ptr(), _dptr(act), _dptr(rew), _dptr(ret), agg, n_exec.data_ptr(), coll.data_ptr(),
-            succ.data_ptr(), C.byref(st) if st is not None else None, B, T, self._stream()))
-        return dict(actions=act, rewards=rew, ret=ret, n_exec=n_exec, collided=coll, success=succ, done=done_out, cond_pos=cp,
+            C.byref(task), hole.data_ptr(), _dptr(act), _dptr(rews), _dptr(ret), agg, n_exec.data_ptr(), coll.data_ptr(),
+            succ.data_ptr(), C.byref(st) if st is not None else None, _dptr(reward_state) if rew_fct == "unbounded" else None,
+            B, T, self._stream()))
+        return dict(actions=act, rewards=rews, ret=ret, n_exec=n_exec, collided=coll, success=succ, done=done_out, cond_pos=cp,
                     cond_vel=cv)
 
     def reacher_reset(self, env: str, q: torch.Tensor, qd: torch.Tensor, traj_steps: torch.Tensor, plan_steps: torch.Tensor,

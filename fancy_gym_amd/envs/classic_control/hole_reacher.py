@@ -3,7 +3,7 @@ Host (NumPy) HoleReacher: a planar chain of unit links that must reach into a ho
 itself.  The single-episode counterpart of the device rollout ``TrajectoryEngine.hole_reacher_rollout`` /
 ``BatchedBlackBox(plant="velocity_direct", reward="hole_reacher")`` and the step-based env behind ``fancy/HoleReacher-v0``.
 
-Behaviour follows fancy_gym/envs/classic_control (read, not copied), rew_fct "simple":
+Behaviour follows fancy_gym/envs/classic_control (read, not copied):
   plant        direct velocity control, dt = 0.01: acc = (a - qd) / dt, qd = a, q += dt * qd
                (base_reacher/base_reacher_direct.py:20-38).  numpy's dtypes are part of the behaviour: a float32 action
                (velocity / position controller, float32 action bounds) makes qd float32, and from then on acc and dt * qd are
@@ -12,8 +12,15 @@ Behaviour follows fancy_gym/envs/classic_control (read, not copied), rew_fct "si
   collisions   a joint outside [-pi, pi] or two non-adjacent links crossing (ccw with a 1e-12 margin), unless
                allow_self_collision (base_reacher.py:105-119, utils.py:1-9); any of 100 points per link left / right of the
                hole below 0 or over the hole below -depth, unless allow_wall_collision (hole_reacher/hole_reacher.py:126-179)
-  reward       -5e-8 sum(acc^2) every step; at step 199 or on collision also -|ee - (x, -depth)|^2 and -collision_penalty
-               * collided; is_success = dist < 0.005 and not collided (hole_reacher/hr_simple_reward.py:19-53)
+  reward       rew_fct (hole_reacher.py:48-58), with dist = |ee - (x, -depth)|:
+               "simple"     -5e-8 sum(acc^2) every step; at step 199 or on collision also -dist^2 and -collision_penalty
+                            * collided; is_success = dist < 0.005 and not collided (hole_reacher/hr_simple_reward.py:19-53)
+               "vel_acc"    -1e-4 sum(qd^2) - 1e-6 sum(acc^2) every step; at step 199 only also -dist^2 - collision_penalty
+                            * collided * dist^2 and is_success = dist < 0.005 and not collided.  A collision before step 199
+                            ends the episode without a distance term (hr_dist_vel_acc_reward.py:20-60; collisions latch)
+               "unbounded"  -5e-6 sum(acc^2) every step; the ee is stored at step 180 or on collision; at step 199 or on
+                            collision also 0.25 exp(-|stored - goal|) if collided, else exp(-|stored - goal|) if the current
+                            ee y > 0, else 1 - stored y; is_success = not collided there (hr_unbounded_reward.py:17-60)
   termination  terminated = collided (hole_reacher.py:76-77); the registration's TimeLimit(200) truncates
   reset        hole width ~ U(0.15, 0.5) unless given, x = +-U(width / 2, 3.5) unless given, then the first joint
                ~ U(pi/4, 3pi/4) when random_start (hole_reacher.py:79-101, base_reacher.py:73-93), in that order
@@ -26,6 +33,8 @@ from ... import _gym
 from ...black_box.raw_interface_wrapper import RawInterfaceWrapper
 
 STEPS_BEFORE_REWARD = 199
+STEP_STORE_EE = 180             # hr_unbounded_reward.py:32
+REWARD_FUNCTIONS = ("simple", "vel_acc", "unbounded")
 MAX_EPISODE_STEPS = 200
 POINTS_PER_LINK = 100
 
@@ -88,8 +97,9 @@ class HoleReacherEnv(_gym.Env):
                  hole_width: Optional[float] = 1.0, random_start: bool = False, allow_self_collision: bool = False,
                  allow_wall_collision: bool = False, collision_penalty: float = 1000, rew_fct: str = "simple",
                  render_mode: Optional[str] = None):
-        if rew_fct != "simple":
-            raise ValueError(f"reward function {rew_fct!r} is not available here (only 'simple', the registered one)")
+        if rew_fct not in REWARD_FUNCTIONS:
+            raise ValueError("Unknown reward function {}".format(rew_fct))
+        self.rew_fct = rew_fct
         self.n_links = int(n_links)
         self.initial_x, self.initial_width, self.initial_depth = hole_x, hole_width, hole_depth
         self.random_start = bool(random_start)
@@ -109,6 +119,8 @@ class HoleReacherEnv(_gym.Env):
         self.hole = np.array([0.0, 1.0, 1.0])
         self.steps = 0
         self._rng = np.random.default_rng()
+        self._is_collided = False       # vel_acc: the collision latch of its reward (reset with the episode)
+        self._end_eff_pos = None        # unbounded: the ee of step 180 / of the collision (kept across resets, as the reference's)
         self._update_joints()
 
     # ---- RawInterfaceWrapper plumbing ---------------------------------------------------------------------------------
@@ -140,6 +152,7 @@ class HoleReacherEnv(_gym.Env):
             self.q = self._start_pos.copy()
         self.qd = np.zeros(self.n_links)
         self.steps = 0
+        self._is_collided = False
         self._update_joints()
         return self._observe(), {}
 
@@ -173,8 +186,22 @@ class HoleReacherEnv(_gym.Env):
         self.qd = action
         self.q = self.q + self.dt * self.qd
         self._update_joints()
-        collided = ((not self.allow_self_collision and self.self_collision())
-                    or (not self.allow_wall_collision and self.wall_collision()))
+        if self.rew_fct == "vel_acc":
+            reward, success, collided = self._reward_vel_acc()
+        elif self.rew_fct == "unbounded":
+            reward, success, collided = self._reward_unbounded()
+        else:
+            reward, success, collided = self._reward_simple()
+        self.steps += 1
+        info = {"is_success": success, "is_collided": bool(collided), "end_effector": self.end_effector.copy()}
+        return self._observe(), reward, bool(collided), False, info
+
+    def _collides(self) -> bool:
+        return ((not self.allow_self_collision and self.self_collision())
+                or (not self.allow_wall_collision and self.wall_collision()))
+
+    def _reward_simple(self):
+        collided = self._collides()
         dist_cost, success = 0.0, False
         if self.steps == self.steps_before_reward or collided:
             dist = np.linalg.norm(self.end_effector - self.goal)
@@ -183,9 +210,43 @@ class HoleReacherEnv(_gym.Env):
         acc_cost = np.sum(self.acc ** 2)
         reward = float(np.dot(np.array((dist_cost, acc_cost, float(collided))),
                               np.array((-1, -5e-8, -self.collision_penalty))))
-        self.steps += 1
-        info = {"is_success": success, "is_collided": bool(collided), "end_effector": self.end_effector.copy()}
-        return self._observe(), reward, bool(collided), False, info
+        return reward, success, collided
+
+    def _reward_vel_acc(self):
+        if not self._is_collided:
+            self._is_collided = self._collides()
+            self._collision_dist = np.linalg.norm(self.end_effector - self.goal)
+        dist_cost = collision_cost = 0.0
+        success = False
+        # the distance terms are paid at step 199 only, also after a collision (which has ended the episode before)
+        if self.steps == self.steps_before_reward:
+            dist = np.linalg.norm(self.end_effector - self.goal)
+            success = bool(dist < 0.005 and not self._is_collided)
+            dist_cost = dist ** 2
+            collision_cost = self._is_collided * self._collision_dist ** 2
+        vel_cost = np.sum(self.qd ** 2)
+        acc_cost = np.sum(self.acc ** 2)
+        reward = float(np.dot(np.array((dist_cost, vel_cost, acc_cost, collision_cost, 0.0)),
+                              np.array((-1, -1e-4, -1e-6, -self.collision_penalty, 0))))
+        return reward, success, self._is_collided
+
+    def _reward_unbounded(self):
+        collided = self._collides()
+        if self.steps == STEP_STORE_EE or collided:
+            self._end_eff_pos = self.end_effector.copy()
+        dist_reward, success = 0.0, False
+        if self.steps == self.steps_before_reward or collided:
+            dist = np.linalg.norm(self._end_eff_pos - self.goal)
+            if collided:
+                dist_reward = 0.25 * np.exp(-dist)
+            elif self.end_effector[1] > 0:
+                dist_reward = np.exp(-dist)
+            else:
+                dist_reward = 1 - self._end_eff_pos[1]
+            success = not collided
+        acc_cost = np.sum(self.acc ** 2)
+        reward = float(np.dot(np.array((dist_reward, acc_cost)), np.array((1, -5e-6))))
+        return reward, success, collided
 
 
 class HoleReacherMPWrapper(RawInterfaceWrapper):

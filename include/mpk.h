@@ -523,7 +523,8 @@ int mpk_reacher_rollout(mpk_handle h, const mpk_rollout_cfg* rc, const float* de
 
 /*
  * The step loop of BlackBoxWrapper.step (black_box_wrapper.py:175-203) around the reference's HoleReacher (ABI 4, appended):
- * envs/classic_control/hole_reacher/hole_reacher.py with rew_fct "simple" (hr_simple_reward.py:19-53) on the direct-velocity plant
+ * envs/classic_control/hole_reacher/hole_reacher.py with rew_fct "simple" (hr_simple_reward.py:19-53; task->rew_fct
+ * MPK_HOLE_REW_SIMPLE -- the other two: mpk_hole_reacher_rollout2 below) on the direct-velocity plant
  * (base_reacher/base_reacher_direct.py:20-38, rc->plant_type MPK_PLANT_VELOCITY_DIRECT).  Per executed step t, a = the clipped
  * controller output (motor / velocity / position; the velocity controller reads des_vel only, des_pos may then be NULL):
  *   acc = (a - qd) / dt ; qd = a ; q = q + dt * qd          in numpy's dtypes: with the velocity / position controller the action is
@@ -554,13 +555,45 @@ typedef struct mpk_hole_task {
     double  collision_penalty;       /* hole_reacher.py:20 (fancy/HoleReacher-v0 registers 100) */
     int32_t allow_self_collision;
     int32_t allow_wall_collision;
-    int32_t steps_before_reward;     /* the step that pays the distance: 199 (hr_simple_reward.py:36) */
-    int32_t reserved0;
+    int32_t steps_before_reward;     /* the step that pays the distance: 199 (hr_simple_reward.py:36); must be 199 unless rew_fct is
+                                        MPK_HOLE_REW_SIMPLE */
+    int32_t rew_fct;                 /* MPK_HOLE_REW_* (hole_reacher.py:48-58); was reserved0 = 0 = simple.  Other values: MPK_EINVAL */
 } mpk_hole_task;
 int mpk_hole_reacher_rollout(mpk_handle h, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel, double* q,
                              double* qd, const int32_t* n_steps, const int32_t* step0, const mpk_hole_task* task, const double* hole,
                              float* actions, double* rewards, double* ret, int32_t agg, int32_t* n_exec, uint8_t* collided,
                              uint8_t* success, const mpk_replan_state* st, int32_t B, int32_t T, void* stream);
+
+/*
+ * HoleReacher's other two reward functions (ABI 4, appended), selected by mpk_hole_task.rew_fct.  Everything else -- plant, collisions,
+ * the break on collision, n_exec, collided, ret, the replanning commit -- is mpk_hole_reacher_rollout's.  "step" below is the env
+ * step step0 + t; steps_before_reward must be 199 (the reference's literals 180 and 199).
+ *   MPK_HOLE_REW_SIMPLE     the reward of mpk_hole_reacher_rollout
+ *   MPK_HOLE_REW_VEL_ACC    (hr_dist_vel_acc_reward.py:20-60)
+ *       rewards[b,t] = -1e-4 * sum(qd^2) - 1e-6 * sum(acc^2) - [step == 199] * (dist^2 + collision_penalty * collided * dist^2)
+ *       with qd the velocity after the step (the action), float32 for the velocity / position controller from the episode's first
+ *       step on (numpy: qd is the float32 action), float64 for the motor controller.  The distance terms are paid at step 199 ONLY:
+ *       a collision before step 199 ends the episode with the velocity and acceleration costs alone (the reference's `or
+ *       self._is_collided` is commented out, :40).  success = dist < 0.005 and not collided, at step 199.
+ *   MPK_HOLE_REW_UNBOUNDED  (hr_unbounded_reward.py:17-60; collision_penalty is not used, hole_reacher.py:54-56)
+ *       at step 180 or on collision: e = the end effector (stored in reward_state[b], which outlives the launch: step 180 and the
+ *       paid step may fall into different plans)
+ *       rewards[b,t] = -5e-6 * sum(acc^2) + [step == 199 or collided] * (collided ? 0.25 * exp(-|e - goal|)
+ *                                                                        : ee_y > 0 ? exp(-|e - goal|) : 1 - e_y)
+ *       with ee_y the CURRENT end effector's y; success = not collided, at that step.
+ *   reward_state  dev double [B, 2], read and written: unbounded's stored end effector.  Every episode writes it before it reads it
+ *                 (at step 180 or on the colliding step), so a reset need not clear it.  Required for MPK_HOLE_REW_UNBOUNDED (NULL:
+ *                 MPK_EINVAL), ignored otherwise.  mpk_hole_reacher_rollout is this entry point with reward_state NULL.
+ * exp is the device math library's (last-ulp agreement with numpy); float64, no FMA contraction.
+ */
+#define MPK_HOLE_REW_SIMPLE      0
+#define MPK_HOLE_REW_VEL_ACC     1
+#define MPK_HOLE_REW_UNBOUNDED   2
+int mpk_hole_reacher_rollout2(mpk_handle h, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel, double* q,
+                              double* qd, const int32_t* n_steps, const int32_t* step0, const mpk_hole_task* task, const double* hole,
+                              float* actions, double* rewards, double* ret, int32_t agg, int32_t* n_exec, uint8_t* collided,
+                              uint8_t* success, const mpk_replan_state* st, double* reward_state, int32_t B, int32_t T,
+                              void* stream);
 
 /*
  * BlackBoxWrapper.reset (black_box_wrapper.py:222-229) for B device-resident episodes, one launch: the integer state

@@ -5,7 +5,9 @@ with sampled holes: verbose = 2 (actions + step rewards stored) against the retu
 reference's 100 sampled points ("hole_sampled" 1), and mpk_reacher_rollout at LongSimpleReacher's shape (5 x 200, reward) as the
 yardstick; a one-core NumPy loop over the host env as the CPU baseline.  Every timed call first restores the start state (two
 [B, 5] float64 copies), so that every launch runs the same episodes.  Captured graphs of 20 calls, median of rounds.
-    python tools/hole_reacher_bench.py [B ...] [--cpu N]
+--rew-fct takes a comma-separated list of the env's reward functions (simple, vel_acc, unbounded; default simple): each B then runs
+every one of them back to back.
+    python tools/hole_reacher_bench.py [B ...] [--cpu N] [--rew-fct simple,vel_acc,unbounded]
 """
 import os
 import sys
@@ -57,6 +59,10 @@ def main():
     args = sys.argv[1:]
     if "--cpu" in args:
         del args[args.index("--cpu"):args.index("--cpu") + 2]
+    rew_fcts = ["simple"]
+    if "--rew-fct" in args:
+        rew_fcts = args[args.index("--rew-fct") + 1].split(",")
+        del args[args.index("--rew-fct"):args.index("--rew-fct") + 2]
     batches = [int(a) for a in args if a.isdigit()] or [1024, 4096, 65536, 262144]
     torch.cuda.set_device(0)
     eng = TrajectoryEngine("promp", "linear", "zero_rbf", D, 5, dt=0.01, duration=2.0, tau=2.0, num_basis_zero_start=1, device=0)
@@ -71,14 +77,19 @@ def main():
         hole_d = torch.as_tensor(hole, device="cuda")
         q, qd = torch.empty_like(q0), torch.empty_like(q0)
         goal = torch.zeros((B, 2), dtype=torch.float64, device="cuda")
+        reward_state = torch.zeros((B, 2), dtype=torch.float64, device="cuda")
         stats = {}
-        for name, sampled, full in (("hole, interval, verbose 2", 0, True), ("hole, interval, ret only", 0, False),
-                                    ("hole, sampled, verbose 2", 1, True), ("hole, sampled, ret only", 1, False)):
+        cases = [(rew, name, sampled, full) for name, sampled, full in (
+            ("interval, verbose 2", 0, True), ("interval, ret only", 0, False), ("sampled, verbose 2", 1, True),
+            ("sampled, ret only", 1, False)) for rew in rew_fcts]
+        for rew, name, sampled, full in cases:
             eng.set_option("hole_sampled", sampled)
+            name = f"hole, {name}" + ("" if rew_fcts == ["simple"] else f", {rew}")
 
             def fn():
                 q.copy_(q0); qd.zero_()
-                r = eng.hole_reacher_rollout(vspec, None, vel_d, q, qd, hole_d, want_actions=full, want_rewards=full)
+                r = eng.hole_reacher_rollout(vspec, None, vel_d, q, qd, hole_d, want_actions=full, want_rewards=full, rew_fct=rew,
+                                             reward_state=reward_state)
                 stats["n"], stats["c"] = r["n_exec"], r["collided"]
             us = graph_time(fn) * 1e6
             fn(); torch.cuda.synchronize()
@@ -92,8 +103,9 @@ def main():
         us = graph_time(fr) * 1e6
         print(f"| LongSimpleReacher reacher_rollout (yardstick) | {B} | {us:.1f} | {B / us * 1e6:.3g} | 200 | - |", flush=True)
     n = int(sys.argv[sys.argv.index("--cpu") + 1]) if "--cpu" in sys.argv else 256
-    eps, mean_steps = cpu_loop(n)
-    print(f"| NumPy host env, one core | {n} | - | {eps:.3g} | {mean_steps:.1f} | - |", flush=True)
+    if n > 0:
+        eps, mean_steps = cpu_loop(n)
+        print(f"| NumPy host env, one core | {n} | - | {eps:.3g} | {mean_steps:.1f} | - |", flush=True)
 
 
 if __name__ == "__main__":
