@@ -218,6 +218,13 @@ class BatchedBlackBox:
         self._plans_since_reset = 0
         self._start32 = None        # fp32 image of the plant state at reset (boundary condition of the first plan)
 
+    @classmethod
+    def from_id(cls, id: str, num_envs: int, **kwargs) -> "BatchedBlackBox":
+        """the BatchedBlackBox of a registered MP id (``fancy_ProMP/HoleReacher-v0`` ...), every constant taken from the registry and
+        the env: ``fancy_gym_amd.make_batched`` (batched_make.py), same arguments"""
+        from .batched_make import make_batched
+        return make_batched(id, num_envs, **kwargs)
+
     # ---- episode control ---------------------------------------------------------------------------------------------
     def check_range(self):
         """

@@ -57,6 +57,25 @@ def _verify_time_limit(mp_time_limit, env_time_limit):
             f"The specified 'time_limit' of {env_time_limit}s does not match the duration of {mp_time_limit}s for the MP."
 
 
+def complete_mp_kwargs(black_box_kwargs: MutableMapping, traj_gen_kwargs: MutableMapping, phase_kwargs: MutableMapping,
+                       action_dim: int, dt: float, env_duration) -> None:
+    """the defaults make_bb derives from the env (reference :107-126), filled into the kwarg groups in place; ``env_duration()`` is
+    get_env_duration of the env, asked only when no duration is given.  Shared with the batched front door
+    (batched_make.resolve_batched_config), so that the two cannot drift apart"""
+    traj_gen_kwargs["action_dim"] = traj_gen_kwargs.get("action_dim", action_dim)
+    if black_box_kwargs.get("duration") is None:
+        black_box_kwargs["duration"] = env_duration()
+    if phase_kwargs.get("tau") is None:
+        phase_kwargs["tau"] = black_box_kwargs["duration"]
+    if black_box_kwargs.get("learn_sub_trajectories") is not None:
+        phase_kwargs["learn_tau"] = True       # sub-trajectories must learn their length (reference :115-117)
+    # at least two env steps, otherwise the finite-difference velocity does not exist (reference :119-126)
+    if phase_kwargs.get("learn_tau") and phase_kwargs.get("tau_bound") is None:
+        phase_kwargs["tau_bound"] = [dt * 2, black_box_kwargs["duration"]]
+    if phase_kwargs.get("learn_delay") and phase_kwargs.get("delay_bound") is None:
+        phase_kwargs["delay_bound"] = [0, black_box_kwargs["duration"] - dt * 2]
+
+
 def make_bb(env: Union[object, str], wrappers: Iterable, black_box_kwargs: MutableMapping,
             traj_gen_kwargs: MutableMapping, controller_kwargs: MutableMapping, phase_kwargs: MutableMapping,
             basis_kwargs: MutableMapping, time_limit: int = None, fallback_max_steps: int = None, **kwargs):
@@ -75,18 +94,8 @@ def make_bb(env: Union[object, str], wrappers: Iterable, black_box_kwargs: Mutab
         env = _gym.make(env, **kwargs)
     env = _make_wrapped_env(env=env, wrappers=wrappers, fallback_max_steps=fallback_max_steps)
 
-    traj_gen_kwargs["action_dim"] = traj_gen_kwargs.get("action_dim", int(np.prod(env.action_space.shape)))
-    if black_box_kwargs.get("duration") is None:
-        black_box_kwargs["duration"] = get_env_duration(env)
-    if phase_kwargs.get("tau") is None:
-        phase_kwargs["tau"] = black_box_kwargs["duration"]
-    if sub_trajs is not None:
-        phase_kwargs["learn_tau"] = True       # sub-trajectories must learn their length (reference :115-117)
-    # at least two env steps, otherwise the finite-difference velocity does not exist (reference :119-126)
-    if phase_kwargs.get("learn_tau") and phase_kwargs.get("tau_bound") is None:
-        phase_kwargs["tau_bound"] = [env.dt * 2, black_box_kwargs["duration"]]
-    if phase_kwargs.get("learn_delay") and phase_kwargs.get("delay_bound") is None:
-        phase_kwargs["delay_bound"] = [0, black_box_kwargs["duration"] - env.dt * 2]
+    complete_mp_kwargs(black_box_kwargs, traj_gen_kwargs, phase_kwargs, action_dim=int(np.prod(env.action_space.shape)),
+                       dt=env.dt, env_duration=lambda: get_env_duration(env))
 
     phase_gen = get_phase_generator(**phase_kwargs)
     basis_gen = get_basis_generator(phase_generator=phase_gen, **basis_kwargs)
