@@ -217,6 +217,11 @@ class BatchedBlackBox:
         self._phase_bounds = None   # [2, n_phase] bounds of the learned tau / delay, on the device
         self._plans_since_reset = 0
         self._start32 = None        # fp32 image of the plant state at reset (boundary condition of the first plan)
+        # partial resets (reset(mask=...), reset_done(), autoreset()): episodes no longer share a clock or a first plan.  `_partial`
+        # holds from the first such reset to the next reset of everybody, `partial_resets` (enable_partial_resets) from the start
+        self.partial_resets = False
+        self._partial = False
+        self._cond_buf = None       # partial_resets + condition_on_desired: the condition lives in ONE pair of buffers (capturable)
 
     @classmethod
     def from_id(cls, id: str, num_envs: int, **kwargs) -> "BatchedBlackBox":
@@ -268,16 +273,32 @@ class BatchedBlackBox:
         host = torch.from_numpy(np.array(seeds, dtype=np.uint64).view(np.int64))
         return dict(seeds=host.to(self.device, non_blocking=False))
 
-    def reset(self, init_pos=None, init_vel=None, goal=None, hole=None, *, seed=None, sample: bool = False):
+    def reset(self, init_pos=None, init_vel=None, goal=None, hole=None, *, seed=None, sample: bool = False, mask=None):
         """start B new episodes from plant state (init_pos, init_vel) [B, D] (default zeros); goal [B, 2] for the
         simple_reacher reward, hole [B, 3] = (x, width, depth) for the hole_reacher reward.
 
         With a reacher reward the episodes can be drawn on the device instead (one launch, mpk_reacher_reset): ``seed`` = an int
         starts episode b as ``env.reset(seed=seed + b)`` starts the registered env (gymnasium's vector-env rule), a sequence of B
         ints seeds each episode; ``sample=True`` continues every episode's stream as ``env.reset()`` would.  The start pose, goal /
-        hole and generators stay on the device (``goal`` / ``hole`` attributes, ``rng_state()``)."""
+        hole and generators stay on the device (``goal`` / ``hole`` attributes, ``rng_state()``).
+
+        ``mask`` (bool or uint8 [B], device or host; with ``seed`` or ``sample=True``) restricts the drawn reset to the rows it selects
+        (one launch, mpk_reacher_autoreset): the others keep plant state, counters, goal / hole, generator, condition and reward state
+        bit for bit, and a ``seed`` seeds the selected rows only.  ``reset_done()`` is the form ``mask = done`` that reads nothing back.
+        From then on the episodes do not share a clock: every plan takes its episode's ``init_time = traj_steps * dt`` from the device
+        counters (ProMP: per-episode-phase kernels; DMP / ProDMP: one shared-phase launch per clock value, ``_trajectory``), and the one-launch steps (mpk_replan_step, mpk_episode_return), which need lockstep under replanning, give way to the
+        separate launches -- the same results.  A partial reset synchronises nothing, so it does not run ``check_range()`` for the
+        episodes it ends: call it yourself where a ProDMP plan can leave the table range.  Not with a learned tau / delay (the phase an
+        episode freezes at its first plan would have to be re-frozen row by row: not built)."""
         drawn = seed is not None or bool(sample)
-        seeding = self._seed_args(seed, bool(sample), any(x is not None for x in (init_pos, init_vel, goal, hole))) if drawn else None
+        explicit = any(x is not None for x in (init_pos, init_vel, goal, hole))
+        if mask is not None and not drawn:
+            raise ValueError("reset(mask=...) restricts a reset drawn on the device: pass seed=... or sample=True with it"
+                             + (", not init_pos / init_vel / goal / hole" if explicit else ""))
+        seeding = self._seed_args(seed, bool(sample), explicit) if drawn else None
+        if mask is not None:
+            self._masked_reset(seeding, self._mask_arg(mask))
+            return self.q, self.qd
         if self._plans_since_reset and self._range_can_overflow() and not torch.cuda.is_current_stream_capturing():
             self.check_range()
         elif self._plans_since_reset:
@@ -307,8 +328,14 @@ class BatchedBlackBox:
             self.engine.episode_reset(self.q, self.qd, self.traj_steps, self.plan_steps, self.done, state(init_pos),
                                       state(init_vel), cond=self._start32)
         self.condition_pos = self.condition_vel = None
+        self._partial = self.partial_resets
+        if self._cond_buf is not None:
+            # the first plan's boundary state is the start state: its fp32 image, in the buffers every later step rewrites
+            for dst, src in zip(self._cond_buf, self._start32):
+                dst.copy_(src)
+            self.condition_pos, self.condition_vel = self._cond_buf
         self._frozen_phase = None
-        self._lockstep = None if (self.device_time and self.do_replanning) else 0
+        self._lockstep = None if ((self.device_time or self.partial_resets) and self.do_replanning) else 0
         self._host_plans = 0
         self._plans_since_reset = 0
         self._prev_done = None              # the done bytes before the next plan: none is done (mpk_gate_flags takes NULL)
@@ -333,6 +360,131 @@ class BatchedBlackBox:
         else:
             self.goal = self._task_buf
 
+    # ---- partial resets ----------------------------------------------------------------------------------------------------
+    def enable_partial_resets(self):
+        """episodes will be reset row by row (BatchedVectorEnv(partial_resets=True)): from the next ``reset`` on every step is the
+        same sequence of launches whatever the episodes do -- per-episode plan times from the device counters, the boundary state of
+        a plan read from the plant state (or, with ``condition_on_desired``, from one pair of buffers that steps and resets rewrite
+        in place) -- so that a step can be captured with replanning"""
+        self._refuse_partial()
+        self.partial_resets = True
+        if self.condition_on_desired and self._cond_buf is None:
+            self._cond_buf = tuple(torch.zeros((self.B, self.D), dtype=torch.float32, device=self.device) for _ in range(2))
+
+    def _refuse_partial(self):
+        if self.reward not in ("simple_reacher", "hole_reacher"):
+            raise ValueError("partial resets draw a reacher's episodes: they need reward='simple_reacher' or 'hole_reacher'")
+        if self._n_phase and not self.learn_sub_trajectories:
+            raise ValueError("partial resets with a learned tau / delay are not built: the phase an episode freezes at its first plan "
+                             "would have to be re-frozen row by row")
+        if self.learn_sub_trajectories:
+            raise ValueError("partial resets with learn_sub_trajectories are not built")
+
+    def _mask_arg(self, mask) -> torch.Tensor:
+        mask = torch.as_tensor(mask)
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"mask must be bool or uint8, got {mask.dtype}")
+        if tuple(mask.shape) != (self.B,):
+            raise ValueError(f"mask must be [{self.B}], got {tuple(mask.shape)}")
+        return mask.to(self.device).contiguous()
+
+    def _autoreset_launch(self, seeding: dict, mask, observe: bool):
+        """the one launch of every partial reset (mpk_reacher_autoreset) and the host bookkeeping that goes with it"""
+        self._refuse_partial()
+        if self._rng is None and not seeding:
+            raise ValueError("a partial reset continues the streams of a seeded reset: call reset(seed=...) first")
+        if self._rng is None:
+            self._rng = torch.zeros((self.B, 5), dtype=torch.int64, device=self.device)
+        if self._task_buf is None:
+            raise ValueError("a partial reset needs episodes drawn on the device: call reset(seed=...) first")
+        if self._plans_since_reset:
+            self.engine.poll_fault()
+        # a reset row's next plan starts from its start state: the kernel writes the fp32 image where that plan reads its condition
+        cond = (self.condition_pos, self.condition_vel) if self.condition_pos is not None else self._start32
+        obs_kw = dict(col_mask=self._obs_mask, time_div=self._obs_time_div) if observe else {}
+        res = self.engine.reacher_autoreset(self.reward, self.q, self.qd, self.traj_steps, self.plan_steps, self.done, self._rng,
+                                            self._task_buf, mask=mask, observe=observe, cond=cond, **obs_kw, **seeding,
+                                            **self.env_kwargs)
+        self._partial = True
+        self._lockstep = None
+        self._prev_done_known = False       # the snapshot of the last step no longer shows the reset rows
+        return res
+
+    def _masked_reset(self, seeding: dict, mask):
+        if (self.hole if self.reward == "hole_reacher" else self.goal) is not self._task_buf or self._task_buf is None:
+            raise ValueError("reset(mask=...) / reset_done() continue episodes that were drawn on the device: call reset(seed=...) first")
+        self._autoreset_launch(seeding, mask, observe=False)
+
+    def reset_done(self):
+        """``reset(sample=True, mask=done)`` without reading ``done`` back: every finished episode starts anew from its own stream,
+        the others run on (one launch)"""
+        self._seed_args(None, True, False)
+        self._masked_reset({}, None)
+        return self.q, self.qd
+
+    def autoreset(self):
+        """what a vector step does after ``step``, in one launch (``observations=True``): (final_obs, obs, reset_mask) -- the
+        observation of the state the step left, ``reset_done()``, and the observation after it (the new episode's first one for the
+        rows that were reset, ``final_obs`` for the others); reset_mask bool [B]"""
+        if not self.observations:
+            raise ValueError("autoreset() needs BatchedBlackBox(..., observations=True)")
+        self._seed_args(None, True, False)
+        if (self.hole if self.reward == "hole_reacher" else self.goal) is not self._task_buf or self._task_buf is None:
+            raise ValueError("autoreset() continues episodes that were drawn on the device: call reset(seed=...) first")
+        final, obs, reset_mask = self._autoreset_launch({}, None, observe=True)
+        return final, obs, reset_mask.view(torch.bool)
+
+    def _plan_condition(self):
+        """(cond_pos, cond_vel) float32 [B, D] of the next plan: the stored desired state, else the plant state -- right after a reset
+        of everybody its fp32 image, which the reset launch wrote (no cast launches)"""
+        if self.condition_pos is not None:
+            return self.condition_pos, self.condition_vel
+        if self._start32 is not None and self._plans_since_reset == 1 and not self._partial:
+            return self._start32
+        return self.q.float(), self.qd.float()
+
+    def _store_condition(self, cond_pos, cond_vel):
+        if self._cond_buf is None:
+            self.condition_pos, self.condition_vel = cond_pos, cond_vel
+            return
+        self._cond_buf[0].copy_(cond_pos)
+        self._cond_buf[1].copy_(cond_vel)
+        self.condition_pos, self.condition_vel = self._cond_buf
+
+    def _plan_time(self):
+        """init_time of the next plan: 0 without replanning, the shared clock while the episodes move in lockstep, else per episode"""
+        if not self.do_replanning:
+            return 0.0
+        if self._lockstep is None:
+            return (self.traj_steps.double() * self.dt).float()
+        return float(self._lockstep * self.dt)
+
+    def _on_clock_grid(self) -> bool:
+        """every live episode's step counter is a multiple of ``every``: a plan ends at the next multiple, at the step limit or at a
+        collision, and the last two end the episode (whose reset starts it at 0).  Not with a plan cap, the validity gate or plans
+        shorter than the schedule's period -- their segments can end anywhere"""
+        return (self.do_replanning and not math.isfinite(self.max_planning_times) and self.pos_limits is None
+                and self.every <= self.T and not self.learn_sub_trajectories)
+
+    def _trajectory(self, params, cond_pos, cond_vel):
+        """the plan (pos, vel) [B, T, D].  In lockstep one launch on the shared clock.  Out of lockstep ProMP takes the per-episode
+        init_time directly: its per-episode-phase kernels give the bits of the shared-phase ones.  DMP's and ProDMP's do not (serial
+        recurrence instead of the response rows; regrouped boundary terms: ~1e-6 of the scale apart), and a single-episode wrapper's
+        plans are shared-phase plans, so where the live counters lie on the clock grid {0, every, 2 every, ...} the batch is planned
+        once per clock value with the shared-phase kernels and every episode keeps the rows of its own clock -- horizon / every
+        launches and in-place selects, nothing read back, the same bits as B single-episode wrappers.  (Rows that are done and were
+        not reset execute nothing; off the grid they keep the plan of clock 0.)"""
+        t = self._plan_time()
+        if not isinstance(t, torch.Tensor) or self.engine.mp_type == "promp" or not self._on_clock_grid():
+            return self.engine.trajectory(params, cond_pos, cond_vel, t)
+        pos, vel = self.engine.trajectory(params, cond_pos, cond_vel, 0.0)
+        for clock in range(self.every, self.horizon, self.every):
+            p, v = self.engine.trajectory(params, cond_pos, cond_vel, float(clock * self.dt))
+            own = (self.traj_steps == clock).view(self.B, 1, 1)
+            torch.where(own, p, pos, out=pos)
+            torch.where(own, v, vel, out=vel)
+        return pos, vel
+
     def rng_state(self, episodes=None) -> list:
         """numpy's ``bit_generator.state`` of the chosen episodes' generators after the last device-drawn reset (synchronises)"""
         if self._rng is None:
@@ -354,13 +506,16 @@ class BatchedBlackBox:
     def _add_observations(self, out: Dict[str, torch.Tensor], start) -> Dict[str, torch.Tensor]:
         """``obs`` and, given the plan-start state, ``step_observations`` (the replay of the executed steps) of a finished step"""
         if start is not None and "des_pos" in out:
-            seg = out["trajectory_length"]
-            task = self.hole if self.reward == "hole_reacher" else self.goal
-            out["step_observations"] = self.engine.reacher_step_observations(
-                self.reward, self.spec, out["des_pos"], out["des_vel"], start[0], start[1], task, seg, self.traj_steps - seg,
-                time_div=self._obs_time_div)
+            out["step_observations"] = self._add_step_observations(out, start)
         out["obs"] = self.observe()
         return out
+
+    def _add_step_observations(self, out, start) -> torch.Tensor:
+        seg = out["trajectory_length"]
+        task = self.hole if self.reward == "hole_reacher" else self.goal
+        return self.engine.reacher_step_observations(
+            self.reward, self.spec, out["des_pos"], out["des_vel"], start[0], start[1], task, seg, self.traj_steps - seg,
+            time_div=self._obs_time_div)
 
     @property
     def current_pos(self) -> torch.Tensor:
@@ -400,11 +555,7 @@ class BatchedBlackBox:
         params = self._plan_params(params)
         cond_pos = self.condition_pos if self.condition_pos is not None else self.q.float()
         cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
-        if self.do_replanning and self._lockstep is None:
-            init_time = (self.traj_steps.double() * self.dt).float()     # per-episode
-        else:
-            init_time = float(self._lockstep * self.dt) if self.do_replanning else 0.0
-        pos, vel = self.engine.trajectory(params, cond_pos, cond_vel, init_time)
+        pos, vel = self._trajectory(params, cond_pos, cond_vel)
         if self.learn_sub_trajectories and self.engine.mp_type == "promp":
             # ProMP's velocity is the forward difference of its positions with the LAST row repeating the one before
             # (mp_pytorch; make_env_helpers.py:119-122): the last row of a sub-trajectory of T_b steps is row T_b - 2, not the
@@ -460,9 +611,7 @@ class BatchedBlackBox:
         gate = self._gate(params)           # (the RAW action: the reference checks tau / delay before clipping, table_tennis_env.py:305-306)
         was_done = self._was_done() if gate is not None else None
         params = self._plan_params(params)
-        first = self._start32 is not None and self._plans_since_reset == 1    # q, qd untouched since reset
-        cond_pos = self.condition_pos if self.condition_pos is not None else (self._start32[0] if first else self.q.float())
-        cond_vel = self.condition_vel if self.condition_vel is not None else (self._start32[1] if first else self.qd.float())
+        cond_pos, cond_vel = self._plan_condition()
         init_time = float(self._lockstep * self.dt) if self.do_replanning else 0.0
         mpt = self.max_planning_times if math.isfinite(self.max_planning_times) else 2 ** 31 - 1
         r = self.engine.replan_step(params, cond_pos, cond_vel, self.spec, self.q, self.qd, self.traj_steps,
@@ -470,7 +619,7 @@ class BatchedBlackBox:
                                     init_time=init_time, condition=self.condition_on_desired, gate=gate)
         seg = r["seg_len"]
         if self.condition_on_desired:
-            self.condition_pos, self.condition_vel = r["cond_pos"], r["cond_vel"]
+            self._store_condition(r["cond_pos"], r["cond_vel"])
         if self.do_replanning:
             # the host mirrors the integer rule -- with the gate too: an invalid plan FINISHES its episode, so every episode
             # that is still live has executed exactly the segments the rule gives (nothing is read back from the device)
@@ -503,9 +652,7 @@ class BatchedBlackBox:
         gate = self._gate(params)
         was_done = self._was_done() if gate is not None else None
         params = self._plan_params(params)
-        first = self._start32 is not None and self._plans_since_reset == 1
-        cond_pos = self.condition_pos if self.condition_pos is not None else (self._start32[0] if first else self.q.float())
-        cond_vel = self.condition_vel if self.condition_vel is not None else (self._start32[1] if first else self.qd.float())
+        cond_pos, cond_vel = self._plan_condition()
         init_time = float(self._lockstep * self.dt) if self.do_replanning else 0.0
         mpt = self.max_planning_times if math.isfinite(self.max_planning_times) else 2 ** 31 - 1
         try:
@@ -518,7 +665,7 @@ class BatchedBlackBox:
             self._lean_ok = False
             return None
         if self.condition_on_desired:
-            self.condition_pos, self.condition_vel = r["cond_pos"], r["cond_vel"]
+            self._store_condition(r["cond_pos"], r["cond_vel"])
         if self.do_replanning:
             self._lockstep += self._host_segment()
         done = r["done"].view(torch.bool)
@@ -545,7 +692,7 @@ class BatchedBlackBox:
             # (black_box_wrapper.py:197-203 stores the desired state only inside the break branch -- terminated, truncated, or the
             # replanning schedule.  With sub-trajectories the schedule is never true: a plan that ends before the episode does leaves
             # condition_pos None, and the next one starts from env.current_pos / current_vel -- self.q / self.qd here.)
-            self.condition_pos, self.condition_vel = self.engine.condition_gather(pos, vel, seg)
+            self._store_condition(*self.engine.condition_gather(pos, vel, seg))
         if self.do_replanning and self._lockstep is not None:
             if self.pos_limits is None:
                 # no validity gate: every episode follows the same integer sequence, which the host can mirror without
@@ -618,13 +765,11 @@ class BatchedBlackBox:
 
     def _step_hole(self, params) -> Dict[str, torch.Tensor]:
         """HoleReacher: the plan, then ONE rollout launch that advances the integer state, executes until the plan ends or the
-        arm collides, and commits the break (mpk_hole_reacher_rollout); at verbose < 2 it stores nothing per step"""
+        arm collides, and commits the break (mpk_hole_reacher_rollout); at verbose < 2 it stores nothing per step.  The plan's
+        init_time is the shared clock while the episodes move in lockstep, per episode from the device counters after a partial reset"""
         params = self._plan_params(params)
-        first = self._start32 is not None and self._plans_since_reset == 1
-        cond_pos = self.condition_pos if self.condition_pos is not None else (self._start32[0] if first else self.q.float())
-        cond_vel = self.condition_vel if self.condition_vel is not None else (self._start32[1] if first else self.qd.float())
-        init_time = float(self._lockstep * self.dt) if self.do_replanning else 0.0
-        pos, vel = self.engine.trajectory(params, cond_pos, cond_vel, init_time)
+        cond_pos, cond_vel = self._plan_condition()
+        pos, vel = self._trajectory(params, cond_pos, cond_vel)
         mpt = self.max_planning_times if math.isfinite(self.max_planning_times) else 2 ** 31 - 1
         full = self.verbose >= 2
         r = self.engine.hole_reacher_rollout(
@@ -633,8 +778,8 @@ class BatchedBlackBox:
             condition=self.condition_on_desired, want_actions=full, want_rewards=full, aggregation=self.reward_aggregation,
             rew_fct=self.rew_fct, reward_state=self._reward_state, **self.hole_task)
         if self.condition_on_desired:
-            self.condition_pos, self.condition_vel = r["cond_pos"], r["cond_vel"]
-        if self.do_replanning:
+            self._store_condition(r["cond_pos"], r["cond_vel"])
+        if self.do_replanning and self._lockstep is not None:
             # a collision finishes its episode: every live episode executed the segment of the integer rule
             self._lockstep += self._host_segment()
         self._prev_done, self._prev_done_known = r["done"], True

@@ -161,7 +161,9 @@ def make_batched(id: str, num_envs: int, *, device=None, verbose: Optional[int] 
     return BatchedBlackBox(traj_gen, controller, int(num_envs), device=device, observations=observations, **cfg)
 
 
-def make_batched_vec(id: str, num_envs: int, **kwargs):
-    """``make_batched`` behind the gymnasium vector-env contract: a ``BatchedVectorEnv`` (same arguments)"""
+def make_batched_vec(id: str, num_envs: int, *, partial_resets: bool = False, **kwargs):
+    """``make_batched`` behind the gymnasium vector-env contract: a ``BatchedVectorEnv`` (same arguments).  ``partial_resets=True``:
+    every episode is reset on its own in the step that ends it (one launch, mpk_reacher_autoreset) instead of all together when the
+    last one ends -- what replanning ids (``black_box_kwargs={"replanning_every": n}``) need, and what lets their steps be captured"""
     from .batched_vector import BatchedVectorEnv
-    return BatchedVectorEnv(make_batched(id, num_envs, **kwargs))
+    return BatchedVectorEnv(make_batched(id, num_envs, **kwargs), partial_resets=partial_resets)

@@ -35,18 +35,33 @@ class BatchedVectorEnv:
 
     With replanning (``black_box_kwargs={"replanning_every": n}``) a step does not end the episode: ``step`` returns the time-aware
     observation of the running episodes and no ``final_obs``, and the autoreset happens in the step in which the LAST episodes reach
-    their step limit -- all episodes are reset together.  Partial resets (an episode that collided early starts anew while the others
-    run on) are not built: such an episode stays done, executes nothing (``trajectory_length`` 0, reward 0) and is reset with the rest.
-    Sub-trajectory learning is refused for the same reason (its episodes end at different steps).
+    their step limit -- all episodes are reset together: in this default mode an episode that collided early stays done, executes
+    nothing (``trajectory_length`` 0, reward 0) and is reset with the rest.
+
+    ``partial_resets=True`` is the vector-env contract per sub-env: an episode that ended in this step starts anew in this step, from
+    its own stream, while the others run on.  ``step`` is then ``BatchedBlackBox.step`` plus ONE launch (mpk_reacher_autoreset: last
+    observation, reset of the finished rows, next observation).  ``obs`` holds the first observation of the new episode for the rows
+    that were reset and the step's observation for the others; ``info["final_obs"]`` [num_envs, n] (the step's observation of every
+    row) and ``info["_final_obs"]`` (bool [num_envs]: the rows that were reset, for which ``final_obs`` is the finished episode's last
+    observation) are present in every step.  Nothing in the step is decided on the host, so ``capture()`` works with replanning too.
+    The episodes leave lockstep: every plan takes its ``init_time`` from its episode's device counter, and the SimpleReacher ids step
+    through the separate plan / rollout launches instead of their one-launch step (same results).  Without replanning every step ends
+    every episode and the mode returns exactly what the default mode returns, plus the all-true ``_final_obs``.  A partial reset
+    synchronises nothing: ``bb.check_range()`` (ProDMP) is the caller's to call.
+
+    Sub-trajectory learning is refused in both modes (its episodes end at different steps, and a partial reset of them is not built).
 
     No host synchronisation beyond what ``BatchedBlackBox.step`` / ``reset`` do themselves.
     """
 
-    def __init__(self, bb: BatchedBlackBox):
+    def __init__(self, bb: BatchedBlackBox, partial_resets: bool = False):
         if not bb.observations:
             raise ValueError("BatchedVectorEnv needs a BatchedBlackBox with observations=True")
         if bb.learn_sub_trajectories:
             raise ValueError("learn_sub_trajectories ends episodes at different steps: partial resets are not built")
+        self.partial_resets = bool(partial_resets)
+        if self.partial_resets:
+            bb.enable_partial_resets()
         self.bb = bb
         self.num_envs = bb.B
         self.single_observation_space = bb.observation_space
@@ -81,6 +96,14 @@ class BatchedVectorEnv:
         if not self._seeded:
             raise ValueError("step before reset: call reset(seed=int) first")
         bb = self.bb
+        if self.partial_resets:
+            # (the step's own observation launch is the autoreset's final_obs: not launched twice)
+            out = bb._step(actions, True)
+            info = {k: v for k, v in out.items() if k not in _NOT_INFO}
+            if bb._obs_start is not None and "des_pos" in out:
+                info["step_observations"] = bb._add_step_observations(out, bb._obs_start)
+            info["final_obs"], obs, info["_final_obs"] = bb.autoreset()
+            return obs, out["rewards"], out["terminated"], out["truncated"], info
         out = bb.step(actions)
         info = {k: v for k, v in out.items() if k not in _NOT_INFO}
         obs = out["obs"]
@@ -93,7 +116,8 @@ class BatchedVectorEnv:
     def capture(self) -> "VectorStepGraph":
         """one whole vector step (plan, rollout, last observation, reset draw, first observation) as one hipGraph: write the actions
         into the returned object's ``actions`` buffer, ``replay()``, read the tuple ``step`` would have returned (the same tensors every
-        replay).  After ``reset(seed=...)``; not with replanning, where the host decides per step whether the episodes are over."""
+        replay).  After ``reset(seed=...)``; in the default mode not with replanning, where the host decides per step whether the
+        episodes are over -- ``partial_resets=True`` has no such decision and captures a replanning step as well."""
         return VectorStepGraph(self)
 
     def close(self):
@@ -108,7 +132,7 @@ class VectorStepGraph:
         bb = env.bb
         if not env._seeded:
             raise ValueError("capture() continues the streams of a seeded reset: call reset(seed=...) first")
-        if bb.do_replanning:
+        if bb.do_replanning and not env.partial_resets:
             raise ValueError("capture() holds a fixed sequence of launches: with replanning the host decides whether a step resets")
         if bb.spec is None:
             raise ValueError("capture() needs a device plant")
@@ -119,6 +143,8 @@ class VectorStepGraph:
         state = [bb.q, bb.qd, bb.traj_steps, bb.plan_steps, bb.done, bb._rng, bb._task_buf, *bb._start32]
         if bb._reward_state is not None:
             state.append(bb._reward_state)
+        if bb._cond_buf is not None:
+            state.extend(bb._cond_buf)
         snapshot = [t.clone() for t in state]
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))

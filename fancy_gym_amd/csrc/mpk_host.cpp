@@ -1336,11 +1336,10 @@ int mpk_episode_reset(mpk_handle hh, const double* init_q, const double* init_qd
                                 stream);
 }
 
-int mpk_reacher_reset(mpk_handle hh, const mpk_reacher_reset_task* task, const uint64_t* seeds, mpk_nprng_state* rng, double* q,
-                      double* qd, float* cond_pos, float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done,
-                      double* task_out, int32_t B, void* stream) {
-    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
-    Handle* h = reinterpret_cast<Handle*>(hh);
+// the checks mpk_reacher_reset and mpk_reacher_autoreset share, and the launch record of the reset; "what" names the entry point
+static int reset_launch(const mpk_reacher_reset_task* task, const uint64_t* seeds, mpk_nprng_state* rng, double* q, double* qd,
+                        float* cond_pos, float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done, double* task_out,
+                        int32_t B, ResetLaunch* out) {
     if (!task) { set_error("task is NULL"); return MPK_EINVAL; }
     if (B < 0) { set_error("B must be >= 0"); return MPK_EINVAL; }
     if (task->env != MPK_RESET_SIMPLE_REACHER && task->env != MPK_RESET_HOLE_REACHER) { set_error("unknown reset env"); return MPK_EINVAL; }
@@ -1360,12 +1359,23 @@ int mpk_reacher_reset(mpk_handle hh, const mpk_reacher_reset_task* task, const u
     if (B == 0) return MPK_OK;
     if (!rng || !q || !qd || !traj_steps || !plan_steps || !done || !task_out) { set_error("NULL buffer"); return MPK_EINVAL; }
     if ((cond_pos == nullptr) != (cond_vel == nullptr)) { set_error("cond_pos and cond_vel go together"); return MPK_EINVAL; }
-    ResetLaunch l;
+    ResetLaunch& l = *out;
     l.seeds = seeds; l.seed_base = task->seed_base; l.seeded_base = task->seed_base_given != 0; l.rng = rng;
     l.q = q; l.qd = qd; l.cond_pos = cond_pos; l.cond_vel = cond_vel; l.traj_steps = traj_steps; l.plan_steps = plan_steps; l.done = done;
     l.task_out = task_out; l.target[0] = task->target[0]; l.target[1] = task->target[1];
     l.hole_width = task->hole_width; l.hole_x = task->hole_x; l.hole_depth = task->hole_depth;
     l.env = task->env; l.random_start = task->random_start != 0;
+    return MPK_OK;
+}
+
+int mpk_reacher_reset(mpk_handle hh, const mpk_reacher_reset_task* task, const uint64_t* seeds, mpk_nprng_state* rng, double* q,
+                      double* qd, float* cond_pos, float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done,
+                      double* task_out, int32_t B, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    ResetLaunch l;
+    const int r = reset_launch(task, seeds, rng, q, qd, cond_pos, cond_vel, traj_steps, plan_steps, done, task_out, B, &l);
+    if (r != MPK_OK || B == 0) return r;
     MPK_ON_DEVICE(h->cfg.device);
     return launch_reacher_reset(l, B, h->dev.D, stream, h->d_fault);
 }
@@ -1405,6 +1415,31 @@ int mpk_reacher_observation(mpk_handle hh, const mpk_obs_cfg* cfg, const double*
     if (!q || !qd || !task || !steps || !out) { set_error("mpk_reacher_observation: NULL buffer"); return MPK_EINVAL; }
     MPK_ON_DEVICE(h->cfg.device);
     return launch_reacher_obs(l, q, qd, task, steps, out, B, stream);
+}
+
+int mpk_reacher_autoreset(mpk_handle hh, const mpk_reacher_reset_task* task, const mpk_obs_cfg* cfg, const uint64_t* seeds,
+                          mpk_nprng_state* rng, double* q, double* qd, float* cond_pos, float* cond_vel, int32_t* traj_steps,
+                          int32_t* plan_steps, uint8_t* done, double* task_io, const uint8_t* mask, uint8_t* reset_mask,
+                          float* final_obs, float* obs, int32_t B, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if ((cfg == nullptr) != (final_obs == nullptr) || (cfg == nullptr) != (obs == nullptr)) {
+        set_error("mpk_reacher_autoreset: cfg, final_obs and obs go together (all NULL: a masked reset alone)");
+        return MPK_EINVAL;
+    }
+    ObsLaunch o;
+    if (cfg) {
+        const int r = obs_layout(h, cfg, "mpk_reacher_autoreset", &o);
+        if (r != MPK_OK) return r;
+        if (task && cfg->env != task->env) { set_error("mpk_reacher_autoreset: cfg->env must be task->env"); return MPK_EINVAL; }
+        if (final_obs == obs) { set_error("mpk_reacher_autoreset: final_obs and obs must be two buffers"); return MPK_EINVAL; }
+    }
+    if (reset_mask && reset_mask == done) { set_error("mpk_reacher_autoreset: reset_mask must not be done"); return MPK_EINVAL; }
+    ResetLaunch l;
+    const int r = reset_launch(task, seeds, rng, q, qd, cond_pos, cond_vel, traj_steps, plan_steps, done, task_io, B, &l);
+    if (r != MPK_OK || B == 0) return r;
+    MPK_ON_DEVICE(h->cfg.device);
+    return launch_reacher_autoreset(l, cfg ? &o : nullptr, mask, reset_mask, final_obs, obs, B, h->dev.D, stream, h->d_fault);
 }
 
 int mpk_reacher_step_observations(mpk_handle hh, const mpk_obs_cfg* cfg, const mpk_rollout_cfg* rc, const float* des_pos,

@@ -219,6 +219,10 @@ int launch_reacher_obs(const ObsLaunch& l, const double* q, const double* qd, co
 int launch_reacher_step_obs(const ObsLaunch& l, const RolloutDev& rc, const float* des_pos, const float* des_vel, const double* q0,
                             const double* qd0, const double* task, const int32_t* n_exec, const int32_t* step0, float* out,
                             double* q_end, double* qd_end, int B, int T, void* stream);
+// mpk_reacher_autoreset (mpk_autoreset.hip): last observation, reset of the selected episodes, next observation in one launch
+// (o == nullptr: the masked reset alone)
+int launch_reacher_autoreset(const ResetLaunch& l, const ObsLaunch* o, const uint8_t* mask, uint8_t* reset_mask, float* final_obs,
+                             float* obs, int B, int D, void* stream, int* fault);
 int launch_gate_flags(const uint8_t* valid, const uint8_t* was_done, const uint8_t* done, uint8_t* terminated, uint8_t* truncated, int B,
                       void* stream);
 int launch_replan_advance(int32_t* traj_steps, int32_t* plan_steps, int32_t* seg_len, uint8_t* done, int every,

@@ -14,8 +14,10 @@
 //   mpk_phase_fused.hip  per-episode phase: the fused entry points (actions, closed loop, replanning step, verbose < 2 step, validity gate)
 //   mpk_rollout.hip      rollout kernels
 //   mpk_hole.hip         HoleReacher: direct-velocity plant, collisions, reward, break on collision
+//   mpk_reacher_env.h    the reacher envs' draw programs and observation row, shared by the three units below
 //   mpk_reset.hip        reacher resets: numpy's generator per episode (mpk_nprng.h), seeded / continued draws
 //   mpk_obs.hip          reacher observations: current rows, per-step rows replayed on the stored plan (mpk_plant.h)
+//   mpk_autoreset.hip    per-episode autoreset of a vector step: last observation, masked reset, next observation (mpk_reacher_env.h)
 //   mpk_misc.hip         integer state, reset, gather, validity, self-tests, trace readout
 #define MPK_AMALGAMATED 1
 #include "mpk_traj_family.hip"
@@ -29,4 +31,5 @@
 #include "mpk_hole.hip"
 #include "mpk_reset.hip"
 #include "mpk_obs.hip"
+#include "mpk_autoreset.hip"
 #include "mpk_misc.hip"

@@ -9,77 +9,13 @@
 //
 // Rows are assembled in LDS in output order and leave as contiguous runs: k_reacher_obs stores the [n_b, n_out] block of its
 // workgroup's episodes, k_reacher_step_obs the S-step pieces [S, n_out] of its wave's 64 episodes, one piece after the other.
-#include "mpk_dev.h"
+#include "mpk_reacher_env.h"
 #include "mpk_plant.h"
 
 namespace mpk {
 
-constexpr int kObsCols = 64;             // >= 3 * kMaxD + 4 full columns + time awareness
 constexpr int kObsBlock = 128;           // k_reacher_obs: episodes (= lanes) per workgroup
 constexpr int kStepObsLds = 8192;        // k_reacher_step_obs: floats of row image per wave (32 KB)
-
-struct ObsLayout {
-    uint64_t mask;                       // full columns written (bit c = column c), never 0 here
-    double time_div;                     // > 0: the time-awareness column
-    int env, D, n_full, n_out;
-};
-
-// s_pos[c] = output position of full column c (c = n_full: the time-awareness column), -1 = not written
-__device__ __forceinline__ void obs_positions(const ObsLayout& L, int* s_pos) {
-    for (int c = threadIdx.x; c <= L.n_full; c += blockDim.x) {
-        int p = -1;
-        if (c < L.n_full) {
-            if ((L.mask >> c) & 1ull) p = __popcll(L.mask & ((1ull << c) - 1ull));
-        } else if (L.time_div > 0.0) {
-            p = L.n_out - 1;
-        }
-        s_pos[c] = p;
-    }
-}
-
-// one observation row into r[0 .. n_out) (output order), from the plant state after `steps` env steps
-template <int MD>
-__device__ __forceinline__ void obs_row(const ObsLayout& L, const int* s_pos, const double* q, const double* qd, double gx, double gy,
-                                        double width, int steps, float* r) {
-    const int D = MD < kMaxD ? MD : L.D;
-    auto put = [&](int c, double v) {
-        const int p = s_pos[c];                  // the same for every lane: a broadcast read, a uniform branch
-        if (p >= 0) r[p] = (float)v;
-    };
-    double ex = 0.0, ey = 0.0, ang = 0.0;
-#pragma unroll
-    for (int d = 0; d < MD; ++d) {
-        if (d >= D) continue;
-        double s, c;
-        sincos(q[d], &s, &c);
-        put(d, c);
-        put(D + d, s);
-        put(2 * D + d, qd[d]);
-        ang = d == 0 ? q[0] : ang + q[d];        // np.cumsum(joint angles)
-        sincos(ang, &s, &c);
-        ex = ex + c;                             // joints[0] + np.cumsum(link vectors): joints[0] = 0
-        ey = ey + s;
-    }
-    int k = 3 * D;
-    if (L.env == MPK_RESET_HOLE_REACHER) put(k++, width);
-    put(k, ex - gx);
-    put(k + 1, ey - gy);
-    put(k + 2, (double)steps);
-    put(L.n_full, (double)steps / L.time_div);  // TimeAwareObservation: t / max_episode_steps (t = the env's step counter)
-}
-
-// goal of episode b: SimpleReacher task [B, 2] = goal; HoleReacher task [B, 3] = (x, width, depth), goal (x, -depth)
-__device__ __forceinline__ void obs_task(const ObsLayout& L, const double* task, int b, double& gx, double& gy, double& width) {
-    if (L.env == MPK_RESET_HOLE_REACHER) {
-        gx = task[3 * (size_t)b];
-        width = task[3 * (size_t)b + 1];
-        gy = -task[3 * (size_t)b + 2];
-    } else {
-        gx = task[2 * (size_t)b];
-        gy = task[2 * (size_t)b + 1];
-        width = 0.0;
-    }
-}
 
 struct ObsArgs {
     ObsLayout L;
@@ -220,12 +156,6 @@ __global__ void __launch_bounds__(64) k_reacher_step_obs(const StepObsArgs a) {
 }
 
 #ifndef MPK_DEVICE_ONLY
-static ObsLayout obs_layout(const ObsLaunch& l) {
-    ObsLayout L;
-    L.env = l.env; L.D = l.D; L.n_full = l.n_full; L.n_out = l.n_out; L.mask = l.mask; L.time_div = l.time_div;
-    return L;
-}
-
 int launch_reacher_obs(const ObsLaunch& l, const double* q, const double* qd, const double* task, const int32_t* steps, float* out,
                        int B, void* stream) {
     ObsArgs a;

@@ -4,103 +4,21 @@
 //   HoleReacher   hole_reacher.py:60-71,79-101, base_reacher.py:73-93: [reseed] width, direction + x, depth, first joint
 //   SimpleReacher simple_reacher.py:46-54,85-96, base_reacher.py:73-93: goal (discarded), [reseed] first joint, goal, [reseed]
 //                 first joint
-#include "mpk_dev.h"
-#include "mpk_nprng.h"
+#include "mpk_reacher_env.h"
 
 namespace mpk {
-
-constexpr int kGoalDrawCap = 4096;      // rejection rounds of one goal draw (1.27 expected); reaching it raises the fault word
-
-struct ResetArgs {
-    const uint64_t* seeds;              // [B] or nullptr
-    uint64_t seed_base;
-    int seeded_base;                    // seeds == nullptr: 1 = episode b is seeded with seed_base + b, 0 = continue
-    NpRng* rng;                         // [B]
-    double* q;
-    double* qd;
-    float* cond_pos;
-    float* cond_vel;
-    int32_t* traj_steps;
-    int32_t* plan_steps;
-    uint8_t* done;
-    double* task_out;                   // [B, 2] goal or [B, 3] hole
-    int* fault;
-    double target0, target1, hole_width, hole_x, hole_depth;
-    int env, random_start, B, D;
-};
-
-// SimpleReacherEnv._generate_goal (simple_reacher.py:85-96): U(-L, L, size=2) until |g| < L, from g = (L, L); L = sum of n_links
-// unit lengths.  |g| as np.linalg.norm of a 2-vector: sqrt(x*x + y*y).  false: the cap was reached (g is then NaN)
-__device__ __forceinline__ bool draw_goal(NpRng& r, double L, double& gx, double& gy) {
-    gx = L; gy = L;
-    for (int it = 0; it < kGoalDrawCap; ++it) {
-        if (sqrt(gx * gx + gy * gy) < L) return true;
-        gx = np_uniform(r, -L, L);
-        gy = np_uniform(r, -L, L);
-    }
-    if (sqrt(gx * gx + gy * gy) < L) return true;
-    gx = gy = __builtin_nan("");
-    return false;
-}
 
 __global__ void __launch_bounds__(256) k_reacher_reset(const ResetArgs a) {
     const long bl = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (bl >= a.B) return;
     const int b = (int)bl;
-    const bool seeded = a.seeds != nullptr || a.seeded_base;
-    const uint64_t seed = a.seeds ? a.seeds[b] : a.seed_base + (uint64_t)b;
-    NpRng r = seeded ? np_seed(seed) : a.rng[b];
-    constexpr double kLo = M_PI / 4.0, kHi = 3.0 * M_PI / 4.0;     // np.pi / 4, 3 * np.pi / 4 (base_reacher.py:81)
-    double q0;
-    bool ok = true;
-    if (a.env == MPK_RESET_HOLE_REACHER) {
-        // _generate_hole (hole_reacher.py:79-101): a NaN kwarg is None (drawn)
-        const double width = isnan(a.hole_width) ? np_uniform(r, 0.15, 0.5) : a.hole_width;
-        double x = a.hole_x;
-        if (isnan(x)) {
-            const double direction = np_choice_pm1(r);
-            x = direction * np_uniform(r, width / 2.0, 3.5);
-        }
-        const double depth = isnan(a.hole_depth) ? np_uniform(r, 1.0, 1.0) : a.hole_depth;   // uniform(1, 1): still one draw
-        q0 = a.random_start ? np_uniform(r, kLo, kHi) : M_PI / 2.0;                           // _start_pos (base_reacher.py:33)
-        a.task_out[3 * (size_t)b] = x;
-        a.task_out[3 * (size_t)b + 1] = width;
-        a.task_out[3 * (size_t)b + 2] = depth;
-    } else {
-        // SimpleReacherEnv.reset (simple_reacher.py:46-54): goal, reset(seed), goal, reset(seed)
-        const bool drawn = isnan(a.target0);
-        const double L = (double)a.D;
-        double gx = a.target0, gy = a.target1;
-        if (drawn && !seeded) ok &= draw_goal(r, L, gx, gy);     // the first goal: overwritten below, its draws are consumed
-        if (a.random_start) (void)np_uniform(r, kLo, kHi);
-        if (drawn) ok &= draw_goal(r, L, gx, gy);
-        if (seeded) r = np_seed(seed);
-        q0 = a.random_start ? np_uniform(r, kLo, kHi) : 0.0;     // SimpleReacher's _start_pos is zeros (simple_reacher.py:29)
-        a.task_out[2 * (size_t)b] = gx;
-        a.task_out[2 * (size_t)b + 1] = gy;
-    }
-    if (!ok) wave_gave_up(a.fault, 512);
-    a.rng[b] = r;
-    // what k_episode_reset writes: the arm straight from q0, at rest, counters zero, the fp32 image of the plant state
-    const size_t row = (size_t)b * a.D;
-    for (int d = 0; d < a.D; ++d) {
-        const double v = d == 0 ? q0 : 0.0;
-        a.q[row + d] = v;
-        a.qd[row + d] = 0.0;
-        if (a.cond_pos) { a.cond_pos[row + d] = (float)v; a.cond_vel[row + d] = 0.0f; }
-    }
-    a.traj_steps[b] = 0; a.plan_steps[b] = 0; a.done[b] = 0;
+    double t0, t1, t2;
+    (void)reset_episode(a, b, t0, t1, t2);       // mpk_reacher_env.h: the draw program and the row's writes
 }
 
 #ifndef MPK_DEVICE_ONLY
 int launch_reacher_reset(const ResetLaunch& l, int B, int D, void* stream, int* fault) {
-    static_assert(sizeof(NpRng) == 40, "mpk_nprng_state is 5 x uint64");
-    ResetArgs a;
-    a.seeds = l.seeds; a.seed_base = l.seed_base; a.seeded_base = l.seeded_base; a.rng = reinterpret_cast<NpRng*>(l.rng);
-    a.q = l.q; a.qd = l.qd; a.cond_pos = l.cond_pos; a.cond_vel = l.cond_vel; a.traj_steps = l.traj_steps;
-    a.plan_steps = l.plan_steps; a.done = l.done; a.task_out = l.task_out; a.fault = fault;
-    a.target0 = l.target[0]; a.target1 = l.target[1]; a.hole_width = l.hole_width; a.hole_x = l.hole_x; a.hole_depth = l.hole_depth;
-    a.env = l.env; a.random_start = l.random_start; a.B = B; a.D = D;
+    const ResetArgs a = reset_args(l, B, D, fault);
     hipLaunchKernelGGL(k_reacher_reset, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     MPK_LAUNCH_CHECK();
     return MPK_OK;

@@ -644,6 +644,18 @@ class TrajectoryEngine:
         ``seed_base`` seeds episode b with seed_base + b, ``seeds`` (uint64 [B] on the device, as int64) one seed per episode; neither
         continues every episode's stream.  The kwargs are the env's: None = drawn.  Everything in place; allocates nothing.
         """
+        t = self._reset_task(env, q, qd, traj_steps, plan_steps, done, rng, task_out, seeds, seed_base, random_start, target,
+                             hole_width, hole_x, hole_depth)
+        B = q.shape[0]
+        cp, cv = cond if cond is not None else (None, None)
+        _lib.check(self._lib.mpk_reacher_reset(self._h, C.byref(t), _dptr(seeds), rng.data_ptr(), q.data_ptr(), qd.data_ptr(),
+                                               _dptr(cp), _dptr(cv), traj_steps.data_ptr(), plan_steps.data_ptr(), done.data_ptr(),
+                                               task_out.data_ptr(), B, self._stream()))
+
+    @staticmethod
+    def _reset_task(env, q, qd, traj_steps, plan_steps, done, rng, task_out, seeds, seed_base, random_start, target, hole_width, hole_x,
+                    hole_depth):
+        """the argument checks of a reacher reset and its mpk_reacher_reset_task"""
         B, D = q.shape
         for t, dt_ in ((q, torch.float64), (qd, torch.float64), (traj_steps, torch.int32), (plan_steps, torch.int32),
                        (done, torch.uint8), (rng, torch.int64), (task_out, torch.float64)):
@@ -660,10 +672,44 @@ class TrajectoryEngine:
         t.hole_width, t.hole_x, t.hole_depth = opt(hole_width), opt(hole_x), opt(hole_depth)
         t.seed_base_given = int(seed_base is not None)
         t.seed_base = int(seed_base) if seed_base is not None else 0
+        return t
+
+    def reacher_autoreset(self, env: str, q: torch.Tensor, qd: torch.Tensor, traj_steps: torch.Tensor, plan_steps: torch.Tensor,
+                          done: torch.Tensor, rng: torch.Tensor, task: torch.Tensor, *, mask: Optional[torch.Tensor] = None,
+                          observe: bool = True, col_mask: int = 0, time_div: float = 0.0, seeds=None, seed_base: Optional[int] = None,
+                          random_start: bool = True, target=None, hole_width=None, hole_x=None, hole_depth=None,
+                          cond: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, reset_mask: Optional[torch.Tensor] = None,
+                          out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """
+        The per-episode autoreset of a vector step in one launch (mpk.h: mpk_reacher_autoreset): ``final_obs`` [B, n_out] = the
+        observation ``reacher_observation`` gives on entry; the episodes selected by ``mask`` (uint8 / bool [B] on the device; None:
+        the ``done`` bytes) are reset as ``reacher_reset`` resets them (same arguments, in place; ``task`` is read and written); ``obs``
+        = the new episode's first observation for them, ``final_obs`` for the others.  Returns (final_obs, obs, reset_mask) -- uint8
+        [B], 1 = reset --; ``observe=False`` is the masked reset alone and returns (None, None, reset_mask).  ``out`` = (final_obs,
+        obs) and ``reset_mask`` are allocated unless given.
+        """
+        t = self._reset_task(env, q, qd, traj_steps, plan_steps, done, rng, task, seeds, seed_base, random_start, target, hole_width,
+                             hole_x, hole_depth)
+        B = q.shape[0]
+        if mask is not None:
+            mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+            assert mask.dtype == torch.uint8 and mask.is_contiguous() and tuple(mask.shape) == (B,) and mask.device == q.device
+        if reset_mask is None:
+            reset_mask = torch.empty(B, dtype=torch.uint8, device=self.device)
+        assert reset_mask.dtype == torch.uint8 and reset_mask.is_contiguous() and tuple(reset_mask.shape) == (B,)
+        c = final = obs = None
+        if observe:
+            c, n_out = self._obs_cfg(env, col_mask, time_div)
+            final, obs = out if out is not None else (torch.empty((B, n_out), dtype=torch.float32, device=self.device) for _ in range(2))
+            for o in (final, obs):
+                assert o.dtype == torch.float32 and o.is_contiguous() and tuple(o.shape) == (B, n_out)
+            assert final.data_ptr() != obs.data_ptr() or B == 0
         cp, cv = cond if cond is not None else (None, None)
-        _lib.check(self._lib.mpk_reacher_reset(self._h, C.byref(t), _dptr(seeds), rng.data_ptr(), q.data_ptr(), qd.data_ptr(),
-                                               _dptr(cp), _dptr(cv), traj_steps.data_ptr(), plan_steps.data_ptr(), done.data_ptr(),
-                                               task_out.data_ptr(), B, self._stream()))
+        _lib.check(self._lib.mpk_reacher_autoreset(
+            self._h, C.byref(t), C.byref(c) if c is not None else None, _dptr(seeds), rng.data_ptr(), q.data_ptr(), qd.data_ptr(),
+            _dptr(cp), _dptr(cv), traj_steps.data_ptr(), plan_steps.data_ptr(), done.data_ptr(), task.data_ptr(), _dptr(mask),
+            reset_mask.data_ptr(), _dptr(final), _dptr(obs), B, self._stream()))
+        return final, obs, reset_mask
 
     def _obs_cfg(self, env: str, col_mask: int, time_div: float):
         c = _lib.mpk_obs_cfg()

@@ -826,6 +826,30 @@ void mpk_comm_destroy(mpk_comm c);
 /* Name of the kernel the last mpk_trajectory* call launched for its main pass (for profiling). */
 const char* mpk_last_kernel(mpk_handle h);
 
+/*
+ * The per-episode autoreset of a vector step over B device-resident reacher episodes, in ONE launch (ABI 4, appended): what
+ * mpk_reacher_observation, a reset of SOME episodes and mpk_reacher_observation again give, bit for bit (the kernels share the draw
+ * programs and the observation row as one text).  Per episode b:
+ *   final_obs[b]  the observation of the state as it is on entry (the row mpk_reacher_observation writes for cfg: same col_mask, same
+ *                 steps / time_div column, steps = traj_steps[b]);
+ *   selected      mask[b] != 0, or with mask == NULL done[b] != 0.  A selected episode runs the draw program of task->env on its own
+ *                 generator -- continuing rng[b], or reseeded from seeds / task->seed_base exactly as mpk_reacher_reset does -- and gets
+ *                 what mpk_reacher_reset writes for its row: q, qd, traj_steps = plan_steps = 0, done = 0, the goal / hole row of
+ *                 task_io, the advanced generator, and the fp32 image of the start state in cond_pos / cond_vel when given;
+ *                 reset_mask[b] = 1, obs[b] = the NEW episode's reset observation;
+ *   otherwise     nothing of episode b changes, reset_mask[b] = 0, obs[b] = final_obs[b].
+ * The goal-draw cap and its fault word (role 512) apply as in mpk_reacher_reset.
+ *   cfg, final_obs, obs   all three given, or all three NULL: the call is then a masked reset alone.  final_obs, obs dev float
+ *                         [B, n_out], two different buffers.
+ *   mask        dev uint8 [B] or NULL; reset_mask dev uint8 [B] or NULL (it may be `mask` itself, not `done`).
+ *   task_io     dev double [B, 2] goal / [B, 3] hole: read for final_obs, written for the selected episodes.
+ * Every other argument as for mpk_reacher_reset.  Allocates nothing and synchronises nothing (it can be captured in a graph).
+ */
+int mpk_reacher_autoreset(mpk_handle h, const mpk_reacher_reset_task* task, const mpk_obs_cfg* cfg, const uint64_t* seeds,
+                          mpk_nprng_state* rng, double* q, double* qd, float* cond_pos, float* cond_vel, int32_t* traj_steps,
+                          int32_t* plan_steps, uint8_t* done, double* task_io, const uint8_t* mask, uint8_t* reset_mask,
+                          float* final_obs, float* obs, int32_t B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
