@@ -111,6 +111,13 @@ class mpk_obs_cfg(C.Structure):
     ]
 
 
+class mpk_env_step_task(C.Structure):
+    _fields_ = [
+        ("env", C.c_int32), ("n_links", C.c_int32), ("dt", C.c_double), ("max_episode_steps", C.c_int32), ("autoreset", C.c_int32),
+        ("hole", mpk_hole_task), ("reserved", C.c_int64 * 2),
+    ]
+
+
 class mpk_replan_state(C.Structure):
     _fields_ = [
         ("traj_steps", C.c_void_p), ("plan_steps", C.c_void_p), ("done", C.c_void_p), ("seg_len", C.c_void_p),
@@ -190,6 +197,8 @@ SIGNATURES = {
     "mpk_last_kernel": (C.c_char_p, [_vp]),
     "mpk_reacher_autoreset": (C.c_int, [_vp, C.POINTER(mpk_reacher_reset_task), C.POINTER(mpk_obs_cfg), _vp, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "mpk_reacher_env_step": (C.c_int, [_vp, C.POINTER(mpk_env_step_task), C.POINTER(mpk_reacher_reset_task), _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -197,9 +206,9 @@ _lib: Optional[C.CDLL] = None
 # the files libmpk.so is built from, in the order mpk_source_hash() is defined over (include/mpk.h)
 _ROOT = os.path.dirname(_HERE)
 KERNEL_UNITS = ("mpk_traj_family.hip", "mpk_traj_ring.hip", "mpk_episode.hip", "mpk_traj_launch.hip", "mpk_traj_wide.hip", "mpk_traj_phase.hip",
-                "mpk_phase_fused.hip", "mpk_rollout.hip", "mpk_hole.hip", "mpk_reset.hip", "mpk_obs.hip", "mpk_autoreset.hip", "mpk_misc.hip")          # translation units of the device code (mpk_traj_family.hip: once per MP type)
+                "mpk_phase_fused.hip", "mpk_rollout.hip", "mpk_hole.hip", "mpk_reset.hip", "mpk_obs.hip", "mpk_autoreset.hip", "mpk_env_step.hip", "mpk_misc.hip")          # translation units of the device code (mpk_traj_family.hip: once per MP type)
 KERNEL_HEADERS = ("mpk_dev.h", "mpk_tile.h", "mpk_traj_tiles.h", "mpk_traj_stream.h", "mpk_traj_flat.h", "mpk_traj_ring.h", "mpk_traj_quad.h",
-                  "mpk_traj_pipe.h", "mpk_reward.h", "mpk_phase.h", "mpk_trace_reader.h", "mpk_nprng.h", "mpk_plant.h", "mpk_reacher_env.h")
+                  "mpk_traj_pipe.h", "mpk_reward.h", "mpk_phase.h", "mpk_trace_reader.h", "mpk_nprng.h", "mpk_plant.h", "mpk_reacher_env.h", "mpk_hole_geom.h")
 SOURCE_FILES = (os.path.join(_ROOT, "include", "mpk.h"), os.path.join(_HERE, "csrc", "mpk_internal.h"),
                 os.path.join(_HERE, "csrc", "mpk_host.cpp")) + \
     tuple(os.path.join(_HERE, "csrc", f) for f in KERNEL_HEADERS + KERNEL_UNITS)

@@ -167,3 +167,51 @@ def make_batched_vec(id: str, num_envs: int, *, partial_resets: bool = False, **
     last one ends -- what replanning ids (``black_box_kwargs={"replanning_every": n}``) need, and what lets their steps be captured"""
     from .batched_vector import BatchedVectorEnv
     return BatchedVectorEnv(make_batched(id, num_envs, **kwargs), partial_resets=partial_resets)
+
+
+def resolve_batched_step_config(id: str, **env_kwargs) -> Dict[str, Any]:
+    """
+    Everything ``BatchedStepEnv`` needs for the registered STEP-BASED reacher id ``id`` (``fancy/SimpleReacher-v0``,
+    ``fancy/LongSimpleReacher-v0``, ``fancy/HoleReacher-v0``), derived: ``env`` ("simple_reacher" / "hole_reacher"), ``n_links``, ``dt``,
+    ``max_episode_steps`` (the registered TimeLimit), ``act_bound`` (the env's max_torque / max_vel, from its action space),
+    ``steps_before_reward``, for HoleReacher ``rew_fct`` / ``collision_penalty`` / ``allow_self_collision`` / ``allow_wall_collision``,
+    and the reset constants ``env_kwargs`` -- all read from a throw-away ``_gym.make(id, **env_kwargs)`` instance and the registry.
+    ValueError, naming the offender, for a movement-primitive id (``make_batched_vec`` steps those), an id whose env is not one of the
+    two reacher families, and an env kwarg the env does not take.
+    """
+    spec = _registered(id)
+    reg = dict(spec.kwargs or {})
+    env_cls = _entry_point(spec)
+    if env_cls is bb_env_constructor or "underlying_id" in reg:
+        raise ValueError(f"{id!r} is a movement-primitive id: a step of it is a whole plan -- use make_batched_vec({id!r}, ...); "
+                         f"make_batched_step_vec takes the step-based id ({reg.get('underlying_id', 'fancy/...')!r})")
+    if inspect.isclass(env_cls):
+        taken = inspect.signature(env_cls.__init__).parameters
+        if not any(p.kind is p.VAR_KEYWORD for p in taken.values()):
+            unknown = sorted(set(env_kwargs) - set(taken))
+            if unknown:
+                raise ValueError(f"{env_cls.__name__} ({id}) takes no {', '.join(repr(k) for k in unknown)}")
+    raw = _gym.make(id, **env_kwargs)
+    env = raw.unwrapped
+    try:
+        task = _reacher_task(env)
+    except ValueError as e:
+        raise ValueError(f"{id!r}: {e}") from None
+    if raw.spec.max_episode_steps is None:
+        raise ValueError(f"{id!r} is registered without max_episode_steps: the device step needs the TimeLimit")
+    high = np.asarray(env.action_space.high, np.float64)
+    out: Dict[str, Any] = dict(id=id, env=task.pop("reward"), n_links=int(env.n_links), dt=float(env.dt),
+                               max_episode_steps=int(raw.spec.max_episode_steps), act_bound=float(high[0]))
+    task.pop("plant")
+    out.update(task)
+    return out
+
+
+def make_batched_step_vec(id: str, num_envs: int, *, device=None, autoreset: bool = True, **env_kwargs):
+    """The ``BatchedStepEnv`` of ``num_envs`` episodes of the registered step-based reacher id ``id`` -- the batched, device-resident
+    ``_gym.make(id, **env_kwargs)`` behind the vector-env contract: one launch per environment step (mpk_reacher_env_step), same-step
+    autoreset (``autoreset=False``: ended rows stay where they are).  Every constant comes from ``resolve_batched_step_config``."""
+    from .batched_step import BatchedStepEnv
+    cfg = resolve_batched_step_config(id, **env_kwargs)
+    cfg.pop("id")
+    return BatchedStepEnv(int(num_envs), device=device, autoreset=autoreset, **cfg)

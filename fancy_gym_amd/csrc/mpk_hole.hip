@@ -5,6 +5,7 @@
 // serial in time; a wave leaves the loop once none of its lanes is live.  float64 without FMA contraction, except where the
 // reference's own numpy flow is float32 (hole_plant_step, mpk_plant.h).
 #include "mpk_dev.h"
+#include "mpk_hole_geom.h"
 #include "mpk_plant.h"
 #include "mpk_reward.h"
 
@@ -32,98 +33,7 @@ struct HoleArgs {
     int D, B, T;
 };
 
-constexpr int kHolePoints = 100;     // np.linspace(0, 1, 100) points per link (hole_reacher.py:149)
 constexpr int kHoleWpb = 4;          // waves per workgroup
-
-// np.linspace(0, 1, 100)[j]: j * (1 / 99), the last point exactly 1
-__device__ __forceinline__ double hole_t(int j) { return j == kHolePoints - 1 ? 1.0 : (double)j * (1.0 / 99.0); }
-
-// ccw / intersect of envs/classic_control/utils.py:1-9
-__device__ __forceinline__ bool hole_ccw(double ax, double ay, double bx, double by, double cx, double cy) {
-    return (cy - ay) * (bx - ax) - (by - ay) * (cx - ax) > 1e-12;
-}
-__device__ __forceinline__ bool hole_intersect(double ax, double ay, double bx, double by, double cx, double cy, double dx, double dy) {
-    return hole_ccw(ax, ay, cx, cy, dx, dy) != hole_ccw(bx, by, cx, cy, dx, dy) &&
-           hole_ccw(ax, ay, bx, by, cx, cy) != hole_ccw(ax, ay, bx, by, dx, dy);
-}
-
-// The point coordinates of a link are v_j = fl(fl(a * t_j) + b), monotone in j (t_j increases, rounding is monotone), so
-// {j : v_j < h} (LESS) and {j : v_j > h} are a prefix or a suffix of [0, 100).  The crossing index comes from one division; the
-// exact predicate at the neighbouring indices then moves it to the true boundary (a step or two; any start would do).
-template <bool LESS>
-__device__ __forceinline__ void hole_interval(double a, double b, double h, int& lo, int& hi) {
-    auto pred = [&](int j) {
-        const double v = a * hole_t(j) + b;
-        return LESS ? v < h : v > h;
-    };
-    if (!(a > 0.0) && !(a < 0.0)) {                  // a constant coordinate, or NaN (no comparison holds)
-        const bool all = pred(0);
-        lo = 0; hi = all ? kHolePoints : 0;
-        return;
-    }
-    const double x = fmin(fmax((h - b) / a * 99.0, 0.0), (double)kHolePoints);   // NaN -> 0
-    int g = (int)ceil(x);
-    if ((a > 0.0) == LESS) {                        // true, then false: [0, g)
-        while (g > 0 && !pred(g - 1)) --g;
-        while (g < kHolePoints && pred(g)) ++g;
-        lo = 0; hi = g;
-    } else {                                        // false, then true: [g, 100)
-        while (g > 0 && pred(g - 1)) --g;
-        while (g < kHolePoints && !pred(g)) ++g;
-        lo = g; hi = kHolePoints;
-    }
-}
-
-// check_wall_collision (hole_reacher.py:151-179) for the link from (x0, y0) along (c, s): any point left of the hole and below 0,
-// right of the hole and below 0, or over the hole and below -depth
-template <bool SAMPLED>
-__device__ __forceinline__ bool hole_link_hits_wall(double c, double s, double x0, double y0, double hl, double hr, double floor_y) {
-    if constexpr (SAMPLED) {
-        bool hit = false;
-        for (int j = 0; j < kHolePoints; ++j) {
-            const double t = hole_t(j);
-            const double px = c * t + x0, py = s * t + y0;
-            hit |= (px < hl && py < 0.0) || (px > hr && py < 0.0) || (px > hl && px < hr && py < floor_y);
-        }
-        return hit;
-    } else {
-        int l0, l1, r0, r1, a0, a1, b0, b1, y0l, y0h, yd0, yd1;
-        hole_interval<true>(s, y0, 0.0, y0l, y0h);
-        hole_interval<true>(c, x0, hl, l0, l1);
-        if (max(l0, y0l) < min(l1, y0h)) return true;
-        hole_interval<false>(c, x0, hr, r0, r1);
-        if (max(r0, y0l) < min(r1, y0h)) return true;
-        hole_interval<true>(s, y0, floor_y, yd0, yd1);
-        hole_interval<false>(c, x0, hl, a0, a1);
-        hole_interval<true>(c, x0, hr, b0, b1);
-        return max(max(a0, b0), yd0) < min(min(a1, b1), yd1);
-    }
-}
-
-// vel_acc's sum(qd^2) (hr_dist_vel_acc_reward.py:54) in numpy's dtypes: qd is the action, float32 for the velocity / position
-// controllers from the first step on (f32), float64 for the motor controller; np.sum adds in order
-template <int MD>
-__device__ __forceinline__ double hole_vel_cost(bool f32, int D, const double* qd) {
-    if (f32) {
-        float c32 = 0.0f;
-#pragma unroll
-        for (int d = 0; d < MD; ++d) {
-            if (d >= D) continue;
-            const float v = (float)qd[d];
-            c32 = c32 + v * v;
-        }
-        return (double)c32;
-    }
-    double c = 0.0;
-#pragma unroll
-    for (int d = 0; d < MD; ++d)
-        if (d < D) c = c + qd[d] * qd[d];
-    return c;
-}
-
-__device__ __noinline__ double hole_unbounded_dist_reward(double dist, bool hit, bool up, double ey) {
-    return hit ? 0.25 * exp(-dist) : (up ? exp(-dist) : 1.0 - ey);
-}
 
 // DC: link count compiled in (0: run time, <= kMaxD); REW: the reward function, MPK_HOLE_REW_*
 template <int DC, bool SAMPLED, int REW>

@@ -1339,7 +1339,7 @@ int mpk_episode_reset(mpk_handle hh, const double* init_q, const double* init_qd
 // the checks mpk_reacher_reset and mpk_reacher_autoreset share, and the launch record of the reset; "what" names the entry point
 static int reset_launch(const mpk_reacher_reset_task* task, const uint64_t* seeds, mpk_nprng_state* rng, double* q, double* qd,
                         float* cond_pos, float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done, double* task_out,
-                        int32_t B, ResetLaunch* out) {
+                        int32_t B, ResetLaunch* out, bool with_plan_state = true) {
     if (!task) { set_error("task is NULL"); return MPK_EINVAL; }
     if (B < 0) { set_error("B must be >= 0"); return MPK_EINVAL; }
     if (task->env != MPK_RESET_SIMPLE_REACHER && task->env != MPK_RESET_HOLE_REACHER) { set_error("unknown reset env"); return MPK_EINVAL; }
@@ -1357,7 +1357,7 @@ static int reset_launch(const mpk_reacher_reset_task* task, const uint64_t* seed
         return MPK_EINVAL;
     }
     if (B == 0) return MPK_OK;
-    if (!rng || !q || !qd || !traj_steps || !plan_steps || !done || !task_out) { set_error("NULL buffer"); return MPK_EINVAL; }
+    if (!rng || !q || !qd || !traj_steps || (with_plan_state && (!plan_steps || !done)) || !task_out) { set_error("NULL buffer"); return MPK_EINVAL; }
     if ((cond_pos == nullptr) != (cond_vel == nullptr)) { set_error("cond_pos and cond_vel go together"); return MPK_EINVAL; }
     ResetLaunch& l = *out;
     l.seeds = seeds; l.seed_base = task->seed_base; l.seeded_base = task->seed_base_given != 0; l.rng = rng;
@@ -1440,6 +1440,58 @@ int mpk_reacher_autoreset(mpk_handle hh, const mpk_reacher_reset_task* task, con
     if (r != MPK_OK || B == 0) return r;
     MPK_ON_DEVICE(h->cfg.device);
     return launch_reacher_autoreset(l, cfg ? &o : nullptr, mask, reset_mask, final_obs, obs, B, h->dev.D, stream, h->d_fault);
+}
+
+int mpk_reacher_env_step(mpk_handle hh, const mpk_env_step_task* step, const mpk_reacher_reset_task* reset, const float* actions,
+                         mpk_nprng_state* rng, double* q, double* qd, int32_t* traj_steps, double* task_io, double* reward_state,
+                         double* reward, uint8_t* terminated, uint8_t* truncated, uint8_t* is_collided, uint8_t* is_success,
+                         uint8_t* reset_mask, float* final_obs, float* obs, int32_t B, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!step) { set_error("mpk_reacher_env_step: step is NULL"); return MPK_EINVAL; }
+    if (!reset) { set_error("mpk_reacher_env_step: reset is NULL"); return MPK_EINVAL; }
+    mpk_obs_cfg oc{};
+    oc.env = step->env; oc.n_links = step->n_links;       // every column, no time column
+    EnvStepLaunch e;
+    int r = obs_layout(h, &oc, "mpk_reacher_env_step", &e.obs_layout);      // unknown env, n_links outside 1 .. 16 or not num_dof
+    if (r != MPK_OK) return r;
+    if (reset->env != step->env) { set_error("mpk_reacher_env_step: reset->env must be step->env"); return MPK_EINVAL; }
+    if (reset->seed_base_given) { set_error("mpk_reacher_env_step: the autoreset continues the streams (seed_base_given must be 0)"); return MPK_EINVAL; }
+    if (step->max_episode_steps < 1) { set_error("mpk_reacher_env_step: max_episode_steps must be >= 1"); return MPK_EINVAL; }
+    if (!(step->dt > 0.0)) { set_error("mpk_reacher_env_step: dt must be > 0"); return MPK_EINVAL; }
+    const bool hole = step->env == MPK_RESET_HOLE_REACHER;
+    const mpk_hole_task& ht = step->hole;
+    if (hole) {
+        if (ht.rew_fct < MPK_HOLE_REW_SIMPLE || ht.rew_fct > MPK_HOLE_REW_UNBOUNDED) { set_error("unknown rew_fct (MPK_HOLE_REW_*)"); return MPK_EINVAL; }
+        if (ht.rew_fct != MPK_HOLE_REW_SIMPLE && ht.steps_before_reward != 199) {
+            set_error("rew_fct vel_acc / unbounded pay at the reference's step 199: steps_before_reward must be 199");
+            return MPK_EINVAL;
+        }
+        if (ht.rew_fct == MPK_HOLE_REW_UNBOUNDED && !reward_state) {
+            set_error("mpk_reacher_env_step: rew_fct unbounded keeps the end effector of step 180 across steps: it needs reward_state [B, 2]");
+            return MPK_EINVAL;
+        }
+    }
+    r = reset_launch(reset, nullptr, rng, q, qd, nullptr, nullptr, traj_steps, nullptr, nullptr, task_io, B, &e.reset, false);
+    if (r != MPK_OK || B == 0) return r;
+    if (!actions || !reward || !terminated || !truncated || !reset_mask || !final_obs || !obs || (hole && (!is_collided || !is_success))) {
+        set_error("mpk_reacher_env_step: NULL buffer");
+        return MPK_EINVAL;
+    }
+    if (final_obs == obs) { set_error("mpk_reacher_env_step: final_obs and obs must be two buffers"); return MPK_EINVAL; }
+    if (terminated == truncated || reset_mask == terminated || reset_mask == truncated) {
+        set_error("mpk_reacher_env_step: terminated, truncated and reset_mask must be three buffers");
+        return MPK_EINVAL;
+    }
+    e.actions = actions; e.reward = reward; e.terminated = terminated; e.truncated = truncated;
+    e.collided = hole ? is_collided : nullptr; e.success = hole ? is_success : nullptr;
+    e.reset_mask = reset_mask; e.final_obs = final_obs; e.obs = obs;
+    e.reward_state = hole && ht.rew_fct == MPK_HOLE_REW_UNBOUNDED ? reward_state : nullptr;
+    e.dt = step->dt; e.penalty = ht.collision_penalty; e.allow_self = ht.allow_self_collision != 0; e.allow_wall = ht.allow_wall_collision != 0;
+    e.steps_before_reward = ht.steps_before_reward; e.max_steps = step->max_episode_steps; e.autoreset = step->autoreset != 0;
+    e.rew_fct = hole ? ht.rew_fct : 0;
+    MPK_ON_DEVICE(h->cfg.device);
+    return launch_reacher_env_step(e, B, h->dev.D, stream, h->d_fault);
 }
 
 int mpk_reacher_step_observations(mpk_handle hh, const mpk_obs_cfg* cfg, const mpk_rollout_cfg* rc, const float* des_pos,

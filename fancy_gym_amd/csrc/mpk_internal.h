@@ -223,6 +223,24 @@ int launch_reacher_step_obs(const ObsLaunch& l, const RolloutDev& rc, const floa
 // (o == nullptr: the masked reset alone)
 int launch_reacher_autoreset(const ResetLaunch& l, const ObsLaunch* o, const uint8_t* mask, uint8_t* reset_mask, float* final_obs,
                              float* obs, int B, int D, void* stream, int* fault);
+// mpk_reacher_env_step (mpk_env_step.hip): one step of the step-based reacher envs plus the same-step autoreset, one launch
+struct EnvStepLaunch {
+    ResetLaunch reset;                  // q, qd, traj_steps, rng, task_out; no seeds, no plan_steps / done / cond
+    ObsLaunch obs_layout;               // the full row
+    const float* actions = nullptr;
+    double* reward_state = nullptr;
+    double* reward = nullptr;
+    uint8_t* terminated = nullptr;
+    uint8_t* truncated = nullptr;
+    uint8_t* collided = nullptr;
+    uint8_t* success = nullptr;
+    uint8_t* reset_mask = nullptr;
+    float* final_obs = nullptr;
+    float* obs = nullptr;
+    double dt = 0.0, penalty = 0.0;
+    int allow_self = 0, allow_wall = 0, steps_before_reward = 0, max_steps = 0, autoreset = 0, rew_fct = 0;
+};
+int launch_reacher_env_step(const EnvStepLaunch& e, int B, int D, void* stream, int* fault);
 int launch_gate_flags(const uint8_t* valid, const uint8_t* was_done, const uint8_t* done, uint8_t* terminated, uint8_t* truncated, int B,
                       void* stream);
 int launch_replan_advance(int32_t* traj_steps, int32_t* plan_steps, int32_t* seg_len, uint8_t* done, int every,

@@ -18,6 +18,8 @@
 //   mpk_reset.hip        reacher resets: numpy's generator per episode (mpk_nprng.h), seeded / continued draws
 //   mpk_obs.hip          reacher observations: current rows, per-step rows replayed on the stored plan (mpk_plant.h)
 //   mpk_autoreset.hip    per-episode autoreset of a vector step: last observation, masked reset, next observation (mpk_reacher_env.h)
+//   mpk_hole_geom.h      HoleReacher's link-crossing / wall tests and dtype-bound reward terms, shared by mpk_hole.hip and the unit below
+//   mpk_env_step.hip     one step of the step-based reacher envs with the same-step autoreset (plant, collisions, reward, observations)
 //   mpk_misc.hip         integer state, reset, gather, validity, self-tests, trace readout
 #define MPK_AMALGAMATED 1
 #include "mpk_traj_family.hip"
@@ -32,4 +34,5 @@
 #include "mpk_reset.hip"
 #include "mpk_obs.hip"
 #include "mpk_autoreset.hip"
+#include "mpk_env_step.hip"
 #include "mpk_misc.hip"

@@ -1,5 +1,5 @@
 // The reacher envs' reset and observation as __device__ functions, shared by k_reacher_reset (mpk_reset.hip), k_reacher_obs /
-// k_reacher_step_obs (mpk_obs.hip) and k_reacher_autoreset (mpk_autoreset.hip): one text of the draw programs and of the observation
+// k_reacher_step_obs (mpk_obs.hip), k_reacher_autoreset (mpk_autoreset.hip) and k_reacher_env_step (mpk_env_step.hip): one text of the draw programs and of the observation
 // row, so the kernels give the same bits by construction.
 //   reset_episode   the draw program of one episode and everything mpk_reacher_reset writes for its row
 //                   HoleReacher   hole_reacher.py:60-71,79-101, base_reacher.py:73-93: [reseed] width, direction + x, depth, first joint
@@ -26,8 +26,8 @@ struct ResetArgs {
     float* cond_pos;
     float* cond_vel;
     int32_t* traj_steps;
-    int32_t* plan_steps;
-    uint8_t* done;
+    int32_t* plan_steps;                // or nullptr
+    uint8_t* done;                      // or nullptr
     double* task_out;                   // [B, 2] goal or [B, 3] hole
     int* fault;
     double target0, target1, hole_width, hole_x, hole_depth;
@@ -96,7 +96,9 @@ __device__ __forceinline__ double reset_episode(const ResetArgs& a, int b, doubl
         a.qd[row + d] = 0.0;
         if (a.cond_pos) { a.cond_pos[row + d] = (float)v; a.cond_vel[row + d] = 0.0f; }
     }
-    a.traj_steps[b] = 0; a.plan_steps[b] = 0; a.done[b] = 0;
+    a.traj_steps[b] = 0;
+    if (a.plan_steps) a.plan_steps[b] = 0;       // (k_reacher_env_step has no plans and no done bytes)
+    if (a.done) a.done[b] = 0;
     return q0;
 }
 

@@ -711,6 +711,56 @@ class TrajectoryEngine:
             reset_mask.data_ptr(), _dptr(final), _dptr(obs), B, self._stream()))
         return final, obs, reset_mask
 
+    def reacher_env_step(self, env: str, actions: torch.Tensor, q: torch.Tensor, qd: torch.Tensor, traj_steps: torch.Tensor,
+                         rng: torch.Tensor, task: torch.Tensor, out: dict, *, dt: float, max_episode_steps: int,
+                         autoreset: bool = True, steps_before_reward: int = 199, rew_fct: str = "simple",
+                         collision_penalty: float = 100.0, allow_self_collision: bool = False, allow_wall_collision: bool = False,
+                         reward_state: Optional[torch.Tensor] = None, random_start: bool = True, target=None, hole_width=None,
+                         hole_x=None, hole_depth=None):
+        """
+        One ``env.step(action)`` of the step-based reacher envs for B device-resident episodes plus the same-step autoreset, in one
+        launch (mpk.h: mpk_reacher_env_step).  ``actions`` float32 [B, D] (not clipped); q, qd, traj_steps, rng, task (and
+        ``reward_state`` for rew_fct "unbounded") are updated in place.  ``out`` holds the result tensors: reward float64 [B],
+        terminated / truncated / reset_mask uint8 [B], final_obs / obs float32 [B, n], and for "hole_reacher" is_collided / is_success
+        uint8 [B].  The reset kwargs are the env's (None = drawn), as for ``reacher_reset``.  Allocates nothing.
+        """
+        B, D = q.shape
+        hole = env == "hole_reacher"
+        n = 3 * D + (4 if hole else 3)
+        assert actions.dtype == torch.float32 and actions.is_contiguous() and tuple(actions.shape) == (B, D)
+        for t, dt_ in ((q, torch.float64), (qd, torch.float64), (traj_steps, torch.int32), (rng, torch.int64), (task, torch.float64),
+                       (out["reward"], torch.float64)):
+            assert t.dtype == dt_ and t.is_contiguous() and t.shape[0] == B
+        assert tuple(rng.shape) == (B, 5) and tuple(task.shape) == (B, 3 if hole else 2)
+        for key in ("terminated", "truncated", "reset_mask") + (("is_collided", "is_success") if hole else ()):
+            assert out[key].dtype == torch.uint8 and out[key].is_contiguous() and tuple(out[key].shape) == (B,)
+        for key in ("final_obs", "obs"):
+            assert out[key].dtype == torch.float32 and out[key].is_contiguous() and tuple(out[key].shape) == (B, n)
+        rew = _lib.hole_rew_fct(rew_fct, steps_before_reward) if hole else 0
+        if hole and rew_fct == "unbounded":
+            if reward_state is None:
+                raise ValueError("rew_fct='unbounded' keeps the end effector of step 180 across steps: pass reward_state "
+                                 "(float64 [B, 2] on the device)")
+            assert reward_state.dtype == torch.float64 and tuple(reward_state.shape) == (B, 2) and reward_state.is_contiguous()
+        nan = float("nan")
+        opt = lambda v: nan if v is None else float(v)        # noqa: E731
+        rt = _lib.mpk_reacher_reset_task()
+        rt.env = _lib.RESET_ENVS[env]
+        rt.random_start = int(bool(random_start))
+        rt.target[0], rt.target[1] = (nan, nan) if target is None else (float(target[0]), float(target[1]))
+        rt.hole_width, rt.hole_x, rt.hole_depth = opt(hole_width), opt(hole_x), opt(hole_depth)
+        st = _lib.mpk_env_step_task()
+        st.env, st.n_links, st.dt = rt.env, D, float(dt)
+        st.max_episode_steps, st.autoreset = int(max_episode_steps), int(bool(autoreset))
+        st.hole = _lib.mpk_hole_task(float(collision_penalty), int(bool(allow_self_collision)), int(bool(allow_wall_collision)),
+                                     int(steps_before_reward), rew)
+        _lib.check(self._lib.mpk_reacher_env_step(
+            self._h, C.byref(st), C.byref(rt), actions.data_ptr(), rng.data_ptr(), q.data_ptr(), qd.data_ptr(), traj_steps.data_ptr(),
+            task.data_ptr(), _dptr(reward_state) if hole and rew_fct == "unbounded" else None, out["reward"].data_ptr(),
+            out["terminated"].data_ptr(), out["truncated"].data_ptr(), _dptr(out.get("is_collided")), _dptr(out.get("is_success")),
+            out["reset_mask"].data_ptr(), out["final_obs"].data_ptr(), out["obs"].data_ptr(), B, self._stream()))
+        return out
+
     def _obs_cfg(self, env: str, col_mask: int, time_div: float):
         c = _lib.mpk_obs_cfg()
         c.env = _lib.RESET_ENVS[env]

@@ -49,7 +49,11 @@ class SimpleReacherEnv(_gym.Env):
     dt = 0.01
 
     def __init__(self, n_links: int, target: Optional[Sequence[float]] = None, random_start: bool = True,
-                 render_mode: Optional[str] = None):
+                 render_mode: Optional[str] = None, numpy_action_dtype: bool = False):
+        # numpy_action_dtype: step a float32 action in numpy's dtypes, as the reference's step-based env and the device step
+        # (mpk_reacher_env_step) do.  Off by default: the device rollouts behind the movement-primitive ids integrate every action
+        # in float64, and this env is their single-episode counterpart (tests/test_host_logic.py pins that route)
+        self.numpy_action_dtype = bool(numpy_action_dtype)
         self.n_links = int(n_links)
         self.fixed_target = None if target is None else np.asarray(target, dtype=np.float64)
         self.random_start = bool(random_start)
@@ -108,7 +112,12 @@ class SimpleReacherEnv(_gym.Env):
                                [self.steps]]).astype(np.float32)
 
     def step(self, action):
-        action = np.asarray(action, dtype=np.float64)
+        if self.numpy_action_dtype and getattr(action, "dtype", None) == np.float32:
+            # no conversion: numpy keeps the Python float dt weak, so a float32 action (the action space's dtype) makes dt * action
+            # and sum(action^2) float32 operations, as in the reference (base_reacher_torque.py:25, simple_reacher.py:68)
+            action = np.asarray(action)
+        else:
+            action = np.asarray(action, dtype=np.float64)
         self.qd = self.qd + self.dt * action
         self.q = self.q + self.dt * self.qd
         gap = end_effector(self.q) - self.goal

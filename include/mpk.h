@@ -850,6 +850,49 @@ int mpk_reacher_autoreset(mpk_handle h, const mpk_reacher_reset_task* task, cons
                           int32_t* plan_steps, uint8_t* done, double* task_io, const uint8_t* mask, uint8_t* reset_mask,
                           float* final_obs, float* obs, int32_t B, void* stream);
 
+/*
+ * One environment step of the reference's STEP-BASED reacher envs over B device-resident episodes, in ONE launch (ABI 4, appended):
+ * what env.step(action) of the gymnasium-wrapped fancy/SimpleReacher-v0, fancy/LongSimpleReacher-v0 and fancy/HoleReacher-v0 does,
+ * followed by the same-step autoreset of a vector env (the contract of mpk_reacher_autoreset, through the same device functions).
+ *   actions   dev float [B, D], the dtype of the env's action space.  NOT clipped: the step-based envs do not clip
+ *             (base_reacher_torque.py:20-37, base_reacher_direct.py:20-38); only the black-box wrapper does.
+ *   plant     in numpy's dtypes for a float32 action.  MPK_RESET_SIMPLE_REACHER: qd = qd + dt * action with dt * action a float32
+ *             product (numpy keeps the Python float dt weak), q = q + dt * qd in float64.  MPK_RESET_HOLE_REACHER: the velocity
+ *             plant of mpk_hole_reacher_rollout with the action as the velocity controller's output -- float64 on an episode's first
+ *             step, float32 acc, dt * qd and sum(acc^2) from step > 0.
+ *   reward    dev double [B].  SimpleReacher (simple_reacher.py:56-72): -[step >= steps_before_reward] * |ee - goal| - sum(action^2),
+ *             the sum in float32 in index order.  HoleReacher: step->hole.rew_fct, exactly as mpk_hole_reacher_rollout2 (collisions,
+ *             joint limits, allow_*, collision_penalty, reward_state dev double [B, 2] for MPK_HOLE_REW_UNBOUNDED).  "step" is the env
+ *             step counter traj_steps[b] BEFORE its increment.
+ *   flags     terminated dev uint8 [B] = collided (HoleReacher; SimpleReacher never terminates); truncated dev uint8 [B] =
+ *             traj_steps[b] + 1 >= max_episode_steps (gymnasium's TimeLimit).  Both may be set in one step.  is_collided, is_success
+ *             dev uint8 [B]: HoleReacher's info entries (required for it, ignored -- may be NULL -- for SimpleReacher).
+ *   final_obs dev float [B, n]: the full _get_obs row after the step (mpk_reacher_observation with col_mask 0, time_div 0: the
+ *             step-based id has neither the context mask nor the time column), n = 3 D + 3 / 3 D + 4.
+ *   autoreset step->autoreset != 0: where terminated | truncated, the episode runs the draw program of `reset` on its own generator
+ *             rng[b] (continued, never reseeded: reset->seed_base_given must be 0) and gets q, qd, traj_steps = 0, its row of task_io and
+ *             the advanced generator; reset_mask[b] = 1 and obs[b] = the NEW episode's reset observation.  Elsewhere (and everywhere
+ *             with autoreset == 0) q, qd are the stepped state, traj_steps is incremented, reset_mask[b] = 0 and obs[b] = final_obs[b].
+ *   q, qd dev double [B, D]; traj_steps dev int32 [B]; task_io dev double [B, 2] goal / [B, 3] hole; rng dev mpk_nprng_state [B];
+ *   reset_mask dev uint8 [B]; final_obs, obs two different buffers.
+ * step->env must be reset->env, step->n_links the handle's num_dof (<= 16).  A NULL or mismatched buffer, an unknown env or rew_fct,
+ * max_episode_steps < 1, or MPK_HOLE_REW_UNBOUNDED without reward_state is MPK_EINVAL before any launch.  Allocates nothing and
+ * synchronises nothing (it can be captured in a graph).  The goal-draw cap and its fault word apply as in mpk_reacher_reset.
+ */
+typedef struct mpk_env_step_task {
+    int32_t env;                     /* MPK_RESET_* */
+    int32_t n_links;                 /* D: the handle's num_dof */
+    double  dt;                      /* the env's dt (base_reacher.py:21: 0.01) */
+    int32_t max_episode_steps;       /* the registered TimeLimit (200) */
+    int32_t autoreset;               /* != 0: same-step autoreset */
+    mpk_hole_task hole;              /* steps_before_reward is read for both envs, the other fields for HoleReacher */
+    int64_t reserved[2];
+} mpk_env_step_task;
+int mpk_reacher_env_step(mpk_handle h, const mpk_env_step_task* step, const mpk_reacher_reset_task* reset, const float* actions,
+                         mpk_nprng_state* rng, double* q, double* qd, int32_t* traj_steps, double* task_io, double* reward_state,
+                         double* reward, uint8_t* terminated, uint8_t* truncated, uint8_t* is_collided, uint8_t* is_success,
+                         uint8_t* reset_mask, float* final_obs, float* obs, int32_t B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
