@@ -17,6 +17,7 @@
 // over the row tiles in time order, then the sixteen slots left to right; mean = that sum / executed steps; last = the last executed
 // step's reward.  (numpy's np.sum adds pairwise: the same value to a few ulp.)
 #include "mpk_reward.h"
+#include "mpk_traj_route.h"
 
 namespace mpk {
 
@@ -326,9 +327,9 @@ __global__ void __launch_bounds__(512) k_episode_return(const TrajArgs a, const 
 
 #ifndef MPK_DEVICE_ONLY
 template <int MP>
-int launch_episode_kernel(const TrajArgs& ta, const ActArgs& aa, const EpArgs& ea, int ct, int nq, int rwd, int blocks, size_t lds,
-                          void* stream) {
-    const int wpb = ea.wpb;
+int launch_episode_kernel(const TrajArgs& ta, const ActArgs& aa, const EpArgs& ea, const EpRoute& r, void* stream) {
+    const int wpb = ea.wpb, ct = r.ct, nq = r.nq, rwd = r.rwd, blocks = r.blocks;
+    const size_t lds = r.lds;
     if constexpr (MP == MPK_MP_DMP) {
         (void)wpb; (void)ta; (void)aa; (void)ea; (void)ct; (void)nq; (void)rwd; (void)blocks; (void)lds; (void)stream;
         set_error("internal: the episode kernel takes promp / prodmp rows");
@@ -345,11 +346,7 @@ int launch_episode_kernel(const TrajArgs& ta, const ActArgs& aa, const EpArgs& e
         };
         auto by_ct = [&](auto nq_tag, auto rw_tag) -> int {
             constexpr int NQ = decltype(nq_tag)::value, RW = decltype(rw_tag)::value;
-            switch (ct) {
-                case 3 + MPK_CTRL_MOTOR: return go(k_episode_return<MP, 3 + MPK_CTRL_MOTOR, NQ, RW>);
-                case 3 + MPK_CTRL_VELOCITY: return go(k_episode_return<MP, 3 + MPK_CTRL_VELOCITY, NQ, RW>);
-                default: return go(k_episode_return<MP, 3 + MPK_CTRL_POSITION, NQ, RW>);
-            }
+            return with_closed_ct(ct, [&](auto c) { return go(k_episode_return<MP, decltype(c)::value, NQ, RW>); });
         };
         using std::integral_constant;
         if (nq == 4) return rwd ? by_ct(integral_constant<int, 4>(), integral_constant<int, 1>()) : by_ct(integral_constant<int, 4>(), integral_constant<int, 0>());
@@ -358,11 +355,11 @@ int launch_episode_kernel(const TrajArgs& ta, const ActArgs& aa, const EpArgs& e
     }
 }
 #ifdef MPK_MP_UNIT
-template int launch_episode_kernel<MPK_MP_UNIT>(const TrajArgs&, const ActArgs&, const EpArgs&, int, int, int, int, size_t, void*);
+template int launch_episode_kernel<MPK_MP_UNIT>(const TrajArgs&, const ActArgs&, const EpArgs&, const EpRoute&, void*);
 #else
-template int launch_episode_kernel<MPK_MP_PROMP>(const TrajArgs&, const ActArgs&, const EpArgs&, int, int, int, int, size_t, void*);
-template int launch_episode_kernel<MPK_MP_DMP>(const TrajArgs&, const ActArgs&, const EpArgs&, int, int, int, int, size_t, void*);
-template int launch_episode_kernel<MPK_MP_PRODMP>(const TrajArgs&, const ActArgs&, const EpArgs&, int, int, int, int, size_t, void*);
+template int launch_episode_kernel<MPK_MP_PROMP>(const TrajArgs&, const ActArgs&, const EpArgs&, const EpRoute&, void*);
+template int launch_episode_kernel<MPK_MP_DMP>(const TrajArgs&, const ActArgs&, const EpArgs&, const EpRoute&, void*);
+template int launch_episode_kernel<MPK_MP_PRODMP>(const TrajArgs&, const ActArgs&, const EpArgs&, const EpRoute&, void*);
 #endif
 #endif  // MPK_DEVICE_ONLY
 

@@ -120,6 +120,8 @@ struct Handle;  // defined in mpk_host.cpp
 // ---- launchers implemented in mpk_kernels.hip (all enqueue on `stream`, none synchronise) -------------------
 int launch_build_shared(const DevCfg& c, float init_time, const SharedTables& st, int32_t* idx_out,
                         int32_t* range_flag, void* stream);
+// (launch_traj_shared / launch_episode_return: the route choice -- plan_traj_shared / plan_episode_return, mpk_traj_route.h -- and ONE
+// launch of the family it names)
 int launch_traj_shared(const DevCfg& c, const SharedTables& st, const float* params, const float* init_pos,
                        const float* init_vel, float* pos, float* vel, float* actions, const RolloutDev* rc,
                        const double* c_pos, const double* c_vel, double* q_state, double* qd_state,

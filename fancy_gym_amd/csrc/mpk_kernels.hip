@@ -8,7 +8,8 @@
 //   mpk_traj_ring.h / .hip   k_traj_ring / k_traj_burst + their launcher, one unit per MP type
 //   mpk_episode.hip      k_episode_return (verbose < 2 step: nothing per step stored), one unit per MP type
 //   mpk_reward.h         SimpleReacher reward on float64 LDS images (rollout + episode kernels)
-//   mpk_traj_launch.hip  k_build_shared + launch_traj_shared (kernel selection rule)
+//   mpk_traj_route.h     TrajRoute / EpRoute (what the selection rule hands to the launchers above), their declarations, dispatch helpers
+//   mpk_traj_launch.hip  k_build_shared + plan_traj_shared (kernel selection rule, one function per family) + launch_traj_shared
 //   mpk_traj_wide.hip    k_traj_wide
 //   mpk_traj_phase.hip   per-episode phase kernels
 //   mpk_phase_fused.hip  per-episode phase: the fused entry points (actions, closed loop, replanning step, verbose < 2 step, validity gate)

@@ -6,190 +6,72 @@
 #include "mpk_traj_flat.h"
 #include "mpk_traj_quad.h"
 #include "mpk_traj_pipe.h"
+#include "mpk_traj_route.h"
 
 namespace mpk {
 
 #ifndef MPK_DEVICE_ONLY
+// the route's family with the call's (MP, CT) pair; the `if constexpr` guards keep the pairs a family never sees from being instantiated
 template <int MP, int CT>
-static int launch_traj_t(const TrajArgs& ta, const ActArgs& aa, bool stream_mode, bool write_through, bool bulk,
-                         int quad, int blocks, size_t lds, void* stream, bool split = false, bool pipe = false) {
-    const dim3 g(blocks), b(256);
-    if (pipe) {
-        if constexpr (MP != MPK_MP_DMP && CT >= 3) {
-            const dim3 b5(320);
-            hipStream_t s5 = (hipStream_t)stream;
-            auto gop = [&](auto lean) {
-                constexpr bool LEAN = decltype(lean)::value;
-                switch (ta.c.KP / 4) {
-                    case 1: hipLaunchKernelGGL((k_traj_pipe<MP, CT, 1, LEAN>), g, b5, lds, s5, ta, aa); break;
-                    case 2: hipLaunchKernelGGL((k_traj_pipe<MP, CT, 2, LEAN>), g, b5, lds, s5, ta, aa); break;
-                    case 3: hipLaunchKernelGGL((k_traj_pipe<MP, CT, 3, LEAN>), g, b5, lds, s5, ta, aa); break;
-                    default: hipLaunchKernelGGL((k_traj_pipe<MP, CT, 4, LEAN>), g, b5, lds, s5, ta, aa); break;
+static int launch_traj_t(const TrajArgs& ta, const ActArgs& aa, const TrajRoute& r, void* stream) {
+    // (full_lds: the kernels whose dynamic LDS can pass 48 KB -- k_traj_stream's bulk form only with the "lds_pad" occupancy knob)
+    auto go = [&](auto kern, unsigned threads, bool full_lds = false) {
+        if (full_lds && r.lds > 48 * 1024) (void)allow_full_lds(kern);
+        hipLaunchKernelGGL(kern, dim3(r.blocks), dim3(threads), r.lds, (hipStream_t)stream, ta, aa);
+    };
+    with_km(ta.c.KP / 4, [&](auto km) {
+        constexpr int KM = decltype(km)::value;
+        switch (r.family) {
+            case TrajFamily::Pipe:
+                if constexpr (MP != MPK_MP_DMP && CT >= 3) {
+                    if (r.gate) go(k_traj_pipe<MP, CT, KM, false, true>, 320);
+                    else if (r.lean) go(k_traj_pipe<MP, CT, KM, true>, 320);
+                    else go(k_traj_pipe<MP, CT, KM, false>, 320);
                 }
-            };
-            auto gog = [&]() {                          // the validity gate: the consumer's chain with the GATE hook (no LEAN form)
-                switch (ta.c.KP / 4) {
-                    case 1: hipLaunchKernelGGL((k_traj_pipe<MP, CT, 1, false, true>), g, b5, lds, s5, ta, aa); break;
-                    case 2: hipLaunchKernelGGL((k_traj_pipe<MP, CT, 2, false, true>), g, b5, lds, s5, ta, aa); break;
-                    case 3: hipLaunchKernelGGL((k_traj_pipe<MP, CT, 3, false, true>), g, b5, lds, s5, ta, aa); break;
-                    default: hipLaunchKernelGGL((k_traj_pipe<MP, CT, 4, false, true>), g, b5, lds, s5, ta, aa); break;
+                break;
+            case TrajFamily::Flat:
+                if constexpr (MP != MPK_MP_DMP && CT < 3) go(k_traj_flat<MP, CT, KM>, 256, true);
+                break;
+            case TrajFamily::Split:
+                if constexpr (MP != MPK_MP_DMP && CT >= 3)
+                    with_flag(r.write_through, [&](auto wt) { go(k_traj_split<MP, CT, KM, decltype(wt)::value>, 256); });
+                break;
+            case TrajFamily::Quarter:
+                if constexpr (MP == MPK_MP_DMP || CT >= 3) {
+                    if (r.nq == 1) go(k_traj_quad<MP, CT, KM, 1>, 256);
+                    else if (r.nq == 2) go(k_traj_quad<MP, CT, KM, 2>, 256);
+                    else go(k_traj_quad<MP, CT, KM, 4>, 256);
                 }
-            };
-            if (ta.gate_valid) gog();
-            else if (ta.lean) gop(std::true_type()); else gop(std::false_type());
+                break;
+            case TrajFamily::Stream:
+                with_flag(r.bulk, [&](auto bulk) { go(k_traj_stream<MP, CT, KM, decltype(bulk)::value>, 256, decltype(bulk)::value); });
+                break;
+            case TrajFamily::Tiles:
+                if constexpr (MP != MPK_MP_DMP && CT < 3)
+                    with_flag(r.write_through, [&](auto wt) { go(k_traj_tiles<MP, CT, KM, decltype(wt)::value>, (unsigned)ta.wpb * 64u); });
+                break;
+            default: break;       // (the ring unit's families: mpk_traj_ring.hip)
         }
-        MPK_LAUNCH_CHECK();
-        return MPK_OK;
-    }
-    // tile-major / split: no dynamic LDS of their own; `lds` then is the occupancy-experiment padding ("lds_pad" option)
-    const size_t pad = (!stream_mode || split) ? lds : 0;
-    hipStream_t s = (hipStream_t)stream;
-    const int km = ta.c.KP / 4;
-    if (ta.flat_img > 0) {
-        if constexpr (MP != MPK_MP_DMP && CT < 3) {
-            auto go = [&](auto kern) {
-                if (lds > 48 * 1024) (void)allow_full_lds(kern);
-                hipLaunchKernelGGL(kern, g, b, lds, s, ta, aa);
-            };
-            switch (km) {
-                case 1: go(k_traj_flat<MP, CT, 1>); break;
-                case 2: go(k_traj_flat<MP, CT, 2>); break;
-                case 3: go(k_traj_flat<MP, CT, 3>); break;
-                default: go(k_traj_flat<MP, CT, 4>); break;
-            }
-        }
-        MPK_LAUNCH_CHECK();
-        return MPK_OK;
-    }
-    if (split) {
-        if constexpr (MP != MPK_MP_DMP && CT >= 3) {
-            if (write_through) {
-                switch (km) {
-                    case 1: hipLaunchKernelGGL((k_traj_split<MP, CT, 1, true>), g, b, pad, s, ta, aa); break;
-                    case 2: hipLaunchKernelGGL((k_traj_split<MP, CT, 2, true>), g, b, pad, s, ta, aa); break;
-                    case 3: hipLaunchKernelGGL((k_traj_split<MP, CT, 3, true>), g, b, pad, s, ta, aa); break;
-                    default: hipLaunchKernelGGL((k_traj_split<MP, CT, 4, true>), g, b, pad, s, ta, aa); break;
-                }
-            } else {
-                switch (km) {
-                    case 1: hipLaunchKernelGGL((k_traj_split<MP, CT, 1, false>), g, b, pad, s, ta, aa); break;
-                    case 2: hipLaunchKernelGGL((k_traj_split<MP, CT, 2, false>), g, b, pad, s, ta, aa); break;
-                    case 3: hipLaunchKernelGGL((k_traj_split<MP, CT, 3, false>), g, b, pad, s, ta, aa); break;
-                    default: hipLaunchKernelGGL((k_traj_split<MP, CT, 4, false>), g, b, pad, s, ta, aa); break;
-                }
-            }
-        }
-    } else if (stream_mode && quad) {
-        if constexpr (MP == MPK_MP_DMP || CT >= 3) {
-            if (quad == 1) {
-                switch (km) {
-                    case 1: hipLaunchKernelGGL((k_traj_quad<MP, CT, 1, 1>), g, b, lds, s, ta, aa); break;
-                    case 2: hipLaunchKernelGGL((k_traj_quad<MP, CT, 2, 1>), g, b, lds, s, ta, aa); break;
-                    case 3: hipLaunchKernelGGL((k_traj_quad<MP, CT, 3, 1>), g, b, lds, s, ta, aa); break;
-                    default: hipLaunchKernelGGL((k_traj_quad<MP, CT, 4, 1>), g, b, lds, s, ta, aa); break;
-                }
-            } else if (quad == 2) {
-                switch (km) {
-                    case 1: hipLaunchKernelGGL((k_traj_quad<MP, CT, 1, 2>), g, b, lds, s, ta, aa); break;
-                    case 2: hipLaunchKernelGGL((k_traj_quad<MP, CT, 2, 2>), g, b, lds, s, ta, aa); break;
-                    case 3: hipLaunchKernelGGL((k_traj_quad<MP, CT, 3, 2>), g, b, lds, s, ta, aa); break;
-                    default: hipLaunchKernelGGL((k_traj_quad<MP, CT, 4, 2>), g, b, lds, s, ta, aa); break;
-                }
-            } else {
-                switch (km) {
-                    case 1: hipLaunchKernelGGL((k_traj_quad<MP, CT, 1, 4>), g, b, lds, s, ta, aa); break;
-                    case 2: hipLaunchKernelGGL((k_traj_quad<MP, CT, 2, 4>), g, b, lds, s, ta, aa); break;
-                    case 3: hipLaunchKernelGGL((k_traj_quad<MP, CT, 3, 4>), g, b, lds, s, ta, aa); break;
-                    default: hipLaunchKernelGGL((k_traj_quad<MP, CT, 4, 4>), g, b, lds, s, ta, aa); break;
-                }
-            }
-        }
-    } else if (stream_mode) {
-        if (bulk) {
-            // more than 48 KB of dynamic LDS only happens with the "lds_pad" occupancy knob (one workgroup per CU)
-            auto big = [&](auto kern) {
-                if (lds > 48 * 1024) (void)allow_full_lds(kern);
-            };
-            switch (km) {
-                case 1: big(k_traj_stream<MP, CT, 1, true>); hipLaunchKernelGGL((k_traj_stream<MP, CT, 1, true>), g, b, lds, s, ta, aa); break;
-                case 2: big(k_traj_stream<MP, CT, 2, true>); hipLaunchKernelGGL((k_traj_stream<MP, CT, 2, true>), g, b, lds, s, ta, aa); break;
-                case 3: big(k_traj_stream<MP, CT, 3, true>); hipLaunchKernelGGL((k_traj_stream<MP, CT, 3, true>), g, b, lds, s, ta, aa); break;
-                default: big(k_traj_stream<MP, CT, 4, true>); hipLaunchKernelGGL((k_traj_stream<MP, CT, 4, true>), g, b, lds, s, ta, aa); break;
-            }
-        } else {
-            switch (km) {
-                case 1: hipLaunchKernelGGL((k_traj_stream<MP, CT, 1, false>), g, b, lds, s, ta, aa); break;
-                case 2: hipLaunchKernelGGL((k_traj_stream<MP, CT, 2, false>), g, b, lds, s, ta, aa); break;
-                case 3: hipLaunchKernelGGL((k_traj_stream<MP, CT, 3, false>), g, b, lds, s, ta, aa); break;
-                default: hipLaunchKernelGGL((k_traj_stream<MP, CT, 4, false>), g, b, lds, s, ta, aa); break;
-            }
-        }
-    } else {
-        if constexpr (MP != MPK_MP_DMP && CT < 3) {
-            const dim3 bt((unsigned)ta.wpb * 64u);
-            if (write_through) {
-                switch (km) {
-                    case 1: hipLaunchKernelGGL((k_traj_tiles<MP, CT, 1, true>), g, bt, pad, s, ta, aa); break;
-                    case 2: hipLaunchKernelGGL((k_traj_tiles<MP, CT, 2, true>), g, bt, pad, s, ta, aa); break;
-                    case 3: hipLaunchKernelGGL((k_traj_tiles<MP, CT, 3, true>), g, bt, pad, s, ta, aa); break;
-                    default: hipLaunchKernelGGL((k_traj_tiles<MP, CT, 4, true>), g, bt, pad, s, ta, aa); break;
-                }
-            } else {
-                switch (km) {
-                    case 1: hipLaunchKernelGGL((k_traj_tiles<MP, CT, 1, false>), g, bt, pad, s, ta, aa); break;
-                    case 2: hipLaunchKernelGGL((k_traj_tiles<MP, CT, 2, false>), g, bt, pad, s, ta, aa); break;
-                    case 3: hipLaunchKernelGGL((k_traj_tiles<MP, CT, 3, false>), g, bt, pad, s, ta, aa); break;
-                    default: hipLaunchKernelGGL((k_traj_tiles<MP, CT, 4, false>), g, bt, pad, s, ta, aa); break;
-                }
-            }
-        }
-    }
+    });
     MPK_LAUNCH_CHECK();
     return MPK_OK;
 }
-#endif  // MPK_DEVICE_ONLY
 
-#ifndef MPK_DEVICE_ONLY
 template <int MP>
-int launch_traj_ct(const TrajArgs& ta, const ActArgs& aa, int ct, bool stream_mode, bool write_through,
-                   bool bulk, int quad, int blocks, size_t lds, void* stream, bool split, bool pipe) {
-    if constexpr (MP != MPK_MP_DMP) {
-        if (pipe) {
-            switch (ct) {
-                case 3 + MPK_CTRL_MOTOR: return launch_traj_t<MP, 3 + MPK_CTRL_MOTOR>(ta, aa, true, false, false, 0, blocks, lds, stream, false, true);
-                case 3 + MPK_CTRL_VELOCITY: return launch_traj_t<MP, 3 + MPK_CTRL_VELOCITY>(ta, aa, true, false, false, 0, blocks, lds, stream, false, true);
-                default: return launch_traj_t<MP, 3 + MPK_CTRL_POSITION>(ta, aa, true, false, false, 0, blocks, lds, stream, false, true);
-            }
-        }
-        if (split) {
-            switch (ct) {
-                case 3 + MPK_CTRL_MOTOR: return launch_traj_t<MP, 3 + MPK_CTRL_MOTOR>(ta, aa, false, write_through, false, 0, blocks, lds, stream, true);
-                case 3 + MPK_CTRL_VELOCITY: return launch_traj_t<MP, 3 + MPK_CTRL_VELOCITY>(ta, aa, false, write_through, false, 0, blocks, lds, stream, true);
-                default: return launch_traj_t<MP, 3 + MPK_CTRL_POSITION>(ta, aa, false, write_through, false, 0, blocks, lds, stream, true);
-            }
-        }
-        switch (ct) {
-            case MPK_CTRL_MOTOR: return launch_traj_t<MP, MPK_CTRL_MOTOR>(ta, aa, stream_mode, write_through, bulk, quad, blocks, lds, stream);
-            case MPK_CTRL_VELOCITY: return launch_traj_t<MP, MPK_CTRL_VELOCITY>(ta, aa, stream_mode, write_through, bulk, quad, blocks, lds, stream);
-            case MPK_CTRL_POSITION: return launch_traj_t<MP, MPK_CTRL_POSITION>(ta, aa, stream_mode, write_through, bulk, quad, blocks, lds, stream);
-            case 3 + MPK_CTRL_MOTOR: return launch_traj_t<MP, 3 + MPK_CTRL_MOTOR>(ta, aa, true, false, bulk, quad, blocks, lds, stream);
-            case 3 + MPK_CTRL_VELOCITY: return launch_traj_t<MP, 3 + MPK_CTRL_VELOCITY>(ta, aa, true, false, bulk, quad, blocks, lds, stream);
-            case 3 + MPK_CTRL_POSITION: return launch_traj_t<MP, 3 + MPK_CTRL_POSITION>(ta, aa, true, false, bulk, quad, blocks, lds, stream);
-            default: break;
-        }
-    }
-    return launch_traj_t<MP, -1>(ta, aa, stream_mode, write_through, bulk, quad, blocks, lds, stream);
+int launch_traj_ct(const TrajArgs& ta, const ActArgs& aa, const TrajRoute& r, void* stream) {
+    auto go = [&](auto ct) { return launch_traj_t<MP, decltype(ct)::value>(ta, aa, r, stream); };
+    if constexpr (MP == MPK_MP_DMP) return go(std::integral_constant<int, -1>());
+    // (the closed-loop-only families take a controller they do not know as the position controller)
+    else return r.family == TrajFamily::Pipe || r.family == TrajFamily::Split ? with_closed_ct(r.ct, go) : with_ct(r.ct, go);
 }
-#endif  // MPK_DEVICE_ONLY
 
-#ifndef MPK_DEVICE_ONLY
 #ifdef MPK_MP_UNIT
-template int launch_traj_ct<MPK_MP_UNIT>(const TrajArgs&, const ActArgs&, int, bool, bool, bool, int, int, size_t, void*, bool, bool);
+template int launch_traj_ct<MPK_MP_UNIT>(const TrajArgs&, const ActArgs&, const TrajRoute&, void*);
 #else
-template int launch_traj_ct<MPK_MP_PROMP>(const TrajArgs&, const ActArgs&, int, bool, bool, bool, int, int, size_t, void*, bool, bool);
-template int launch_traj_ct<MPK_MP_DMP>(const TrajArgs&, const ActArgs&, int, bool, bool, bool, int, int, size_t, void*, bool, bool);
-template int launch_traj_ct<MPK_MP_PRODMP>(const TrajArgs&, const ActArgs&, int, bool, bool, bool, int, int, size_t, void*, bool, bool);
+template int launch_traj_ct<MPK_MP_PROMP>(const TrajArgs&, const ActArgs&, const TrajRoute&, void*);
+template int launch_traj_ct<MPK_MP_DMP>(const TrajArgs&, const ActArgs&, const TrajRoute&, void*);
+template int launch_traj_ct<MPK_MP_PRODMP>(const TrajArgs&, const ActArgs&, const TrajRoute&, void*);
 #endif
-#endif
+#endif  // MPK_DEVICE_ONLY
 
 }  // namespace mpk

@@ -1,12 +1,15 @@
 // k_traj_ring / k_traj_burst behind one template launcher per MP type (-DMPK_MP_UNIT=0 promp, 1 dmp, 2 prodmp: one translation
 // unit each, like mpk_traj_family.hip; without MPK_MP_UNIT -- the single-unit build mpk_kernels.hip -- all three are instantiated).
 #include "mpk_traj_ring.h"
+#include "mpk_traj_route.h"
 
 namespace mpk {
 
 #ifndef MPK_DEVICE_ONLY
 template <int MP, int CT>
-static int launch_ring_t(const TrajArgs& ta, const ActArgs& aa, int blocks, size_t lds, void* stream) {
+static int launch_ring_t(const TrajArgs& ta, const ActArgs& aa, const TrajRoute& r, void* stream) {
+    const int blocks = r.blocks;
+    const size_t lds = r.lds;
     if constexpr (MP == MPK_MP_DMP) {
         (void)ta; (void)aa; (void)blocks; (void)lds; (void)stream;
         set_error("internal: k_traj_ring is promp / prodmp");
@@ -29,19 +32,14 @@ static int launch_ring_t(const TrajArgs& ta, const ActArgs& aa, int blocks, size
     const dim3 g(blocks);
     hipStream_t s = (hipStream_t)stream;
     const int km = ta.c.KP / 4;
-    if (ta.burst == 1) {
+    if (r.family == TrajFamily::Burst) {
         if constexpr (MP != MPK_MP_DMP && CT < 3) {
             const dim3 bb((unsigned)(ta.ring_m * ta.ring_np) * 64u);
             auto go = [&](auto kern) {
                 if (lds > 48 * 1024) (void)allow_full_lds(kern);
                 hipLaunchKernelGGL(kern, g, bb, lds, s, ta, aa);
             };
-            switch (km) {
-                case 1: go(k_traj_burst<MP, CT, 1>); break;
-                case 2: go(k_traj_burst<MP, CT, 2>); break;
-                case 3: go(k_traj_burst<MP, CT, 3>); break;
-                default: go(k_traj_burst<MP, CT, 4>); break;
-            }
+            with_km(km, [&](auto k) { go(k_traj_burst<MP, CT, decltype(k)::value>); });
         } else {
             set_error("internal: k_traj_burst is open loop, promp / prodmp");
             return MPK_EINVAL;
@@ -49,7 +47,7 @@ static int launch_ring_t(const TrajArgs& ta, const ActArgs& aa, int blocks, size
         MPK_LAUNCH_CHECK();
         return MPK_OK;
     }
-    if (ta.burst == 2) {
+    if (r.family == TrajFamily::FlatD) {
         // k_traj_flat with the DoF count compiled in (the launcher sends only D = 5 / 7 with <= 8 columns here)
         const dim3 bf(256);
         auto gof = [&](auto kern) {
@@ -75,41 +73,25 @@ static int launch_ring_t(const TrajArgs& ta, const ActArgs& aa, int blocks, size
     };
     if (km <= 2 && ta.c.D == 7) by_km(std::integral_constant<int, 7>());
     else if (km <= 2 && ta.c.D == 5) by_km(std::integral_constant<int, 5>());
-    else {
-        switch (km) {
-            case 1: go(k_traj_ring<MP, CT, 1, 0>); break;
-            case 2: go(k_traj_ring<MP, CT, 2, 0>); break;
-            case 3: go(k_traj_ring<MP, CT, 3, 0>); break;
-            default: go(k_traj_ring<MP, CT, 4, 0>); break;
-        }
-    }
+    else with_km(km, [&](auto k) { go(k_traj_ring<MP, CT, decltype(k)::value, 0>); });
     MPK_LAUNCH_CHECK();
     return MPK_OK;
     }
 }
 
 template <int MP>
-int launch_traj_ring(const TrajArgs& ta, const ActArgs& aa, int ct, int blocks, size_t lds, void* stream) {
-    if constexpr (MP != MPK_MP_DMP) {
-        switch (ct) {
-            case MPK_CTRL_MOTOR: return launch_ring_t<MP, MPK_CTRL_MOTOR>(ta, aa, blocks, lds, stream);
-            case MPK_CTRL_VELOCITY: return launch_ring_t<MP, MPK_CTRL_VELOCITY>(ta, aa, blocks, lds, stream);
-            case MPK_CTRL_POSITION: return launch_ring_t<MP, MPK_CTRL_POSITION>(ta, aa, blocks, lds, stream);
-            case 3 + MPK_CTRL_MOTOR: return launch_ring_t<MP, 3 + MPK_CTRL_MOTOR>(ta, aa, blocks, lds, stream);
-            case 3 + MPK_CTRL_VELOCITY: return launch_ring_t<MP, 3 + MPK_CTRL_VELOCITY>(ta, aa, blocks, lds, stream);
-            case 3 + MPK_CTRL_POSITION: return launch_ring_t<MP, 3 + MPK_CTRL_POSITION>(ta, aa, blocks, lds, stream);
-            default: break;
-        }
-    }
-    return launch_ring_t<MP, -1>(ta, aa, blocks, lds, stream);
+int launch_traj_ring(const TrajArgs& ta, const ActArgs& aa, const TrajRoute& r, void* stream) {
+    auto go = [&](auto ct) { return launch_ring_t<MP, decltype(ct)::value>(ta, aa, r, stream); };
+    if constexpr (MP == MPK_MP_DMP) return go(std::integral_constant<int, -1>());
+    else return with_ct(r.ct, go);
 }
 
 #ifdef MPK_MP_UNIT
-template int launch_traj_ring<MPK_MP_UNIT>(const TrajArgs&, const ActArgs&, int, int, size_t, void*);
+template int launch_traj_ring<MPK_MP_UNIT>(const TrajArgs&, const ActArgs&, const TrajRoute&, void*);
 #else
-template int launch_traj_ring<MPK_MP_PROMP>(const TrajArgs&, const ActArgs&, int, int, size_t, void*);
-template int launch_traj_ring<MPK_MP_DMP>(const TrajArgs&, const ActArgs&, int, int, size_t, void*);
-template int launch_traj_ring<MPK_MP_PRODMP>(const TrajArgs&, const ActArgs&, int, int, size_t, void*);
+template int launch_traj_ring<MPK_MP_PROMP>(const TrajArgs&, const ActArgs&, const TrajRoute&, void*);
+template int launch_traj_ring<MPK_MP_DMP>(const TrajArgs&, const ActArgs&, const TrajRoute&, void*);
+template int launch_traj_ring<MPK_MP_PRODMP>(const TrajArgs&, const ActArgs&, const TrajRoute&, void*);
 #endif
 #endif
 
