@@ -29,7 +29,7 @@ DMP_FIRST_SAMPLE_MODES = {"init": 0, "step": 1}
 REWARD_TYPES = {None: 0, "none": 0, "simple_reacher": 1}       # MPK_REWARD_*
 AGG_MODES = {"sum": 0, "mean": 1, "last": 2}                   # MPK_AGG_*
 OPTION_KEYS = ("mapping", "bulk", "quad", "pd_quad", "write_through", "ipw", "phase", "phase_table", "phase_chunk",
-               "pd_simple", "split", "lds_pad", "pipe", "flat", "phase_flat", "ring", "ring_np", "ring_ns", "ring_m", "ring_dbg", "ring_parts", "tiles_wpb", "serial_order", "ring_nc", "pd_generic", "dmp_response", "ablations", "ring_tb", "pd_helper", "phase_waves", "phase_split", "phase_pipe", "pd_pipe", "hole_sampled")
+               "pd_simple", "split", "lds_pad", "pipe", "flat", "phase_flat", "ring", "ring_np", "ring_ns", "ring_m", "ring_dbg", "ring_parts", "tiles_wpb", "serial_order", "ring_nc", "pd_generic", "dmp_response", "ablations", "ring_tb", "pd_helper", "phase_waves", "phase_split", "phase_pipe", "pd_pipe", "hole_sampled", "vjp_generic")
 
 
 class MPKLibraryError(RuntimeError):
@@ -199,13 +199,14 @@ SIGNATURES = {
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mpk_reacher_env_step": (C.c_int, [_vp, C.POINTER(mpk_env_step_task), C.POINTER(mpk_reacher_reset_task), _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "mpk_trajectory_vjp": (C.c_int, [_vp, _vp, _vp, _dbl, _vp, _vp, _vp, _i32, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
 
 # the files libmpk.so is built from, in the order mpk_source_hash() is defined over (include/mpk.h)
 _ROOT = os.path.dirname(_HERE)
-KERNEL_UNITS = ("mpk_traj_family.hip", "mpk_traj_ring.hip", "mpk_episode.hip", "mpk_traj_launch.hip", "mpk_traj_wide.hip", "mpk_traj_phase.hip",
+KERNEL_UNITS = ("mpk_traj_family.hip", "mpk_traj_ring.hip", "mpk_episode.hip", "mpk_traj_launch.hip", "mpk_traj_wide.hip", "mpk_traj_vjp.hip", "mpk_traj_phase.hip",
                 "mpk_phase_fused.hip", "mpk_rollout.hip", "mpk_hole.hip", "mpk_reset.hip", "mpk_obs.hip", "mpk_autoreset.hip", "mpk_env_step.hip", "mpk_misc.hip")          # translation units of the device code (mpk_traj_family.hip: once per MP type)
 KERNEL_HEADERS = ("mpk_dev.h", "mpk_tile.h", "mpk_traj_tiles.h", "mpk_traj_stream.h", "mpk_traj_flat.h", "mpk_traj_ring.h", "mpk_traj_quad.h",
                   "mpk_traj_pipe.h", "mpk_traj_route.h", "mpk_reward.h", "mpk_phase.h", "mpk_trace_reader.h", "mpk_nprng.h", "mpk_plant.h", "mpk_reacher_env.h", "mpk_hole_geom.h")

@@ -481,6 +481,9 @@ class BatchedBlackBox:
         for clock in range(self.every, self.horizon, self.every):
             p, v = self.engine.trajectory(params, cond_pos, cond_vel, float(clock * self.dt))
             own = (self.traj_steps == clock).view(self.B, 1, 1)
+            if pos.requires_grad:                     # a differentiable plan: autograd takes no out=
+                pos, vel = torch.where(own, p, pos), torch.where(own, v, vel)
+                continue
             torch.where(own, p, pos, out=pos)
             torch.where(own, v, vel, out=vel)
         return pos, vel

@@ -758,6 +758,7 @@ const OptKey kOptKeys[] = {
     {"pd_helper", &Tuning::pd_helper, 0, 1},     {"phase_waves", &Tuning::phase_waves, 1, 32},
     {"phase_split", &Tuning::phase_split, 1, 64},   {"phase_pipe", &Tuning::phase_pipe, 0, 1},
     {"pd_pipe", &Tuning::pd_pipe, 0, 1},         {"hole_sampled", &Tuning::hole_sampled, 0, 1},
+    {"vjp_generic", &Tuning::vjp_generic, 0, 1},
 };
 const OptKey* find_opt(const char* key) {
     if (!key) return nullptr;
@@ -1012,6 +1013,33 @@ int mpk_trajectory(mpk_handle hh, const float* params, const float* init_pos, co
     if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
     return traj_common(reinterpret_cast<Handle*>(hh), params, init_pos, init_vel, init_time, init_time_shared,
                        pos, vel, nullptr, nullptr, nullptr, nullptr, B, stream);
+}
+
+// the transpose of mpk_trajectory's shared-phase map: same tables (built or reused for (init_time_shared, T) exactly as there), one launch
+int mpk_trajectory_vjp(mpk_handle hh, const float* g_pos, const float* g_vel, double init_time_shared, float* g_params,
+                       float* g_init_pos, float* g_init_vel, int32_t B, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (B < 0) { set_error("B must be >= 0"); return MPK_EINVAL; }
+    if (h->cfg.learn_tau || h->cfg.learn_delay) {
+        set_error("mpk_trajectory_vjp: a learned tau / delay makes the trajectory non-linear in those two parameters (and they are "
+                  "clipped to their bounds): only shared-phase handles are differentiable");
+        return MPK_ENOTIMPL;
+    }
+    const Tuning tune = effective_tuning(h);
+    const bool dmp = h->cfg.mp_type == MPK_MP_DMP;
+    if (dmp && (h->cfg.dmp_first_sample == MPK_DMP_FIRST_IS_STEP || !dmp_response(h, nullptr, tune))) {
+        set_error("mpk_trajectory_vjp: a DMP handle is differentiable on its response route only (<= 16 DoF, <= 13 basis functions, "
+                  "alpha ds <= 1, dmp_first_sample = init, option \"dmp_response\" not 0)");
+        return MPK_ENOTIMPL;
+    }
+    if (B == 0 || h->dev.D == 0 || (!g_params && !g_init_pos && !g_init_vel)) return MPK_OK;
+    MPK_ON_DEVICE(h->cfg.device);
+    SharedTables st;
+    int rc = get_shared(h, (float)init_time_shared, stream, &st, dmp);
+    if (rc != MPK_OK) return rc;
+    return launch_traj_vjp(dmp ? h->dev_resp : h->dev, st, g_pos, g_vel, g_params, g_init_pos, g_init_vel, B, h->num_cu, stream,
+                           &h->last_kernel, tune);
 }
 
 int mpk_trajectory_actions(mpk_handle hh, const float* params, const float* init_pos, const float* init_vel,

@@ -36,7 +36,7 @@ struct Tuning {
         phase_chunk = -1, pd_simple = -1, split = -1, lds_pad = -1, pipe = -1, flat = -1, phase_flat = -1,
         ring = -1, ring_np = -1, ring_ns = -1, ring_m = -1, ring_dbg = -1, ring_parts = -1, tiles_wpb = -1, serial_order = -1, ring_nc = -1,
         pd_generic = -1, dmp_response = -1, ablations = -1, ring_tb = -1, pd_helper = -1, phase_waves = -1, phase_split = -1, phase_pipe = -1, pd_pipe = -1,
-        hole_sampled = -1;
+        hole_sampled = -1, vjp_generic = -1;
 };
 
 // ---- device-side configuration (kernel argument, by value) --------------------------------------------------
@@ -138,6 +138,12 @@ int launch_reward_aggregate(const double* rewards, const int32_t* seg_len, int a
 int launch_traj_wide(const DevCfg& c, const SharedTables& st, const float* params, const float* init_pos,
                      const float* init_vel, float* pos, float* vel, int B, int num_cu, void* stream,
                      const char** kernel_name);
+// mpk_trajectory_vjp (mpk_traj_vjp.hip): the transpose of the shared-phase map, (g_pos, g_vel) [B, T, D] -> g_params [B, P], g_init_pos /
+// g_init_vel [B, D]; any input or output may be nullptr (term skipped / not written).  Tile route (matrix cores) for <= kMaxD DoF and
+// <= kMaxKP columns, else -- or with tune.vjp_generic == 1 -- one workgroup per episode on the vector ALU.  c: the configuration the
+// tables were built for (a DMP handle's response configuration); MPK_ENOTIMPL for plain-DMP forcing tables.
+int launch_traj_vjp(const DevCfg& c, const SharedTables& st, const float* g_pos, const float* g_vel, float* g_params, float* g_init_pos,
+                    float* g_init_vel, int B, int num_cu, void* stream, const char** kernel_name, const Tuning& tune);
 int launch_traj_rows(const DevCfg& c, const float* params, const float* init_pos, const float* init_vel,
                      const float* init_time, float init_time_shared, float* pos, float* vel, int32_t* range_flag,
                      int B, int num_cu, void* stream, const char** kernel_name, const Tuning& tune);

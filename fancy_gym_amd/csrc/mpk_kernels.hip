@@ -11,6 +11,7 @@
 //   mpk_traj_route.h     TrajRoute / EpRoute (what the selection rule hands to the launchers above), their declarations, dispatch helpers
 //   mpk_traj_launch.hip  k_build_shared + plan_traj_shared (kernel selection rule, one function per family) + launch_traj_shared
 //   mpk_traj_wide.hip    k_traj_wide
+//   mpk_traj_vjp.hip     k_traj_vjp_tile / k_traj_vjp_generic: the shared-phase map transposed (mpk_trajectory_vjp)
 //   mpk_traj_phase.hip   per-episode phase kernels
 //   mpk_phase_fused.hip  per-episode phase: the fused entry points (actions, closed loop, replanning step, verbose < 2 step, validity gate)
 //   mpk_rollout.hip      rollout kernels
@@ -28,6 +29,7 @@
 #include "mpk_episode.hip"
 #include "mpk_traj_launch.hip"
 #include "mpk_traj_wide.hip"
+#include "mpk_traj_vjp.hip"
 #include "mpk_traj_phase.hip"
 #include "mpk_phase_fused.hip"
 #include "mpk_rollout.hip"

@@ -79,6 +79,26 @@ class RolloutSpec:
             self._keep.append(keep)
 
 
+class _TrajectoryFn(torch.autograd.Function):
+    """``TrajectoryEngine.trajectory`` with a backward: forward = the mpk_trajectory launch as without autograd, backward = one
+    mpk_trajectory_vjp launch on the current stream; ``needs_input_grad`` decides which of its outputs are computed at all"""
+
+    @staticmethod
+    def forward(ctx, engine, init_time, out, params, init_pos, init_vel):
+        ctx.engine, ctx.init_time = engine, init_time
+        ctx.set_materialize_grads(False)          # an output the loss never saw arrives as None: its term is skipped, not read
+        return engine._trajectory_launch(params, init_pos, init_vel, None, init_time, out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_pos, g_vel):
+        need = ctx.needs_input_grad[3:6]
+        if g_pos is None and g_vel is None:
+            return (None,) * 6
+        g_params, g_init_pos, g_init_vel = ctx.engine.trajectory_vjp(g_pos, g_vel, ctx.init_time, need=need)
+        return None, None, None, g_params, g_init_pos, g_init_vel
+
+
 class TrajectoryEngine:
     """
     One configured movement primitive on one GPU.  Constructor arguments mirror the kwarg groups the reference hands
@@ -211,7 +231,7 @@ class TrajectoryEngine:
         B = params.shape[0]
         if params.shape[1] != self.num_params:
             raise ValueError(f"params has {params.shape[1]} entries per episode, expected {self.num_params}")
-        D, T = self.num_dof, self.num_steps
+        D = self.num_dof
         init_pos, init_vel = self._f32(init_pos, (B, D)), self._f32(init_vel, (B, D))
         it_t = None
         it_s = 0.0
@@ -219,6 +239,19 @@ class TrajectoryEngine:
             it_t = self._f32(init_time, (B,))
         else:
             it_s = float(init_time)
+        if torch.is_grad_enabled() and (params.requires_grad or init_pos.requires_grad or init_vel.requires_grad):
+            # differentiable: the same forward launch, and one mpk_trajectory_vjp launch as its backward (shared phase only)
+            if self.config.learn_tau or self.config.learn_delay:
+                raise NotImplementedError("trajectory() is differentiable for a shared phase only: with a learned tau / delay the "
+                                          "trajectory is not linear in those two parameters, and they are clipped to their bounds")
+            if it_t is not None:
+                raise NotImplementedError("trajectory() is differentiable for one init_time shared by the batch only: pass a float, "
+                                          "not a per-episode tensor")
+            return _TrajectoryFn.apply(self, it_s, out, params, init_pos, init_vel)
+        return self._trajectory_launch(params, init_pos, init_vel, it_t, it_s, out)
+
+    def _trajectory_launch(self, params, init_pos, init_vel, it_t, it_s, out):
+        B, D, T = params.shape[0], self.num_dof, self.num_steps
         if out is None:
             pos = torch.empty((B, T, D), dtype=torch.float32, device=self.device)
             vel = torch.empty((B, T, D), dtype=torch.float32, device=self.device)
@@ -227,6 +260,43 @@ class TrajectoryEngine:
         _lib.check(self._lib.mpk_trajectory(self._h, params.data_ptr(), init_pos.data_ptr(), init_vel.data_ptr(),
                                             _dptr(it_t), it_s, pos.data_ptr(), vel.data_ptr(), B, self._stream()))
         return pos, vel
+
+    def trajectory_vjp(self, g_pos: Optional[torch.Tensor], g_vel: Optional[torch.Tensor], init_time: float = 0.0, *,
+                       need: Sequence[bool] = (True, True, True), out: Optional[Sequence[Optional[torch.Tensor]]] = None
+                       ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """
+        The vector-Jacobian product of ``trajectory`` for a shared phase (mpk.h: mpk_trajectory_vjp), one launch: gradients of a loss
+        w.r.t. pos / vel [B, T, D] (either may be None: that output did not reach the loss) -> (g_params [B, P], g_init_pos [B, D],
+        g_init_vel [B, D]) float32 on the device.  ``need[i]`` False: that output is not computed (None is returned in its place);
+        ``out``: buffers to write the needed ones into.  NotImplementedError for a learned tau / delay and for a DMP outside its
+        response route.
+        """
+        ref = g_pos if g_pos is not None else g_vel
+        if ref is None:
+            raise ValueError("trajectory_vjp needs g_pos or g_vel")
+        D, T = self.num_dof, self.num_steps
+        B = ref.shape[0]
+        gs = []
+        for name, g in (("g_pos", g_pos), ("g_vel", g_vel)):
+            if g is not None:
+                g = torch.as_tensor(g, dtype=torch.float32, device=self.device)
+                if g.shape != (B, T, D):
+                    raise ValueError(f"{name} must be [{B}, {T}, {D}], got {tuple(g.shape)}")
+                g = g.contiguous()
+            gs.append(g)
+        res = []
+        for i, shape in enumerate(((B, self.num_params), (B, D), (B, D))):
+            if not need[i]:
+                res.append(None)
+            elif out is not None and out[i] is not None:
+                if out[i].shape != shape or out[i].dtype != torch.float32 or not out[i].is_contiguous() or out[i].device != self.device:
+                    raise ValueError(f"out[{i}] must be a contiguous float32 tensor of shape {shape} on {self.device}")
+                res.append(out[i])
+            else:
+                res.append(torch.empty(shape, dtype=torch.float32, device=self.device))
+        _lib.check(self._lib.mpk_trajectory_vjp(self._h, _dptr(gs[0]), _dptr(gs[1]), float(init_time), _dptr(res[0]), _dptr(res[1]),
+                                                _dptr(res[2]), B, self._stream()))
+        return res[0], res[1], res[2]
 
     def check_range(self):
         """synchronise and raise RuntimeError if a per-episode-phase ProDMP launch left the pre-computed table range"""

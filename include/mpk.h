@@ -267,6 +267,8 @@ int mpk_set_duration(mpk_handle h, double duration, double dt);
  *   "ablations"     1 lets the ablation bits of "ring_dbg" take effect (default: they are masked out)
  *   "hole_sampled"  1 mpk_hole_reacher_rollout tests the wall on the reference's 100 points per link instead of the index intervals
  *                   (A/B runs and tests: the same verdicts bit for bit)
+ *   "vjp_generic"   1 mpk_trajectory_vjp takes its one-workgroup-per-episode route also for shapes the matrix-core route covers
+ *                   (A/B runs and tests)
  * Unknown key or value out of range: MPK_EINVAL.  mpk_get_option returns the effective value (MPK_OPT_AUTO if automatic).
  */
 #define MPK_OPT_AUTO (-1)
@@ -892,6 +894,25 @@ int mpk_reacher_env_step(mpk_handle h, const mpk_env_step_task* step, const mpk_
                          mpk_nprng_state* rng, double* q, double* qd, int32_t* traj_steps, double* task_io, double* reward_state,
                          double* reward, uint8_t* terminated, uint8_t* truncated, uint8_t* is_collided, uint8_t* is_success,
                          uint8_t* reset_mask, float* final_obs, float* obs, int32_t B, void* stream);
+
+/*
+ * The vector-Jacobian product of mpk_trajectory for a handle with a SHARED phase (appended under ABI 4): with no learned tau / delay and
+ * one init_time for the batch, pos and vel are linear in (params, init_pos, init_vel) -- ProMP and ProDMP by construction, DMP through
+ * the response rows of its explicit Euler map -- so the gradient of any scalar loss is the launch's own basis table contracted over
+ * time with the loss's gradients w.r.t. pos and vel:
+ *   g_pos, g_vel   dev float [B, T, D], contiguous; either may be NULL (that output did not reach the loss): the term is skipped
+ *   g_params       dev float [B, P]     out, d loss / d params   (weights_scale, goal_scale, relative_goal, disable_* applied transposed)
+ *   g_init_pos     dev float [B, D]     out, d loss / d init_pos (exact zeros where the configuration never reads it: ProMP without a
+ *   g_init_vel     dev float [B, D]     out, d loss / d init_vel  zero-padded basis; ProMP's init_vel); any output may be NULL: not written
+ * One launch on `stream` (plus the table builder when (init_time_shared, T) is not cached, exactly as mpk_trajectory); nothing is
+ * allocated or synchronised.  <= 16 DoF and <= 16 contraction columns run on the matrix cores (k_traj_vjp_tile), every other shape on
+ * k_traj_vjp_generic; no atomics, an episode is reduced inside one workgroup: results are the same bits from run to run, and do not
+ * depend on the alignment of g_pos / g_vel.  MPK_ENOTIMPL: a handle with a learned tau / delay (the map is not linear in them and they
+ * are clipped), and a DMP handle outside its response route (more than 16 DoF or 13 basis functions, alpha ds > 1,
+ * MPK_DMP_FIRST_IS_STEP, option "dmp_response" 0).
+ */
+int mpk_trajectory_vjp(mpk_handle h, const float* g_pos, const float* g_vel, double init_time_shared,
+                       float* g_params, float* g_init_pos, float* g_init_vel, int32_t B, void* stream);
 
 #ifdef __cplusplus
 }
