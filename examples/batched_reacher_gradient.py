@@ -1,0 +1,62 @@
+#!/usr/bin/env python3
+"""
+Gradient ascent on the return of `fancy_ProDMP/LongSimpleReacher-v0`, all on the device.
+
+Every episode of the batch (its own start pose and goal, drawn by the seeded device reset) gets its own ProDMP parameter vector, and
+Adam climbs the mean return through `BatchedBlackBox.step(params, differentiable=True)`: plan -> PD controller -> clip -> torque
+plant -> SimpleReacher reward -> aggregation forward, and two launches backward -- `mpk_reacher_rollout_vjp` (the rollout's adjoint)
+and `mpk_trajectory_vjp` (the plan's).  `examples/batched_reacher_search.py` climbs the same return without derivatives.
+
+    python examples/batched_reacher_gradient.py [--envs 4096] [--iters 100] [--lr 0.02] [--seed 0]
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from fancy_gym_amd import make_batched  # noqa: E402
+
+ID = "fancy_ProDMP/LongSimpleReacher-v0"
+
+
+def optimise(envs: int = 4096, iters: int = 100, lr: float = 0.02, seed: int = 0, verbose: bool = True):
+    """returns (mean return of the initial parameters, mean return after ``iters`` Adam steps) on the same seeded episodes"""
+    bb = make_batched(ID, envs, observations=False)
+    params = torch.zeros((envs, bb.engine.num_params), device=bb.device, requires_grad=True)
+    opt = torch.optim.Adam([params], lr=lr)
+    returns = []
+    t0 = time.perf_counter()
+    for it in range(iters + 1):
+        bb.reset(seed=seed)                      # the same episodes every iteration
+        if it == iters:
+            with torch.no_grad():
+                returns.append(bb.step(params)["rewards"].mean())
+            break
+        ret = bb.step(params, differentiable=True)["rewards"].mean()
+        opt.zero_grad(set_to_none=True)
+        (-ret).backward()
+        opt.step()
+        returns.append(ret.detach())
+        if verbose and it % 10 == 0:
+            print(f"iteration {it:4d}: mean return {float(ret):.4f}")
+    torch.cuda.synchronize()
+    first, last = float(returns[0]), float(returns[-1])
+    if verbose:
+        print(f"mean return {first:.4f} -> {last:.4f} after {iters} Adam steps on {envs} episodes "
+              f"({(time.perf_counter() - t0) / max(iters, 1) * 1e3:.2f} ms per iteration)")
+    return first, last
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--lr", type=float, default=0.02)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    torch.manual_seed(a.seed)
+    optimise(a.envs, a.iters, a.lr, a.seed)

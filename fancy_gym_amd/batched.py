@@ -713,14 +713,45 @@ class BatchedBlackBox:
 
     _PER_STEP = ("des_pos", "des_vel", "step_actions", "step_rewards")
 
-    def step(self, params, fuse: bool = True) -> Dict[str, torch.Tensor]:
-        out = self._step(params, fuse)
+    def step(self, params, fuse: bool = True, differentiable: bool = False) -> Dict[str, torch.Tensor]:
+        """one plan of every episode.  ``differentiable=True`` (reward "simple_reacher"; off by default, and then nothing changes on any
+        path): the step takes the separate launches under autograd -- differentiable ``get_trajectory`` -> differentiable
+        ``reacher_rollout`` -> ``reward_aggregate`` -- so that ``out["rewards"]`` (and ``step_rewards``) carry the graph back to
+        ``params``: the same values, state and integer outputs as ``step(params, fuse=False)``, and a backward of two launches,
+        mpk_reacher_rollout_vjp and mpk_trajectory_vjp.  With replanning the gradient is that of THIS step's reward w.r.t. THIS
+        step's parameters: the plant state and the condition the plan starts from are constants of the graph, nothing flows into
+        earlier steps.  NotImplementedError: another reward, ``pos_limits``, and what ``trajectory`` refuses under autograd (a learned
+        tau / delay, per-episode plan times after partial resets)."""
+        if differentiable:
+            self._refuse_differentiable()
+        out = self._step(params, fuse, differentiable)
         # (the plan-start state for the replay of step_observations: a copy taken by _step before the plan)
         return self._add_observations(out, self._obs_start) if self.observations else out
 
-    def _step(self, params, fuse: bool) -> Dict[str, torch.Tensor]:
+    def _refuse_differentiable(self):
+        if self.reward != "simple_reacher":
+            raise NotImplementedError(f"step(differentiable=True) is built for reward='simple_reacher' (the torque double integrator), "
+                                      f"not for reward={self.reward!r}: HoleReacher's return is discontinuous at collisions")
+        if self.pos_limits is not None:
+            raise NotImplementedError("step(differentiable=True) does not take pos_limits: the validity gate ends episodes on a "
+                                      "threshold of the plan, which has no derivative")
+        if self._n_phase:
+            raise NotImplementedError("step(differentiable=True) needs a shared phase: with a learned tau / delay the trajectory is "
+                                      "not linear in those two parameters, and they are clipped to their bounds")
+        if self.do_replanning and self._lockstep is None:
+            raise NotImplementedError("step(differentiable=True) needs one plan time for the batch: after partial resets (or with "
+                                      "device_time) every episode has its own init_time, which trajectory() refuses under autograd")
+
+    def _step(self, params, fuse: bool, differentiable: bool = False) -> Dict[str, torch.Tensor]:
         self._plans_since_reset += 1
         self._obs_start = (self.q.clone(), self.qd.clone()) if self.observations and self.verbose >= 2 else None
+        if differentiable:
+            with torch.enable_grad():
+                out = self._step_full(params, fuse=False, differentiable=True)
+            if self.verbose < 2:
+                for k in self._PER_STEP:
+                    out.pop(k, None)
+            return out
         if self.reward == "hole_reacher":
             return self._step_hole(params)
         if fuse and self._can_episode_return():
@@ -733,7 +764,7 @@ class BatchedBlackBox:
                 out.pop(k, None)
         return out
 
-    def _step_full(self, params, fuse: bool = True) -> Dict[str, torch.Tensor]:
+    def _step_full(self, params, fuse: bool = True, differentiable: bool = False) -> Dict[str, torch.Tensor]:
         if fuse and self._can_fuse():
             return self._step_fused(params)
         out = self.get_trajectory(params)
@@ -757,6 +788,10 @@ class BatchedBlackBox:
             seg = self.engine.replan_advance(self.traj_steps, self.plan_steps, self.done, self.every, int(mpt),
                                              self.horizon)
         if self.reward is not None:
+            if not differentiable:
+                # (a plan that kept its graph -- params.requires_grad_() -- is rolled out as a constant, as before step(differentiable=True)
+                # existed: no clone of the state, no grad_fn on the rewards)
+                pos, vel = pos.detach(), vel.detach()
             act, rew = self.engine.reacher_rollout(self.spec, pos, vel, self.q, self.qd, self.goal, n_steps=seg,
                                                    step0=self.traj_steps - seg,
                                                    steps_before_reward=self.steps_before_reward)

@@ -1295,6 +1295,37 @@ int mpk_reacher_rollout(mpk_handle hh, const mpk_rollout_cfg* rc, const float* d
                                   actions, rewards, B, T, stream, effective_tuning(h), h->d_fault);
 }
 
+// the adjoint of mpk_reacher_rollout: nothing of the forward's launch is reused but its inputs (the plan-start state is an argument)
+int mpk_reacher_rollout_vjp(mpk_handle hh, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel, const double* q0,
+                            const double* qd0, const int32_t* n_steps, const int32_t* step0, const double* goal,
+                            int32_t steps_before_reward, const double* g_rewards, const double* g_q, const double* g_qd,
+                            float* g_des_pos, float* g_des_vel, double* g_q0, double* g_qd0, double* g_goal, int32_t B, int32_t T,
+                            void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (B < 0 || T < 0) { set_error("B and T must be >= 0"); return MPK_EINVAL; }
+    if (rc && rc->plant_type != MPK_PLANT_DOUBLE_INTEGRATOR && rc->plant_type >= 0 && rc->plant_type <= 2) {
+        set_error("mpk_reacher_rollout_vjp differentiates the torque double integrator (MPK_PLANT_DOUBLE_INTEGRATOR) only: a static "
+                  "plant -- the metaworld controller's frozen state among them -- has no rollout to transpose, and HoleReacher's "
+                  "direct-velocity plant is not built");
+        return MPK_ENOTIMPL;
+    }
+    if (h->dev.D > kMaxD) {
+        set_error("mpk_reacher_rollout_vjp: " + std::to_string(h->dev.D) + " DoF, the kernel takes at most 16 (one lane per (episode, "
+                  "DoF), the links of a paid step summed inside a wave)");
+        return MPK_ENOTIMPL;
+    }
+    RolloutDev rd;
+    int r = fill_rollout(h, rc, &rd);
+    if (r != MPK_OK) return r;
+    if (B == 0 || h->dev.D == 0) return MPK_OK;
+    if (!g_des_pos && !g_des_vel && !g_q0 && !g_qd0 && !g_goal) return MPK_OK;
+    if (!q0 || !qd0 || !goal || (T > 0 && (!des_pos || !des_vel))) { set_error("NULL buffer"); return MPK_EINVAL; }
+    MPK_ON_DEVICE(h->cfg.device);
+    return launch_reacher_rollout_vjp(rd, h->dev.D, des_pos, des_vel, q0, qd0, n_steps, step0, goal, steps_before_reward, g_rewards,
+                                      g_q, g_qd, g_des_pos, g_des_vel, g_q0, g_qd0, g_goal, B, T, stream, &h->last_kernel);
+}
+
 int mpk_hole_reacher_rollout(mpk_handle hh, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel, double* q,
                              double* qd, const int32_t* n_steps, const int32_t* step0, const mpk_hole_task* task, const double* hole,
                              float* actions, double* rewards, double* ret, int32_t agg, int32_t* n_exec, uint8_t* collided,

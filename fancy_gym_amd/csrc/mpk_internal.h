@@ -171,6 +171,14 @@ int launch_reacher_rollout(const RolloutDev& rc, int D, const float* des_pos, co
                            double* qd, const int32_t* n_steps, const int32_t* step0, const double* goal,
                            int steps_before_reward, float* actions, double* rewards, int B, int T, void* stream,
                            const Tuning& tune, int* fault);
+// mpk_reacher_rollout_vjp (mpk_rollout_vjp.hip): the adjoint of launch_reacher_rollout's computation, one launch; any upstream gradient
+// and any output may be nullptr (0 / not written).  MPK_ENOTIMPL: more than kMaxD DoF, a plant other than the double integrator, a
+// horizon whose tile checkpoints do not fit the LDS.
+int launch_reacher_rollout_vjp(const RolloutDev& rc, int D, const float* des_pos, const float* des_vel, const double* q0,
+                               const double* qd0, const int32_t* n_steps, const int32_t* step0, const double* goal,
+                               int steps_before_reward, const double* g_rewards, const double* g_q, const double* g_qd,
+                               float* g_des_pos, float* g_des_vel, double* g_q0, double* g_qd0, double* g_goal, int B, int T,
+                               void* stream, const char** kernel_name);
 // mpk_hole_reacher_rollout (mpk_hole.hip): the HoleReacher step loop with its break on collision
 struct HoleLaunch {
     RolloutDev rc;

@@ -99,6 +99,55 @@ class _TrajectoryFn(torch.autograd.Function):
         return None, None, None, g_params, g_init_pos, g_init_vel
 
 
+class _ReacherRolloutFn(torch.autograd.Function):
+    """``TrajectoryEngine.reacher_rollout`` with a backward: forward = a copy of the plan-start (q, qd) and the mpk_reacher_rollout launch
+    as without autograd, backward = one mpk_reacher_rollout_vjp launch; the actions and the in-place q, qd carry no graph"""
+
+    @staticmethod
+    def forward(ctx, engine, spec, q, qd, n_steps, step0, steps_before_reward, want_actions, out, des_pos, des_vel, goal):
+        ctx.engine, ctx.spec, ctx.n_steps, ctx.step0, ctx.sbr = engine, spec, n_steps, step0, int(steps_before_reward)
+        ctx.start = (q.clone(), qd.clone())
+        ctx.save_for_backward(des_pos, des_vel, goal)
+        act, rew = engine._reacher_rollout_launch(spec, des_pos, des_vel, q, qd, goal, n_steps, step0, steps_before_reward,
+                                                  want_actions, out)
+        if act is None:
+            return rew
+        ctx.mark_non_differentiable(act)
+        return act, rew
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        g_rew = grads[-1]
+        des_pos, des_vel, goal = ctx.saved_tensors
+        need = ctx.needs_input_grad[9:12]
+        g_pos, g_vel, _, _, g_goal = ctx.engine.reacher_rollout_vjp(
+            ctx.spec, des_pos, des_vel, ctx.start[0], ctx.start[1], goal, g_rew, n_steps=ctx.n_steps, step0=ctx.step0,
+            steps_before_reward=ctx.sbr, need=(need[0], need[1], False, False, need[2]))
+        return (None,) * 9 + (g_pos, g_vel, g_goal)
+
+
+class _RewardAggregateFn(torch.autograd.Function):
+    """``reward_aggregate`` with a backward: the value is the mpk_reward_aggregate launch's, bit for bit; the aggregation is linear, so
+    the gradient of the step rewards is g_ret[b] times 1 (sum), 1 / seg (mean) or the last-step indicator (last) for t < seg[b]"""
+
+    @staticmethod
+    def forward(ctx, engine, seg_len, aggregation, rewards):
+        ctx.seg, ctx.agg, ctx.T = seg_len, aggregation, rewards.shape[1]
+        return engine._reward_aggregate_launch(rewards, seg_len, aggregation)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_ret):
+        seg = ctx.seg.view(-1, 1)
+        t = torch.arange(ctx.T, device=g_ret.device, dtype=seg.dtype).view(1, -1)
+        g = g_ret.view(-1, 1)
+        if ctx.agg == "mean":
+            g = g / seg.clamp(min=1).to(g.dtype)
+        live = (t == seg - 1) if ctx.agg == "last" else (t < seg)
+        return None, None, None, torch.where(live, g, torch.zeros((), dtype=g.dtype, device=g.device))
+
+
 class TrajectoryEngine:
     """
     One configured movement primitive on one GPU.  Constructor arguments mirror the kwarg groups the reference hands
@@ -583,9 +632,15 @@ class TrajectoryEngine:
     def reward_aggregate(self, rewards: torch.Tensor, seg_len: torch.Tensor, aggregation: str = "sum") -> torch.Tensor:
         """reward_aggregation over each episode's executed steps (black_box_wrapper.py:216) of step rewards [B, T] float64, in the
         order of additions of episode_return (mpk.h: mpk_reward_aggregate): the two paths agree bit for bit"""
-        B, T = rewards.shape
         assert rewards.dtype == torch.float64 and rewards.is_contiguous()
         seg_len = seg_len.to(device=self.device, dtype=torch.int32).contiguous()
+        if torch.is_grad_enabled() and rewards.requires_grad:
+            # differentiable step rewards (reacher_rollout under autograd): the same launch, a linear backward
+            return _RewardAggregateFn.apply(self, seg_len, aggregation, rewards)
+        return self._reward_aggregate_launch(rewards, seg_len, aggregation)
+
+    def _reward_aggregate_launch(self, rewards, seg_len, aggregation):
+        B, T = rewards.shape
         out = torch.empty(B, dtype=torch.float64, device=self.device)
         _lib.check(self._lib.mpk_reward_aggregate(self._h, rewards.data_ptr(), seg_len.data_ptr(), _lib.AGG_MODES[aggregation],
                                                   out.data_ptr(), B, T, self._stream()))
@@ -617,6 +672,11 @@ class TrajectoryEngine:
         """
         pd_rollout + SimpleReacherEnv's per-step reward (simple_reacher.py:56-72) on the torque double integrator:
         returns (actions float32 [B, T, D] or None, rewards float64 [B, T]); q, qd are updated in place.
+
+        Differentiable: with grad enabled and ``des_pos``, ``des_vel`` or ``goal`` requiring grad, the same launch runs on a copy-protected
+        plan-start state (q, qd are cloned first) and ``rewards`` carries a ``grad_fn`` whose backward is ONE mpk_reacher_rollout_vjp
+        launch (``reacher_rollout_vjp``); the actions and the in-place q, qd carry no graph.  The plan-start state is a constant of that
+        graph.  Otherwise -- no requires_grad, or under no_grad -- nothing changes.
         """
         self._refuse_metaworld(spec, "reacher_rollout")
         B, T, D = des_pos.shape
@@ -624,20 +684,81 @@ class TrajectoryEngine:
         assert q.dtype == torch.float64 and qd.dtype == torch.float64 and q.is_contiguous() and qd.is_contiguous()
         des_pos, des_vel = des_pos.contiguous(), des_vel.contiguous()
         goal = torch.as_tensor(goal, dtype=torch.float64, device=self.device).expand(B, 2).contiguous()
+        if n_steps is not None:
+            n_steps = n_steps.to(device=self.device, dtype=torch.int32).contiguous()
+        if step0 is not None:
+            step0 = step0.to(device=self.device, dtype=torch.int32).contiguous()
+        if torch.is_grad_enabled() and (des_pos.requires_grad or des_vel.requires_grad or goal.requires_grad):
+            res = _ReacherRolloutFn.apply(self, spec, q, qd, n_steps, step0, steps_before_reward, want_actions, out, des_pos, des_vel,
+                                          goal)
+            return res if isinstance(res, tuple) else (None, res)
+        return self._reacher_rollout_launch(spec, des_pos, des_vel, q, qd, goal, n_steps, step0, steps_before_reward, want_actions,
+                                            out)
+
+    def _reacher_rollout_launch(self, spec, des_pos, des_vel, q, qd, goal, n_steps, step0, steps_before_reward, want_actions, out):
+        B, T, D = des_pos.shape
         if out is not None:
             act, rew = out
         else:
             act = torch.empty((B, T, D), dtype=torch.float32, device=self.device) if want_actions else None
             rew = torch.empty((B, T), dtype=torch.float64, device=self.device)
-        if n_steps is not None:
-            n_steps = n_steps.to(device=self.device, dtype=torch.int32).contiguous()
-        if step0 is not None:
-            step0 = step0.to(device=self.device, dtype=torch.int32).contiguous()
         _lib.check(self._lib.mpk_reacher_rollout(self._h, C.byref(spec.c), des_pos.data_ptr(), des_vel.data_ptr(),
                                                  q.data_ptr(), qd.data_ptr(), _dptr(n_steps), _dptr(step0),
                                                  goal.data_ptr(), int(steps_before_reward), _dptr(act),
                                                  rew.data_ptr(), B, T, self._stream()))
         return act, rew
+
+    def reacher_rollout_vjp(self, spec: RolloutSpec, des_pos: torch.Tensor, des_vel: torch.Tensor, q0: torch.Tensor,
+                            qd0: torch.Tensor, goal: torch.Tensor, g_rewards: Optional[torch.Tensor], *,
+                            g_q: Optional[torch.Tensor] = None, g_qd: Optional[torch.Tensor] = None,
+                            n_steps: Optional[torch.Tensor] = None, step0: Optional[torch.Tensor] = None,
+                            steps_before_reward: int = 199, need: Sequence[bool] = (True, True, True, True, True),
+                            out: Optional[Sequence[Optional[torch.Tensor]]] = None):
+        """
+        The vector-Jacobian product of ``reacher_rollout`` (mpk.h: mpk_reacher_rollout_vjp), one launch: the gradients of a loss w.r.t.
+        the step rewards [B, T] float64 and the final state (``g_q``, ``g_qd`` [B, D] float64; any of the three may be None = 0) ->
+        (g_des_pos, g_des_vel float32 [B, T, D], g_q0, g_qd0 float64 [B, D], g_goal float64 [B, 2]).  ``q0``, ``qd0`` are the state at
+        the START of the plan (reacher_rollout overwrites its q, qd: pass a copy taken before), and a constant here and there: under
+        replanning this is the gradient of ONE plan's rewards w.r.t. that plan's trajectory.  ``need[i]`` False: that output is not
+        computed (None in its place); ``out``: buffers for the needed ones.  NotImplementedError: more than 16 DoF, a plant other than
+        the double integrator (the metaworld controller), horizons beyond about 2 100 steps.
+        """
+        if getattr(spec, "metaworld", False) or spec.plant != "double_integrator":
+            raise NotImplementedError("reacher_rollout_vjp differentiates the torque double integrator only (plant='double_integrator'): "
+                                      "the metaworld controller runs on a frozen state, HoleReacher's direct-velocity plant is not built")
+        B, T, D = des_pos.shape
+        assert des_pos.dtype == torch.float32 and des_vel.dtype == torch.float32
+        des_pos, des_vel = des_pos.detach().contiguous(), des_vel.detach().contiguous()
+        q0, qd0 = self._f64(q0, (B, D)).detach(), self._f64(qd0, (B, D)).detach()
+        goal = torch.as_tensor(goal, dtype=torch.float64, device=self.device).detach().expand(B, 2).contiguous()
+        ups = []
+        for name, g, shape in (("g_rewards", g_rewards, (B, T)), ("g_q", g_q, (B, D)), ("g_qd", g_qd, (B, D))):
+            if g is not None:
+                g = torch.as_tensor(g, dtype=torch.float64, device=self.device)
+                if tuple(g.shape) != shape:
+                    raise ValueError(f"{name} must be {list(shape)}, got {list(g.shape)}")
+                g = g.detach().contiguous()
+            ups.append(g)
+        if n_steps is not None:
+            n_steps = n_steps.to(device=self.device, dtype=torch.int32).contiguous()
+        if step0 is not None:
+            step0 = step0.to(device=self.device, dtype=torch.int32).contiguous()
+        res = []
+        for i, (shape, dtype) in enumerate((((B, T, D), torch.float32), ((B, T, D), torch.float32), ((B, D), torch.float64),
+                                            ((B, D), torch.float64), ((B, 2), torch.float64))):
+            if not need[i]:
+                res.append(None)
+            elif out is not None and out[i] is not None:
+                if tuple(out[i].shape) != shape or out[i].dtype != dtype or not out[i].is_contiguous() or out[i].device != self.device:
+                    raise ValueError(f"out[{i}] must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+                res.append(out[i])
+            else:
+                res.append(torch.empty(shape, dtype=dtype, device=self.device))
+        _lib.check(self._lib.mpk_reacher_rollout_vjp(
+            self._h, C.byref(spec.c), des_pos.data_ptr(), des_vel.data_ptr(), q0.data_ptr(), qd0.data_ptr(), _dptr(n_steps),
+            _dptr(step0), goal.data_ptr(), int(steps_before_reward), _dptr(ups[0]), _dptr(ups[1]), _dptr(ups[2]), _dptr(res[0]),
+            _dptr(res[1]), _dptr(res[2]), _dptr(res[3]), _dptr(res[4]), B, T, self._stream()))
+        return tuple(res)
 
     def hole_reacher_rollout(self, spec: RolloutSpec, des_pos: Optional[torch.Tensor], des_vel: torch.Tensor, q: torch.Tensor,
                              qd: torch.Tensor, hole: torch.Tensor, *, collision_penalty: float = 100.0,

@@ -914,6 +914,43 @@ int mpk_reacher_env_step(mpk_handle h, const mpk_env_step_task* step, const mpk_
 int mpk_trajectory_vjp(mpk_handle h, const float* g_pos, const float* g_vel, double init_time_shared,
                        float* g_params, float* g_init_pos, float* g_init_vel, int32_t B, void* stream);
 
+/*
+ * The vector-Jacobian product of mpk_reacher_rollout (appended under ABI 4): controller, clip, torque double integrator and
+ * SimpleReacher's reward transposed -- the gradient of any scalar loss of the step rewards and the final state w.r.t. the desired
+ * trajectory, the plan-start state and the goal, one launch.  The forward it transposes (mpk_reacher_rollout above), per executed step
+ * t < n_steps[b] with the state (q, qd) before the step:
+ *   u  = Kp (des_pos_t - q) + Kd (des_vel_t - qd)     motor;  u = des_pos_t (position), u = des_vel_t (velocity)
+ *   a  = clip(u, lo, hi)          m = (lo <= u) && (u <= hi)    (the derivative of clip; 1 AT a bound: torch.clamp's convention)
+ *   qd' = qd + dt a ;  q' = q + dt qd'
+ *   c_l = sum_{j<=l} q'_j ;  ee = sum_l (cos c_l, sin c_l) ;  diff = ee - goal ;  dist = |diff|
+ *   r_t = -(step0 + t >= steps_before_reward ? dist : 0) - sum_d a_d^2
+ * The adjoint: lq, lqd start as g_q, g_qd; t runs from n_steps[b] - 1 down to 0; sx_j = sum_{l>=j} -sin c_l, sy_j = sum_{l>=j} cos c_l:
+ *   paid step (step0 + t >= steps_before_reward):  lq_j += -g_r (diff_x sx_j + diff_y sy_j) / dist ;  g_goal += g_r diff / dist
+ *   lqd += dt lq
+ *   la = dt lqd - 2 a g_r ;  lu = m la
+ *   g_des_pos_t = Kp lu, g_des_vel_t = Kd lu     (position: lu, 0;  velocity: 0, lu)
+ *   motor only:  lq -= Kp lu ;  lqd -= Kd lu
+ * and at the end g_q0 = lq, g_qd0 = lqd.  A paid step with dist = 0 contributes no distance term.
+ *   rc, des_pos, des_vel, n_steps, step0, goal, steps_before_reward   as mpk_reacher_rollout
+ *   q0, qd0      dev double [B, D]     the state at the START of the plan (mpk_reacher_rollout overwrites its q, qd: keep a copy); const
+ *   g_rewards    dev double [B, T] or NULL   d loss / d rewards (entries t >= n_steps[b] are not used); NULL = 0
+ *   g_q, g_qd    dev double [B, D] or NULL   d loss / d final state; NULL = 0
+ *   g_des_pos, g_des_vel   dev float [B, T, D] out, the float64 result rounded once; rows t >= n_steps[b] are exact zeros; any alignment
+ *   g_q0, g_qd0  dev double [B, D] out;  g_goal dev double [B, 2] out.  Any output may be NULL: not written.
+ * An episode with n_steps = 0 passes g_q, g_qd through unchanged.  float64 without FMA contraction, the forward's operations for u, a and
+ * the plant.  k_reacher_rollout_vjp (mpk_last_kernel names the instantiation): the forward's lane map -- one lane per (episode, DoF),
+ * floor(64 / D) episodes per wave, D compiled in for 2, 5 and 7 --; a forward sweep leaves (q, qd) at every 16-step tile boundary in LDS,
+ * the tiles are then replayed and reversed last to first.  No atomics, an episode never leaves its wave: the same bits from run to run
+ * and for any pointer alignment.  Allocates nothing, synchronises nothing, waits for no other wave.
+ * MPK_ENOTIMPL: more than 16 DoF; a horizon whose checkpoints (1 KB of LDS per 16 steps) do not fit the CU's 160 KB (about 2 100
+ * steps); a plant other than MPK_PLANT_DOUBLE_INTEGRATOR (so the metaworld controller, which runs on a frozen state only).
+ */
+int mpk_reacher_rollout_vjp(mpk_handle h, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel, const double* q0,
+                            const double* qd0, const int32_t* n_steps, const int32_t* step0, const double* goal,
+                            int32_t steps_before_reward, const double* g_rewards, const double* g_q, const double* g_qd,
+                            float* g_des_pos, float* g_des_vel, double* g_q0, double* g_qd0, double* g_goal, int32_t B, int32_t T,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
