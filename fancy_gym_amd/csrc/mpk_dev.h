@@ -100,6 +100,17 @@ constexpr size_t kRingTicketBytes = 192 * 1024;
 //   32 768 episodes (275 MB)  quad 54.8 / 51.8   ring 63.6 / 57.1        36 864 (310 MB)  quad 73.5 / 72.2   ring 69.5 / 65.2
 //   34 816 (292 MB)           quad 65.0 / 60.7   ring 66.8 / 58.0        40 960 (344 MB)  quad 92.6, duo 127.5   ring 84.5 / 76.9
 constexpr double kRingClosedBytes = 295.0 * 1024 * 1024;
+// prodmp, learned phase: rows of the pre-computed table an episode can reach -- scaled time <= (last grid time + init_time - smallest delay) /
+// smallest tau (the kernels clip tau and delay to their bounds) -- for a launch whose episodes share init_time
+static int prodmp_rows_reachable(const DevCfg& c, float init_time_shared) {
+    const float tau_lo = c.learn_tau ? c.tau_lo : c.tau, delay_lo = c.learn_delay ? c.delay_lo : c.delay;
+    if ((double)c.t_last > 0.0 && tau_lo > 0.f) {
+        const double s_max = ((double)c.t_last + (double)init_time_shared - (double)delay_lo) / (double)tau_lo;
+        const double r = s_max / (double)c.scaled_dt + 4.0;
+        if (r < (double)c.n_pc) return r < 4.0 ? 4 : (int)r;
+    }
+    return c.n_pc;
+}
 
 // Kernels that may take more than the default 64 KB of dynamic LDS: the function attribute is raised ONCE per kernel
 // instantiation to the CU's whole LDS (160 KB), not per launch with the launch's size -- hipFuncSetAttribute rewrites state of a
@@ -122,6 +133,23 @@ static hipError_t allow_full_lds_addr(const void* fn) {
 }
 template <class K>
 static hipError_t allow_full_lds(K kern) { return allow_full_lds_addr(reinterpret_cast<const void*>(kern)); }
+// ... as a launcher's step: nothing to do up to kLdsDefault; MPK_OK or MPK_EHIP with the error text set
+template <class K>
+static int allow_lds(K kern, size_t lds) {
+    if (lds <= kLdsDefault) return MPK_OK;
+    const hipError_t e = allow_full_lds(kern);
+    if (e == hipSuccess) return MPK_OK;
+    set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
+    return MPK_EHIP;
+}
+// one launch: the LDS attribute where the launch needs it, the launch, the launch check
+template <class K, class... Args>
+static int launch_kernel(K kern, dim3 grid, dim3 block, size_t lds, void* stream, const Args&... args) {
+    if (const int rc = allow_lds(kern, lds)) return rc;
+    hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, args...);
+    MPK_LAUNCH_CHECK();
+    return MPK_OK;
+}
 #endif
 
 // ------------------------------------------------------------------------------------------------------------

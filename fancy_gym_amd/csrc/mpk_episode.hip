@@ -335,15 +335,7 @@ int launch_episode_kernel(const TrajArgs& ta, const ActArgs& aa, const EpArgs& e
         set_error("internal: the episode kernel takes promp / prodmp rows");
         return MPK_EINVAL;
     } else {
-        auto go = [&](auto kern) -> int {
-            if (lds > kLdsDefault) {
-                hipError_t e = allow_full_lds(kern);
-                if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return MPK_EHIP; }
-            }
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * wpb), lds, (hipStream_t)stream, ta, aa, ea);
-            MPK_LAUNCH_CHECK();
-            return MPK_OK;
-        };
+        auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(64 * wpb), lds, stream, ta, aa, ea); };
         auto by_ct = [&](auto nq_tag, auto rw_tag) -> int {
             constexpr int NQ = decltype(nq_tag)::value, RW = decltype(rw_tag)::value;
             return with_closed_ct(ct, [&](auto c) { return go(k_episode_return<MP, decltype(c)::value, NQ, RW>); });

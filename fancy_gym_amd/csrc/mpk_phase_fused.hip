@@ -31,6 +31,7 @@
 // "finished without a step" (replan_write), condition = row 0, its action rows rewritten as zeros.  Valid plans -- the common case --
 // pay one compare per position.
 #include "mpk_phase.h"
+#include "mpk_traj_route.h"
 
 namespace mpk {
 
@@ -695,16 +696,47 @@ bool phase_fused_capable(const DevCfg& c) {
     return true;
 }
 
-int launch_phase_fused(const DevCfg& c, const float* params, const float* init_pos, const float* init_vel, float init_time_shared,
-                       float* pos, float* vel, float* actions, const RolloutDev& rc, double* q, double* qd, const int32_t* n_steps,
-                       const ReplanDev* rp, const GateDev* gate, double* ret, int32_t* seg_out, int32_t* range_flag, int B, int num_cu,
-                       void* stream, const char** kernel_name, const Tuning& tune, int* fault) {
-    if (!phase_fused_capable(c)) return MPK_ENOTIMPL;
-    const bool prodmp = c.mp_type == MPK_MP_PRODMP;
-    const int need = prodmp ? c.nb + 3 : c.KT;
-    const int KQ = (!prodmp && need <= 4) ? 1 : 2, KS = 4 * KQ;
+// ---- launch_phase_fused: the route choice (plan_phase_fused: arithmetic only, no HIP call, nothing allocated) and ONE launch of what it names
+struct FusedRoute {
+    int mp, kq;             // MP type and column quads (promp 1 / 2, prodmp 2)
+    bool lds_table;         // prodmp: the row table in LDS
+    int dc;                 // DoF count compiled in (7; 0: run time)
+    int ct;                 // MPK_CTRL_* on the frozen state, 3 + MPK_CTRL_* closed loop
+    bool pipe;              // closed loop: the producer / consumer workgroup
+    int blocks, threads;
+    size_t lds;
+    const char* name;       // what mpk_last_kernel reports: static storage
+};
+
+static const char* fused_name(bool prodmp, bool lds_table, bool pipe, bool closed, bool out) {
+    // [MP type][plain, row table in LDS, pipeline][frozen-state actions, closed loop, closed loop without per-step outputs]; promp has no
+    // row table, the pipeline is a closed-loop form
+    static const char* const names[2][3][3] = {
+        {{"k_phase_fused<promp,act>", "k_phase_fused<promp,closed>", "k_phase_fused<promp,closed,lean>"},
+         {"k_phase_fused<promp,act>", "k_phase_fused<promp,closed>", "k_phase_fused<promp,closed,lean>"},
+         {"k_phase_fused<promp,act>", "k_phase_fused<promp,pipe,closed>", "k_phase_fused<promp,pipe,closed,lean>"}},
+        {{"k_phase_fused<prodmp,act>", "k_phase_fused<prodmp,closed>", "k_phase_fused<prodmp,closed,lean>"},
+         {"k_phase_fused<prodmp,lds,act>", "k_phase_fused<prodmp,lds,closed>", "k_phase_fused<prodmp,lds,closed,lean>"},
+         {"k_phase_fused<prodmp,act>", "k_phase_fused<prodmp,pipe,closed>", "k_phase_fused<prodmp,pipe,closed,lean>"}}};
+    return names[prodmp ? 1 : 0][lds_table ? 1 : (pipe ? 2 : 0)][!closed ? 0 : (out ? 1 : 2)];
+}
+
+// the facts of a fused launch every decision reads (FusedArgs carries the configuration, the pointers and B)
+struct FusedFacts {
+    const DevCfg& c;
+    const Tuning& tune;
+    bool prodmp, closed, out;       // closed loop (double integrator) / frozen-state actions; out: per-step outputs are stored
+    int KQ, KS;                     // column quads, columns
+    int e_max;                      // episodes a chunk can hold
+    int B, num_cu;
+};
+
+// the arguments that are copies of the call's; MPK_OK or the gate's MPK_EINVAL
+static int fill_fused_args(const DevCfg& c, const float* params, const float* init_pos, const float* init_vel, float init_time_shared,
+                           float* pos, float* vel, float* actions, const RolloutDev& rc, double* q, double* qd, const int32_t* n_steps,
+                           const ReplanDev* rp, const GateDev* gate, double* ret, int32_t* seg_out, int32_t* range_flag, int B, int* fault,
+                           FusedArgs& fa, FusedLim& fl) {
     const bool closed = rc.plant_type == MPK_PLANT_DOUBLE_INTEGRATOR;
-    FusedArgs fa{};
     fa.c = c;
     fa.params = params; fa.init_pos = init_pos; fa.init_vel = init_vel; fa.init_time_shared = init_time_shared;
     fa.pos = pos; fa.vel = vel; fa.actions = actions;
@@ -715,7 +747,6 @@ int launch_phase_fused(const DevCfg& c, const float* params, const float* init_p
     fa.ret = ret; fa.seg_out = seg_out;
     fa.B = B;
     fa.fault = fault;
-    FusedLim fl{};
     for (int d = 0; d < c.D; ++d) { fl.pg[d] = rc.pg[d]; fl.dg[d] = rc.dg[d]; fl.lo[d] = rc.lo[d]; fl.hi[d] = rc.hi[d]; }
     if (gate) {
         if (!closed) { set_error("the validity gate needs the double-integrator plant"); return MPK_EINVAL; }
@@ -730,103 +761,126 @@ int launch_phase_fused(const DevCfg& c, const float* params, const float* init_p
             fl.glo32[d] = f32_at_least(gate->lo[d]); fl.ghi32[d] = f32_at_most(gate->hi[d]);
         }
     }
-    // chunks of E episodes: one lane per (episode, DoF) in the recurrence, 16 E items per tile; "phase_chunk" overrides.  Measured
-    // (profiles/r06_phase_fused_chunks.md, us at 8 192 / 65 536 episodes, chunks of 4 against 8): TableTennis-ProDMP actions 58.8 / 488
-    // against 82.9 / 536, closed loop 74.7 / 588 against 92.9 / 554, verbose < 2 step 50.3 / 367 against 50.9 / 248; BeerPong-ProMP
-    // actions 62.9 / 490 against 88.3 / 494, closed loop 78.0 / 636 against 101 / 526 -- the recurrence costs a wave the same whatever
-    // its lanes carry, so the closed loop wants eight once a launch has more chunks of eight than the chip holds waves; the frozen-state
-    // actions (no dependent chain) and every launch below that prefer the larger number of waves
-    const int e_max = 64 / c.D > 8 ? 8 : 64 / c.D;
-    int E = e_max >= 8 ? 8 : (e_max >= 4 ? 4 : e_max);
-    {
-        const long simds = (long)num_cu * 4;
-        if (E == 8 && (!closed || ((long)B + 7) / 8 < 4 * simds)) E = 4;
-        // small launches: smaller chunks until every SIMD has a wave.  Below ~8 000 episodes a launch takes what ONE wave takes for its 22
-        // tiles whatever its lanes carry (us at 1 024 / 2 048 / 4 096 episodes of TableTennis-ProDMP, chunks of 2: closed loop 54.4 / 54.4 /
-        // 64.5, chunks of 4: 61.0 / 61.8 / 62.8, chunks of 8: 88 / 88 / 91 -- the second round of items and the extra flush passes of a
-        // fuller chunk are serial time on that wave), so the chunk is the smallest that still fills the chip's SIMDs once
-        // (the frozen-state actions spread a chunk's TILES over waves instead -- below --, and keep chunks of four)
-        while (closed && E > 2 && ((long)B + E - 1) / E < simds && (E / 2) * c.D >= 8) E >>= 1;
-    }
-    // closed loop of a small launch: the chunk on a workgroup of 1 + kPipeProducers waves (PIPE: the kernel's comment), ONE round of workgroups -- two
-    // are resident on a CU (189 registers) --; not for promp horizons of 16 n + 1 steps
-    // (a tile that starts at the last step reads the velocity carry); "phase_pipe" 1 / 0 forces / forbids
-    const bool pipe_ok = closed && (prodmp || c.T % 16 != 1);
-    const int e_top = e_max >= 8 ? 8 : (e_max >= 4 ? 4 : e_max);
-    constexpr long kPipeWgsPerCu = MPK_PF_PIPE_WAVES >= 3 ? 3 : 2;     // resident workgroups per CU (registers: the kernel's launch bounds)
-    bool pipe = pipe_ok && ((long)B + e_top - 1) / e_top <= kPipeWgsPerCu * (long)num_cu;
-    if (tune.phase_pipe >= 0) pipe = tune.phase_pipe == 1 && pipe_ok;
+    return MPK_OK;
+}
+
+// closed loop of a small launch: the chunk on a workgroup of 1 + kPipeProducers waves (PIPE: the kernel's comment), ONE round of workgroups -- two
+// are resident on a CU (189 registers) --; not for promp horizons of 16 n + 1 steps
+// (a tile that starts at the last step reads the velocity carry); "phase_pipe" 1 / 0 forces / forbids
+constexpr long kPipeWgsPerCu = MPK_PF_PIPE_WAVES >= 3 ? 3 : 2;     // resident workgroups per CU (registers: the kernel's launch bounds)
+static bool fused_pipe_form(const FusedFacts& f) {
+    const bool pipe_ok = f.closed && (f.prodmp || f.c.T % 16 != 1);
+    const int e_top = f.e_max >= 8 ? 8 : (f.e_max >= 4 ? 4 : f.e_max);
+    const bool pipe = pipe_ok && ((long)f.B + e_top - 1) / e_top <= kPipeWgsPerCu * (long)f.num_cu;
+    return f.tune.phase_pipe >= 0 ? f.tune.phase_pipe == 1 && pipe_ok : pipe;
+}
+
+// chunks of E episodes: one lane per (episode, DoF) in the recurrence, 16 E items per tile; "phase_chunk" overrides.  Measured
+// (profiles/r06_phase_fused_chunks.md, us at 8 192 / 65 536 episodes, chunks of 4 against 8): TableTennis-ProDMP actions 58.8 / 488
+// against 82.9 / 536, closed loop 74.7 / 588 against 92.9 / 554, verbose < 2 step 50.3 / 367 against 50.9 / 248; BeerPong-ProMP
+// actions 62.9 / 490 against 88.3 / 494, closed loop 78.0 / 636 against 101 / 526 -- the recurrence costs a wave the same whatever
+// its lanes carry, so the closed loop wants eight once a launch has more chunks of eight than the chip holds waves; the frozen-state
+// actions (no dependent chain) and every launch below that prefer the larger number of waves
+static int fused_chunk(const FusedFacts& f, bool pipe) {
+    const int e_max = f.e_max, e_top = e_max >= 8 ? 8 : (e_max >= 4 ? 4 : e_max);
+    const long simds = (long)f.num_cu * 4, B = f.B;
+    int E = e_top;
+    if (E == 8 && (!f.closed || (B + 7) / 8 < 4 * simds)) E = 4;
+    // small launches: smaller chunks until every SIMD has a wave.  Below ~8 000 episodes a launch takes what ONE wave takes for its 22
+    // tiles whatever its lanes carry (us at 1 024 / 2 048 / 4 096 episodes of TableTennis-ProDMP, chunks of 2: closed loop 54.4 / 54.4 /
+    // 64.5, chunks of 4: 61.0 / 61.8 / 62.8, chunks of 8: 88 / 88 / 91 -- the second round of items and the extra flush passes of a
+    // fuller chunk are serial time on that wave), so the chunk is the smallest that still fills the chip's SIMDs once
+    // (the frozen-state actions spread a chunk's TILES over waves instead -- fused_tile_split --, and keep chunks of four)
+    while (f.closed && E > 2 && (B + E - 1) / E < simds && (E / 2) * f.c.D >= 8) E >>= 1;
     if (pipe) {
         // chunks of four where two workgroups per CU hold the launch (one round of items per tile, two flush passes), else eight.
         // TableTennis-ProDMP closed loop / verbose < 2, us (profiles/r06_phase_pipe.md): 1 024 episodes 32.0 / 28.1 (one-wave form 52.8 /
         // 39.0), 2 048: 34.9 / 30.1 (52.5 / 38.8), 4 096: 42.7 / 31.4 (61.8 / 38.6); BeerPong-ProMP 1 024: 32.0 / 26.6 (59.2 / 47.7)
         E = e_max >= 4 ? 4 : e_max;
-        if (((long)B + E - 1) / E > kPipeWgsPerCu * (long)num_cu && e_top > E) E = e_top;
+        if ((B + E - 1) / E > kPipeWgsPerCu * (long)f.num_cu && e_top > E) E = e_top;
     }
-    if (tune.phase_chunk >= 1 && tune.phase_chunk <= e_max) E = tune.phase_chunk;
+    if (f.tune.phase_chunk >= 1 && f.tune.phase_chunk <= e_max) E = f.tune.phase_chunk;
+    return E;
+}
+
+// the LDS layout of a wave (pipeline form: of the workgroup) for chunks of E, and the store policy
+static void fill_fused_layout(const FusedFacts& f, int E, bool pipe, FusedArgs& fa) {
+    const DevCfg& c = f.c;
     fa.chunk = E;
-    fa.x_pad = c.D * KS;
-    const bool out = pos != nullptr;
-    fa.vec_ok = out && ((reinterpret_cast<uintptr_t>(pos) | reinterpret_cast<uintptr_t>(vel) | reinterpret_cast<uintptr_t>(actions)) & 15u) == 0 ? 1 : 0;
+    fa.x_pad = c.D * f.KS;
+    fa.vec_ok = f.out && ((reinterpret_cast<uintptr_t>(fa.pos) | reinterpret_cast<uintptr_t>(fa.vel) | reinterpret_cast<uintptr_t>(fa.actions)) & 15u) == 0 ? 1 : 0;
     fa.td3 = (c.T * c.D) & 3;
     // (staging two or four tiles per flush -- 896- / 1 792-byte store runs -- was measured and lost: profiles/r06_phase_fused_large.md; carrying the
     // option cost the tile loop 3 - 9 %)
     fa.pitch = (16 * c.D + 3 + 3) / 4 * 4;              // 16 steps + up to three floats of shift, whole 16-byte chunks
     fa.t_pad = (c.T + 3) / 4 * 4;
-    fa.c_pad = prodmp ? KS + 4 : (4 * c.n_total + 6 + 3) / 4 * 4;
-    fa.car_pad = prodmp ? 0 : (E * 2 * c.D + 3) / 4 * 4;
+    fa.c_pad = f.prodmp ? f.KS + 4 : (4 * c.n_total + 6 + 3) / 4 * 4;
+    fa.car_pad = f.prodmp ? 0 : (E * 2 * c.D + 3) / 4 * 4;
     fa.inv_d = 65536u / (unsigned)c.D + 1u;
     fa.inv_ch = 65536u / (unsigned)(fa.pitch / 4) + 1u;
     fa.wave_floats = E * fa.x_pad + 16 * E + fa.car_pad + 4 * E + 3 * E * fa.pitch;
     if (pipe) fa.wave_floats += (2 * kPipeProducers - 1) * 3 * E * fa.pitch + 16 + kPipeProducers * fa.car_pad;
+    fa.wt = f.out && (double)f.B * c.T * c.D * 12.0 <= kWtBytes ? 1 : 0;
+    if (f.tune.write_through >= 0) fa.wt = f.tune.write_through != 0 ? 1 : 0;
+}
+
+// prodmp: the row table in LDS when that still leaves eight waves on a CU and the launch fills them ("phase_table" 0: from L2, 1: wherever
+// it fits); then it joins the workgroup's shared bytes and sets the waves per workgroup
+static bool fused_lds_table(const FusedFacts& f, bool pipe, long chunks, size_t wave_bytes, size_t& shared_bytes, int& wpb, FusedArgs& fa) {
+    if (!f.prodmp) return false;
+    const int rows_needed = prodmp_rows_reachable(f.c, fa.init_time_shared);
+    const size_t tab_bytes = (size_t)rows_needed * (2 * f.KS + 4) * sizeof(float);
+    bool lds_table = tab_bytes + shared_bytes + 8 * wave_bytes <= kLdsPerCu && chunks >= (long)f.num_cu * 8;
+    if (f.tune.phase_table == 0 || pipe) lds_table = false;
+    if (f.tune.phase_table == 1 && !pipe && tab_bytes + shared_bytes + wave_bytes <= kLdsPerCu) lds_table = true;
+    if (!lds_table) return false;
+    fa.tab_pad = rows_needed * (2 * f.KS + 4);
+    shared_bytes += tab_bytes;
+    wpb = (int)((kLdsPerCu - shared_bytes) / wave_bytes);
+    wpb = wpb > MPK_PF_TL_THREADS / 64 ? MPK_PF_TL_THREADS / 64 : wpb;
+    return true;
+}
+
+// frozen-state actions of a small launch: the tiles of a chunk on several waves (each repeats the chunk's prologue) until the chip's
+// SIMDs hold four waves each, eight units per chunk at most; "phase_split" overrides (1 = whole chunks).  TableTennis-ProDMP / BeerPong-
+// ProMP, us, whole chunks -> split (profiles/r06_phase_fused_chunks.md): 1 024 episodes 40.9 -> 12.4 / 49.1 -> 14.6, 2 048: 42.6 -> 19.2 /
+// 49.2 -> 20.3, 4 096: 52.3 -> 30.8 / 54.2 -> 29.2, 8 192: 59.6 -> 61.7 (row table in LDS: stays whole) / 62.7 -> 50.4.
+// promp: a tile that starts AT the last step reads the velocity carry of the tile before it, so such horizons (T = 16 n + 1) stay whole
+static void fused_tile_split(const FusedFacts& f, long chunks, bool lds_table, FusedArgs& fa) {
+    const int nrt = (f.c.T + 15) / 16;
+    fa.nsplit = 1;
+    fa.split_tiles = nrt;
+    if (f.closed || !(f.prodmp || f.c.T % 16 != 1)) return;
+    const long simds = (long)f.num_cu * 4;
+    long want = chunks < 4 * simds ? (4 * simds + chunks - 1) / chunks : 1;
+    want = want > 8 ? 8 : want;
+    if (lds_table && want <= 2) want = 1;
+    if (f.tune.phase_split >= 1) want = f.tune.phase_split;
+    want = want > nrt ? nrt : want;
+    fa.split_tiles = (int)((nrt + want - 1) / want);
+    fa.nsplit = (nrt + fa.split_tiles - 1) / fa.split_tiles;
+}
+
+// the decisions in their order: pipeline form, chunk, LDS layout, row table, tile split, waves per workgroup, blocks.  Fills the rest of
+// the arguments and the route; MPK_OK, or the code the launch returns without launching
+static int plan_phase_fused(const RolloutDev& rc, int num_cu, const Tuning& tune, FusedArgs& fa, FusedRoute& r) {
+    const DevCfg& c = fa.c;
+    const bool prodmp = c.mp_type == MPK_MP_PRODMP;
+    const int KQ = (!prodmp && c.KT <= 4) ? 1 : 2;
+    const FusedFacts f{c, tune, prodmp, rc.plant_type == MPK_PLANT_DOUBLE_INTEGRATOR, fa.pos != nullptr, KQ, 4 * KQ, 64 / c.D > 8 ? 8 : 64 / c.D,
+                       fa.B, num_cu};
+    const bool pipe = fused_pipe_form(f);
+    const int E = fused_chunk(f, pipe);
+    fill_fused_layout(f, E, pipe, fa);
     const size_t wave_bytes = (size_t)fa.wave_floats * sizeof(float);
     size_t shared_bytes = (size_t)(fa.t_pad + fa.c_pad) * sizeof(float);
-    fa.wt = out && (double)B * c.T * c.D * 12.0 <= kWtBytes ? 1 : 0;
-    if (tune.write_through >= 0) fa.wt = tune.write_through != 0 ? 1 : 0;
     if (wave_bytes + shared_bytes > kLdsPerCu) return MPK_ENOTIMPL;
-    const long chunks = ((long)B + E - 1) / E;
-    // prodmp: the row table in LDS when that still leaves eight waves on a CU and the launch fills them ("phase_table" 0: from L2)
-    bool lds_table = false;
+    const long chunks = ((long)f.B + E - 1) / E;
     int wpb = (int)((kLdsDefault - shared_bytes) / wave_bytes);
     wpb = wpb > 4 ? 4 : (wpb < 1 ? 1 : wpb);
-    if (prodmp) {
-        int rows_needed = c.n_pc;
-        const float tau_lo = c.learn_tau ? c.tau_lo : c.tau, delay_lo = c.learn_delay ? c.delay_lo : c.delay;
-        if ((double)c.t_last > 0.0 && tau_lo > 0.f) {
-            const double s_max = ((double)c.t_last + (double)init_time_shared - (double)delay_lo) / (double)tau_lo;
-            const double r = s_max / (double)c.scaled_dt + 4.0;
-            if (r < (double)c.n_pc) rows_needed = r < 4.0 ? 4 : (int)r;
-        }
-        const size_t tab_bytes = (size_t)rows_needed * (2 * KS + 4) * sizeof(float);
-        lds_table = tab_bytes + shared_bytes + 8 * wave_bytes <= kLdsPerCu && chunks >= (long)num_cu * 8;
-        if (tune.phase_table == 0 || pipe) lds_table = false;
-        if (tune.phase_table == 1 && !pipe && tab_bytes + shared_bytes + wave_bytes <= kLdsPerCu) lds_table = true;
-        if (lds_table) {
-            fa.tab_pad = rows_needed * (2 * KS + 4);
-            shared_bytes += tab_bytes;
-            wpb = (int)((kLdsPerCu - shared_bytes) / wave_bytes);
-            wpb = wpb > MPK_PF_TL_THREADS / 64 ? MPK_PF_TL_THREADS / 64 : wpb;
-        }
-    }
+    const bool lds_table = fused_lds_table(f, pipe, chunks, wave_bytes, shared_bytes, wpb, fa);
     if (tune.tiles_wpb > 0 && wpb > tune.tiles_wpb) wpb = tune.tiles_wpb;
-    // frozen-state actions of a small launch: the tiles of a chunk on several waves (each repeats the chunk's prologue) until the chip's
-    // SIMDs hold four waves each, eight units per chunk at most; "phase_split" overrides (1 = whole chunks).  TableTennis-ProDMP / BeerPong-
-    // ProMP, us, whole chunks -> split (profiles/r06_phase_fused_chunks.md): 1 024 episodes 40.9 -> 12.4 / 49.1 -> 14.6, 2 048: 42.6 -> 19.2 /
-    // 49.2 -> 20.3, 4 096: 52.3 -> 30.8 / 54.2 -> 29.2, 8 192: 59.6 -> 61.7 (row table in LDS: stays whole) / 62.7 -> 50.4.
-    // promp: a tile that starts AT the last step reads the velocity carry of the tile before it, so such horizons (T = 16 n + 1) stay whole
-    fa.nsplit = 1;
-    const int nrt = (c.T + 15) / 16;
-    fa.split_tiles = nrt;
-    if (!closed && (prodmp || c.T % 16 != 1)) {
-        const long simds = (long)num_cu * 4;
-        long want = chunks < 4 * simds ? (4 * simds + chunks - 1) / chunks : 1;
-        want = want > 8 ? 8 : want;
-        if (lds_table && want <= 2) want = 1;
-        if (tune.phase_split >= 1) want = tune.phase_split;
-        want = want > nrt ? nrt : want;
-        fa.split_tiles = (int)((nrt + want - 1) / want);
-        fa.nsplit = (nrt + fa.split_tiles - 1) / fa.split_tiles;
-    }
+    fused_tile_split(f, chunks, lds_table, fa);
     const long units = chunks * fa.nsplit;
     if (units < (long)num_cu * wpb) {                  // fewer chunks than one workgroup per CU would take: smaller workgroups
         const int w = (int)((units + num_cu - 1) / num_cu);
@@ -840,48 +894,57 @@ int launch_phase_fused(const DevCfg& c, const float* params, const float* init_p
     long blocks = (units + wpb - 1) / wpb;
     if (blocks > (long)num_cu * per_cu) blocks = (long)num_cu * per_cu;
     if (pipe) blocks = chunks;                          // one workgroup per chunk, no loop
-    auto go = [&](auto kern) -> int {
-        if (lds > kLdsDefault) {
-            hipError_t e = allow_full_lds(kern);
-            if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return MPK_EHIP; }
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(pipe ? 64 * (1 + kPipeProducers) : 64 * wpb), lds, (hipStream_t)stream, fa, fl);
-        MPK_LAUNCH_CHECK();
-        return MPK_OK;
-    };
-    const int ct = (closed ? 3 : 0) + rc.controller_type;
-    const bool dc7 = c.D == 7 && tune.pd_generic != 1;
+    const int ct = (f.closed ? 3 : 0) + rc.controller_type;
+    r.mp = c.mp_type; r.kq = KQ; r.lds_table = lds_table; r.pipe = pipe;
+    r.dc = c.D == 7 && tune.pd_generic != 1 ? 7 : 0;
+    r.ct = ct >= 0 && ct <= 5 ? ct : 5;                 // (with_ct's range; anything else ran the closed-loop position controller's kernel)
+    r.blocks = (int)blocks;
+    r.threads = pipe ? 64 * (1 + kPipeProducers) : 64 * wpb;
+    r.lds = lds;
+    r.name = fused_name(prodmp, lds_table, pipe, f.closed, f.out);
+    return MPK_OK;
+}
+
+static int launch_fused_route(const FusedArgs& fa, const FusedLim& fl, const FusedRoute& r, void* stream) {
+    auto go = [&](auto kern) { return launch_kernel(kern, dim3((unsigned)r.blocks), dim3(r.threads), r.lds, stream, fa, fl); };
     auto by_ct = [&](auto mp_tag, auto kq_tag, auto tl_tag, auto dc_tag) -> int {
-        constexpr int MP = decltype(mp_tag)::value, KQ_ = decltype(kq_tag)::value, DC = decltype(dc_tag)::value;
-        constexpr bool TL = decltype(tl_tag)::value;
-        switch (ct) {
-            case 0: return go(k_phase_fused<MP, KQ_, TL, DC, 0>);
-            case 1: return go(k_phase_fused<MP, KQ_, TL, DC, 1>);
-            case 2: return go(k_phase_fused<MP, KQ_, TL, DC, 2>);
-            case 3: if constexpr (!TL) { if (pipe) return go(k_phase_fused<MP, KQ_, false, DC, 3, true>); } return go(k_phase_fused<MP, KQ_, TL, DC, 3>);
-            case 4: if constexpr (!TL) { if (pipe) return go(k_phase_fused<MP, KQ_, false, DC, 4, true>); } return go(k_phase_fused<MP, KQ_, TL, DC, 4>);
-            default: if constexpr (!TL) { if (pipe) return go(k_phase_fused<MP, KQ_, false, DC, 5, true>); } return go(k_phase_fused<MP, KQ_, TL, DC, 5>);
-        }
+        return with_ct(r.ct, [&](auto ct_tag) -> int {
+            constexpr int MP = decltype(mp_tag)::value, KQ = decltype(kq_tag)::value, DC = decltype(dc_tag)::value, CT = decltype(ct_tag)::value;
+            constexpr bool TL = decltype(tl_tag)::value;
+            if constexpr (CT < 0) return MPK_EINVAL;    // (no such route: the plan folds the controller into 0 .. 5)
+            else {
+                if constexpr (!TL && CT >= 3) {         // (the pipeline: closed loop, rows from L2)
+                    if (r.pipe) return go(k_phase_fused<MP, KQ, false, DC, CT, true>);
+                }
+                return go(k_phase_fused<MP, KQ, TL, DC, CT>);
+            }
+        });
     };
-    using std::integral_constant;
-    using std::bool_constant;
-    typedef integral_constant<int, MPK_MP_PRODMP> PD;
-    typedef integral_constant<int, MPK_MP_PROMP> PM;
-    typedef integral_constant<int, 1> I1;
-    typedef integral_constant<int, 2> I2;
-    typedef integral_constant<int, 0> D0;
-    typedef integral_constant<int, 7> D7;
-    if (prodmp) {
-        *kernel_name = closed ? (out ? (lds_table ? "k_phase_fused<prodmp,lds,closed>" : (pipe ? "k_phase_fused<prodmp,pipe,closed>" : "k_phase_fused<prodmp,closed>"))
-                                     : (lds_table ? "k_phase_fused<prodmp,lds,closed,lean>" : (pipe ? "k_phase_fused<prodmp,pipe,closed,lean>" : "k_phase_fused<prodmp,closed,lean>")))
-                              : (lds_table ? "k_phase_fused<prodmp,lds,act>" : "k_phase_fused<prodmp,act>");
-        if (lds_table) return dc7 ? by_ct(PD(), I2(), bool_constant<true>(), D7()) : by_ct(PD(), I2(), bool_constant<true>(), D0());
-        return dc7 ? by_ct(PD(), I2(), bool_constant<false>(), D7()) : by_ct(PD(), I2(), bool_constant<false>(), D0());
-    }
-    *kernel_name = closed ? (out ? (pipe ? "k_phase_fused<promp,pipe,closed>" : "k_phase_fused<promp,closed>")
-                                 : (pipe ? "k_phase_fused<promp,pipe,closed,lean>" : "k_phase_fused<promp,closed,lean>")) : "k_phase_fused<promp,act>";
-    if (KQ == 1) return dc7 ? by_ct(PM(), I1(), bool_constant<false>(), D7()) : by_ct(PM(), I1(), bool_constant<false>(), D0());
-    return dc7 ? by_ct(PM(), I2(), bool_constant<false>(), D7()) : by_ct(PM(), I2(), bool_constant<false>(), D0());
+    auto by_dc = [&](auto mp_tag, auto kq_tag, auto tl_tag) -> int {
+        return r.dc == 7 ? by_ct(mp_tag, kq_tag, tl_tag, std::integral_constant<int, 7>()) : by_ct(mp_tag, kq_tag, tl_tag, std::integral_constant<int, 0>());
+    };
+    typedef std::integral_constant<int, MPK_MP_PRODMP> PD;
+    typedef std::integral_constant<int, MPK_MP_PROMP> PM;
+    typedef std::integral_constant<int, 1> I1;
+    typedef std::integral_constant<int, 2> I2;
+    if (r.mp == MPK_MP_PRODMP) return r.lds_table ? by_dc(PD(), I2(), std::true_type()) : by_dc(PD(), I2(), std::false_type());
+    return r.kq == 1 ? by_dc(PM(), I1(), std::false_type()) : by_dc(PM(), I2(), std::false_type());
+}
+
+int launch_phase_fused(const DevCfg& c, const float* params, const float* init_pos, const float* init_vel, float init_time_shared,
+                       float* pos, float* vel, float* actions, const RolloutDev& rc, double* q, double* qd, const int32_t* n_steps,
+                       const ReplanDev* rp, const GateDev* gate, double* ret, int32_t* seg_out, int32_t* range_flag, int B, int num_cu,
+                       void* stream, const char** kernel_name, const Tuning& tune, int* fault) {
+    if (!phase_fused_capable(c)) return MPK_ENOTIMPL;
+    FusedArgs fa{};
+    FusedLim fl{};
+    FusedRoute r;
+    int rc_ = fill_fused_args(c, params, init_pos, init_vel, init_time_shared, pos, vel, actions, rc, q, qd, n_steps, rp, gate, ret, seg_out,
+                              range_flag, B, fault, fa, fl);
+    if (rc_ == MPK_OK) rc_ = plan_phase_fused(rc, num_cu, tune, fa, r);
+    if (rc_ != MPK_OK) return rc_;
+    *kernel_name = r.name;
+    return launch_fused_route(fa, fl, r, stream);
 }
 #endif  // MPK_DEVICE_ONLY
 

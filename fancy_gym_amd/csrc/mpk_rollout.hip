@@ -874,187 +874,233 @@ __global__ void __launch_bounds__(256) k_reacher_rollout(const RolloutDev rc, co
 }
 
 #ifndef MPK_DEVICE_ONLY
+// ---- the rollout launchers: the route choice (plan_rollout: arithmetic only, no HIP call, nothing allocated) and ONE launch of what it names
+enum class RollFamily : int {
+    Generic,          // k_pd_rollout: one lane per (episode, DoF)
+    GenericReward,    // k_reacher_rollout: ... with the reward
+    Tiles,            // k_pd_rollout_tiles
+    Pipe,             // k_pd_rollout_pipe: producer / consumer workgroups, four groups per consumer
+};
+
+struct RollRoute {
+    RollFamily family;
+    int ng;             // Tiles: groups per wave
+    bool rw;            // SimpleReacher's reward
+    int ct, dc;         // controller (-1: run time) and DoF count (0: run time) compiled in
+    bool hw;            // Tiles with the reward: helper waves (-DMPK_ABLATIONS builds)
+    int blocks, threads;
+    size_t lds;
+};
+
+// what launch_reacher_rollout has on top of launch_pd_rollout
+struct RollReward {
+    const int32_t* step0;
+    const double* goal;
+    double* rewards;
+    int steps_before_reward;
+};
+
+// the facts of a rollout launch every family's rule reads; PdArgs carries the shape (D, B, T, rc) and, on the tile routes, G
+struct RollFacts {
+    const Tuning& tune;
+    bool reward;        // launch_reacher_rollout; where the two entry points differ, the condition says `reward`
+    int NTW;            // episodes per group (tile routes)
+};
+
+// the generic kernels: one lane per (episode, DoF); the reward kernel keeps an episode's DoFs in one wave
+static void plan_roll_generic(const RollFacts& f, const PdArgs& pa, RollRoute& r) {
+    r.family = f.reward ? RollFamily::GenericReward : RollFamily::Generic;
+    const int per_wave = f.reward ? 64 / pa.D : 64;
+    const long waves = ((f.reward ? (long)pa.B : (long)pa.B * pa.D) + per_wave - 1) / per_wave;
+    r.blocks = (int)((waves + 3) / 4);
+}
+
+// the tile-streaming kernels' shape rule and their part of PdArgs (reward: evaluated per tile by all lanes, see k_pd_rollout_tiles, RW)
+static bool fill_roll_tile_args(RollFacts& f, PdArgs& pa, int* fault) {
+    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    const int D = pa.D, T = pa.T, last_rows = T - (T - 1) / 16 * 16;
+    // (reward, D = 1: sixteen episodes per group, more than the reward pass's two register sets -- the generic kernel)
+    const bool tiles_ok = D >= (f.reward ? 2 : 1) && D <= kMaxD && (T * D) % 4 == 0 && (last_rows * D) % 4 == 0 && aligned16(pa.des_pos) &&
+                          aligned16(pa.des_vel) && (!pa.actions || aligned16(pa.actions)) && f.tune.pd_simple != 1;
+    if (!tiles_ok) return false;
+    pa.wt = (double)pa.B * T * D * 12.0 <= kCachedBytes ? 1 : 0;     // desired (pos, vel) + actions stay cached
+    if (f.tune.write_through >= 0) pa.wt = f.tune.write_through != 0 ? 1 : 0;
+    pa.fault = fault;
+    int sh = 0;
+    while ((1 << sh) < D) ++sh;
+    pa.sh = sh;
+    f.NTW = 16 >> sh;
+    pa.G = (pa.B + f.NTW - 1) / f.NTW;
+    pa.inv_seg4 = 65536u / (unsigned)(4 * D) + 1u;
+    return true;
+}
+
+// the motor controller on 2 / 5 links with the reward (the reference's SimpleReacher environments: simple_reacher/mp_wrapper.py:11-16;
+// the pipeline form: 5 links only), 5 / 7 DoF without it: controller and DoF count compiled in; everything else, and "pd_generic" 1,
+// on the run-time form of the same code
+static void roll_compiled_shape(const RollFacts& f, const PdArgs& pa, bool pipe_form, RollRoute& r) {
+    const int D = pa.D;
+    if (f.tune.pd_generic == 1) return;
+    if (!f.reward) { if (D == 7 || D == 5) r.dc = D; }
+    else if (pa.rc.controller_type == MPK_CTRL_MOTOR && (D == 5 || (D == 2 && !pipe_form))) { r.ct = MPK_CTRL_MOTOR; r.dc = D; }
+}
+
+// small launches: the producer / consumer workgroup (k_pd_rollout_pipe), while four workgroups per CU hold the launch -- with the reward
+// two (60 KB of LDS each), and four groups per consumer there, so at most two episodes per group; "pd_pipe" 1 / 0 forces / forbids
+static bool plan_roll_pipe(const RollFacts& f, const PdArgs& pa, RollRoute& r) {
+    const long punits = ((long)pa.G + 3) / 4;
+    const long pipe_wgs = (f.reward ? 2L : 4L) * 256;
+    const bool pipe_fits = !f.reward || f.NTW <= 2;
+    bool pipe = pipe_fits && f.tune.pd_quad < 0 && punits <= pipe_wgs;
+    if (f.tune.pd_pipe >= 0) pipe = f.tune.pd_pipe == 1 && pipe_fits;
+    if (!pipe) return false;
+    r.family = RollFamily::Pipe;
+    r.ng = 4;
+    roll_compiled_shape(f, pa, true, r);
+    r.lds = ((size_t)kRollPipeNP * 4 * (f.reward ? 5 : 3) * kStageStride + 16) * sizeof(float);
+    r.blocks = (int)(punits < pipe_wgs ? punits : pipe_wgs);
+    r.threads = 64 * (1 + kRollPipeNP);
+    return true;
+}
+
+// groups per wave (lane quarter j runs group j's recurrence: NG x fewer serial instructions per episode) chosen by the
+// waves per SIMD it leaves (1024 SIMDs): four from 5 groups per SIMD on, two from 1.5, else one ("pd_quad": 0 one, 2 four,
+// 3 two).  Measured (profiles/r04_rollout.md; second session, after the tile loop stopped waiting for its stores, cfg2 shape:
+// 3 072 episodes 12.7 -> 11.3 us with two, 10 240 / 12 288 / 14 336: 24.1 / 26.5 / 30.6 -> 21.6 / 23.2 / 24.9 us with four;
+// 8 192: two 16.8, four 17.1)
+// (second session, with the reward: 10 240 / 12 288 / 14 336 episodes 85.0 / 85.8 / 100.3 -> 78.6 / 78.9 / 79.4 us with four groups per
+// wave, 3 072: 48.0 -> 42.6 with two; 8 192: two 52.5, four 68)
+static int roll_groups_per_wave(const RollFacts& f, const PdArgs& pa) {
+    const int quad_mode = f.tune.pd_quad < 0 ? 1 : f.tune.pd_quad;
+    const long simds = 1024;
+    int ng = 1;
+    if (quad_mode == 2) ng = 4;
+    else if (quad_mode == 3) ng = 2;
+    else if (quad_mode == 1) {
+        ng = pa.G >= 5 * simds ? 4 : (2 * pa.G >= 3 * simds ? 2 : 1);
+        // reward, round 6: beyond ~10 groups per SIMD two groups per wave again (one tile of input lookahead: the larger number of waves hides
+        // more of the loads) -- LongSimpleReacher + reward, us, four / two: 16 384 episodes 50.2 / 53.9, 24 576: 86.2 / 78.3, 32 768: 118 / 108,
+        // 65 536: 229 / 213, 262 144: 871 / 840 (profiles/r06_rollout_reward.md)
+        if (f.reward && pa.G >= 10 * simds) ng = 2;
+    }
+    if (f.reward) while (ng > 1 && ng * f.NTW > 8) ng >>= 1;       // the reward pass holds the inputs of two passes (eight episodes) in registers
+    return ng;
+}
+
+// k_pd_rollout_tiles: whatever the pipeline form leaves
+static void plan_roll_tiles(const RollFacts& f, const PdArgs& pa, RollRoute& r) {
+    r.family = RollFamily::Tiles;
+    roll_compiled_shape(f, pa, false, r);
+    const int ng = r.ng = roll_groups_per_wave(f, pa);
+    const int units = (pa.G + ng - 1) / ng;
+    int blocks = (units + 3) / 4;
+    if (blocks > 2048) blocks = 2048;
+    // Beyond the caches ONE workgroup of four waves per CU instead of eight (round 5): the persistent waves walk the units in order,
+    // and fewer read / write streams per CU stream faster -- cfg2 shape 131 072 / 262 144 / 524 288 episodes 235 / 497 / 991 ->
+    // 225 / 448 / 870 us, LongSimpleReacher shape 65 536 / 131 072: 186 / 361 -> 172 / 328; neutral at 400 MB, slower below
+    // (16 384 episodes of the reacher shape: 37 -> 43 us).  Uneven numbers of workgroups per CU lose (192, 384 blocks), two waves per
+    // CU lose half.  The reward variant needs its occupancy (794 -> 897 us at 262 144) and keeps eight.  "phase_waves": A/B runs (waves per CU).
+    if (f.tune.phase_waves > 0) { if (blocks > 64 * f.tune.phase_waves) blocks = 64 * f.tune.phase_waves; }
+    else if (!f.reward && (double)pa.B * pa.T * pa.D * 12.0 >= 512.0 * 1024 * 1024 && blocks > 256) blocks = 256;
+    if (blocks >= 8) blocks = (blocks + 7) / 8 * 8;
+    r.blocks = blocks;
+    // helper waves for the control-cost pass (k_pd_rollout_tiles<.., HW>): built, tested, measured SLOWER, therefore only on request
+    // ("pd_helper" 1).  LongSimpleReacher + reward, us without / with helpers: 2 048 episodes 19.8 / 20.7, 4 096: 23.5 / 25.0,
+    // 8 192: 30.9 / 47.0, 16 384: 50.1 / 76.0, 65 536: 217 / 321 (profiles/r05_rollout.md) -- one workgroup barrier per tile ties
+    // four latency-bound chain waves (and the helpers that share their SIMDs) to the slowest of them, and the second float64 action
+    // buffer takes a resident workgroup per CU away; the pass it moves off the chain waves is 820 of 4 070 cycles per tile
+    r.hw = f.reward && MPK_RW_HELPER && f.tune.pd_helper == 1;
+    // staging strides per group: desired pos | vel | actions, with the reward + the float64 actions (helper waves: two buffers of them)
+    r.lds = (size_t)4 * ng * (f.reward ? (r.hw ? 7 : 5) : 3) * kStageStride * sizeof(float);
+    if (r.hw) { r.lds += (2 * 4 * kRwSlots * kRwSlotInts + 8) * sizeof(float); r.threads = 384; }
+}
+
+// rw == nullptr: launch_pd_rollout.  The families in their order of precedence: generic where the tile kernels' shape rule declines, the
+// pipeline form for small launches, the tile kernel for the rest
+static void plan_rollout(const RolloutDev& rc, int D, const float* des_pos, const float* des_vel, double* q, double* qd, const int32_t* n_steps,
+                         float* actions, const RollReward* rw, int B, int T, const Tuning& tune, int* fault, PdArgs& pa, RollRoute& r) {
+    RollFacts f{tune, rw != nullptr, 0};
+    pa.rc = rc; pa.des_pos = des_pos; pa.des_vel = des_vel; pa.Q = q; pa.QD = qd; pa.n_steps = n_steps;
+    pa.actions = actions; pa.D = D; pa.B = B; pa.T = T;
+    if (rw) { pa.step0 = rw->step0; pa.goal = rw->goal; pa.rewards = rw->rewards; pa.steps_before_reward = rw->steps_before_reward; }
+    r = RollRoute{};
+    r.rw = f.reward; r.ng = 1; r.ct = -1; r.threads = 256;
+    if (!fill_roll_tile_args(f, pa, fault)) return plan_roll_generic(f, pa, r);
+    if (!plan_roll_pipe(f, pa, r)) plan_roll_tiles(f, pa, r);
+}
+
+// a route's (reward, controller, DoF count) as template arguments: the shapes that are compiled in, anything else the run-time form
+template <typename F>
+static int with_roll_shape(const RollRoute& r, F&& f) {
+    using std::integral_constant;
+    typedef integral_constant<int, -1> Any;
+    typedef integral_constant<int, MPK_CTRL_MOTOR> Motor;
+    if (r.rw) {
+        if (r.ct == MPK_CTRL_MOTOR && r.dc == 5) return f(std::true_type(), Motor(), integral_constant<int, 5>());
+        if (r.ct == MPK_CTRL_MOTOR && r.dc == 2) return f(std::true_type(), Motor(), integral_constant<int, 2>());
+        return f(std::true_type(), Any(), integral_constant<int, 0>());
+    }
+    if (r.dc == 7) return f(std::false_type(), Any(), integral_constant<int, 7>());
+    if (r.dc == 5) return f(std::false_type(), Any(), integral_constant<int, 5>());
+    return f(std::false_type(), Any(), integral_constant<int, 0>());
+}
+
+// groups per wave (4 / 2; anything else takes 1)
+template <typename F>
+static int with_ng(int ng, F&& f) {
+    if (ng == 4) return f(std::integral_constant<int, 4>());
+    if (ng == 2) return f(std::integral_constant<int, 2>());
+    return f(std::integral_constant<int, 1>());
+}
+
+static int launch_rollout(const PdArgs& pa, const RollRoute& r, void* stream) {
+    const dim3 grid(r.blocks), block(r.threads);
+    auto go = [&](auto kern) { return launch_kernel(kern, grid, block, r.lds, stream, pa); };
+    switch (r.family) {
+        case RollFamily::Generic:
+            return launch_kernel(k_pd_rollout, grid, block, 0, stream, pa.rc, pa.D, pa.des_pos, pa.des_vel, pa.Q, pa.QD, pa.n_steps, pa.actions,
+                                 pa.B, pa.T);
+        case RollFamily::GenericReward:
+            return launch_kernel(k_reacher_rollout, grid, block, 0, stream, pa.rc, pa.D, pa.des_pos, pa.des_vel, pa.Q, pa.QD, pa.n_steps, pa.step0,
+                                 pa.goal, pa.steps_before_reward, pa.actions, pa.rewards, pa.B, pa.T);
+        case RollFamily::Pipe:
+            return with_roll_shape(r, [&](auto rw, auto ct, auto dc) {
+                constexpr bool RW = decltype(rw)::value;
+                constexpr int CT = decltype(ct)::value, DC = decltype(dc)::value;
+                if constexpr (RW && DC == 2) return go(k_pd_rollout_pipe<4, true, -1, 0>);      // (not compiled in: the plan does not name it)
+                else return go(k_pd_rollout_pipe<4, RW, CT, DC>);
+            });
+        default:
+            return with_roll_shape(r, [&](auto rw, auto ct, auto dc) {
+                return with_ng(r.ng, [&](auto ng) {
+                    constexpr bool RW = decltype(rw)::value;
+                    constexpr int CT = decltype(ct)::value, DC = decltype(dc)::value, NG = decltype(ng)::value;
+                    if constexpr (RW && MPK_RW_HELPER != 0) {
+                        if (r.hw) return go(k_pd_rollout_tiles<NG, true, CT, DC, true>);
+                    }
+                    return go(k_pd_rollout_tiles<NG, RW, CT, DC>);
+                });
+            });
+    }
+}
+
 int launch_reacher_rollout(const RolloutDev& rc, int D, const float* des_pos,
                            const float* des_vel, double* q, double* qd, const int32_t* n_steps, const int32_t* step0,
                            const double* goal, int steps_before_reward, float* actions, double* rewards, int B, int T,
                            void* stream, const Tuning& tune, int* fault) {
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-    const int last_rows = T - (T - 1) / 16 * 16;
-    // (D = 1: sixteen episodes per group, more than the reward pass's two register sets -- the generic kernel)
-    const bool tiles_ok = D >= 2 && D <= kMaxD && (T * D) % 4 == 0 && (last_rows * D) % 4 == 0 && aligned16(des_pos) &&
-                          aligned16(des_vel) && (!actions || aligned16(actions)) && tune.pd_simple != 1;
-    if (tiles_ok) {
-        // the tile-streaming rollout with the reward evaluated per tile by all lanes (see k_pd_rollout_tiles, RW)
-        PdArgs pa;
-        pa.rc = rc; pa.des_pos = des_pos; pa.des_vel = des_vel; pa.Q = q; pa.QD = qd; pa.n_steps = n_steps;
-        pa.actions = actions; pa.D = D; pa.B = B; pa.T = T;
-        pa.wt = (double)B * T * D * 12.0 <= kCachedBytes ? 1 : 0;     // desired (pos, vel) + actions stay cached
-        if (tune.write_through >= 0) pa.wt = tune.write_through != 0 ? 1 : 0;
-        pa.step0 = step0; pa.goal = goal; pa.rewards = rewards; pa.steps_before_reward = steps_before_reward;
-        pa.fault = fault;
-        int sh = 0;
-        while ((1 << sh) < D) ++sh;
-        pa.sh = sh;
-        const int NTW = 16 >> sh;
-        pa.G = (B + NTW - 1) / NTW;
-        pa.inv_seg4 = 65536u / (unsigned)(4 * D) + 1u;
-        // groups per wave by the waves per SIMD they leave, as launch_pd_rollout ("pd_quad": 0 one, 2 four, 3 two)
-        const int quad_mode = tune.pd_quad < 0 ? 1 : tune.pd_quad;
-        const long simds = 1024;
-        int ng = 1;
-        if (quad_mode == 2) ng = 4;
-        else if (quad_mode == 3) ng = 2;
-        // (second session: the thresholds of launch_pd_rollout -- with the reward 10 240 / 12 288 / 14 336 episodes 85.0 / 85.8 / 100.3 ->
-        // 78.6 / 78.9 / 79.4 us with four groups per wave, 3 072: 48.0 -> 42.6 with two; 8 192: two 52.5, four 68)
-        // round 6: beyond ~10 groups per SIMD two groups per wave again (one tile of input lookahead: the larger number of waves hides more
-        // of the loads) -- LongSimpleReacher + reward, us, four / two: 16 384 episodes 50.2 / 53.9, 24 576: 86.2 / 78.3, 32 768: 118 / 108,
-        // 65 536: 229 / 213, 262 144: 871 / 840 (profiles/r06_rollout_reward.md)
-        else if (quad_mode == 1) ng = pa.G >= 10 * simds ? 2 : (pa.G >= 5 * simds ? 4 : (2 * pa.G >= 3 * simds ? 2 : 1));
-        while (ng > 1 && ng * NTW > 8) ng >>= 1;       // the reward pass holds the inputs of two passes (eight episodes) in registers
-        // small launches: the producer / consumer workgroup (k_pd_rollout_pipe: four groups per consumer, so at most two episodes per group),
-        // while two workgroups per CU (60 KB of LDS each) hold the launch; "pd_pipe" 1 / 0 forces / forbids
-        {
-            const long punits = ((long)pa.G + 3) / 4;
-            bool pipe = NTW <= 2 && tune.pd_simple != 1 && tune.pd_quad < 0 && punits <= 2L * 256;
-            if (tune.pd_pipe >= 0) pipe = tune.pd_pipe == 1 && NTW <= 2;
-            if (pipe) {
-                const size_t plds = ((size_t)kRollPipeNP * 4 * 5 * kStageStride + 16) * sizeof(float);
-                const int pblocks = (int)(punits < 2L * 256 ? punits : 2L * 256);
-                auto gop = [&](auto kern) -> int {
-                    if (plds > kLdsDefault) {
-                        hipError_t e = allow_full_lds(kern);
-                        if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return MPK_EHIP; }
-                    }
-                    hipLaunchKernelGGL(kern, dim3(pblocks), dim3(64 * (1 + kRollPipeNP)), plds, (hipStream_t)stream, pa);
-                    MPK_LAUNCH_CHECK();
-                    return MPK_OK;
-                };
-                if (rc.controller_type == MPK_CTRL_MOTOR && D == 5 && tune.pd_generic != 1) return gop(k_pd_rollout_pipe<4, true, MPK_CTRL_MOTOR, 5>);
-                return gop(k_pd_rollout_pipe<4, true, -1, 0>);
-            }
-        }
-        const int units = (pa.G + ng - 1) / ng;
-        int blocks = (units + 3) / 4;
-        if (blocks > 2048) blocks = 2048;
-        if (tune.phase_waves > 0 && blocks > 64 * tune.phase_waves) blocks = 64 * tune.phase_waves;   // (A/B runs: waves per CU)
-        if (blocks >= 8) blocks = (blocks + 7) / 8 * 8;
-        // helper waves for the control-cost pass (k_pd_rollout_tiles<.., HW>): built, tested, measured SLOWER, therefore only on request
-        // ("pd_helper" 1).  LongSimpleReacher + reward, us without / with helpers: 2 048 episodes 19.8 / 20.7, 4 096: 23.5 / 25.0,
-        // 8 192: 30.9 / 47.0, 16 384: 50.1 / 76.0, 65 536: 217 / 321 (profiles/r05_rollout.md) -- one workgroup barrier per tile ties
-        // four latency-bound chain waves (and the helpers that share their SIMDs) to the slowest of them, and the second float64 action
-        // buffer takes a resident workgroup per CU away; the pass it moves off the chain waves is 820 of 4 070 cycles per tile
-        const bool hw = MPK_RW_HELPER && tune.pd_helper == 1;
-        const size_t lds = hw ? ((size_t)4 * ng * 7 * kStageStride + 2 * 4 * kRwSlots * kRwSlotInts + 8) * sizeof(float)
-                              : (size_t)4 * ng * 5 * kStageStride * sizeof(float);
-        auto go = [&](auto kern) -> int {
-            if (lds > kLdsDefault) {
-                hipError_t e = allow_full_lds(kern);
-                if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return MPK_EHIP; }
-            }
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(hw ? 384 : 256), lds, (hipStream_t)stream, pa);
-            MPK_LAUNCH_CHECK();
-            return MPK_OK;
-        };
-        // the motor controller on 2 / 5 links (the reference's SimpleReacher environments: simple_reacher/mp_wrapper.py:11-16) with
-        // controller and link count compiled in; everything else on the run-time form of the same code
-        auto by_ng = [&](auto ct_tag, auto dc_tag) -> int {
-            constexpr int CT = decltype(ct_tag)::value, DC = decltype(dc_tag)::value;
-            if constexpr (MPK_RW_HELPER != 0) {
-                if (hw) return ng == 4 ? go(k_pd_rollout_tiles<4, true, CT, DC, true>) : (ng == 2 ? go(k_pd_rollout_tiles<2, true, CT, DC, true>) : go(k_pd_rollout_tiles<1, true, CT, DC, true>));
-            }
-            return ng == 4 ? go(k_pd_rollout_tiles<4, true, CT, DC>) : (ng == 2 ? go(k_pd_rollout_tiles<2, true, CT, DC>) : go(k_pd_rollout_tiles<1, true, CT, DC>));
-        };
-        using std::integral_constant;
-        if (rc.controller_type == MPK_CTRL_MOTOR && D == 5 && tune.pd_generic != 1) return by_ng(integral_constant<int, MPK_CTRL_MOTOR>(), integral_constant<int, 5>());
-        if (rc.controller_type == MPK_CTRL_MOTOR && D == 2 && tune.pd_generic != 1) return by_ng(integral_constant<int, MPK_CTRL_MOTOR>(), integral_constant<int, 2>());
-        return by_ng(integral_constant<int, -1>(), integral_constant<int, 0>());
-    }
-    const int epw = 64 / D;
-    const long waves = ((long)B + epw - 1) / epw;
-    hipLaunchKernelGGL(k_reacher_rollout, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, rc, D,
-                       des_pos, des_vel, q, qd, n_steps, step0, goal, steps_before_reward, actions, rewards, B, T);
-    MPK_LAUNCH_CHECK();
-    return MPK_OK;
+    const RollReward rw{step0, goal, rewards, steps_before_reward};
+    PdArgs pa{};
+    RollRoute r;
+    plan_rollout(rc, D, des_pos, des_vel, q, qd, n_steps, actions, &rw, B, T, tune, fault, pa, r);
+    return launch_rollout(pa, r, stream);
 }
-#endif  // MPK_DEVICE_ONLY
 
-#ifndef MPK_DEVICE_ONLY
 int launch_pd_rollout(const RolloutDev& rc, int D, const float* des_pos, const float* des_vel, double* q, double* qd,
                       const int32_t* n_steps, float* actions, int B, int T, void* stream, const Tuning& tune, int* fault) {
-    auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-    const int last_rows = T - (T - 1) / 16 * 16;
-    const bool tiles_ok = D >= 1 && D <= kMaxD && (T * D) % 4 == 0 && (last_rows * D) % 4 == 0 && aligned16(des_pos) &&
-                          aligned16(des_vel) && (!actions || aligned16(actions)) && tune.pd_simple != 1;
-    if (tiles_ok) {
-        PdArgs pa;
-        pa.rc = rc; pa.des_pos = des_pos; pa.des_vel = des_vel; pa.Q = q; pa.QD = qd; pa.n_steps = n_steps;
-        pa.actions = actions; pa.D = D; pa.B = B; pa.T = T;
-        pa.wt = (double)B * T * D * 12.0 <= kCachedBytes ? 1 : 0;     // desired (pos, vel) + actions stay cached
-        if (tune.write_through >= 0) pa.wt = tune.write_through != 0 ? 1 : 0;
-        pa.step0 = nullptr; pa.goal = nullptr; pa.rewards = nullptr; pa.steps_before_reward = 0; pa.fault = fault;
-        int sh = 0;
-        while ((1 << sh) < D) ++sh;
-        pa.sh = sh;
-        const int NTW = 16 >> sh;
-        pa.G = (B + NTW - 1) / NTW;
-        pa.inv_seg4 = 65536u / (unsigned)(4 * D) + 1u;
-        // groups per wave (lane quarter j runs group j's recurrence: NG x fewer serial instructions per episode) chosen by the
-        // waves per SIMD it leaves (1024 SIMDs): four from 5 groups per SIMD on, two from 1.5, else one ("pd_quad": 0 one, 2 four,
-        // 3 two).  Measured (profiles/r04_rollout.md; second session, after the tile loop stopped waiting for its stores, cfg2 shape:
-        // 3 072 episodes 12.7 -> 11.3 us with two, 10 240 / 12 288 / 14 336: 24.1 / 26.5 / 30.6 -> 21.6 / 23.2 / 24.9 us with four;
-        // 8 192: two 16.8, four 17.1)
-        const int quad_mode = tune.pd_quad < 0 ? 1 : tune.pd_quad;
-        const long simds = 1024;
-        int ng = 1;
-        if (quad_mode == 2) ng = 4;
-        else if (quad_mode == 3) ng = 2;
-        else if (quad_mode == 1) ng = pa.G >= 5 * simds ? 4 : (2 * pa.G >= 3 * simds ? 2 : 1);
-        // small launches: the producer / consumer workgroup (k_pd_rollout_pipe), while four workgroups per CU hold the launch
-        {
-            const long punits = ((long)pa.G + 3) / 4;
-            bool pipe = tune.pd_quad < 0 && punits <= 4L * 256;
-            if (tune.pd_pipe >= 0) pipe = tune.pd_pipe == 1;
-            if (pipe) {
-                const size_t plds = ((size_t)kRollPipeNP * 4 * 3 * kStageStride + 16) * sizeof(float);
-                const int pblocks = (int)(punits < 4L * 256 ? punits : 4L * 256);
-                const dim3 pb(64 * (1 + kRollPipeNP));
-                if (D == 7 && tune.pd_generic != 1) hipLaunchKernelGGL((k_pd_rollout_pipe<4, false, -1, 7>), dim3(pblocks), pb, plds, (hipStream_t)stream, pa);
-                else if (D == 5 && tune.pd_generic != 1) hipLaunchKernelGGL((k_pd_rollout_pipe<4, false, -1, 5>), dim3(pblocks), pb, plds, (hipStream_t)stream, pa);
-                else hipLaunchKernelGGL((k_pd_rollout_pipe<4, false, -1, 0>), dim3(pblocks), pb, plds, (hipStream_t)stream, pa);
-                MPK_LAUNCH_CHECK();
-                return MPK_OK;
-            }
-        }
-        const int units = (pa.G + ng - 1) / ng;
-        int blocks = (units + 3) / 4;
-        if (blocks > 2048) blocks = 2048;
-        // Beyond the caches ONE workgroup of four waves per CU instead of eight (round 5): the persistent waves walk the units in order,
-        // and fewer read / write streams per CU stream faster -- cfg2 shape 131 072 / 262 144 / 524 288 episodes 235 / 497 / 991 ->
-        // 225 / 448 / 870 us, LongSimpleReacher shape 65 536 / 131 072: 186 / 361 -> 172 / 328; neutral at 400 MB, slower below
-        // (16 384 episodes of the reacher shape: 37 -> 43 us).  Uneven numbers of workgroups per CU lose (192, 384 blocks), two waves per
-        // CU lose half.  The reward variant needs its occupancy (794 -> 897 us at 262 144) and keeps eight.  "phase_waves": A/B runs.
-        if (tune.phase_waves > 0) { if (blocks > 64 * tune.phase_waves) blocks = 64 * tune.phase_waves; }
-        else if ((double)B * T * D * 12.0 >= 512.0 * 1024 * 1024 && blocks > 256) blocks = 256;
-        if (blocks >= 8) blocks = (blocks + 7) / 8 * 8;
-        const size_t lds = (size_t)4 * ng * 3 * kStageStride * sizeof(float);
-        auto by_ng = [&](auto dc_tag) {
-            constexpr int DC = decltype(dc_tag)::value;
-            if (ng == 4) hipLaunchKernelGGL((k_pd_rollout_tiles<4, false, -1, DC>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, pa);
-            else if (ng == 2) hipLaunchKernelGGL((k_pd_rollout_tiles<2, false, -1, DC>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, pa);
-            else hipLaunchKernelGGL((k_pd_rollout_tiles<1, false, -1, DC>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, pa);
-        };
-        if (D == 7 && tune.pd_generic != 1) by_ng(std::integral_constant<int, 7>());
-        else if (D == 5 && tune.pd_generic != 1) by_ng(std::integral_constant<int, 5>());
-        else by_ng(std::integral_constant<int, 0>());
-        MPK_LAUNCH_CHECK();
-        return MPK_OK;
-    }
-    const long n = (long)B * D;
-    const int blocks = (int)((n + 255) / 256);
-    hipLaunchKernelGGL(k_pd_rollout, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rc, D, des_pos, des_vel, q, qd,
-                       n_steps, actions, B, T);
-    MPK_LAUNCH_CHECK();
-    return MPK_OK;
+    PdArgs pa{};
+    RollRoute r;
+    plan_rollout(rc, D, des_pos, des_vel, q, qd, n_steps, actions, nullptr, B, T, tune, fault, pa, r);
+    return launch_rollout(pa, r, stream);
 }
 #endif  // MPK_DEVICE_ONLY
 

@@ -313,15 +313,7 @@ int launch_reacher_rollout_vjp(const RolloutDev& rc, int D, const float* des_pos
     }
     const int E = 64 / D;
     const unsigned blocks = (unsigned)(((long)B + E - 1) / E);
-    auto go = [&](auto kern) -> int {
-        if (lds > kLdsDefault) {
-            hipError_t e = allow_full_lds(kern);
-            if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return MPK_EHIP; }
-        }
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, (hipStream_t)stream, va);
-        MPK_LAUNCH_CHECK();
-        return MPK_OK;
-    };
+    auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(64), lds, stream, va); };
     auto by_d = [&](auto ct_tag, const char* n2, const char* n5, const char* n7, const char* n0) -> int {
         constexpr int CT = decltype(ct_tag)::value;
         if (D == 2) { *kernel_name = n2; return go(k_reacher_rollout_vjp<CT, 2>); }

@@ -1499,166 +1499,271 @@ int launch_fast_rows_table(const DevCfg& c, float* out, void* stream) {
     return MPK_OK;
 }
 
-static int launch_traj_phase(const DevCfg& c, const PhaseArgs& base, int num_cu, void* stream,
-                             const char** kernel_name, const Tuning& tune) {
-    PhaseArgs pa = base;
-    const bool dmp = c.mp_type == MPK_MP_DMP;
-    bool flat = false, modelled = false;   // prodmp: chunk size chosen by the cost model (no balance rule on top)
-    // dmp: + goal, y0, ydot0 columns; prodmp: weights, goal, y1 | y2 (a goal offset is added to the goal itself here)
-    const int need = c.mp_type == MPK_MP_PRODMP ? c.nb + 3 : c.KT + (dmp ? 3 : 0);
-    if (need > 16 || c.D > 64) return MPK_ENOTIMPL;
-    const int KQ = need <= 4 && c.mp_type == MPK_MP_PROMP ? 1 : (need <= 8 ? 2 : 4), KS = KQ * 4;
-    if (c.D * KS > 256) return MPK_ENOTIMPL;
-    if (c.mp_type == MPK_MP_PRODMP && (!c.rows32 || c.rows32_stride != 2 * KS + 4)) return MPK_ENOTIMPL;
-    pa.t_pad = (c.T + 3) / 4 * 4;
-    pa.x_pad = c.D * KS;
-    pa.o_pad = (64 * c.D + 4 + 3) / 4 * 4;
-    if (dmp) {
-        // a wave owns chunks of E consecutive episodes, one lane per (episode, DoF) in the Euler recurrence
-        // measured at 7 DoF, T = 200 (us at B = 4096 / 65536): E = 1 94 / 1220, 2 67 / 633, 3 70 / 479, **4 62 / 406**, 6 96 / 454,
-        // 9 131 / 503 -- four episodes make the 64 (episode, step) items of a tile exactly one round of the wave, and the
-        // per-wave LDS (6.8 KB) still lets 20 waves share a CU; "phase_chunk" overrides (up to 64 / D, at most 16)
-        const int e_max = 64 / c.D > 16 ? 16 : 64 / c.D;
-        int E = e_max < 4 ? e_max : 4;
-        if (tune.phase_chunk >= 1 && tune.phase_chunk <= e_max) E = tune.phase_chunk;
-        pa.chunk = E;
-        pa.o_pad = E * 16 * c.D;                                  // one (pos or vel) tile of the chunk
-        pa.wave_floats = E * pa.x_pad + 8 * E + E * 16 + 2 * pa.o_pad;
-        pa.vec_ok = ((reinterpret_cast<uintptr_t>(pa.pos) | reinterpret_cast<uintptr_t>(pa.vel)) & 15u) == 0 && (c.T * c.D) % 4 == 0 ? 1 : 0;
-        // forcing rows by interpolation (fast_rows_build / _eval) where the table's error bound was derived: up to five basis
-        // functions in eight columns; "phase_table" 0: the exact rows
-        pa.h_pad = KS == 8 && tune.phase_table != 0 && c.rows32 && c.rows32_stride == 8 ? kFastRows * KS : 0;
+// ---- launch_traj_phase: the route choice (plan_traj_phase: arithmetic only, no HIP call, nothing allocated) and ONE launch of what it names
+enum class PhaseFamily : int {
+    Wave,         // k_traj_phase: promp / prodmp, a wave per chunk (prodmp: row table in LDS or from L2, per-episode or flat rounds)
+    DmpWave,      // k_traj_phase_dmp: a wave per chunk
+    DmpWg,        // k_traj_phase_dmp_wg: a workgroup per chunk
+    DmpPipe,      // k_traj_phase_dmp_pipe: a workgroup per chunk, wave 0 only steps
+};
+
+struct PhaseRoute {
+    PhaseFamily family;
+    int mp, kq;             // MP type and column quads
+    bool lds_table, flat;   // Wave, prodmp
+    int dc;                 // DoF count compiled in (7; 0: run time)
+    int ntb;                // DmpWg: tiles per block (5 / 4 / 2)
+    long blocks;
+    int threads;
+    size_t lds;
+    const char* name;       // what mpk_last_kernel reports: static storage
+};
+
+// the facts of a launch every exit's rule reads (PhaseArgs carries the pointers, B and the pads)
+struct PhaseFacts {
+    const DevCfg& c;
+    const Tuning& tune;
+    int num_cu;
+    bool dmp, prodmp;
+    int KQ, KS;
+};
+
+// dmp: a wave owns chunks of E consecutive episodes, one lane per (episode, DoF) in the Euler recurrence
+// measured at 7 DoF, T = 200 (us at B = 4096 / 65536): E = 1 94 / 1220, 2 67 / 633, 3 70 / 479, **4 62 / 406**, 6 96 / 454,
+// 9 131 / 503 -- four episodes make the 64 (episode, step) items of a tile exactly one round of the wave, and the
+// per-wave LDS (6.8 KB) still lets 20 waves share a CU; "phase_chunk" overrides (up to 64 / D, at most 16)
+static void fill_phase_dmp_chunk(const PhaseFacts& f, PhaseArgs& pa) {
+    const DevCfg& c = f.c;
+    const int e_max = 64 / c.D > 16 ? 16 : 64 / c.D;
+    int E = e_max < 4 ? e_max : 4;
+    if (f.tune.phase_chunk >= 1 && f.tune.phase_chunk <= e_max) E = f.tune.phase_chunk;
+    pa.chunk = E;
+    pa.o_pad = E * 16 * c.D;                                  // one (pos or vel) tile of the chunk
+    pa.wave_floats = E * pa.x_pad + 8 * E + E * 16 + 2 * pa.o_pad;
+    pa.vec_ok = ((reinterpret_cast<uintptr_t>(pa.pos) | reinterpret_cast<uintptr_t>(pa.vel)) & 15u) == 0 && (c.T * c.D) % 4 == 0 ? 1 : 0;
+    // forcing rows by interpolation (fast_rows_build / _eval) where the table's error bound was derived: up to five basis
+    // functions in eight columns; "phase_table" 0: the exact rows
+    pa.h_pad = f.KS == 8 && f.tune.phase_table != 0 && c.rows32 && c.rows32_stride == 8 ? kFastRows * f.KS : 0;
+}
+
+// prodmp: per-episode rounds with one episode per chunk, or flat rounds (k_traj_phase<.., FL>) over chunks of up to 8
+// episodes -- whichever has the shorter critical path per wave: passes over the resident waves x (rounds of a chunk +
+// ~2.5 rounds of per-chunk work: inputs, columns, boundary factors); a flat round costs ~15 % more (per-lane episode
+// constants).  Measured at cfg2 + learned tau (T = 100): B = 4096 11.7 us per-episode vs 15 - 24 flat; 16 384 31.9 vs
+// 23.4 - 24.8 (5 - 7 episodes per chunk); 65 536 94 vs 89; 262 144 equal (HBM) -- profiles/r03_per_episode_phase.md.
+// "phase_flat" / "phase_chunk" override.  Returns the chunk (E: the promp rule's); modelled: no balance rule on top
+static int phase_prodmp_chunk(const PhaseFacts& f, const PhaseArgs& pa, int E, bool& flat, bool& modelled) {
+    const DevCfg& c = f.c;
+    const Tuning& tune = f.tune;
+    const int KS = f.KS, num_cu = f.num_cu;
+    int e_max = 320 / c.P;
+    e_max = e_max > 8 ? 8 : e_max;
+    e_max = e_max > 64 / c.D ? 64 / c.D : e_max;
+    const size_t shared0 = (size_t)(pa.t_pad + KS + 4) * sizeof(float);
+    const size_t tab_bytes = (size_t)c.n_pc * (2 * KS + 4) * sizeof(float);
+    auto resident = [&](int e, bool fl) -> long {           // waves of the whole chip for this layout (as plan_phase_wave)
+        const int img_in = e * (c.P + 2 * c.D + 1), img_cols = e * (pa.x_pad + (fl ? 12 : 3));
+        const size_t wb = (size_t)(2 * (((img_in > img_cols ? img_in : img_cols) + 3) / 4 * 4) + 2 * pa.o_pad) * sizeof(float);
+        const bool tab = tune.phase_table != 0 && tab_bytes + 8 * wb <= kLdsPerCu - shared0 && (long)pa.B >= (long)num_cu * 8;
+        int w = tab ? (int)((kLdsPerCu - shared0 - tab_bytes) / wb) : (int)((kLdsDefault - shared0) / wb);
+        w = tab ? (w > 16 ? 16 : w) : (w > 4 ? 4 : (w < 1 ? 1 : w));
+        int pc = (int)(kLdsPerCu / (wb * w + shared0 + (tab ? tab_bytes : 0)));
+        pc = pc > 32 / w ? 32 / w : (pc < 1 ? 1 : pc);
+        return (long)num_cu * pc * w;
+    };
+    auto cost = [&](int e, bool fl) -> double {
+        const long chunks = ((long)pa.B + e - 1) / e, W = resident(e, fl);
+        const double passes = (double)((chunks + W - 1) / W);
+        const double rounds = fl ? 1.15 * (double)((e * c.T + 63) / 64) : (double)(e * ((c.T + 63) / 64));
+        return passes * (rounds + 2.5);
+    };
+    if (tune.phase_flat == 0) {
+        flat = false;
+    } else if (tune.phase_flat == 1) {
+        flat = true;
+        double best = 1e300;
+        for (int e = 1; e <= e_max; ++e)
+            if (cost(e, true) < best - 1e-9) { best = cost(e, true); E = e; }
+        modelled = true;
     } else {
-        // chunks of up to 4 consecutive episodes whose parameter rows fit the loader's 5 x 64 values and whose boundary
-        // states fit one 64-lane load
-        int E = 320 / c.P;
-        E = E > 4 ? 4 : E;
-        E = E > 64 / c.D ? 64 / c.D : E;
-        if (E < 1) return MPK_ENOTIMPL;
-        // prodmp: per-episode rounds with one episode per chunk, or flat rounds (k_traj_phase<.., FL>) over chunks of up to 8
-        // episodes -- whichever has the shorter critical path per wave: passes over the resident waves x (rounds of a chunk +
-        // ~2.5 rounds of per-chunk work: inputs, columns, boundary factors); a flat round costs ~15 % more (per-lane episode
-        // constants).  Measured at cfg2 + learned tau (T = 100): B = 4096 11.7 us per-episode vs 15 - 24 flat; 16 384 31.9 vs
-        // 23.4 - 24.8 (5 - 7 episodes per chunk); 65 536 94 vs 89; 262 144 equal (HBM) -- profiles/r03_per_episode_phase.md.
-        // "phase_flat" / "phase_chunk" override.
-        if (c.mp_type == MPK_MP_PRODMP) {
-            int e_max = 320 / c.P;
-            e_max = e_max > 8 ? 8 : e_max;
-            e_max = e_max > 64 / c.D ? 64 / c.D : e_max;
-            const size_t shared0 = (size_t)(pa.t_pad + KS + 4) * sizeof(float);
-            const size_t tab_bytes = (size_t)c.n_pc * (2 * KS + 4) * sizeof(float);
-            auto resident = [&](int e, bool fl) -> long {           // waves of the whole chip for this layout (as below)
-                const int img_in = e * (c.P + 2 * c.D + 1), img_cols = e * (pa.x_pad + (fl ? 12 : 3));
-                const size_t wb = (size_t)(2 * (((img_in > img_cols ? img_in : img_cols) + 3) / 4 * 4) + 2 * pa.o_pad) * sizeof(float);
-                const bool tab = tune.phase_table != 0 && tab_bytes + 8 * wb <= kLdsPerCu - shared0 && (long)pa.B >= (long)num_cu * 8;
-                int w = tab ? (int)((kLdsPerCu - shared0 - tab_bytes) / wb) : (int)((kLdsDefault - shared0) / wb);
-                w = tab ? (w > 16 ? 16 : w) : (w > 4 ? 4 : (w < 1 ? 1 : w));
-                int pc = (int)(kLdsPerCu / (wb * w + shared0 + (tab ? tab_bytes : 0)));
-                pc = pc > 32 / w ? 32 / w : (pc < 1 ? 1 : pc);
-                return (long)num_cu * pc * w;
-            };
-            auto cost = [&](int e, bool fl) -> double {
-                const long chunks = ((long)pa.B + e - 1) / e, W = resident(e, fl);
-                const double passes = (double)((chunks + W - 1) / W);
-                const double rounds = fl ? 1.15 * (double)((e * c.T + 63) / 64) : (double)(e * ((c.T + 63) / 64));
-                return passes * (rounds + 2.5);
-            };
-            if (tune.phase_flat == 0) {
-                flat = false;
-            } else if (tune.phase_flat == 1) {
-                flat = true;
-                double best = 1e300;
-                for (int e = 1; e <= e_max; ++e)
-                    if (cost(e, true) < best - 1e-9) { best = cost(e, true); E = e; }
-                modelled = true;
-            } else {
-                double best = cost(1, false);
-                E = 1; flat = false;
-                for (int e = 2; e <= e_max; ++e)
-                    if (cost(e, true) < best * 0.97) { best = cost(e, true); E = e; flat = true; }
-                modelled = true;
-            }
-            if (flat && tune.phase_chunk >= 1 && tune.phase_chunk <= e_max) E = tune.phase_chunk;
-            if (tune.phase_chunk >= 1) modelled = flat;
-        }
-        pa.chunk = E;
-        // prodmp: the image is rewritten in place into [E][x_pad] columns + [E][3] clipped phase values (flat rounds: [E][4]
-        // + [E][4] float64 boundary-condition factors)
-        const int img_in = E * (c.P + 2 * c.D + 1), img_cols = c.mp_type == MPK_MP_PRODMP ? E * (pa.x_pad + (flat ? 12 : 3)) : 0;
-        pa.img_pad = ((img_in > img_cols ? img_in : img_cols) + 3) / 4 * 4;
-        pa.wave_floats = 2 * pa.img_pad + 2 * pa.o_pad + (c.mp_type == MPK_MP_PRODMP ? 0 : pa.x_pad);
+        double best = cost(1, false);
+        E = 1; flat = false;
+        for (int e = 2; e <= e_max; ++e)
+            if (cost(e, true) < best * 0.97) { best = cost(e, true); E = e; flat = true; }
+        modelled = true;
     }
-    pa.c_pad = c.mp_type == MPK_MP_PRODMP ? KS + 4 : (4 * c.n_total + 6 + 3) / 4 * 4;
-    if (!dmp) pa.h_pad = 0;
-    const size_t wave_bytes = (size_t)pa.wave_floats * sizeof(float);
-    size_t shared_bytes = (size_t)(pa.t_pad + pa.c_pad + pa.h_pad) * sizeof(float);
-    if (wave_bytes + shared_bytes > kLdsPerCu) return MPK_ENOTIMPL;
+    if (flat && tune.phase_chunk >= 1 && tune.phase_chunk <= e_max) E = tune.phase_chunk;
+    if (tune.phase_chunk >= 1) modelled = flat;
+    return E;
+}
+
+// promp / prodmp: chunks of up to 4 consecutive episodes whose parameter rows fit the loader's 5 x 64 values and whose boundary
+// states fit one 64-lane load (prodmp: phase_prodmp_chunk on top); false: no episode fits
+static bool fill_phase_chunk(const PhaseFacts& f, PhaseArgs& pa, bool& flat, bool& modelled) {
+    const DevCfg& c = f.c;
+    int E = 320 / c.P;
+    E = E > 4 ? 4 : E;
+    E = E > 64 / c.D ? 64 / c.D : E;
+    if (E < 1) return false;
+    if (f.prodmp) E = phase_prodmp_chunk(f, pa, E, flat, modelled);
+    pa.chunk = E;
+    // prodmp: the image is rewritten in place into [E][x_pad] columns + [E][3] clipped phase values (flat rounds: [E][4]
+    // + [E][4] float64 boundary-condition factors)
+    const int img_in = E * (c.P + 2 * c.D + 1), img_cols = f.prodmp ? E * (pa.x_pad + (flat ? 12 : 3)) : 0;
+    pa.img_pad = ((img_in > img_cols ? img_in : img_cols) + 3) / 4 * 4;
+    pa.wave_floats = 2 * pa.img_pad + 2 * pa.o_pad + (f.prodmp ? 0 : pa.x_pad);
+    return true;
+}
+
+// ---- dmp, few chunks (the wave-per-chunk kernel would run at one wave per SIMD or fewer, latency bound): a workgroup per chunk,
+// four tiles of rows at once (k_traj_phase_dmp_wg).  "phase_flat" 1 forces it, 0 forbids it (A/B runs, tests)
+// two geometries: chunks of (up to) four episodes in blocks of four tiles, or -- when that needs more than one round of
+// resident workgroups -- chunks of eight in blocks of two tiles (twice the episodes per round)
+// (the interpolation table here too since it is a copy of the handle's: cfg3' at 4 096 episodes 26.8 us on the exact rows,
+// 21.9 with the table; when every workgroup built it for its one or two chunks it cost more than it saved, 35.3 vs 31)
+struct DmpWgGeom {
+    bool take;          // the workgroup kernels take the launch
+    int E, NTB;         // episodes per chunk, tiles per block
+    long chunks;
+    size_t lds;
+    int res;            // resident workgroups per CU
+};
+
+static DmpWgGeom dmp_wg_geometry(const PhaseFacts& f, const PhaseArgs& pa) {
+    const DevCfg& c = f.c;
+    const int KQ = f.KQ, num_cu = f.num_cu;
+    auto wg_bytes = [&](int e, int ntb) {
+        return ((size_t)pa.c_pad + pa.h_pad + pa.t_pad + (size_t)e * pa.x_pad + 8 * e + (size_t)e * 16 * ntb +
+                2 * (size_t)e * 16 * ntb * c.D) * sizeof(float);
+    };
+    auto wg_resident = [&](size_t bytes) {
+        int r = (int)(kLdsPerCu / bytes);                        // LDS, and five (four) by its 86 - 108 registers
+        return r > (KQ == 2 ? 5 : 4) ? (KQ == 2 ? 5 : 4) : r;
+    };
+    const bool user_chunk = f.tune.phase_chunk >= 1;
+    DmpWgGeom g{false, pa.chunk, 4, 0, 0, 0};
+    const bool wg_ok = pa.chunk <= 4 && pa.chunk * c.D <= 64 && wg_bytes(pa.chunk, 4) <= kLdsPerCu;
+    g.chunks = ((long)pa.B + g.E - 1) / g.E;
+    if (wg_ok && !user_chunk && pa.chunk == 4 && 8 * c.D <= 64 && g.chunks > (long)num_cu * wg_resident(wg_bytes(4, 4)) &&
+        wg_bytes(8, 2) <= kLdsPerCu) {
+        g.E = 8; g.NTB = 2;
+        g.chunks = ((long)pa.B + 7) / 8;
+    }
+    // five waves, blocks of 80 steps: where that is a block fewer and a CU holds at most two workgroups (with four, the 20 waves did
+    // not fit the CU's SIMDs -- 4 096 episodes 29.7 us against 20.1; "tiles_wpb" 4: the four-wave geometry, for A/B runs)
+    if (wg_ok && g.NTB == 4 && KQ == 2 && (c.T + 79) / 80 < (c.T + 63) / 64 && wg_bytes(g.E, 5) * 4 <= kLdsPerCu &&
+        g.chunks <= (long)num_cu * 2 && f.tune.tiles_wpb != 4)
+        g.NTB = 5;
+    g.lds = wg_bytes(g.E, g.NTB);
+    g.res = wg_resident(g.lds);
+    // (beyond ONE round of resident workgroups the wave-per-chunk kernel is as fast: cfg3' at 6 144 episodes in chunks of
+    // four 58 vs 61 us)
+    g.take = wg_ok && f.tune.phase_flat != 0 && (f.tune.phase_flat == 1 || g.chunks <= (long)num_cu * g.res);
+    return g;
+}
+
+// the pipeline form (k_traj_phase_dmp_pipe: wave 0 only steps, three helper waves build and store around it in blocks of 48
+// steps, two buffers): chunks of up to four episodes, eight columns, more than one block, and the launch in ONE round of its
+// resident workgroups ("pipe" 0: the plain workgroup kernel, for A/B runs and tests)
+static bool plan_phase_dmp_pipe(const PhaseFacts& f, const DmpWgGeom& g, PhaseArgs& pa, PhaseRoute& r) {
+    const DevCfg& c = f.c;
+    const size_t pipe_lds = ((size_t)pa.c_pad + pa.h_pad + pa.t_pad + (size_t)g.E * pa.x_pad + 8 * g.E + 2 * (size_t)g.E * 48 +
+                             4 * (size_t)g.E * 48 * c.D) * sizeof(float);
+    int pipe_res = (int)(kLdsPerCu / pipe_lds);
+    pipe_res = pipe_res > 4 ? 4 : pipe_res;
+    const bool pipe_form = g.E <= 4 && g.NTB != 2 && f.KQ == 2 && c.T > 48 && f.tune.pipe != 0 && pipe_res >= 1 &&
+                           g.chunks <= (long)f.num_cu * pipe_res;
+    if (!(g.take && pipe_form)) return false;
+    pa.chunk = g.E;
+    r.family = PhaseFamily::DmpPipe;
+    r.blocks = g.chunks; r.threads = 256; r.lds = pipe_lds;
+    r.name = "k_traj_phase<dmp,wg,pipe>";
+    return true;
+}
+
+static bool plan_phase_dmp_wg(const PhaseFacts& f, const DmpWgGeom& g, PhaseArgs& pa, PhaseRoute& r) {
+    if (!g.take) return false;
+    pa.chunk = g.E;
+    r.family = PhaseFamily::DmpWg;
+    r.ntb = g.NTB;
+    r.blocks = g.chunks < (long)f.num_cu * g.res ? g.chunks : (long)f.num_cu * g.res;
+    r.threads = g.NTB == 5 ? 320 : 256;
+    r.lds = g.lds;
+    r.name = "k_traj_phase<dmp,wg>";
+    return true;
+}
+
+// ---- the wave-per-chunk kernels (k_traj_phase, k_traj_phase_dmp): whatever the dmp workgroup kernels leave
+// dmp with the interpolation table: the waves of a workgroup share one copy of it (16.5 KB): eight waves per workgroup where that puts
+// more waves on a CU -- cfg3': 45 KB x 3 = 12 waves per CU with four, 73 KB x 2 = 16 with eight, i.e. 16 384 instead of 12 288 episodes in
+// ONE round of resident waves (round 5: 16 384 episodes 87.6 -> 69.0 us, 32 768: 150.8 -> 137.9, 65 536: 279 -> 265)
+static bool phase_dmp_eight_waves(const PhaseFacts& f, const PhaseArgs& pa, size_t wave_bytes, size_t shared_bytes) {
+    auto resident = [&](int w) {
+        const size_t l = wave_bytes * w + shared_bytes;
+        if (l > kLdsPerCu) return 0;
+        const int pc = (int)(kLdsPerCu / l);
+        return w * (pc > 32 / w ? 32 / w : pc);
+    };
+    // (only where four waves per workgroup need a second round: a single round runs faster with fewer waves per SIMD --
+    // 12 288 episodes 59 us with twelve waves per CU, 69 with sixteen)
+    const long chunks = ((long)pa.B + pa.chunk - 1) / pa.chunk;
+    // (a tie goes to eight: half as many workgroups build the table, and half as many copies of it sit in the CU's LDS --
+    // cfg3' at 65 536 episodes 236 us with four waves per workgroup, 217 with eight, sixteen waves per CU either way)
+    return resident(8) >= resident(4) && chunks > (long)f.num_cu * resident(4);
+}
+
+// prodmp: stage the row table in LDS when it leaves room for at least 8 waves ("phase_table" 0: gather from L2); then it joins the
+// workgroup's shared bytes and sets the waves per workgroup
+static bool phase_lds_table(const PhaseFacts& f, bool flat, size_t wave_bytes, size_t& shared_bytes, int& wpb, PhaseArgs& pa) {
+    const DevCfg& c = f.c;
+    if (!f.prodmp) return false;
+    const size_t full_bytes = (size_t)c.n_pc * (2 * f.KS + 4) * sizeof(float);
+    const size_t room = kLdsPerCu - shared_bytes;
+    if (!(full_bytes + 8 * wave_bytes <= room && (long)pa.B >= (long)f.num_cu * 8) || f.tune.phase_table == 0) return false;
+    // the rows an episode can reach; per-episode init_times are device data: the whole table then
+    const int rows_needed = pa.init_time ? c.n_pc : prodmp_rows_reachable(c, pa.init_time_shared);
+    pa.tab_pad = rows_needed * (2 * f.KS + 4);
+    shared_bytes += (size_t)pa.tab_pad * sizeof(float);
+    wpb = (int)((kLdsPerCu - shared_bytes) / wave_bytes);
+    wpb = wpb > 16 ? 16 : wpb;
+    // Fewer waves per CU for large launches of the flat rounds: every wave writes its own chunk's run of HBM, and sixteen streams
+    // per CU write slower than eight (round 5, alternating rounds on three boxes; workgroups of four waves = two workgroups per
+    // CU by the table's LDS: 65 536 episodes 87.5 / 102.6 us with sixteen waves per workgroup, 74.7 / 90.8 with four; 262 144:
+    // 368 -> 350; against workgroups of eight: 24 576 28.7 -> 27.2, 32 768 41.0 -> 35.8, 131 072 167 -> 158, 262 144 288 -> 281;
+    // workgroups of two lose again: 302.  At 16 384 and below the sixteen are faster: 21.5 against 23.0).
+    // "tiles_wpb" 1 .. 8 sets the cap itself (A/B runs).
+    if (f.tune.tiles_wpb > 0) wpb = wpb > f.tune.tiles_wpb ? f.tune.tiles_wpb : wpb;
+    else if (flat && wpb > 4 && pa.B >= 24576) wpb = 4;
+    return true;
+}
+
+// balance: a wave's work is quantised in E episodes, so smaller chunks while a resident wave gets fewer than 4 -- applied LAST, to
+// pa.chunk alone: the LDS layout, the waves per workgroup and the resident waves stay those of the chunk the sizes were derived from
+static void phase_balance_chunk(const PhaseFacts& f, long resident, PhaseArgs& pa) {
+    int E = pa.chunk;
+    while (E > 1 && (long)pa.B / E < 4 * resident) E >>= 1;
+    if (f.tune.phase_chunk >= 1 && f.tune.phase_chunk <= pa.chunk) E = f.tune.phase_chunk;
+    pa.chunk = E;
+}
+
+static const char* phase_wave_name(const PhaseFacts& f, bool lds_table, bool flat) {
+    if (f.dmp) return "k_traj_phase<dmp>";
+    if (!f.prodmp) return "k_traj_phase<promp>";
+    if (lds_table) return flat ? "k_traj_phase<prodmp,lds,flat>" : "k_traj_phase<prodmp,lds>";
+    return flat ? "k_traj_phase<prodmp,flat>" : "k_traj_phase<prodmp>";
+}
+
+static void plan_phase_wave(const PhaseFacts& f, bool flat, bool modelled, size_t wave_bytes, size_t shared_bytes, PhaseArgs& pa, PhaseRoute& r) {
+    const int num_cu = f.num_cu;
     int wpb = (int)((kLdsDefault - shared_bytes) / wave_bytes);
     wpb = wpb > 4 ? 4 : (wpb < 1 ? 1 : wpb);
-    if (dmp && pa.h_pad > 0 && wpb == 4) {
-        // the waves of a workgroup share one copy of the row table (16.5 KB): eight waves per workgroup where that puts more waves
-        // on a CU -- cfg3': 45 KB x 3 = 12 waves per CU with four, 73 KB x 2 = 16 with eight, i.e. 16 384 instead of 12 288 episodes in
-        // ONE round of resident waves (round 5: 16 384 episodes 87.6 -> 69.0 us, 32 768: 150.8 -> 137.9, 65 536: 279 -> 265)
-        auto resident = [&](int w) {
-            const size_t l = wave_bytes * w + shared_bytes;
-            if (l > kLdsPerCu) return 0;
-            const int pc = (int)(kLdsPerCu / l);
-            return w * (pc > 32 / w ? 32 / w : pc);
-        };
-        // (only where four waves per workgroup need a second round: a single round runs faster with fewer waves per SIMD --
-        // 12 288 episodes 59 us with twelve waves per CU, 69 with sixteen)
-        const long chunks_ = ((long)pa.B + pa.chunk - 1) / pa.chunk;
-        // (a tie goes to eight: half as many workgroups build the table, and half as many copies of it sit in the CU's LDS --
-        // cfg3' at 65 536 episodes 236 us with four waves per workgroup, 217 with eight, sixteen waves per CU either way)
-        if (resident(8) >= resident(4) && chunks_ > (long)num_cu * resident(4)) wpb = 8;
-    }
-    // prodmp: stage the row table in LDS when it leaves room for at least 8 waves ("phase_table" 0: gather from L2)
-    bool lds_table = false;
-    if (c.mp_type == MPK_MP_PRODMP) {
-        const size_t full_bytes = (size_t)c.n_pc * (2 * KS + 4) * sizeof(float);
-        const size_t room = kLdsPerCu - shared_bytes;
-        lds_table = full_bytes + 8 * wave_bytes <= room && (long)pa.B >= (long)num_cu * 8;
-        if (tune.phase_table == 0) lds_table = false;
-        if (lds_table) {
-            // rows an episode can reach: scaled time <= (last grid time + init_time - smallest delay) / smallest tau (the kernels clip tau
-            // and delay to their bounds); per-episode init_times are device data: the whole table then
-            int rows_needed = c.n_pc;
-            if (!pa.init_time) {
-                const float tau_lo = c.learn_tau ? c.tau_lo : c.tau, delay_lo = c.learn_delay ? c.delay_lo : c.delay;
-                const double t_last = (double)c.t_last;
-                if (t_last > 0.0 && tau_lo > 0.f) {
-                    const double s_max = (t_last + (double)pa.init_time_shared - (double)delay_lo) / (double)tau_lo;
-                    const double r = s_max / (double)c.scaled_dt + 4.0;
-                    if (r < (double)c.n_pc) rows_needed = r < 4.0 ? 4 : (int)r;
-                }
-            }
-            pa.tab_pad = rows_needed * (2 * KS + 4);
-            const size_t tab_bytes = (size_t)pa.tab_pad * sizeof(float);
-            shared_bytes += tab_bytes;
-            wpb = (int)((kLdsPerCu - shared_bytes) / wave_bytes);
-            wpb = wpb > 16 ? 16 : wpb;
-            // Fewer waves per CU for large launches of the flat rounds: every wave writes its own chunk's run of HBM, and sixteen streams
-            // per CU write slower than eight (round 5, alternating rounds on three boxes; workgroups of four waves = two workgroups per
-            // CU by the table's LDS: 65 536 episodes 87.5 / 102.6 us with sixteen waves per workgroup, 74.7 / 90.8 with four; 262 144:
-            // 368 -> 350; against workgroups of eight: 24 576 28.7 -> 27.2, 32 768 41.0 -> 35.8, 131 072 167 -> 158, 262 144 288 -> 281;
-            // workgroups of two lose again: 302.  At 16 384 and below the sixteen are faster: 21.5 against 23.0).
-            // "tiles_wpb" 1 .. 8 sets the cap itself (A/B runs).
-            if (tune.tiles_wpb > 0) wpb = wpb > tune.tiles_wpb ? tune.tiles_wpb : wpb;
-            else if (flat && wpb > 4 && pa.B >= 24576) wpb = 4;
-        }
-    }
+    if (f.dmp && pa.h_pad > 0 && wpb == 4 && phase_dmp_eight_waves(f, pa, wave_bytes, shared_bytes)) wpb = 8;
+    const bool lds_table = phase_lds_table(f, flat, wave_bytes, shared_bytes, wpb, pa);
     size_t lds = wave_bytes * wpb + shared_bytes;
     int per_cu = (int)(kLdsPerCu / lds);
     per_cu = per_cu > 32 / wpb ? 32 / wpb : per_cu;
-    if (tune.phase_waves > 0 && per_cu * wpb > tune.phase_waves) per_cu = tune.phase_waves / wpb > 1 ? tune.phase_waves / wpb : 1;
-    if (!dmp && !modelled) {
-        // chunks cost balance (a wave's work is quantised in E episodes): only when every resident wave still gets >= 4
-        const long resident = (long)num_cu * per_cu * wpb;
-        int E = pa.chunk;
-        while (E > 1 && (long)pa.B / E < 4 * resident) E >>= 1;
-        if (tune.phase_chunk >= 1 && tune.phase_chunk <= pa.chunk) E = tune.phase_chunk;
-        pa.chunk = E;
-    }
+    if (f.tune.phase_waves > 0 && per_cu * wpb > f.tune.phase_waves) per_cu = f.tune.phase_waves / wpb > 1 ? f.tune.phase_waves / wpb : 1;
+    if (!f.dmp && !modelled) phase_balance_chunk(f, (long)num_cu * per_cu * wpb, pa);
     const long units = ((long)pa.B + pa.chunk - 1) / pa.chunk;
     // fewer chunks than one workgroup per CU would take: smaller workgroups, so that every CU gets its share (round 5: chunks of two
     // at 4 096 episodes were 128 workgroups of 16 waves on 256 CUs)
@@ -1669,118 +1774,90 @@ static int launch_traj_phase(const DevCfg& c, const PhaseArgs& base, int num_cu,
     }
     long blocks = (units + wpb - 1) / wpb;
     if (blocks > (long)num_cu * per_cu) blocks = (long)num_cu * per_cu;
-    auto go = [&](auto kern) -> int {
-        if (lds > kLdsDefault) {
-            hipError_t e = allow_full_lds(kern);
-            if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return MPK_EHIP; }
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * wpb), lds, (hipStream_t)stream, pa);
+    r.family = f.dmp ? PhaseFamily::DmpWave : PhaseFamily::Wave;
+    r.lds_table = lds_table; r.flat = flat;
+    r.blocks = blocks; r.threads = 64 * wpb; r.lds = lds;
+    r.name = phase_wave_name(f, lds_table, flat);
+}
+
+// the facts once, then the exits in their order of precedence: dmp pipeline, dmp workgroup, the wave kernels.  Fills the rest of
+// PhaseArgs and the route; MPK_ENOTIMPL (nothing named): the shape is k_traj_rows' (launch_traj_rows)
+static int plan_traj_phase(const DevCfg& c, int num_cu, const Tuning& tune, PhaseArgs& pa, PhaseRoute& r) {
+    const bool dmp = c.mp_type == MPK_MP_DMP, prodmp = c.mp_type == MPK_MP_PRODMP;
+    // dmp: + goal, y0, ydot0 columns; prodmp: weights, goal, y1 | y2 (a goal offset is added to the goal itself here)
+    const int need = prodmp ? c.nb + 3 : c.KT + (dmp ? 3 : 0);
+    if (need > 16 || c.D > 64) return MPK_ENOTIMPL;
+    const int KQ = need <= 4 && c.mp_type == MPK_MP_PROMP ? 1 : (need <= 8 ? 2 : 4), KS = KQ * 4;
+    if (c.D * KS > 256) return MPK_ENOTIMPL;
+    if (prodmp && (!c.rows32 || c.rows32_stride != 2 * KS + 4)) return MPK_ENOTIMPL;
+    const PhaseFacts f{c, tune, num_cu, dmp, prodmp, KQ, KS};
+    pa.t_pad = (c.T + 3) / 4 * 4;
+    pa.x_pad = c.D * KS;
+    pa.o_pad = (64 * c.D + 4 + 3) / 4 * 4;
+    bool flat = false, modelled = false;   // prodmp: flat rounds; chunk size chosen by the cost model (no balance rule on top)
+    if (dmp) fill_phase_dmp_chunk(f, pa);
+    else if (!fill_phase_chunk(f, pa, flat, modelled)) return MPK_ENOTIMPL;
+    pa.c_pad = prodmp ? KS + 4 : (4 * c.n_total + 6 + 3) / 4 * 4;
+    if (!dmp) pa.h_pad = 0;
+    const size_t wave_bytes = (size_t)pa.wave_floats * sizeof(float);
+    const size_t shared_bytes = (size_t)(pa.t_pad + pa.c_pad + pa.h_pad) * sizeof(float);
+    if (wave_bytes + shared_bytes > kLdsPerCu) return MPK_ENOTIMPL;
+    r = PhaseRoute{};
+    r.mp = c.mp_type; r.kq = KQ;
+    // (seven DoF, <= 8 columns: the instantiations with the DoF loop unrolled -- the kernels are issue bound; "pd_generic" 1: the run-time
+    // loop, for A/B runs and tests)
+    r.dc = c.D == 7 && KQ <= 2 && tune.pd_generic != 1 ? 7 : 0;
+    if (dmp) {
+        const DmpWgGeom g = dmp_wg_geometry(f, pa);
+        if (plan_phase_dmp_pipe(f, g, pa, r) || plan_phase_dmp_wg(f, g, pa, r)) return MPK_OK;
+    }
+    plan_phase_wave(f, flat, modelled, wave_bytes, shared_bytes, pa, r);
+    return MPK_OK;
+}
+
+static int launch_phase_route(const PhaseArgs& pa, const PhaseRoute& r, void* stream, const char** kernel_name) {
+    const dim3 grid((unsigned)r.blocks), block(r.threads);
+    auto go = [&](auto kern) { return launch_kernel(kern, grid, block, r.lds, stream, pa); };
+    if (r.family == PhaseFamily::DmpPipe) {
+        // as before the plan: the LDS attribute comes BEFORE the name (a failure there keeps the name of the kernel before it), and a 7-DoF
+        // handle raises <2, 7>'s also where "pd_generic" 1 launches <2> -- so this exit does not go through launch_kernel
+        if (const int rc = pa.c.D == 7 ? allow_lds(k_traj_phase_dmp_pipe<2, 7>, r.lds) : allow_lds(k_traj_phase_dmp_pipe<2>, r.lds)) return rc;
+        *kernel_name = r.name;
+        if (r.dc == 7) hipLaunchKernelGGL((k_traj_phase_dmp_pipe<2, 7>), grid, block, r.lds, (hipStream_t)stream, pa);
+        else hipLaunchKernelGGL(k_traj_phase_dmp_pipe<2>, grid, block, r.lds, (hipStream_t)stream, pa);
         MPK_LAUNCH_CHECK();
         return MPK_OK;
-    };
-    switch (c.mp_type) {
-        case MPK_MP_PRODMP:
-            // (seven DoF, <= 8 columns: the instantiations with the DoF loop unrolled; "pd_generic" 1: the run-time loop, for A/B runs and tests)
-            if (lds_table) {
-                *kernel_name = flat ? "k_traj_phase<prodmp,lds,flat>" : "k_traj_phase<prodmp,lds>";
-                if (KQ == 2 && c.D == 7 && tune.pd_generic != 1)
-                    return flat ? go(k_traj_phase<MPK_MP_PRODMP, 2, true, true, 7>) : go(k_traj_phase<MPK_MP_PRODMP, 2, true, false, 7>);
-                if (flat) return KQ == 2 ? go(k_traj_phase<MPK_MP_PRODMP, 2, true, true>) : go(k_traj_phase<MPK_MP_PRODMP, 4, true, true>);
-                return KQ == 2 ? go(k_traj_phase<MPK_MP_PRODMP, 2, true>) : go(k_traj_phase<MPK_MP_PRODMP, 4, true>);
-            }
-            *kernel_name = flat ? "k_traj_phase<prodmp,flat>" : "k_traj_phase<prodmp>";
-            if (KQ == 2 && c.D == 7 && tune.pd_generic != 1)
-                return flat ? go(k_traj_phase<MPK_MP_PRODMP, 2, false, true, 7>) : go(k_traj_phase<MPK_MP_PRODMP, 2, false, false, 7>);
-            if (flat) return KQ == 2 ? go(k_traj_phase<MPK_MP_PRODMP, 2, false, true>) : go(k_traj_phase<MPK_MP_PRODMP, 4, false, true>);
-            return KQ == 2 ? go(k_traj_phase<MPK_MP_PRODMP, 2, false>) : go(k_traj_phase<MPK_MP_PRODMP, 4, false>);
-        case MPK_MP_PROMP:
-            *kernel_name = "k_traj_phase<promp>";
-            if (c.D == 7 && KQ <= 2 && tune.pd_generic != 1)      // (seven DoF: the DoF chains unrolled side by side, as prodmp's)
-                return KQ == 1 ? go(k_traj_phase<MPK_MP_PROMP, 1, false, false, 7>) : go(k_traj_phase<MPK_MP_PROMP, 2, false, false, 7>);
-            if (KQ == 1) return go(k_traj_phase<MPK_MP_PROMP, 1, false>);
-            return KQ == 2 ? go(k_traj_phase<MPK_MP_PROMP, 2, false>) : go(k_traj_phase<MPK_MP_PROMP, 4, false>);
-        default: {
-            // few chunks (the wave-per-chunk kernel would run at one wave per SIMD or fewer, latency bound): a workgroup per chunk,
-            // four tiles of rows at once (k_traj_phase_dmp_wg).  "phase_flat" 1 forces it, 0 forbids it (A/B runs, tests)
-            // two geometries: chunks of (up to) four episodes in blocks of four tiles, or -- when that needs more than one round of
-            // resident workgroups -- chunks of eight in blocks of two tiles (twice the episodes per round)
-            // (the interpolation table here too since it is a copy of the handle's: cfg3' at 4 096 episodes 26.8 us on the exact rows,
-            // 21.9 with the table; when every workgroup built it for its one or two chunks it cost more than it saved, 35.3 vs 31)
-            const int wg_h = pa.h_pad;
-            auto wg_bytes = [&](int e, int ntb) {
-                return ((size_t)pa.c_pad + wg_h + pa.t_pad + (size_t)e * pa.x_pad + 8 * e + (size_t)e * 16 * ntb +
-                        2 * (size_t)e * 16 * ntb * c.D) * sizeof(float);
-            };
-            auto wg_resident = [&](size_t bytes) {
-                int r = (int)(kLdsPerCu / bytes);                        // LDS, and five (four) by its 86 - 108 registers
-                return r > (KQ == 2 ? 5 : 4) ? (KQ == 2 ? 5 : 4) : r;
-            };
-            const bool user_chunk = tune.phase_chunk >= 1;
-            int wgE = pa.chunk, wgNTB = 4;
-            bool wg_ok = pa.chunk <= 4 && pa.chunk * c.D <= 64 && wg_bytes(pa.chunk, 4) <= kLdsPerCu;
-            long chunks = ((long)pa.B + wgE - 1) / wgE;
-            if (wg_ok && !user_chunk && pa.chunk == 4 && 8 * c.D <= 64 && chunks > (long)num_cu * wg_resident(wg_bytes(4, 4)) &&
-                wg_bytes(8, 2) <= kLdsPerCu) {
-                wgE = 8; wgNTB = 2;
-                chunks = ((long)pa.B + 7) / 8;
-            }
-            // five waves, blocks of 80 steps: where that is a block fewer and a CU holds at most two workgroups (with four, the 20 waves did
-            // not fit the CU's SIMDs -- 4 096 episodes 29.7 us against 20.1; "tiles_wpb" 4: the four-wave geometry, for A/B runs)
-            if (wg_ok && wgNTB == 4 && KQ == 2 && (c.T + 79) / 80 < (c.T + 63) / 64 && wg_bytes(wgE, 5) * 4 <= kLdsPerCu &&
-                chunks <= (long)num_cu * 2 && tune.tiles_wpb != 4)
-                wgNTB = 5;
-            const size_t wg_lds = wg_bytes(wgE, wgNTB);
-            const int wg_res = wg_resident(wg_lds);
-            // the pipeline form (k_traj_phase_dmp_pipe: wave 0 only steps, three helper waves build and store around it in blocks of 48
-            // steps, two buffers): chunks of up to four episodes, eight columns, more than one block, and the launch in ONE round of its
-            // resident workgroups ("pipe" 0: the plain workgroup kernel, for A/B runs and tests)
-            const size_t pipe_lds = ((size_t)pa.c_pad + wg_h + pa.t_pad + (size_t)wgE * pa.x_pad + 8 * wgE + 2 * (size_t)wgE * 48 +
-                                     4 * (size_t)wgE * 48 * c.D) * sizeof(float);
-            int pipe_res = (int)(kLdsPerCu / pipe_lds);
-            pipe_res = pipe_res > 4 ? 4 : pipe_res;
-            const bool pipe_form = wg_ok && wgE <= 4 && wgNTB != 2 && KQ == 2 && c.T > 48 && tune.pipe != 0 && pipe_res >= 1 &&
-                                   chunks <= (long)num_cu * pipe_res;
-            // (beyond ONE round of resident workgroups the wave-per-chunk kernel is as fast: cfg3' at 6 144 episodes in chunks of
-            // four 58 vs 61 us)
-            const bool wg = wg_ok && tune.phase_flat != 0 && (tune.phase_flat == 1 || chunks <= (long)num_cu * wg_res);
-            if (wg && pipe_form) {
-                pa.h_pad = wg_h;
-                pa.chunk = wgE;
-                if (pipe_lds > kLdsDefault) {
-                    hipError_t e = c.D == 7 ? allow_full_lds(k_traj_phase_dmp_pipe<2, 7>) : allow_full_lds(k_traj_phase_dmp_pipe<2>);
-                    if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return MPK_EHIP; }
-                }
-                *kernel_name = "k_traj_phase<dmp,wg,pipe>";
-                if (c.D == 7 && tune.pd_generic != 1)
-                    hipLaunchKernelGGL((k_traj_phase_dmp_pipe<2, 7>), dim3((unsigned)chunks), dim3(256), pipe_lds, (hipStream_t)stream, pa);
-                else
-                    hipLaunchKernelGGL(k_traj_phase_dmp_pipe<2>, dim3((unsigned)chunks), dim3(256), pipe_lds, (hipStream_t)stream, pa);
-                MPK_LAUNCH_CHECK();
-                return MPK_OK;
-            }
-            if (wg) {
-                pa.h_pad = wg_h;
-                pa.chunk = wgE;
-                long nb = chunks < (long)num_cu * wg_res ? chunks : (long)num_cu * wg_res;
-                auto gow = [&](auto kern) -> int {
-                    if (wg_lds > kLdsDefault) {
-                        hipError_t e = allow_full_lds(kern);
-                        if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return MPK_EHIP; }
-                    }
-                    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(wgNTB == 5 ? 320 : 256), wg_lds, (hipStream_t)stream, pa);
-                    MPK_LAUNCH_CHECK();
-                    return MPK_OK;
-                };
-                *kernel_name = "k_traj_phase<dmp,wg>";
-                if (wgNTB == 5) return gow(k_traj_phase_dmp_wg<2, 5>);
-                if (wgNTB == 4) return KQ == 2 ? gow(k_traj_phase_dmp_wg<2, 4>) : gow(k_traj_phase_dmp_wg<4, 4>);
-                return KQ == 2 ? gow(k_traj_phase_dmp_wg<2, 2>) : gow(k_traj_phase_dmp_wg<4, 2>);
-            }
-            *kernel_name = "k_traj_phase<dmp>";
-            if (KQ == 2 && c.D == 7 && tune.pd_generic != 1) return go(k_traj_phase_dmp<2, 7>);      // (seven DoF compiled in: the kernel is issue bound)
-            return KQ == 2 ? go(k_traj_phase_dmp<2>) : go(k_traj_phase_dmp<4>);
-        }
     }
+    *kernel_name = r.name;
+    if (r.family == PhaseFamily::DmpWg) {
+        if (r.ntb == 5) return go(k_traj_phase_dmp_wg<2, 5>);
+        if (r.ntb == 4) return r.kq == 2 ? go(k_traj_phase_dmp_wg<2, 4>) : go(k_traj_phase_dmp_wg<4, 4>);
+        return r.kq == 2 ? go(k_traj_phase_dmp_wg<2, 2>) : go(k_traj_phase_dmp_wg<4, 2>);
+    }
+    if (r.family == PhaseFamily::DmpWave) {
+        if (r.dc == 7) return go(k_traj_phase_dmp<2, 7>);
+        return r.kq == 2 ? go(k_traj_phase_dmp<2>) : go(k_traj_phase_dmp<4>);
+    }
+    if (r.mp == MPK_MP_PROMP) {
+        if (r.dc == 7) return r.kq == 1 ? go(k_traj_phase<MPK_MP_PROMP, 1, false, false, 7>) : go(k_traj_phase<MPK_MP_PROMP, 2, false, false, 7>);
+        if (r.kq == 1) return go(k_traj_phase<MPK_MP_PROMP, 1, false>);
+        return r.kq == 2 ? go(k_traj_phase<MPK_MP_PROMP, 2, false>) : go(k_traj_phase<MPK_MP_PROMP, 4, false>);
+    }
+    auto prodmp = [&](auto tl_tag) -> int {
+        constexpr bool TL = decltype(tl_tag)::value;
+        if (r.dc == 7) return r.flat ? go(k_traj_phase<MPK_MP_PRODMP, 2, TL, true, 7>) : go(k_traj_phase<MPK_MP_PRODMP, 2, TL, false, 7>);
+        if (r.flat) return r.kq == 2 ? go(k_traj_phase<MPK_MP_PRODMP, 2, TL, true>) : go(k_traj_phase<MPK_MP_PRODMP, 4, TL, true>);
+        return r.kq == 2 ? go(k_traj_phase<MPK_MP_PRODMP, 2, TL>) : go(k_traj_phase<MPK_MP_PRODMP, 4, TL>);
+    };
+    return r.lds_table ? prodmp(std::true_type()) : prodmp(std::false_type());
+}
+
+static int launch_traj_phase(const DevCfg& c, const PhaseArgs& base, int num_cu, void* stream,
+                             const char** kernel_name, const Tuning& tune) {
+    PhaseArgs pa = base;
+    PhaseRoute r;
+    const int rc = plan_traj_phase(c, num_cu, tune, pa, r);
+    return rc != MPK_OK ? rc : launch_phase_route(pa, r, stream, kernel_name);
 }
 #endif  // MPK_DEVICE_ONLY
 
@@ -1884,15 +1961,7 @@ int launch_traj_rows(const DevCfg& c, const float* params, const float* init_pos
     if (lds > kLdsPerCu) { set_error("trajectory too large for the per-episode kernel's LDS budget"); return MPK_EINVAL; }
     RowArgs ra{c, params, init_pos, init_vel, init_time, init_time_shared, pos, vel, range_flag, B};
     int blocks = B < num_cu * 8 ? B : num_cu * 8;
-    auto go = [&](auto kern) -> int {
-        if (lds > kLdsDefault) {
-            hipError_t e = allow_full_lds(kern);
-            if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return MPK_EHIP; }
-        }
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, (hipStream_t)stream, ra);
-        MPK_LAUNCH_CHECK();
-        return MPK_OK;
-    };
+    auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(256), lds, stream, ra); };
     switch (c.mp_type) {
         case MPK_MP_PRODMP: *kernel_name = "k_traj_rows<prodmp>"; return go(k_traj_rows<MPK_MP_PRODMP>);
         case MPK_MP_PROMP: *kernel_name = "k_traj_rows<promp>"; return go(k_traj_rows<MPK_MP_PROMP>);

@@ -247,15 +247,7 @@ int launch_traj_vjp(const DevCfg& c, const SharedTables& st, const float* g_pos,
         const int per_cu = (int)(kLdsPerCu / lds) < 1 ? 1 : ((int)(kLdsPerCu / lds) > 8 ? 8 : (int)(kLdsPerCu / lds));
         const long units = ((long)va.G + 3) / 4;
         const int blocks = (int)(units < (long)num_cu * per_cu ? units : (long)num_cu * per_cu);
-        auto go = [&](auto kern) -> int {
-            if (lds > kLdsDefault) {
-                hipError_t e = allow_full_lds(kern);
-                if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return MPK_EHIP; }
-            }
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, (hipStream_t)stream, va);
-            MPK_LAUNCH_CHECK();
-            return MPK_OK;
-        };
+        auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(256), lds, stream, va); };
         *kernel_name = c.dmp_resp ? "k_traj_vjp_tile<dmp_resp>" : (promp ? "k_traj_vjp_tile<promp>" : "k_traj_vjp_tile<prodmp>");
         return promp ? go(k_traj_vjp_tile<MPK_MP_PROMP>) : go(k_traj_vjp_tile<MPK_MP_PRODMP>);
     }

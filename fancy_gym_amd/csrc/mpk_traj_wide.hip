@@ -406,15 +406,7 @@ int launch_traj_wide(const DevCfg& c, const SharedTables& st, const float* param
     wa.n_units = (n_groups + 3) / 4;
     const int per_cu = nout * MT <= 16 ? 2 : 1;                           // see the kernel's launch bounds
     const int blocks = wa.n_units < num_cu * per_cu ? wa.n_units : num_cu * per_cu;
-    auto go = [&](auto kern) -> int {
-        if (lds > kLdsDefault) {
-            hipError_t e = allow_full_lds(kern);
-            if (e != hipSuccess) { set_error(std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); return MPK_EHIP; }
-        }
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, (hipStream_t)stream, wa);
-        MPK_LAUNCH_CHECK();
-        return MPK_OK;
-    };
+    auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(256), lds, stream, wa); };
     auto pick = [&](auto mp_tag) -> int {
         constexpr int MPV = decltype(mp_tag)::value;
         switch (MT) {
