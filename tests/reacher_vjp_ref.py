@@ -20,8 +20,27 @@ CASES = {
     "b3_t200_d5_registered": (3, 200, 5, -1000.0, 1000.0, 199, 0.01),
     "b7_t33_d7_clipped": (7, 33, 7, -0.3, 0.45, 20, 0.1),
     "b1000_t200_d5": (1000, 200, 5, -1000.0, 1000.0, 199, 0.01),
+    # appended (the seed and the n_steps rotation depend on a case's index): the DoF counts that are not compiled in -- the run-time-D
+    # instantiations, idle lanes at D = 3 and 6, 64 and 4 episodes per wave at D = 1 and 16 --, a part-full last wave behind a full one
+    # (70 = 64 + 6, 23 = 21 + 2, 19 = 16 + 3), T on a tile boundary, a single tile, a single step (n_steps of 17 above T), and two
+    # horizons whose checkpoints take the launch above 64 KB of LDS
+    "b70_t48_d1": (70, 48, 1, -1000.0, 1000.0, 40, 0.1),
+    "b23_t40_d3": (23, 40, 3, -1000.0, 1000.0, 30, 0.1),
+    "b19_t33_d4_clipped": (19, 33, 4, -0.4, 0.6, 20, 0.1),
+    "b9_t32_d8": (9, 32, 8, -1000.0, 1000.0, 25, 0.1),
+    "b7_t19_d16": (7, 19, 16, -1000.0, 1000.0, 10, 0.1),
+    "b7_t16_d6": (7, 16, 6, -1000.0, 1000.0, 10, 0.1),
+    "b7_t1_d3": (7, 1, 3, -1000.0, 1000.0, 0, 0.1),
+    "b4_t2000_d5_long": (4, 2000, 5, -1000.0, 1000.0, 1990, 0.01),
+    "b4_t2000_d1_long": (4, 2000, 1, -1000.0, 1000.0, 1990, 0.01),
 }
-CLIPPED = ("b5_t35_d5_clipped_all_paid", "b7_t33_d7_clipped")
+CLIPPED = ("b5_t35_d5_clipped_all_paid", "b7_t33_d7_clipped", "b19_t33_d4_clipped")
+ORIGINAL = tuple(CASES)[:5]                                   # the references of these agree to 1e-15
+LONG = ("b4_t2000_d5_long", "b4_t2000_d1_long")               # seconds of autograd each: the motor controller only
+# every case with the motor controller; the first two and the appended short ones with the other two as well
+CTRL_CASES = [(n, "motor") for n in CASES] + \
+             [(n, k) for n in CASES if n in ORIGINAL[:2] or (n not in ORIGINAL and n not in LONG) for k in ("position", "velocity")]
+COMPILED_D = (2, 5, 7)                                        # k_reacher_rollout_vjp<ctrl, D>; every other D: <ctrl>
 SUBSET = 64          # rows of the large case that are compared with the reference
 OUTPUTS = ("g_des_pos", "g_des_vel", "g_q0", "g_qd0", "g_goal")
 
@@ -29,8 +48,14 @@ OUTPUTS = ("g_des_pos", "g_des_vel", "g_q0", "g_qd0", "g_goal")
 @functools.lru_cache(maxsize=None)
 def make_case(name, controller="motor", seed=0):
     """the inputs of one case as a dict of read-only numpy arrays (des_pos / des_vel float32, the rest float64 / int32)"""
-    B, T, D, lo, hi, sbr, dt = CASES[name]
-    rng = np.random.default_rng(1000 * seed + 17 * list(CASES).index(name) + {"motor": 0, "position": 1, "velocity": 2}[controller])
+    index = list(CASES).index(name)
+    return recipe(name, CASES[name], controller, 1000 * seed + 17 * index + {"motor": 0, "position": 1, "velocity": 2}[controller], index)
+
+
+def recipe(name, shape, controller, rng_seed, rot):
+    """the one recipe of every case: ``shape`` as a CASES entry, ``rot`` rotates the executed-step counts"""
+    B, T, D, lo, hi, sbr, dt = shape
+    rng = np.random.default_rng(rng_seed)
     t = np.arange(T)[None, :, None] / T
     amp = rng.uniform(-1.0, 1.0, (B, 1, D))
     freq = rng.uniform(0.5, 2.0, (B, 1, D))
@@ -47,12 +72,31 @@ def make_case(name, controller="motor", seed=0):
     # executed steps T, T - 1, 17, 16, 1, 0 in one batch (rotated per case so that the five-episode cases see all of them between
     # them); a different step offset per episode
     lens = np.array([T, T - 1, 17, 16, 1, 0])
-    c["n_steps"] = np.roll(lens, list(CASES).index(name))[np.arange(B) % 6].astype(np.int32)
+    c["n_steps"] = np.roll(lens, rot)[np.arange(B) % 6].astype(np.int32)
     c["step0"] = (np.arange(B) % 3).astype(np.int32)
     for v in c.values():
         if isinstance(v, np.ndarray):
             v.setflags(write=False)
     return c
+
+
+def at_the_goal():
+    """two one-link episodes under the position controller, every step paid: episode 0 sits on its goal throughout (des_pos = q0 = qd0 =
+    0, goal = (1, 0): q' = 0 and the end effector is (cos 0, sin 0), dist exactly 0) with non-zero upstream gradients, episode 1 is an
+    ordinary row of the recipe"""
+    base = recipe("at_the_goal", (2, 20, 1, -1000.0, 1000.0, 0, 0.1), "position", 777, 0)
+    c = dict(base)
+    for k in ("des_pos", "q0", "qd0", "goal"):
+        c[k] = base[k].copy()
+        c[k][0] = 0.0
+    c["goal"][0] = (1.0, 0.0)
+    c["n_steps"], c["step0"] = np.array([20, 20], np.int32), np.array([0, 0], np.int32)
+    return c
+
+
+def compared(c):
+    """the leading rows of a case that the references cover: all of them up to 256 episodes, SUBSET of a larger case"""
+    return SUBSET if c["B"] > 256 else c["B"]
 
 
 def rows(c, idx):
@@ -161,7 +205,7 @@ def numpy_sweep(c, use=(True, True, True)):
         dist = np.sqrt((diff * diff).sum(1))
         sx = np.cumsum((-sn)[:, ::-1], axis=1)[:, ::-1]           # sum_{l >= j} -sin c_l
         sy = np.cumsum(cs[:, ::-1], axis=1)[:, ::-1]
-        w = np.where(paid, gr / dist, 0.0)
+        w = np.where(paid & (dist > 0.0), gr / np.where(dist > 0.0, dist, 1.0), 0.0)   # (mpk.h: dist = 0 contributes no distance term)
         lq = lq - w[:, None] * (diff[:, :1] * sx + diff[:, 1:] * sy)
         g_goal = g_goal + w[:, None] * diff
         lqd_n = lqd + dt * lq
@@ -190,12 +234,17 @@ def conditions(c):
                 min_dist=float(dist[paid].min()) if paid.any() else np.inf, n_paid=int(paid.sum()))
 
 
+def kernel_name(c):
+    """the instantiation mpk_last_kernel must name for a case"""
+    return f"k_reacher_rollout_vjp<{c['controller']}, {c['D']}>" if c["D"] in COMPILED_D else f"k_reacher_rollout_vjp<{c['controller']}>"
+
+
 @functools.lru_cache(maxsize=None)
 def reference(name, controller="motor", use=(True, True, True)):
     """the autograd gradients of a case (the large case: of its first SUBSET rows), computed once and shared; read-only"""
     c = make_case(name, controller)
-    if c["B"] > SUBSET:
-        c = rows(c, np.arange(SUBSET))
+    if compared(c) < c["B"]:
+        c = rows(c, np.arange(compared(c)))
     ref = autograd(c, use)
     for v in ref.values():
         v.setflags(write=False)

@@ -2,9 +2,10 @@
 mpk_reacher_rollout_vjp, the autograd wiring of TrajectoryEngine.reacher_rollout and BatchedBlackBox.step(differentiable=True) on the GPU.
 
 Yardstick: torch autograd of the float64 CPU restatement of oracle.reacher_rollout (tests/reacher_vjp_ref.py; it agrees with a
-hand-written numpy reverse sweep to delta_ref <= 1e-15, tests/test_reacher_vjp_host.py).  Bounds per output array:
+hand-written numpy reverse sweep to delta_ref <= 1e-15, the cases appended later to <= 5.2e-15, tests/test_reacher_vjp_host.py).  Bounds per
+output array:
   float64 outputs (g_q0, g_qd0, g_goal)   |gpu - ref| <= 1e-12 max|ref|   -- the project's contract for device against host float64
-                                          with cos / sin (README parity row); three orders of magnitude above delta_ref
+                                          with cos / sin (README parity row); two to three orders of magnitude above delta_ref
   float32 outputs (g_des_pos, g_des_vel)  |gpu - ref| <= 2^-24 |ref| + 1e-12 max|ref|   -- one rounding of the float64 result
 Every comparison prints its maximum before it asserts.
 """
@@ -12,6 +13,7 @@ import functools
 import importlib.util
 import itertools
 import os
+import re
 
 import numpy as np
 import pytest
@@ -22,7 +24,7 @@ from . import reacher_vjp_ref as R
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CTRL_CASES = [(n, "motor") for n in R.CASES] + [(n, k) for n in list(R.CASES)[:2] for k in ("position", "velocity")]
+CTRL_CASES = R.CTRL_CASES
 
 
 @functools.lru_cache(maxsize=None)
@@ -75,9 +77,9 @@ def check(name, got, ref):
 def test_against_the_float64_reference(name, controller):
     c = R.make_case(name, controller)
     res, eng = launch(c)
-    assert eng.last_kernel().startswith("k_reacher_rollout_vjp<" + controller)
+    assert eng.last_kernel() == R.kernel_name(c)          # <ctrl, 2 | 5 | 7>, or <ctrl> alone: the run-time-D instantiation
     full = {k: v.cpu().numpy() for k, v in zip(R.OUTPUTS, res)}
-    n = min(c["B"], R.SUBSET)
+    n = R.compared(c)
     check(f"{name} {controller}", {k: v[:n] for k, v in full.items()}, R.reference(name, controller))
     # rows behind the executed steps are exact zeros; an episode that executes nothing passes g_q, g_qd through unchanged
     dead = np.arange(c["T"])[None] >= c["n_steps"][:, None]
@@ -174,7 +176,16 @@ def test_null_inputs_and_outputs():
 
 
 def test_autograd_through_reacher_rollout():
-    c = R.make_case("b7_t33_d7_clipped")
+    autograd_through_reacher_rollout("b7_t33_d7_clipped")
+
+
+def test_autograd_through_reacher_rollout_at_a_run_time_dof_count():
+    assert R.kernel_name(R.make_case("b23_t40_d3")) == "k_reacher_rollout_vjp<motor>"
+    autograd_through_reacher_rollout("b23_t40_d3")
+
+
+def autograd_through_reacher_rollout(name):
+    c = R.make_case(name)
     eng, spec = engine(c["D"], c["T"], c["dt"]), spec_of(c)
     kw = dict(n_steps=dev(c["n_steps"]), step0=dev(c["step0"]), steps_before_reward=c["sbr"])
 
@@ -193,7 +204,7 @@ def test_autograd_through_reacher_rollout():
     assert torch.equal(q, q0) and torch.equal(qd, qd0) and not q.requires_grad and not qd.requires_grad
     g_r = dev(c["g_r"])
     (g_r * rew).sum().backward()
-    assert eng.last_kernel().startswith("k_reacher_rollout_vjp<motor, 7>")
+    assert eng.last_kernel() == R.kernel_name(c)
     bare, _ = launch(c, use=(True, False, False))
     assert torch.equal(dp.grad, bare[0]) and torch.equal(dv.grad, bare[1]) and torch.equal(goal.grad, bare[4])
     assert bool(dp.grad.any()) and bool(goal.grad.any())
@@ -306,9 +317,67 @@ def test_batched_black_box_refusals():
         long.reacher_rollout_vjp(RolloutSpec("motor", 2, plant="double_integrator", dt=0.01), z, z, s, s, torch.zeros((1, 2)), None)
 
 
+@pytest.mark.parametrize("D", [5, 1])
+def test_horizon_limit_is_the_one_the_refusal_names(D):
+    """T = 2000 is accepted (the long cases above); T = 2200 is refused, and the refusal names the largest T the checkpoints fit: a
+    launch at exactly that T -- the whole LDS of a CU but for less than 1 KB -- returns and matches the reference, T + 1 is refused.
+    The limit is taken from the message on purpose: the message, the LDS carve and the launch have to agree."""
+    def zeros(T):
+        z = torch.zeros((2, T, D), device="cuda")
+        s = torch.zeros((2, D), dtype=torch.float64, device="cuda")
+        return z, z, s, s, torch.zeros((2, 2), dtype=torch.float64, device="cuda"), None
+
+    from fancy_gym_amd import RolloutSpec
+    spec = RolloutSpec("motor", D, np.full(D, 0.6), 0.075 + 0.01 * np.arange(D), -1000.0, 1000.0, plant="double_integrator", dt=0.01)
+    with pytest.raises(NotImplementedError, match=r"at most \d+ steps") as info:
+        engine(D, 2200, 0.01).reacher_rollout_vjp(spec, *zeros(2200))
+    limit = int(re.search(r"at most (\d+) steps", str(info.value)).group(1))
+    print(f"D = {D}: the refusal at T = 2200 names at most {limit} steps")
+    assert 2000 <= limit < 2200
+    c = dict(R.recipe(f"limit_d{D}", (2, limit, D, -1000.0, 1000.0, limit - 10, 0.01), "motor", 4242 + D, 0))
+    c["n_steps"] = np.array([limit, 17], np.int32)
+    res, eng = launch(c)
+    assert eng.last_kernel() == R.kernel_name(c)
+    got = {k: v.cpu().numpy() for k, v in zip(R.OUTPUTS, res)}
+    assert all(np.isfinite(v).all() for v in got.values())
+    check(f"T = {limit} D = {D}", got, R.autograd(c))
+    assert not got["g_des_pos"][1, 17:].any() and not got["g_des_vel"][1, 17:].any()
+    cond = R.conditions(c)
+    assert cond["n_paid"] > 0 and cond["min_dist"] > 1e-3 and cond["saturated"] == 0.0 and cond["bound_gap"] >= 1e-9
+    with pytest.raises(NotImplementedError, match=f"at most {limit} steps"):
+        engine(D, limit + 1, 0.01).reacher_rollout_vjp(spec, *zeros(limit + 1))
+
+
+def test_a_paid_step_at_the_goal_contributes_no_distance_term():
+    """include/mpk.h: "A paid step with dist = 0 contributes no distance term".  Episode 0 sits on its goal at every step (one link,
+    position controller, des_pos = q0 = qd0 = 0, goal = (1, 0): q' = 0, the end effector is (cos 0, sin 0)); episode 1 is an ordinary
+    row of the recipe in the same wave (reacher_vjp_ref.at_the_goal).  Reference: numpy_sweep, whose paid weight is 0 where dist == 0
+    (autograd divides by dist)."""
+    c = R.at_the_goal()               # (what the reference gives here: tests/test_reacher_vjp_host.py)
+    ref = R.numpy_sweep(c)
+    # the device forward at the same inputs: reward = -dist - a^2, so an exact 0 says dist == 0 there too (printed, not required)
+    eng = engine(1, 20, 0.1)
+    _, rew = eng.reacher_rollout(spec_of(c), dev(c["des_pos"]), dev(c["des_vel"]), dev(c["q0"]), dev(c["qd0"]), dev(c["goal"]),
+                                 n_steps=dev(c["n_steps"]), step0=dev(c["step0"]), steps_before_reward=0, want_actions=False)
+    print(f"device forward, episode 0: max |reward| = {float(rew[0].abs().max()):.3e} (0: dist is exactly 0 on the device)")
+    res, eng = launch(c)
+    assert eng.last_kernel() == "k_reacher_rollout_vjp<position>"
+    got = {k: v.cpu().numpy() for k, v in zip(R.OUTPUTS, res)}
+    assert all(np.isfinite(v).all() for v in got.values())
+    assert np.array_equal(got["g_goal"][0], np.zeros(2))
+    check("dist = 0", got, ref)
+    for e in (0, 1):
+        check(f"dist = 0, episode {e}", {k: v[e:e + 1] for k, v in got.items()}, {k: v[e:e + 1] for k, v in ref.items()})
+
+
 def test_layout_and_determinism():
-    """input and output pointers 4 and 8 bytes off a 16-byte boundary: the same bits; two runs: the same bits"""
-    c = R.make_case("b5_t35_d5_clipped_all_paid")
+    """input and output pointers 4 and 8 bytes off a 16-byte boundary: the same bits; two runs: the same bits -- at a compiled-in DoF
+    count and at a run-time one with an idle lane and a part-full last wave"""
+    for name in ("b5_t35_d5_clipped_all_paid", "b23_t40_d3"):
+        layout_and_determinism(R.make_case(name))
+
+
+def layout_and_determinism(c):
     B, T, D = c["B"], c["T"], c["D"]
     base, _ = launch(c)
     again, _ = launch(c)
@@ -326,7 +395,8 @@ def test_layout_and_determinism():
             return buf, v
         (_, dp), (_, dv) = shifted(c["des_pos"]), shifted(c["des_vel"])
         (bp, gp), (bv, gv) = shifted(), shifted()
-        res, _ = launch(c, des=(dp, dv), out=[gp, gv, None, None, None])
+        res, eng = launch(c, des=(dp, dv), out=[gp, gv, None, None, None])
+        assert eng.last_kernel() == R.kernel_name(c)
         assert res[0].data_ptr() == gp.data_ptr() and res[1].data_ptr() == gv.data_ptr()
         for a, b in zip(base, res):
             assert torch.equal(a, b), shift

@@ -12,6 +12,7 @@ pays.  Every comparison prints both maxima before it asserts.
 import functools
 import importlib.util
 import os
+import re
 
 import numpy as np
 import pytest
@@ -48,13 +49,46 @@ CONFIGS = {
     "cfg1_promp_199_steps": CFG1[:4] + (3.98, 0.0, "tile"),
     "promp_plain_rbf_50_steps": (O.PhaseCfg("linear", tau=1.0), O.BasisCfg("rbf", num_basis=6), O.TrajCfg("promp", action_dim=5),
                                  0.02, 1.0, 0.0, "tile"),
+    # the tile limit of 16 contraction columns (accumulator rows 12 .. 15 reach real columns) and the first generic shape behind it;
+    # prodmp: num_basis weights + goal + the two boundary columns, promp (rbf): num_basis (COLUMNS below, checked against the oracle)
+    "prodmp_16_columns_7_dof": (O.PhaseCfg("exp", tau=1.0, alpha_phase=3.0), O.BasisCfg("prodmp", num_basis=13, alpha=15),
+                                O.TrajCfg("prodmp", action_dim=7), 0.02, 0.6, 0.0, "tile"),
+    "prodmp_17_columns_7_dof": (O.PhaseCfg("exp", tau=1.0, alpha_phase=3.0), O.BasisCfg("prodmp", num_basis=14, alpha=15),
+                                O.TrajCfg("prodmp", action_dim=7), 0.02, 0.6, 0.0, "generic"),
+    "promp_16_columns_3_dof": (O.PhaseCfg("linear", tau=1.0), O.BasisCfg("rbf", num_basis=16), O.TrajCfg("promp", action_dim=3),
+                               0.02, 0.8, 0.0, "tile"),
+    # DoF counts: 1 (16 episodes per group, no shift), 8 (a full power of two), 11 (one episode per group, five idle tile columns)
+    "prodmp_1_dof": (O.PhaseCfg("exp", tau=1.5, alpha_phase=3.0), O.BasisCfg("prodmp", num_basis=5, alpha=10),
+                     O.TrajCfg("prodmp", action_dim=1), 0.02, 1.0, 0.0, "tile"),
+    "prodmp_8_dof": (O.PhaseCfg("exp", tau=1.5, alpha_phase=3.0), O.BasisCfg("prodmp", num_basis=5, alpha=10),
+                     O.TrajCfg("prodmp", action_dim=8), 0.02, 0.6, 0.0, "tile"),
+    "prodmp_11_dof": (O.PhaseCfg("exp", tau=1.5, alpha_phase=3.0), O.BasisCfg("prodmp", num_basis=5, alpha=10),
+                      O.TrajCfg("prodmp", action_dim=11), 0.02, 0.6, 0.0, "tile"),
 }
+# horizons of 1, 2, 3 and 5 steps: T * D below the alignment head, a single chunk, the odd tail chunk without a paired iteration
+for _D in (3, 7):
+    for _T in (1, 2, 3, 5):
+        CONFIGS[f"prodmp_{_T}_steps_{_D}_dof"] = (O.PhaseCfg("exp", tau=1.5, alpha_phase=3.0), O.BasisCfg("prodmp", num_basis=5, alpha=10),
+                                                  O.TrajCfg("prodmp", action_dim=_D), 0.02, _T * 0.02, 0.0, "tile")
+    for _T in (2, 3, 5):
+        CONFIGS[f"promp_{_T}_steps_{_D}_dof"] = (O.PhaseCfg("linear", tau=1.0), O.BasisCfg("rbf", num_basis=6),
+                                                 O.TrajCfg("promp", action_dim=_D), 0.02, _T * 0.02, 0.0, "tile")
+# contraction columns of the configurations that are named after them
+COLUMNS = {"prodmp_12_columns_16_dof": 12, "prodmp_16_columns_7_dof": 16, "prodmp_17_columns_7_dof": 17, "promp_16_columns_3_dof": 16}
+# cfg2's handle (7 DoF, two episodes per group) around the horizon at which its gradient images no longer fit a CU's LDS
+LDS_BOUNDARY = {f"cfg2_prodmp_{_T}_steps": CFG2[:4] + (_T * 0.02, 0.0, _route) for _T, _route in ((277, "tile"), (280, "tile"), (281, "generic"))}
+# ... and cfg2 at 25 steps (an odd T * D: every episode's rows start at another alignment) for the batch that wraps around the grid
+OTHER = dict(LDS_BOUNDARY, cfg2_prodmp_25_steps=CFG2[:4] + (0.5, 0.0, "tile"))
+
+
+def config(name):
+    return CONFIGS[name] if name in CONFIGS else OTHER[name]
 
 
 @functools.lru_cache(maxsize=None)
 def jacobian(name):
     """float64 J [2, T, D, n] over the n = P + 2 D inputs of ONE episode (the map is the same for every episode) and (P, D, T)"""
-    pc, bc, tc, dt, duration, init_time, _ = CONFIGS[name]
+    pc, bc, tc, dt, duration, init_time, _ = config(name)
     P, D = O.num_params(pc, bc, tc), tc.action_dim
     n = P + 2 * D
     x = np.zeros((n + 1, n))
@@ -103,7 +137,7 @@ def check(name, got, ref, e32, what):
 
 
 def engine_for(name):
-    pc, bc, tc, dt, duration, _, _ = CONFIGS[name]
+    pc, bc, tc, dt, duration, _, _ = config(name)
     return make_engine(pc, bc, tc, dt, duration)
 
 
@@ -120,11 +154,89 @@ def test_vjp_matches_the_float64_jacobian(name, B):
     gp, gv = grads(name, B, seed=B)
     got = eng.trajectory_vjp(dev(gp), dev(gv), init_time)
     torch.cuda.synchronize()
-    assert eng.last_kernel().startswith(f"k_traj_vjp_{route}<"), eng.last_kernel()
-    if "dmp_response" in name:
-        assert "dmp_resp" in eng.last_kernel()
+    mp = "dmp_resp" if "dmp_response" in name else config(name)[2].trajectory_generator_type
+    assert eng.last_kernel() == f"k_traj_vjp_{route}<{mp}>", eng.last_kernel()
     ref, e32 = reference(name, gp, gv)
     check(name, got, ref, e32, f"{name} B={B}")
+    steps = re.search(r"_(\d+)_steps", name)
+    assert steps is None or eng.num_steps == int(steps.group(1))
+    if name in COLUMNS:
+        # the columns a DoF contracts: the inputs its trajectory depends on (prodmp: its parameters, init_pos, init_vel)
+        J, P, D, _ = jacobian(name)
+        used = np.abs(J).sum(axis=(0, 1)).astype(bool)                      # [D, n]
+        assert used[0].sum() == COLUMNS[name] and (used.sum(axis=1) == COLUMNS[name]).all()
+
+
+def test_promp_with_one_step_is_refused():
+    eng = make_engine(O.PhaseCfg("linear", tau=1.0), O.BasisCfg("rbf", num_basis=6), O.TrajCfg("promp", action_dim=3), 0.02, 0.02)
+    assert eng.num_steps == 1
+    g = torch.ones((2, 1, 3), device="cuda")
+    with pytest.raises(ValueError, match="promp needs at least two time steps"):
+        eng.trajectory_vjp(g, g)
+
+
+def tile_lds_bytes(T, D):
+    """launch_traj_vjp's arithmetic: the transposed tables [2][TP][16] and, per wave, the (pos, vel) images of a group's episodes"""
+    sh = int(np.ceil(np.log2(D))) if D > 1 else 0
+    ntw, tp = 16 >> sh, (T + 3) // 4 * 4
+    stride = (tp * D + 3 + 31) // 32 * 32 + (0 if ntw == 1 else max(32 // ntw, 4))
+    return (2 * tp * 16 + 4 * 2 * ntw * stride) * 4, tp, stride
+
+
+@pytest.mark.parametrize("B", [1, 3])
+def test_lds_fallback_boundary(B):
+    """a 7-DoF handle: T = 280 takes a CU's whole LDS (163 840 bytes) and is still the tile route, T = 281 is the generic route"""
+    assert tile_lds_bytes(280, 7) == (163840, 280, 2000) and tile_lds_bytes(277, 7)[0] == 163840
+    assert tile_lds_bytes(276, 7)[0] < 163840 < tile_lds_bytes(281, 7)[0]
+    kernels = []
+    for name in LDS_BOUNDARY:
+        eng = engine_for(name)
+        assert eng.num_steps == int(name.split("_")[2])
+        gp, gv = grads(name, B, seed=B)
+        got = eng.trajectory_vjp(dev(gp), dev(gv), 0.0)
+        torch.cuda.synchronize()
+        kernels.append(eng.last_kernel())
+        ref, e32 = reference(name, gp, gv)
+        check(name, got, ref, e32, f"{name} B={B}")
+    assert kernels == ["k_traj_vjp_tile<prodmp>", "k_traj_vjp_tile<prodmp>", "k_traj_vjp_generic<prodmp>"], kernels
+
+
+# ---- 1b. batches beyond the grid caps: the grid-stride loops wrap ------------------------------------------------------------------------
+@pytest.mark.parametrize("name,per_cu,extra,kernel", [
+    ("prodmp_12_columns_16_dof", 32, 809, "k_traj_vjp_tile<prodmp>"),       # one episode per group: four waves x at most 8 per CU
+    ("cfg2_prodmp_25_steps", 64, 117, "k_traj_vjp_tile<prodmp>"),           # two per group; odd: the last group after the wrap part full
+    ("promp_wide_20_basis", 8, 77, "k_traj_vjp_generic<promp>"),            # one episode per workgroup, at most 8 per CU
+])
+def test_batch_wraps_around_the_grid(name, per_cu, extra, kernel):
+    """more episodes than the grid covers in one pass (the launchers cap it at 8 workgroups per CU whatever the LDS allows): every row
+    against J^T g, and the bits of the same gradients launched in slices of 64 episodes -- an episode's reduction never leaves its
+    tile column (its thread), so the grouping cannot change them -- and of a second identical launch"""
+    B = per_cu * torch.cuda.get_device_properties(0).multi_processor_count + extra
+    eng = engine_for(name)
+    gp_h, gv_h = grads(name, B, seed=11)
+    gp, gv = dev(gp_h), dev(gv_h)
+    big = eng.trajectory_vjp(gp, gv, 0.0)
+    torch.cuda.synchronize()
+    assert eng.last_kernel() == kernel
+    ref, e32 = reference(name, gp_h, gv_h)
+    check(name, big, ref, e32, f"{name} B={B}")
+    again = eng.trajectory_vjp(gp, gv, 0.0)
+    for x, y in zip(big, again):
+        assert torch.equal(x.view(torch.int32), y.view(torch.int32))
+    parts = []
+    for i, lo in enumerate(range(0, B, 64)):
+        own = []
+        for g in (gp, gv):                      # storage of its own, 4, 8 or 12 bytes past a 16-byte boundary
+            part = g[lo:lo + 64]
+            buf = torch.empty(part.numel() + 4, device="cuda")
+            view = buf[1 + i % 3:1 + i % 3 + part.numel()].view(part.shape)
+            view.copy_(part)
+            assert view.data_ptr() % 16 == 4 * (1 + i % 3) and view.is_contiguous()
+            own.append(view)
+        parts.append(eng.trajectory_vjp(own[0], own[1], 0.0))
+        assert eng.last_kernel() == kernel
+    for j, x in enumerate(big):
+        assert torch.equal(x.view(torch.int32), torch.cat([p[j] for p in parts]).view(torch.int32)), j
 
 
 # ---- 2. adjoint identity against the forward kernels -----------------------------------------------------------------------------------
