@@ -915,38 +915,54 @@ static int fill_gate(const Handle* h, const mpk_validity_gate* g, GateDev* out) 
     return MPK_OK;
 }
 
-// one k_phase_fused launch (per-episode phase): the common tail of the four fused entry points
-static int phase_fused_common(Handle* h, const float* params, const float* init_pos, const float* init_vel, double init_time_shared,
-                              float* pos, float* vel, float* actions, const RolloutDev& rd, double* q, double* qd,
-                              const int32_t* n_steps, const ReplanDev* rp, const GateDev* gate, double* ret, int32_t* seg_out,
-                              int32_t B, void* stream) {
-    if (!params || !init_pos || !init_vel) { set_error("NULL buffer"); return MPK_EINVAL; }
-    {
-        const int fr = pending_ring_fault(h);
-        if (fr != MPK_OK) return fr;
-    }
-    return launch_phase_fused(h->dev, params, init_pos, init_vel, (float)init_time_shared, pos, vel, actions, rd, q, qd, n_steps, rp,
-                              gate, ret, seg_out, h->d_flag, B, h->num_cu, stream, &h->last_kernel, effective_tuning(h), h->d_fault);
+// the replanning state of a call, checked and copied; init_pos / init_vel: the call's boundary inputs, which the gather must not overwrite
+// (nullptr: the call has none)
+static int fill_replan(const mpk_replan_state* st, const float* init_pos, const float* init_vel, ReplanDev* rp) {
+    if (!st || !st->traj_steps || !st->plan_steps || !st->done || !st->seg_len) { set_error("NULL replanning state"); return MPK_EINVAL; }
+    if ((st->cond_pos == nullptr) != (st->cond_vel == nullptr)) { set_error("cond_pos and cond_vel go together"); return MPK_EINVAL; }
+    if (st->every < 1 || st->horizon < 1) { set_error("every and horizon must be >= 1"); return MPK_EINVAL; }
+    if (st->cond_pos && (st->cond_pos == init_pos || st->cond_vel == init_vel)) { set_error("cond_pos / cond_vel must not alias init_pos / init_vel"); return MPK_EINVAL; }
+    rp->traj_steps = st->traj_steps; rp->plan_steps = st->plan_steps; rp->done = st->done; rp->seg_len = st->seg_len;
+    rp->done_out = st->done_out; rp->cond_pos = st->cond_pos; rp->cond_vel = st->cond_vel;
+    rp->every = st->every; rp->max_planning_times = st->max_planning_times; rp->horizon = st->horizon;
+    return MPK_OK;
 }
 
-static int traj_common(Handle* h, const float* params, const float* init_pos, const float* init_vel,
-                       const float* init_time, double init_time_shared, float* pos, float* vel, float* actions,
-                       const RolloutDev* rd, const double* c_pos, const double* c_vel, int32_t B, void* stream,
-                       double* q_state = nullptr, double* qd_state = nullptr, const int32_t* n_steps = nullptr,
-                       const ReplanDev* rp = nullptr, const GateDev* gate = nullptr) {
-    if (B < 0) { set_error("B must be >= 0"); return MPK_EINVAL; }
-    if (B == 0 || h->dev.D == 0) return MPK_OK;     // empty batch: nothing to do (buffers may be NULL)
-    if (!params || !init_pos || !init_vel || !pos || !vel) { set_error("NULL buffer"); return MPK_EINVAL; }
+// where a launch of this handle runs; the kernel it names goes to mpk_last_kernel (the ring's ticket: ticket_slot, where a route can take it)
+static LaunchSite launch_site(Handle* h, const Tuning& tune, void* stream) {
+    LaunchSite at;
+    at.num_cu = h->num_cu; at.tune = tune; at.stream = stream; at.kernel_name = &h->last_kernel;
+    at.fault = h->d_fault; at.range_flag = h->d_flag;
+    return at;
+}
+
+// mpk_last_kernel for a launch whose name needs the handle's buffer: a DMP handle's response launch (resp) ran ProDMP's kernel and says so
+static void report_kernel(Handle* h, const char* name, bool resp) {
+    h->kernel_name_buf = name;
+    const size_t at = resp ? h->kernel_name_buf.find("prodmp") : std::string::npos;
+    if (at != std::string::npos) h->kernel_name_buf.replace(at, 6, "dmp_resp");
+    h->last_kernel = h->kernel_name_buf.c_str();
+}
+
+// one k_phase_fused launch (per-episode phase): the common tail of the four fused entry points
+static int phase_fused_common(Handle* h, const TrajRequest& q, void* stream) {
+    if (!q.params || !q.init_pos || !q.init_vel) { set_error("NULL buffer"); return MPK_EINVAL; }
+    if (const int fr = pending_ring_fault(h); fr != MPK_OK) return fr;
+    return launch_phase_fused(h->dev, q, launch_site(h, effective_tuning(h), stream));
+}
+
+static int traj_common(Handle* h, const TrajRequest& req, void* stream) {
+    if (req.B < 0) { set_error("B must be >= 0"); return MPK_EINVAL; }
+    if (req.B == 0 || h->dev.D == 0) return MPK_OK;     // empty batch: nothing to do (buffers may be NULL)
+    if (!req.params || !req.init_pos || !req.init_vel || !req.pos || !req.vel) { set_error("NULL buffer"); return MPK_EINVAL; }
     MPK_ON_DEVICE(h->cfg.device);
-    {
-        const int fr = pending_ring_fault(h);
-        if (fr != MPK_OK) return fr;
-    }
-    const Tuning tune = effective_tuning(h);
+    if (const int fr = pending_ring_fault(h); fr != MPK_OK) return fr;
+    TrajRequest q = req;
+    LaunchSite at = launch_site(h, effective_tuning(h), stream);
     if (h->cfg.mp_type == MPK_MP_DMP && h->cfg.dmp_first_sample == MPK_DMP_FIRST_IS_STEP) {
         // the boundary state advanced by one Euler step (k_dmp_prestep) is what the trajectory kernels start from.
         // The scratch grows with the largest batch seen: the first call with a larger batch allocates (include/mpk.h).
-        const size_t need = (size_t)B * h->dev.D;
+        const size_t need = (size_t)q.B * h->dev.D;
         if (need > h->pre_cap) {
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
             if (hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
@@ -961,58 +977,77 @@ static int traj_common(Handle* h, const float* params, const float* init_pos, co
         }
         float* p1 = h->d_pre;
         float* v1 = h->d_pre + h->pre_cap;
-        int rc = launch_dmp_prestep(h->dev, params, init_pos, init_vel, init_time, (float)init_time_shared, p1, v1, B, stream);
+        int rc = launch_dmp_prestep(h->dev, q, p1, v1, stream);
         if (rc != MPK_OK) return rc;
-        init_pos = p1; init_vel = v1;
+        q.init_pos = p1; q.init_vel = v1;
     }
-    if (shared_phase(h, init_time) && wide_capable(h) && !actions && !q_state && !rp && traj_wide_fits(h->dev)) {
+    if (shared_phase(h, q.init_time) && wide_capable(h) && !q.actions && !q.q_state && !q.rp && traj_wide_fits(h->dev)) {
         SharedTables st;
-        int rc = get_shared(h, (float)init_time_shared, stream, &st);
+        int rc = get_shared(h, q.init_time_shared, stream, &st);
         if (rc != MPK_OK) return rc;
-        rc = launch_traj_wide(h->dev, st, params, init_pos, init_vel, pos, vel, B, h->num_cu, stream, &h->last_kernel);
+        rc = launch_traj_wide(h->dev, st, q, at);
         if (rc != MPK_ENOTIMPL) return rc;      // horizons beyond one row-tile block (promp / dmp): per-episode kernels
     }
-    if (dmp_response(h, init_time, tune)) {
+    if (dmp_response(h, q.init_time, at.tune)) {
         // DMP as a two-output contraction of the Euler map's response rows (k_build_shared): every shared-phase kernel family of
         // ProDMP, fused actions and the closed loop included
         SharedTables st;
-        int rc = get_shared(h, (float)init_time_shared, stream, &st, true);
+        int rc = get_shared(h, q.init_time_shared, stream, &st, true);
         if (rc != MPK_OK) return rc;
-        unsigned* ticket = ticket_slot(h, stream);
         const char* name = "";
-        rc = launch_traj_shared(h->dev_resp, st, params, init_pos, init_vel, pos, vel, actions, rd, c_pos, c_vel,
-                                q_state, qd_state, n_steps, B, h->num_cu, stream, &name, tune, rp, ticket, h->d_fault, gate);
-        if (rc == MPK_OK) {
-            h->kernel_name_buf = name;
-            const size_t at = h->kernel_name_buf.find("prodmp");
-            if (at != std::string::npos) h->kernel_name_buf.replace(at, 6, "dmp_resp");
-            h->last_kernel = h->kernel_name_buf.c_str();
-        }
+        LaunchSite resp = at;
+        resp.ticket = ticket_slot(h, stream); resp.kernel_name = &name;
+        rc = launch_traj_shared(h->dev_resp, st, q, resp);
+        if (rc == MPK_OK) report_kernel(h, name, true);
         // (horizons beyond the episode-major kernels' LDS: the serial kernels below; fused entry points fall back to two launches)
-        if (rc != MPK_ENOTIMPL || actions) return rc;
+        if (rc != MPK_ENOTIMPL || q.actions) return rc;
     }
-    if (shared_phase(h, init_time) && mfma_capable(h)) {
+    if (shared_phase(h, q.init_time) && mfma_capable(h)) {
         SharedTables st;
-        int rc = get_shared(h, (float)init_time_shared, stream, &st);
+        int rc = get_shared(h, q.init_time_shared, stream, &st);
         if (rc != MPK_OK) return rc;
-        unsigned* ticket = ticket_slot(h, stream);
-        rc = launch_traj_shared(h->dev, st, params, init_pos, init_vel, pos, vel, actions, rd, c_pos, c_vel,
-                                q_state, qd_state, n_steps, B, h->num_cu, stream, &h->last_kernel, tune, rp, ticket, h->d_fault, gate);
+        at.ticket = ticket_slot(h, stream);
+        rc = launch_traj_shared(h->dev, st, q, at);
         // horizons whose basis tables do not fit the episode-major kernel's LDS: the per-episode kernels below (dmp) or,
         // for fused actions / rollouts, the caller's two-launch path
-        if (rc != MPK_ENOTIMPL || actions) return rc;
+        if (rc != MPK_ENOTIMPL || q.actions) return rc;
     }
-    if (actions) { set_error("fused actions need a shared-phase configuration with D <= 16 and <= 16 basis columns"); return MPK_ENOTIMPL; }
-    return launch_traj_rows(h->dev, params, init_pos, init_vel, init_time, (float)init_time_shared, pos, vel,
-                            h->d_flag, B, h->num_cu, stream, &h->last_kernel, tune);
+    if (q.actions) { set_error("fused actions need a shared-phase configuration with D <= 16 and <= 16 basis columns"); return MPK_ENOTIMPL; }
+    return launch_traj_rows(h->dev, q, at);
+}
+
+// the one-launch form of a request with a controller: the shared-phase kernels, or k_phase_fused for a learned phase; MPK_ENOTIMPL where
+// neither takes it -- then trajectory_only(q) and the separate launches give the same result
+static int try_one_launch(Handle* h, const TrajRequest& q, void* stream) {
+    if (fused_capable(h)) return traj_common(h, q, stream);
+    if (fused_phase_capable(h) && q.B > 0 && q.pos && q.vel) return phase_fused_common(h, q, stream);
+    return MPK_ENOTIMPL;
+}
+
+// the same request without controller, plant state, replanning state and gate: what the separate launches start with
+static TrajRequest trajectory_only(const TrajRequest& q) {
+    TrajRequest t = q;
+    t.actions = nullptr; t.rc = nullptr; t.c_pos = t.c_vel = nullptr; t.q_state = t.qd_state = nullptr; t.n_steps = nullptr;
+    t.rp = nullptr; t.gate = nullptr;
+    return t;
+}
+
+// what every trajectory entry point asks for
+static TrajRequest traj_request(const float* params, const float* init_pos, const float* init_vel, double init_time_shared, float* pos,
+                                float* vel, int32_t B) {
+    TrajRequest q;
+    q.params = params; q.init_pos = init_pos; q.init_vel = init_vel; q.init_time_shared = (float)init_time_shared;
+    q.pos = pos; q.vel = vel; q.B = B;
+    return q;
 }
 
 int mpk_trajectory(mpk_handle hh, const float* params, const float* init_pos, const float* init_vel,
                    const float* init_time, double init_time_shared, float* pos, float* vel, int32_t B,
                    void* stream) {
     if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
-    return traj_common(reinterpret_cast<Handle*>(hh), params, init_pos, init_vel, init_time, init_time_shared,
-                       pos, vel, nullptr, nullptr, nullptr, nullptr, B, stream);
+    TrajRequest q = traj_request(params, init_pos, init_vel, init_time_shared, pos, vel, B);
+    q.init_time = init_time;
+    return traj_common(reinterpret_cast<Handle*>(hh), q, stream);
 }
 
 // the transpose of mpk_trajectory's shared-phase map: same tables (built or reused for (init_time_shared, T) exactly as there), one launch
@@ -1054,19 +1089,13 @@ int mpk_trajectory_actions(mpk_handle hh, const float* params, const float* init
     if (r != MPK_OK) return r;
     MPK_ON_DEVICE(h->cfg.device);
     if (rd.plant_type != MPK_PLANT_STATIC) { set_error("mpk_trajectory_actions tracks a frozen state (MPK_PLANT_STATIC); use mpk_trajectory_rollout"); return MPK_EINVAL; }
-    if (fused_capable(h)) {
-        r = traj_common(h, params, init_pos, init_vel, nullptr, init_time_shared, pos, vel, actions, &rd, c_pos, c_vel,
-                        B, stream);
-        if (r != MPK_ENOTIMPL) return r;
-    } else if (fused_phase_capable(h) && B > 0 && pos && vel) {
-        r = phase_fused_common(h, params, init_pos, init_vel, init_time_shared, pos, vel, actions, rd, const_cast<double*>(c_pos),
-                               const_cast<double*>(c_vel), nullptr, nullptr, nullptr, nullptr, nullptr, B, stream);
-        if (r != MPK_ENOTIMPL) return r;
-    }
+    TrajRequest q = traj_request(params, init_pos, init_vel, init_time_shared, pos, vel, B);
+    q.actions = actions; q.rc = &rd; q.c_pos = c_pos; q.c_vel = c_vel;
+    r = try_one_launch(h, q, stream);
+    if (r != MPK_ENOTIMPL) return r;
     // what the fused kernels do not cover (dmp with a learned phase, > 16 DoF or basis columns): same result
     // from two launches
-    r = traj_common(h, params, init_pos, init_vel, nullptr, init_time_shared, pos, vel, nullptr, nullptr, nullptr,
-                    nullptr, B, stream);
+    r = traj_common(h, trajectory_only(q), stream);
     if (r != MPK_OK) return r;
     return launch_pd_rollout(rd, h->dev.D, pos, vel, const_cast<double*>(c_pos), const_cast<double*>(c_vel), nullptr,
                              actions, B, h->dev.T, stream, effective_tuning(h), h->d_fault);
@@ -1084,18 +1113,12 @@ int mpk_trajectory_rollout(mpk_handle hh, const float* params, const float* init
     if (r != MPK_OK) return r;
     MPK_ON_DEVICE(h->cfg.device);
     if (rd.plant_type != MPK_PLANT_DOUBLE_INTEGRATOR) { set_error("mpk_trajectory_rollout integrates MPK_PLANT_DOUBLE_INTEGRATOR; for a frozen state use mpk_trajectory_actions"); return MPK_EINVAL; }
-    if (fused_capable(h)) {
-        r = traj_common(h, params, init_pos, init_vel, nullptr, init_time_shared, pos, vel, actions, &rd, nullptr,
-                        nullptr, B, stream, q, qd, n_steps);
-        if (r != MPK_ENOTIMPL) return r;
-    } else if (fused_phase_capable(h) && B > 0 && pos && vel) {
-        r = phase_fused_common(h, params, init_pos, init_vel, init_time_shared, pos, vel, actions, rd, q, qd, n_steps, nullptr, nullptr,
-                               nullptr, nullptr, B, stream);
-        if (r != MPK_ENOTIMPL) return r;
-    }
+    TrajRequest req = traj_request(params, init_pos, init_vel, init_time_shared, pos, vel, B);
+    req.actions = actions; req.rc = &rd; req.q_state = q; req.qd_state = qd; req.n_steps = n_steps;
+    r = try_one_launch(h, req, stream);
+    if (r != MPK_ENOTIMPL) return r;
     // dmp with a learned phase, horizons beyond the fused kernel's LDS tables, > 16 DoF or basis columns: trajectory kernel + rollout kernel, same result
-    r = traj_common(h, params, init_pos, init_vel, nullptr, init_time_shared, pos, vel, nullptr, nullptr, nullptr,
-                    nullptr, B, stream);
+    r = traj_common(h, trajectory_only(req), stream);
     if (r != MPK_OK) return r;
     return launch_pd_rollout(rd, h->dev.D, pos, vel, q, qd, n_steps, actions, B, h->dev.T, stream, effective_tuning(h), h->d_fault);
 }
@@ -1108,13 +1131,12 @@ int mpk_replan_step_gated(mpk_handle hh, const float* params, const float* init_
     Handle* h = reinterpret_cast<Handle*>(hh);
     if (B < 0) { set_error("B must be >= 0"); return MPK_EINVAL; }
     if (B == 0) return MPK_OK;
-    if (!st || !st->traj_steps || !st->plan_steps || !st->done || !st->seg_len) { set_error("NULL replanning state"); return MPK_EINVAL; }
-    if ((st->cond_pos == nullptr) != (st->cond_vel == nullptr)) { set_error("cond_pos and cond_vel go together"); return MPK_EINVAL; }
-    if (st->every < 1 || st->horizon < 1) { set_error("every and horizon must be >= 1"); return MPK_EINVAL; }
+    ReplanDev rp;
+    int r = fill_replan(st, init_pos, init_vel, &rp);
+    if (r != MPK_OK) return r;
     if (!actions || !q || !qd) { set_error("NULL buffer"); return MPK_EINVAL; }
-    if (st->cond_pos && (st->cond_pos == init_pos || st->cond_vel == init_vel)) { set_error("cond_pos / cond_vel must not alias init_pos / init_vel"); return MPK_EINVAL; }
     RolloutDev rd;
-    int r = fill_rollout(h, rc, &rd);
+    r = fill_rollout(h, rc, &rd);
     if (r != MPK_OK) return r;
     if (rd.plant_type != MPK_PLANT_DOUBLE_INTEGRATOR) { set_error("mpk_replan_step integrates MPK_PLANT_DOUBLE_INTEGRATOR"); return MPK_EINVAL; }
     GateDev gd;
@@ -1123,24 +1145,14 @@ int mpk_replan_step_gated(mpk_handle hh, const float* params, const float* init_
         if (r != MPK_OK) return r;
     }
     MPK_ON_DEVICE(h->cfg.device);
-    ReplanDev rp;
-    rp.traj_steps = st->traj_steps; rp.plan_steps = st->plan_steps; rp.done = st->done; rp.seg_len = st->seg_len;
-    rp.done_out = st->done_out; rp.cond_pos = st->cond_pos; rp.cond_vel = st->cond_vel;
-    rp.every = st->every; rp.max_planning_times = st->max_planning_times; rp.horizon = st->horizon;
-    if (fused_capable(h)) {
-        // ONE launch: integer state, trajectory, (validity gate,) controller + plant, condition gather
-        r = traj_common(h, params, init_pos, init_vel, nullptr, init_time_shared, pos, vel, actions, &rd, nullptr,
-                        nullptr, B, stream, q, qd, nullptr, &rp, gate ? &gd : nullptr);
-        if (r != MPK_ENOTIMPL) return r;
-    } else if (fused_phase_capable(h) && pos && vel) {
-        r = phase_fused_common(h, params, init_pos, init_vel, init_time_shared, pos, vel, actions, rd, q, qd, nullptr, &rp,
-                               gate ? &gd : nullptr, nullptr, nullptr, B, stream);
-        if (r != MPK_ENOTIMPL) return r;
-    }
+    // ONE launch: integer state, trajectory, (validity gate,) controller + plant, condition gather
+    TrajRequest req = traj_request(params, init_pos, init_vel, init_time_shared, pos, vel, B);
+    req.actions = actions; req.rc = &rd; req.q_state = q; req.qd_state = qd; req.rp = &rp; req.gate = gate ? &gd : nullptr;
+    r = try_one_launch(h, req, stream);
+    if (r != MPK_ENOTIMPL) return r;
     // what the fused kernels do not cover (dmp with a learned phase, long horizons, > 16 DoF or basis columns): the same
     // result from the separate kernels
-    r = traj_common(h, params, init_pos, init_vel, nullptr, init_time_shared, pos, vel, nullptr, nullptr, nullptr,
-                    nullptr, B, stream);
+    r = traj_common(h, trajectory_only(req), stream);
     if (r != MPK_OK) return r;
     if (gate) {
         // the plan is judged first; an invalid one finishes its episode (done |= !valid) before the integer rule looks at it
@@ -1179,13 +1191,8 @@ int mpk_episode_return_gated(mpk_handle hh, const float* params, const float* in
     if (reward == MPK_REWARD_SIMPLE_REACHER && !goal) { set_error("the reacher reward needs goal [B, 2]"); return MPK_EINVAL; }
     ReplanDev rp;
     if (st) {
-        if (!st->traj_steps || !st->plan_steps || !st->done || !st->seg_len) { set_error("NULL replanning state"); return MPK_EINVAL; }
-        if ((st->cond_pos == nullptr) != (st->cond_vel == nullptr)) { set_error("cond_pos and cond_vel go together"); return MPK_EINVAL; }
-        if (st->every < 1 || st->horizon < 1) { set_error("every and horizon must be >= 1"); return MPK_EINVAL; }
-        if (st->cond_pos && (st->cond_pos == init_pos || st->cond_vel == init_vel)) { set_error("cond_pos / cond_vel must not alias init_pos / init_vel"); return MPK_EINVAL; }
-        rp.traj_steps = st->traj_steps; rp.plan_steps = st->plan_steps; rp.done = st->done; rp.seg_len = st->seg_len;
-        rp.done_out = st->done_out; rp.cond_pos = st->cond_pos; rp.cond_vel = st->cond_vel;
-        rp.every = st->every; rp.max_planning_times = st->max_planning_times; rp.horizon = st->horizon;
+        const int rr = fill_replan(st, init_pos, init_vel, &rp);
+        if (rr != MPK_OK) return rr;
     }
     RolloutDev rd;
     int r = fill_rollout(h, rc, &rd);
@@ -1197,38 +1204,32 @@ int mpk_episode_return_gated(mpk_handle hh, const float* params, const float* in
         if (r != MPK_OK) return r;
     }
     MPK_ON_DEVICE(h->cfg.device);
-    {
-        const int fr = pending_ring_fault(h);
-        if (fr != MPK_OK) return fr;
-    }
+    if (const int fr = pending_ring_fault(h); fr != MPK_OK) return fr;
+    // (no per-step outputs; with a replanning state the steps come from its rule)
+    TrajRequest req = traj_request(params, init_pos, init_vel, init_time_shared, nullptr, nullptr, B);
+    req.rc = &rd; req.q_state = q; req.qd_state = qd; req.n_steps = st ? nullptr : n_steps; req.rp = st ? &rp : nullptr;
+    req.gate = gate ? &gd : nullptr;
+    req.ep.reward = reward; req.ep.goal = goal; req.ep.step0 = step0; req.ep.steps_before_reward = steps_before_reward; req.ep.agg = agg;
+    req.ep.ret = ret; req.ep.seg_out = seg_out;
     if (fused_phase_capable(h)) {
         // learned tau / delay: k_phase_fused without stores (no device reward for these families: include/mpk.h)
         if (reward != MPK_REWARD_NONE) { set_error("mpk_episode_return: a per-episode phase has no device reward"); return MPK_ENOTIMPL; }
-        return phase_fused_common(h, params, init_pos, init_vel, init_time_shared, nullptr, nullptr, nullptr, rd, q, qd,
-                                  st ? nullptr : n_steps, st ? &rp : nullptr, gate ? &gd : nullptr, ret, seg_out, B, stream);
+        return phase_fused_common(h, req, stream);
     }
     if (!fused_capable(h)) { set_error("mpk_episode_return needs a shared phase with <= 16 contraction columns and DoF, or a learned phase with <= 8 columns"); return MPK_ENOTIMPL; }
-    const Tuning tune = effective_tuning(h);
     if (h->cfg.mp_type == MPK_MP_DMP && h->cfg.dmp_first_sample == MPK_DMP_FIRST_IS_STEP) {
         set_error("mpk_episode_return: MPK_DMP_FIRST_IS_STEP handles take the separate launches");
         return MPK_ENOTIMPL;
     }
     const bool resp = h->cfg.mp_type == MPK_MP_DMP;
     SharedTables stt;
-    r = get_shared(h, (float)init_time_shared, stream, &stt, resp);
+    r = get_shared(h, req.init_time_shared, stream, &stt, resp);
     if (r != MPK_OK) return r;
     const char* name = "";
-    r = launch_episode_return(resp ? h->dev_resp : h->dev, stt, params, init_pos, init_vel, rd, q, qd, st ? nullptr : n_steps,
-                              st ? &rp : nullptr, reward, goal, step0, steps_before_reward, agg, ret, seg_out, B, h->num_cu, stream,
-                              &name, tune, gate ? &gd : nullptr);
-    if (r == MPK_OK) {
-        h->kernel_name_buf = name;
-        if (resp) {
-            const size_t at = h->kernel_name_buf.find("prodmp");
-            if (at != std::string::npos) h->kernel_name_buf.replace(at, 6, "dmp_resp");
-        }
-        h->last_kernel = h->kernel_name_buf.c_str();
-    }
+    LaunchSite at = launch_site(h, effective_tuning(h), stream);
+    at.kernel_name = &name;
+    r = launch_episode_return(resp ? h->dev_resp : h->dev, stt, req, at);
+    if (r == MPK_OK) report_kernel(h, name, resp);
     return r;
 }
 
@@ -1365,12 +1366,8 @@ int mpk_hole_reacher_rollout2(mpk_handle hh, const mpk_rollout_cfg* rc, const fl
     const bool need_vel = rc->controller_type != MPK_CTRL_POSITION || (st && st->cond_pos);
     if ((need_pos && !des_pos) || (need_vel && !des_vel) || !q || !qd || !hole) { set_error("NULL buffer"); return MPK_EINVAL; }
     if (st) {
-        if (!st->traj_steps || !st->plan_steps || !st->done || !st->seg_len) { set_error("NULL replanning state buffer"); return MPK_EINVAL; }
-        if ((st->cond_pos == nullptr) != (st->cond_vel == nullptr)) { set_error("cond_pos and cond_vel go together"); return MPK_EINVAL; }
-        if (st->every < 1 || st->horizon < 1) { set_error("every and horizon must be >= 1"); return MPK_EINVAL; }
-        hl.rp.traj_steps = st->traj_steps; hl.rp.plan_steps = st->plan_steps; hl.rp.done = st->done; hl.rp.seg_len = st->seg_len;
-        hl.rp.done_out = st->done_out; hl.rp.cond_pos = st->cond_pos; hl.rp.cond_vel = st->cond_vel;
-        hl.rp.every = st->every; hl.rp.max_planning_times = st->max_planning_times; hl.rp.horizon = st->horizon;
+        r = fill_replan(st, nullptr, nullptr, &hl.rp);
+        if (r != MPK_OK) return r;
     }
     hl.des_pos = des_pos; hl.des_vel = des_vel; hl.q = q; hl.qd = qd; hl.n_steps = n_steps; hl.step0 = step0; hl.hole = hole;
     hl.actions = actions; hl.rewards = rewards; hl.ret = ret; hl.n_exec = n_exec; hl.collided = collided; hl.success = success;

@@ -117,54 +117,73 @@ struct SharedTables {
 
 struct Handle;  // defined in mpk_host.cpp
 
-// ---- launchers implemented in mpk_kernels.hip (all enqueue on `stream`, none synchronise) -------------------
+// ---- a trajectory call as ONE value, from the entry point (mpk_host.cpp) to the route plans -----------------------------------------
+// the extras of mpk_episode_return (ret == nullptr: not that call)
+struct EpisodeAsk {
+    int reward = 0, steps_before_reward = 0, agg = 0;                  // MPK_REWARD_*, MPK_AGG_*
+    const double* goal = nullptr;
+    const int32_t* step0 = nullptr;
+    double* ret = nullptr;                                              // [B]
+    int32_t* seg_out = nullptr;                                         // [B], optional
+};
+// What the caller asks for, and nothing about where it runs.  The planners derive their facts from the pointers: q_state != nullptr is
+// the closed loop, actions != nullptr a fused controller (rc is read), pos == nullptr the lean learned-phase launch (mpk_episode_return).
+struct TrajRequest {
+    const float *params = nullptr, *init_pos = nullptr, *init_vel = nullptr;   // [B, P], [B, D], [B, D]
+    const float* init_time = nullptr;                                   // [B] per episode; nullptr: init_time_shared
+    float init_time_shared = 0.f;
+    float *pos = nullptr, *vel = nullptr, *actions = nullptr;           // [B, T, D] out
+    const RolloutDev* rc = nullptr;                                     // controller and plant
+    const double *c_pos = nullptr, *c_vel = nullptr;                    // [B, D] the frozen state fused actions track (MPK_PLANT_STATIC)
+    double *q_state = nullptr, *qd_state = nullptr;                     // [B, D] in/out: the plant state of the closed loop
+    const int32_t* n_steps = nullptr;                                   // [B] steps to execute (nullptr: all, or rp's rule)
+    const ReplanDev* rp = nullptr;
+    const GateDev* gate = nullptr;
+    EpisodeAsk ep;
+    int B = 0;
+};
+// where a launch runs and reports; the route plans get num_cu, tune, ticket and fault of it and never the stream
+struct LaunchSite {
+    int num_cu = 0;
+    Tuning tune;
+    void* stream = nullptr;
+    const char** kernel_name = nullptr;  // set to the launched kernel's name (static storage)
+    unsigned* ticket = nullptr;          // k_traj_ring's batch counter (nullptr: static batch assignment)
+    int* fault = nullptr;                // the handle's fault word
+    int32_t* range_flag = nullptr;       // ProDMP with a per-episode phase: raised beyond the pre-computed range
+};
+
+// ---- launchers implemented in mpk_kernels.hip (all enqueue on the site's `stream`, none synchronise) -------------------
 int launch_build_shared(const DevCfg& c, float init_time, const SharedTables& st, int32_t* idx_out,
                         int32_t* range_flag, void* stream);
 // (launch_traj_shared / launch_episode_return: the route choice -- plan_traj_shared / plan_episode_return, mpk_traj_route.h -- and ONE
 // launch of the family it names)
-int launch_traj_shared(const DevCfg& c, const SharedTables& st, const float* params, const float* init_pos,
-                       const float* init_vel, float* pos, float* vel, float* actions, const RolloutDev* rc,
-                       const double* c_pos, const double* c_vel, double* q_state, double* qd_state,
-                       const int32_t* n_steps, int B, int num_cu, void* stream, const char** kernel_name,
-                       const Tuning& tune, const ReplanDev* rp = nullptr, unsigned* ticket = nullptr, int* fault = nullptr,
-                       const GateDev* gate = nullptr);
-int launch_episode_return(const DevCfg& c, const SharedTables& st, const float* params, const float* init_pos, const float* init_vel,
-                          const RolloutDev& rc, double* q_state, double* qd_state, const int32_t* n_steps, const ReplanDev* rp,
-                          int reward_type, const double* goal, const int32_t* step0, int steps_before_reward, int agg, double* ret,
-                          int32_t* seg_out, int B, int num_cu, void* stream, const char** kernel_name, const Tuning& tune,
-                          const GateDev* gate = nullptr);
+int launch_traj_shared(const DevCfg& c, const SharedTables& st, const TrajRequest& q, const LaunchSite& at);
+int launch_episode_return(const DevCfg& c, const SharedTables& st, const TrajRequest& q, const LaunchSite& at);
 int launch_reward_aggregate(const double* rewards, const int32_t* seg_len, int agg, double* out, int B, int T, void* stream);
 // shared phase, more than kMaxKP contraction columns: k-chunked GEMM on the matrix cores (trajectory only)
-int launch_traj_wide(const DevCfg& c, const SharedTables& st, const float* params, const float* init_pos,
-                     const float* init_vel, float* pos, float* vel, int B, int num_cu, void* stream,
-                     const char** kernel_name);
+int launch_traj_wide(const DevCfg& c, const SharedTables& st, const TrajRequest& q, const LaunchSite& at);
 // mpk_trajectory_vjp (mpk_traj_vjp.hip): the transpose of the shared-phase map, (g_pos, g_vel) [B, T, D] -> g_params [B, P], g_init_pos /
 // g_init_vel [B, D]; any input or output may be nullptr (term skipped / not written).  Tile route (matrix cores) for <= kMaxD DoF and
 // <= kMaxKP columns, else -- or with tune.vjp_generic == 1 -- one workgroup per episode on the vector ALU.  c: the configuration the
 // tables were built for (a DMP handle's response configuration); MPK_ENOTIMPL for plain-DMP forcing tables.
 int launch_traj_vjp(const DevCfg& c, const SharedTables& st, const float* g_pos, const float* g_vel, float* g_params, float* g_init_pos,
                     float* g_init_vel, int B, int num_cu, void* stream, const char** kernel_name, const Tuning& tune);
-int launch_traj_rows(const DevCfg& c, const float* params, const float* init_pos, const float* init_vel,
-                     const float* init_time, float init_time_shared, float* pos, float* vel, int32_t* range_flag,
-                     int B, int num_cu, void* stream, const char** kernel_name, const Tuning& tune);
+int launch_traj_rows(const DevCfg& c, const TrajRequest& q, const LaunchSite& at);
 int launch_pd_rollout(const RolloutDev& rc, int D, const float* des_pos, const float* des_vel, double* q,
                       double* qd, const int32_t* n_steps, float* actions, int B, int T, void* stream,
                       const Tuning& tune, int* fault = nullptr);
 // the fused entry points with a per-episode phase (learned tau / delay), promp / prodmp with <= 8 contraction columns and <= 16 DoF
-// (mpk_phase_fused.hip): rc.plant_type static = actions for the frozen state (q, qd), double integrator = closed loop; pos == nullptr:
-// nothing per step is stored (mpk_episode_return).  MPK_ENOTIMPL for other shapes.
+// (mpk_phase_fused.hip): rc->plant_type static = actions for the frozen state (c_pos, c_vel), double integrator = closed loop on (q_state,
+// qd_state); pos == nullptr: nothing per step is stored (mpk_episode_return: ep.ret / ep.seg_out).  MPK_ENOTIMPL for other shapes.
 bool phase_fused_capable(const DevCfg& c);
-int launch_phase_fused(const DevCfg& c, const float* params, const float* init_pos, const float* init_vel, float init_time_shared,
-                       float* pos, float* vel, float* actions, const RolloutDev& rc, double* q, double* qd, const int32_t* n_steps,
-                       const ReplanDev* rp, const GateDev* gate, double* ret, int32_t* seg_out, int32_t* range_flag, int B, int num_cu,
-                       void* stream, const char** kernel_name, const Tuning& tune, int* fault);
+int launch_phase_fused(const DevCfg& c, const TrajRequest& q, const LaunchSite& at);
 // per-episode-phase DMP: the interpolation table of the forcing rows (mpk_traj_phase.hip fast_rows_build), built once per handle
 int fast_rows_floats(const DevCfg& c);      // 0: none for this shape
 int fast_rows_stride(const DevCfg& c);      // floats per node = the consuming kernels' KS
 int launch_fast_rows_table(const DevCfg& c, float* out, void* stream);
 // MPK_DMP_FIRST_IS_STEP: (init_pos, init_vel) advanced by one Euler step from init_time to the first grid time
-int launch_dmp_prestep(const DevCfg& c, const float* params, const float* init_pos, const float* init_vel,
-                       const float* init_time, float init_time_shared, float* pos1, float* vel1, int B, void* stream);
+int launch_dmp_prestep(const DevCfg& c, const TrajRequest& q, float* pos1, float* vel1, void* stream);
 int launch_condition_gather(const float* pos, const float* vel, const int32_t* seg_len, float* cond_pos, float* cond_vel,
                             int B, int T, int D, void* stream);
 int launch_reacher_rollout(const RolloutDev& rc, int D, const float* des_pos, const float* des_vel, double* q,

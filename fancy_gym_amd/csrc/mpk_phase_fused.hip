@@ -731,27 +731,29 @@ struct FusedFacts {
     int B, num_cu;
 };
 
-// the arguments that are copies of the call's; MPK_OK or the gate's MPK_EINVAL
-static int fill_fused_args(const DevCfg& c, const float* params, const float* init_pos, const float* init_vel, float init_time_shared,
-                           float* pos, float* vel, float* actions, const RolloutDev& rc, double* q, double* qd, const int32_t* n_steps,
-                           const ReplanDev* rp, const GateDev* gate, double* ret, int32_t* seg_out, int32_t* range_flag, int B, int* fault,
-                           FusedArgs& fa, FusedLim& fl) {
+// the arguments that are copies of the request's; MPK_OK or the gate's MPK_EINVAL
+static int fill_fused_args(const DevCfg& c, const TrajRequest& q, int32_t* range_flag, int* fault, FusedArgs& fa, FusedLim& fl) {
+    const RolloutDev& rc = *q.rc;
+    const GateDev* const gate = q.gate;
     const bool closed = rc.plant_type == MPK_PLANT_DOUBLE_INTEGRATOR;
     fa.c = c;
-    fa.params = params; fa.init_pos = init_pos; fa.init_vel = init_vel; fa.init_time_shared = init_time_shared;
-    fa.pos = pos; fa.vel = vel; fa.actions = actions;
-    fa.q = q; fa.qd = qd; fa.n_steps = n_steps;
-    if (rp) fa.rp = *rp;
+    fa.params = q.params; fa.init_pos = q.init_pos; fa.init_vel = q.init_vel; fa.init_time_shared = q.init_time_shared;
+    fa.pos = q.pos; fa.vel = q.vel; fa.actions = q.actions;
+    // (the kernel's state pointers: the closed loop's plant state, else the frozen state, which it only reads)
+    fa.q = q.q_state ? q.q_state : const_cast<double*>(q.c_pos);
+    fa.qd = q.qd_state ? q.qd_state : const_cast<double*>(q.c_vel);
+    fa.n_steps = q.n_steps;
+    if (q.rp) fa.rp = *q.rp;
     fa.plant_dt = rc.dt;
     fa.flag = range_flag;
-    fa.ret = ret; fa.seg_out = seg_out;
-    fa.B = B;
+    fa.ret = q.ep.ret; fa.seg_out = q.ep.seg_out;
+    fa.B = q.B;
     fa.fault = fault;
     for (int d = 0; d < c.D; ++d) { fl.pg[d] = rc.pg[d]; fl.dg[d] = rc.dg[d]; fl.lo[d] = rc.lo[d]; fl.hi[d] = rc.hi[d]; }
     if (gate) {
         if (!closed) { set_error("the validity gate needs the double-integrator plant"); return MPK_EINVAL; }
         fa.gate = 1;
-        fa.raw_params = gate->raw_params ? gate->raw_params : params;
+        fa.raw_params = gate->raw_params ? gate->raw_params : q.params;
         fa.valid = gate->valid; fa.penalty = gate->penalty;
         fa.check_td = gate->check_td;
         fa.tau_b[0] = gate->tau_b[0]; fa.tau_b[1] = gate->tau_b[1];
@@ -931,20 +933,16 @@ static int launch_fused_route(const FusedArgs& fa, const FusedLim& fl, const Fus
     return r.kq == 1 ? by_dc(PM(), I1(), std::false_type()) : by_dc(PM(), I2(), std::false_type());
 }
 
-int launch_phase_fused(const DevCfg& c, const float* params, const float* init_pos, const float* init_vel, float init_time_shared,
-                       float* pos, float* vel, float* actions, const RolloutDev& rc, double* q, double* qd, const int32_t* n_steps,
-                       const ReplanDev* rp, const GateDev* gate, double* ret, int32_t* seg_out, int32_t* range_flag, int B, int num_cu,
-                       void* stream, const char** kernel_name, const Tuning& tune, int* fault) {
+int launch_phase_fused(const DevCfg& c, const TrajRequest& q, const LaunchSite& at) {
     if (!phase_fused_capable(c)) return MPK_ENOTIMPL;
     FusedArgs fa{};
     FusedLim fl{};
     FusedRoute r;
-    int rc_ = fill_fused_args(c, params, init_pos, init_vel, init_time_shared, pos, vel, actions, rc, q, qd, n_steps, rp, gate, ret, seg_out,
-                              range_flag, B, fault, fa, fl);
-    if (rc_ == MPK_OK) rc_ = plan_phase_fused(rc, num_cu, tune, fa, r);
+    int rc_ = fill_fused_args(c, q, at.range_flag, at.fault, fa, fl);
+    if (rc_ == MPK_OK) rc_ = plan_phase_fused(*q.rc, at.num_cu, at.tune, fa, r);
     if (rc_ != MPK_OK) return rc_;
-    *kernel_name = r.name;
-    return launch_fused_route(fa, fl, r, stream);
+    *at.kernel_name = r.name;
+    return launch_fused_route(fa, fl, r, at.stream);
 }
 #endif  // MPK_DEVICE_ONLY
 

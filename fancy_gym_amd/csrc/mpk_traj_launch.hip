@@ -198,30 +198,37 @@ static void fill_gate_args(const GateDev* gate, const float* params, int D, Traj
     }
 }
 
+// what plan_traj_shared and plan_episode_return both copy from the request: configuration, tables, inputs, the batch and its episode
+// groups, plant and replanning state, the controller's gains and limits (gains: a controller runs), the gate
+static void fill_request_args(const DevCfg& c, const SharedTables& st, const TrajRequest& q, bool gains, TrajArgs& ta, ActArgs& aa) {
+    ta.wpb = 4; ta.ring_parts = 1;
+    if (q.rp) ta.rp = *q.rp;
+    ta.q_state = q.q_state; ta.qd_state = q.qd_state; ta.n_steps = q.n_steps; ta.plant_dt = q.rc ? q.rc->dt : 0.0;
+    ta.c = c; ta.A = st.A; ta.aux = st.aux; ta.TS = st.TS;
+    ta.params = q.params; ta.init_pos = q.init_pos; ta.init_vel = q.init_vel;
+    ta.B = q.B;
+    int sh = 0;
+    while ((1 << sh) < c.D) ++sh;  // DP = next power of two >= D (<= 16)
+    ta.sh = sh;
+    const int NTW = 16 >> sh;
+    ta.G = (q.B + NTW - 1) / NTW;
+    if (gains)
+        for (int d = 0; d < c.D; ++d) { aa.pg[d] = q.rc->pg[d]; aa.dg[d] = q.rc->dg[d]; aa.lo[d] = q.rc->lo[d]; aa.hi[d] = q.rc->hi[d]; }
+    fill_gate_args(q.gate, q.params, c.D, ta, aa);
+}
+
 // mpk_episode_return: plan + controller + plant + reward + aggregation of a `verbose < 2` step in one launch (k_episode_return).
 // MPK_ENOTIMPL where the tables do not fit beside the images (long horizons): the caller's separate launches take those.
 // The geometry choice; no HIP call, no allocation.  (A route's name is set as soon as its kernel is known, also where the plan then declines.)
-int plan_episode_return(const DevCfg& c, const SharedTables& st, const float* params, const float* init_pos, const float* init_vel,
-                        const RolloutDev& rc, double* q_state, double* qd_state, const int32_t* n_steps, const ReplanDev* rp,
-                        int reward_type, const double* goal, const int32_t* step0, int steps_before_reward, int agg, double* ret,
-                        int32_t* seg_out, int B, int num_cu, const Tuning& tune, const GateDev* gate, TrajArgs& ta, ActArgs& aa,
-                        EpArgs& ea, EpRoute& r) {
-    ta.wpb = 4; ta.ring_parts = 1;
-    if (rp) ta.rp = *rp;
-    ta.q_state = q_state; ta.qd_state = qd_state; ta.n_steps = n_steps; ta.plant_dt = rc.dt;
-    ta.c = c; ta.A = st.A; ta.aux = st.aux; ta.TS = st.TS;
-    ta.params = params; ta.init_pos = init_pos; ta.init_vel = init_vel;
-    ta.B = B;
-    int sh = 0;
-    while ((1 << sh) < c.D) ++sh;
-    ta.sh = sh;
-    const int NTW = 16 >> sh;
-    ta.G = (B + NTW - 1) / NTW;
+int plan_episode_return(const DevCfg& c, const SharedTables& st, const TrajRequest& q, int num_cu, const Tuning& tune, TrajArgs& ta,
+                        ActArgs& aa, EpArgs& ea, EpRoute& r) {
+    const int reward_type = q.ep.reward;
+    fill_request_args(c, st, q, true, ta, aa);
+    const int NTW = 16 >> ta.sh;
     const int SEG = 16 * c.D;
-    ta.pitch = SEG; ta.cps = SEG / 4 > 0 ? SEG / 4 : 1; ta.inv_cps = 65536u / (unsigned)ta.cps + 1u; ta.vec_ok = 1;
-    for (int d = 0; d < c.D; ++d) { aa.pg[d] = rc.pg[d]; aa.dg[d] = rc.dg[d]; aa.lo[d] = rc.lo[d]; aa.hi[d] = rc.hi[d]; }
-    fill_gate_args(gate, params, c.D, ta, aa);
-    ea.ret = ret; ea.goal = goal; ea.step0 = step0; ea.seg_out = seg_out; ea.steps_before_reward = steps_before_reward; ea.agg = agg;
+    ta.pitch = SEG; ta.cps = SEG / 4 > 0 ? SEG / 4 : 1; ta.inv_cps = 65536u / (unsigned)ta.cps + 1u; ta.vec_ok = 1;      // (never the shifted staging image)
+    ea.ret = q.ep.ret; ea.goal = q.ep.goal; ea.step0 = q.ep.step0; ea.seg_out = q.ep.seg_out; ea.steps_before_reward = q.ep.steps_before_reward;
+    ea.agg = q.ep.agg;
     ea.km = c.KP / 4;
     const size_t table_bytes = ((size_t)st.n_out * c.KP * st.TS + st.TS) * sizeof(float);
     // groups per wave: four while that still gives every SIMD a wave (the chain is latency bound: more lanes per instruction),
@@ -247,7 +254,7 @@ int plan_episode_return(const DevCfg& c, const SharedTables& st, const float* pa
     if (blocks > cap) blocks = cap;
     if (blocks >= 8) blocks = (blocks + 7) / 8 * 8;
     r.blocks = (int)blocks;
-    r.ct = rc.controller_type + 3; r.nq = nq; r.rwd = reward_type;
+    r.ct = q.rc->controller_type + 3; r.nq = nq; r.rwd = reward_type;
     const bool pd = c.mp_type == MPK_MP_PRODMP;
     r.name = reward_type ? (pd ? "k_episode_return<prodmp,reacher>" : "k_episode_return<promp,reacher>")
                          : (pd ? "k_episode_return<prodmp>" : "k_episode_return<promp>");
@@ -255,20 +262,15 @@ int plan_episode_return(const DevCfg& c, const SharedTables& st, const float* pa
     return MPK_OK;
 }
 
-int launch_episode_return(const DevCfg& c, const SharedTables& st, const float* params, const float* init_pos, const float* init_vel,
-                          const RolloutDev& rc, double* q_state, double* qd_state, const int32_t* n_steps, const ReplanDev* rp,
-                          int reward_type, const double* goal, const int32_t* step0, int steps_before_reward, int agg, double* ret,
-                          int32_t* seg_out, int B, int num_cu, void* stream, const char** kernel_name, const Tuning& tune,
-                          const GateDev* gate) {
+int launch_episode_return(const DevCfg& c, const SharedTables& st, const TrajRequest& q, const LaunchSite& at) {
     TrajArgs ta{};
     ActArgs aa{};
     EpArgs ea{};
     EpRoute r{};
-    const int rc_ = plan_episode_return(c, st, params, init_pos, init_vel, rc, q_state, qd_state, n_steps, rp, reward_type, goal, step0,
-                                        steps_before_reward, agg, ret, seg_out, B, num_cu, tune, gate, ta, aa, ea, r);
-    if (r.name) *kernel_name = r.name;
+    const int rc_ = plan_episode_return(c, st, q, at.num_cu, at.tune, ta, aa, ea, r);
+    if (r.name) *at.kernel_name = r.name;
     if (rc_ != MPK_OK) return rc_;
-    return by_mp_type(c.mp_type, [&](auto mp) { return launch_episode_kernel<decltype(mp)::value>(ta, aa, ea, r, stream); });
+    return by_mp_type(c.mp_type, [&](auto mp) { return launch_episode_kernel<decltype(mp)::value>(ta, aa, ea, r, at.stream); });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -620,16 +622,15 @@ static const char* traj_kernel_name(const TrajRoute& r, int mp_type, bool act, b
     return names[k][mp_type][r.gate ? 3 : closed ? 2 : act ? 1 : 0];
 }
 
-int plan_traj_shared(const DevCfg& c, const SharedTables& st, const float* params, const float* init_pos, const float* init_vel,
-                     float* pos, float* vel, float* actions, const RolloutDev* rc, const double* c_pos, const double* c_vel,
-                     double* q_state, double* qd_state, const int32_t* n_steps, int B, int num_cu, const Tuning& tune, const ReplanDev* rp,
-                     unsigned* ticket, int* fault, const GateDev* gate, TrajArgs& ta, ActArgs& aa, TrajRoute& r) {
+int plan_traj_shared(const DevCfg& c, const SharedTables& st, const TrajRequest& q, int num_cu, const Tuning& tune, unsigned* ticket,
+                     int* fault, TrajArgs& ta, ActArgs& aa, TrajRoute& r) {
+    const int B = q.B;
     TrajFacts f{c, tune};
     f.B = B; f.num_cu = num_cu; f.ticket = ticket;
     f.dmp = c.mp_type == MPK_MP_DMP;
-    f.closed = q_state != nullptr;
-    f.act = actions != nullptr;
-    f.gated = gate != nullptr;       // validity gate: the lane-quarter closed-loop kernels (k_traj_quad / duo / mono: gate_pass) and k_traj_pipe
+    f.closed = q.q_state != nullptr;
+    f.act = q.actions != nullptr;
+    f.gated = q.gate != nullptr;     // validity gate: the lane-quarter closed-loop kernels (k_traj_quad / duo / mono: gate_pass) and k_traj_pipe
     const bool dmp = f.dmp, closed = f.closed, act = f.act, gated = f.gated;
     if (gated && !(closed && act)) { set_error("the validity gate belongs to the closed-loop step"); return MPK_EINVAL; }
     ta.fault = fault;
@@ -637,23 +638,14 @@ int plan_traj_shared(const DevCfg& c, const SharedTables& st, const float* param
     // the bits that leave outputs unwritten (1 no production, 2 no stores, 128 a batch never published; open loop: 8 no input loads)
     // count only after mpk_set_option(.., "ablations", 1) -- measurements and fault injection, never by accident
     if (tune.ablations != 1) ta.ring_dbg &= ~(1 | 2 | 128 | (closed ? 0 : 8));
-    ta.wpb = 4; ta.ring_parts = 1;
-    if (rp) ta.rp = *rp;
-    ta.q_state = q_state; ta.qd_state = qd_state; ta.n_steps = n_steps; ta.plant_dt = rc ? rc->dt : 0.0;
-    ta.c = c; ta.A = st.A; ta.aux = st.aux; ta.TS = st.TS;
-    ta.params = params; ta.init_pos = init_pos; ta.init_vel = init_vel;
-    ta.pos = pos; ta.vel = vel; ta.actions = actions; ta.c_pos = c_pos; ta.c_vel = c_vel;
-    ta.B = B;
-    int sh = 0;
-    while ((1 << sh) < c.D) ++sh;  // DP = next power of two >= D (<= 16)
-    ta.sh = sh;
-    const int NTW = f.NTW = 16 >> sh;
-    ta.G = (B + NTW - 1) / NTW;
+    fill_request_args(c, st, q, act, ta, aa);
+    ta.pos = q.pos; ta.vel = q.vel; ta.actions = q.actions; ta.c_pos = q.c_pos; ta.c_vel = q.c_vel;
+    const int NTW = f.NTW = 16 >> ta.sh;
     f.nst = 2 + (act ? 1 : 0);
     const int SEG = 16 * c.D, seg4 = SEG / 4, TD = f.TD = c.T * c.D;
     auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-    const bool ptr_ok = f.ptr_ok = aligned16(pos) && aligned16(vel) && (!act || aligned16(actions));
-    f.in_ok = aligned16(params) && aligned16(init_pos) && aligned16(init_vel) && (!act || closed || (aligned16(c_pos) && aligned16(c_vel)));
+    const bool ptr_ok = f.ptr_ok = aligned16(q.pos) && aligned16(q.vel) && (!act || aligned16(q.actions));
+    f.in_ok = aligned16(q.params) && aligned16(q.init_pos) && aligned16(q.init_vel) && (!act || closed || (aligned16(q.c_pos) && aligned16(q.c_vel)));
     // T*D % 4 != 0: episodes start 0..3 floats past a 16-byte boundary -> shifted staging image (one spare chunk per
     // episode segment), if the segments of a group still fit the 64 lanes of a wave
     // (misaligned output pointers take the generic store path, whose staging image is never shifted)
@@ -663,12 +655,7 @@ int plan_traj_shared(const DevCfg& c, const SharedTables& st, const float* param
     ta.cps = ta.shifted ? seg4 + 1 : seg4;
     ta.inv_cps = 65536u / (unsigned)ta.cps + 1u;
     ta.vec_ok = ptr_ok && (TD % 4 == 0 || ta.shifted);
-    int ct = -1;
-    if (act) {
-        ct = rc->controller_type + (closed ? 3 : 0);
-        for (int d = 0; d < c.D; ++d) { aa.pg[d] = rc->pg[d]; aa.dg[d] = rc->dg[d]; aa.lo[d] = rc->lo[d]; aa.hi[d] = rc->hi[d]; }
-    }
-    fill_gate_args(gate, params, c.D, ta, aa);
+    const int ct = act ? q.rc->controller_type + (closed ? 3 : 0) : -1;
     f.NRT = (c.T + 15) / 16;
     f.max_waves = (long)num_cu * 32;     // 8 waves per SIMD resident
     f.lds_pad = tune.lds_pad > 0 ? (size_t)tune.lds_pad * 1024 : 0;
@@ -735,23 +722,18 @@ int plan_traj_shared(const DevCfg& c, const SharedTables& st, const float* param
     return gated && dmp ? MPK_ENOTIMPL : MPK_OK;
 }
 
-int launch_traj_shared(const DevCfg& c, const SharedTables& st, const float* params, const float* init_pos,
-                       const float* init_vel, float* pos, float* vel, float* actions, const RolloutDev* rc,
-                       const double* c_pos, const double* c_vel, double* q_state, double* qd_state,
-                       const int32_t* n_steps, int B, int num_cu, void* stream, const char** kernel_name,
-                       const Tuning& tune, const ReplanDev* rp, unsigned* ticket, int* fault, const GateDev* gate) {
+int launch_traj_shared(const DevCfg& c, const SharedTables& st, const TrajRequest& q, const LaunchSite& at) {
     TrajArgs ta{};
     ActArgs aa{};
     TrajRoute r{};
-    const int rc_ = plan_traj_shared(c, st, params, init_pos, init_vel, pos, vel, actions, rc, c_pos, c_vel, q_state, qd_state, n_steps, B,
-                                     num_cu, tune, rp, ticket, fault, gate, ta, aa, r);
-    if (r.name) *kernel_name = r.name;
+    const int rc_ = plan_traj_shared(c, st, q, at.num_cu, at.tune, at.ticket, at.fault, ta, aa, r);
+    if (r.name) *at.kernel_name = r.name;
     if (rc_ != MPK_OK) return rc_;
     switch (r.family) {
         case TrajFamily::RingOpen: case TrajFamily::RingClosed: case TrajFamily::Burst: case TrajFamily::FlatD:
-            return by_mp_type(c.mp_type, [&](auto mp) { return launch_traj_ring<decltype(mp)::value>(ta, aa, r, stream); });
+            return by_mp_type(c.mp_type, [&](auto mp) { return launch_traj_ring<decltype(mp)::value>(ta, aa, r, at.stream); });
         default:
-            return by_mp_type(c.mp_type, [&](auto mp) { return launch_traj_ct<decltype(mp)::value>(ta, aa, r, stream); });
+            return by_mp_type(c.mp_type, [&](auto mp) { return launch_traj_ct<decltype(mp)::value>(ta, aa, r, at.stream); });
     }
 }
 #endif  // MPK_DEVICE_ONLY

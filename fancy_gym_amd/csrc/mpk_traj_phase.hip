@@ -1928,19 +1928,18 @@ __global__ void __launch_bounds__(256) k_dmp_prestep(const DevCfg c, const float
 }
 
 #ifndef MPK_DEVICE_ONLY
-int launch_dmp_prestep(const DevCfg& c, const float* params, const float* init_pos, const float* init_vel,
-                       const float* init_time, float init_time_shared, float* pos1, float* vel1, int B, void* stream) {
-    hipLaunchKernelGGL(k_dmp_prestep, dim3((unsigned)(((long)B * c.D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c,
-                       params, init_pos, init_vel, init_time, init_time_shared, pos1, vel1, B);
+int launch_dmp_prestep(const DevCfg& c, const TrajRequest& q, float* pos1, float* vel1, void* stream) {
+    hipLaunchKernelGGL(k_dmp_prestep, dim3((unsigned)(((long)q.B * c.D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c,
+                       q.params, q.init_pos, q.init_vel, q.init_time, q.init_time_shared, pos1, vel1, q.B);
     MPK_LAUNCH_CHECK();
     return MPK_OK;
 }
 #endif  // MPK_DEVICE_ONLY
 
 #ifndef MPK_DEVICE_ONLY
-int launch_traj_rows(const DevCfg& c, const float* params, const float* init_pos, const float* init_vel,
-                     const float* init_time, float init_time_shared, float* pos, float* vel, int32_t* range_flag,
-                     int B, int num_cu, void* stream, const char** kernel_name, const Tuning& tune) {
+int launch_traj_rows(const DevCfg& c, const TrajRequest& q, const LaunchSite& at) {
+    const Tuning& tune = at.tune;
+    const int B = q.B, num_cu = at.num_cu;
     if (c.mp_type == MPK_MP_PROMP && c.T < 2) {
         set_error("promp needs at least two time steps for the finite-difference velocity");
         return MPK_EINVAL;
@@ -1948,10 +1947,10 @@ int launch_traj_rows(const DevCfg& c, const float* params, const float* init_pos
     // wave-per-episode kernel whenever the shape fits it ("phase" 0: the workgroup-per-episode kernel below)
     const bool wave_kernel = tune.phase != 0;
     if (wave_kernel) {
-        PhaseArgs pa{c, params, init_pos, init_vel, init_time, init_time_shared, pos, vel, range_flag, B, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        PhaseArgs pa{c, q.params, q.init_pos, q.init_vel, q.init_time, q.init_time_shared, q.pos, q.vel, at.range_flag, B, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         pa.wt = (double)B * c.T * c.D * 8.0 <= kWtBytes ? 1 : 0;
         if (tune.write_through >= 0) pa.wt = tune.write_through != 0 ? 1 : 0;
-        const int rc = launch_traj_phase(c, pa, num_cu, stream, kernel_name, tune);
+        const int rc = launch_traj_phase(c, pa, num_cu, at.stream, at.kernel_name, tune);
         if (rc != MPK_ENOTIMPL) return rc;
     }
     const int nrow = c.mp_type == MPK_MP_PRODMP ? 2 : 1;
@@ -1959,13 +1958,13 @@ int launch_traj_rows(const DevCfg& c, const float* params, const float* init_pos
                           (c.mp_type == MPK_MP_DMP ? (size_t)c.T * c.D : 0) + c.T + 8;
     const size_t lds = floats * sizeof(float);
     if (lds > kLdsPerCu) { set_error("trajectory too large for the per-episode kernel's LDS budget"); return MPK_EINVAL; }
-    RowArgs ra{c, params, init_pos, init_vel, init_time, init_time_shared, pos, vel, range_flag, B};
+    RowArgs ra{c, q.params, q.init_pos, q.init_vel, q.init_time, q.init_time_shared, q.pos, q.vel, at.range_flag, B};
     int blocks = B < num_cu * 8 ? B : num_cu * 8;
-    auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(256), lds, stream, ra); };
+    auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(256), lds, at.stream, ra); };
     switch (c.mp_type) {
-        case MPK_MP_PRODMP: *kernel_name = "k_traj_rows<prodmp>"; return go(k_traj_rows<MPK_MP_PRODMP>);
-        case MPK_MP_PROMP: *kernel_name = "k_traj_rows<promp>"; return go(k_traj_rows<MPK_MP_PROMP>);
-        default: *kernel_name = "k_traj_rows<dmp>"; return go(k_traj_rows<MPK_MP_DMP>);
+        case MPK_MP_PRODMP: *at.kernel_name = "k_traj_rows<prodmp>"; return go(k_traj_rows<MPK_MP_PRODMP>);
+        case MPK_MP_PROMP: *at.kernel_name = "k_traj_rows<promp>"; return go(k_traj_rows<MPK_MP_PROMP>);
+        default: *at.kernel_name = "k_traj_rows<dmp>"; return go(k_traj_rows<MPK_MP_DMP>);
     }
 }
 #endif  // MPK_DEVICE_ONLY

@@ -40,18 +40,14 @@ struct EpRoute {
 };
 
 #ifndef MPK_DEVICE_ONLY
-// the route choice (mpk_traj_launch.hip): the inputs of launch_traj_shared / launch_episode_return (mpk_internal.h) without the stream;
-// they fill value-initialised arguments and the route, call nothing of the HIP runtime and allocate nothing.  MPK_OK, or the code the
-// launch returns without launching (a route's name is set as soon as its kernel is known, also where the plan then declines)
-int plan_traj_shared(const DevCfg& c, const SharedTables& st, const float* params, const float* init_pos, const float* init_vel,
-                     float* pos, float* vel, float* actions, const RolloutDev* rc, const double* c_pos, const double* c_vel,
-                     double* q_state, double* qd_state, const int32_t* n_steps, int B, int num_cu, const Tuning& tune, const ReplanDev* rp,
-                     unsigned* ticket, int* fault, const GateDev* gate, TrajArgs& ta, ActArgs& aa, TrajRoute& r);
-int plan_episode_return(const DevCfg& c, const SharedTables& st, const float* params, const float* init_pos, const float* init_vel,
-                        const RolloutDev& rc, double* q_state, double* qd_state, const int32_t* n_steps, const ReplanDev* rp,
-                        int reward_type, const double* goal, const int32_t* step0, int steps_before_reward, int agg, double* ret,
-                        int32_t* seg_out, int B, int num_cu, const Tuning& tune, const GateDev* gate, TrajArgs& ta, ActArgs& aa,
-                        EpArgs& ea, EpRoute& r);
+// the route choice (mpk_traj_launch.hip): the request of launch_traj_shared / launch_episode_return (mpk_internal.h) and, of the launch
+// site, what a rule reads -- never the stream; they fill value-initialised arguments and the route, call nothing of the HIP runtime and
+// allocate nothing.  MPK_OK, or the code the launch returns without launching (a route's name is set as soon as its kernel is known,
+// also where the plan then declines)
+int plan_traj_shared(const DevCfg& c, const SharedTables& st, const TrajRequest& q, int num_cu, const Tuning& tune, unsigned* ticket,
+                     int* fault, TrajArgs& ta, ActArgs& aa, TrajRoute& r);
+int plan_episode_return(const DevCfg& c, const SharedTables& st, const TrajRequest& q, int num_cu, const Tuning& tune, TrajArgs& ta,
+                        ActArgs& aa, EpArgs& ea, EpRoute& r);
 
 template <int MP>
 int launch_traj_ct(const TrajArgs& ta, const ActArgs& aa, const TrajRoute& r, void* stream);      // mpk_traj_family.hip

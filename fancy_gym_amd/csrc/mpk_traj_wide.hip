@@ -371,9 +371,8 @@ __global__ void __launch_bounds__(256, ((MP == MPK_MP_PRODMP ? 2 : 1) * MT <= 16
 // promp / dmp keep the whole horizon in one row-tile block of at most 32 tiles
 bool traj_wide_fits(const DevCfg& c) { return c.mp_type == MPK_MP_PRODMP || (c.T + 15) / 16 <= 32; }
 
-int launch_traj_wide(const DevCfg& c, const SharedTables& st, const float* params, const float* init_pos,
-                     const float* init_vel, float* pos, float* vel, int B, int num_cu, void* stream,
-                     const char** kernel_name) {
+int launch_traj_wide(const DevCfg& c, const SharedTables& st, const TrajRequest& q, const LaunchSite& at) {
+    const int B = q.B, num_cu = at.num_cu;
     if (c.mp_type == MPK_MP_PROMP && c.T < 2) {
         set_error("promp needs at least two time steps for the finite-difference velocity");
         return MPK_EINVAL;
@@ -399,14 +398,14 @@ int launch_traj_wide(const DevCfg& c, const SharedTables& st, const float* param
     const size_t lds_main = stage_bytes(KC) > epi_bytes ? stage_bytes(KC) : epi_bytes;
     const size_t lds = lds_main + (c.mp_type == MPK_MP_PRODMP ? 0 : (size_t)st.TS * sizeof(float));
     const int cgpe = c.D <= 16 ? 1 : (c.D + 15) / 16;
-    WideArgs wa{c, st.A, st.aux, st.TS, params, init_pos, init_vel, pos, vel, B, c.D <= 16 ? 16 / c.D : 1, 0, KC, n_rt, SA, cgpe,
+    WideArgs wa{c, st.A, st.aux, st.TS, q.params, q.init_pos, q.init_vel, q.pos, q.vel, B, c.D <= 16 ? 16 / c.D : 1, 0, KC, n_rt, SA, cgpe,
                 (int)(lds_main / sizeof(float))};
     if (cgpe > 1 && (long long)B * cgpe > 0x7fffffffLL - 8) return MPK_ENOTIMPL;
     const int n_groups = cgpe == 1 ? (B + wa.epg - 1) / wa.epg : B * cgpe;
     wa.n_units = (n_groups + 3) / 4;
     const int per_cu = nout * MT <= 16 ? 2 : 1;                           // see the kernel's launch bounds
     const int blocks = wa.n_units < num_cu * per_cu ? wa.n_units : num_cu * per_cu;
-    auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(256), lds, stream, wa); };
+    auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(256), lds, at.stream, wa); };
     auto pick = [&](auto mp_tag) -> int {
         constexpr int MPV = decltype(mp_tag)::value;
         switch (MT) {
@@ -425,9 +424,9 @@ int launch_traj_wide(const DevCfg& c, const SharedTables& st, const float* param
         return go(k_traj_wide<MPV, 16>);
     };
     switch (c.mp_type) {
-        case MPK_MP_PRODMP: *kernel_name = "k_traj_wide<prodmp>"; return pick(std::integral_constant<int, MPK_MP_PRODMP>());
-        case MPK_MP_PROMP: *kernel_name = "k_traj_wide<promp>"; return pick(std::integral_constant<int, MPK_MP_PROMP>());
-        default: *kernel_name = "k_traj_wide<dmp>"; return pick(std::integral_constant<int, MPK_MP_DMP>());
+        case MPK_MP_PRODMP: *at.kernel_name = "k_traj_wide<prodmp>"; return pick(std::integral_constant<int, MPK_MP_PRODMP>());
+        case MPK_MP_PROMP: *at.kernel_name = "k_traj_wide<promp>"; return pick(std::integral_constant<int, MPK_MP_PROMP>());
+        default: *at.kernel_name = "k_traj_wide<dmp>"; return pick(std::integral_constant<int, MPK_MP_DMP>());
     }
 }
 #endif  // MPK_DEVICE_ONLY

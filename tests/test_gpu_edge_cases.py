@@ -132,6 +132,15 @@ def test_wide_per_episode_phase_stays_on_the_row_kernel():
     assert torch.equal(p0, p1) and torch.equal(v0, v1)      # same rows, same ascending-k fmaf chain: same bits
 
 
+@pytest.mark.parametrize("mp", ["promp", "dmp"])
+def test_wide_shapes_beyond_one_row_tile_block_take_the_row_kernel(mp):
+    """promp / dmp keep the whole horizon in ONE block of at most 32 row tiles of k_traj_wide (traj_wide_fits): from T = 513 on the
+    wide route declines and the workgroup-per-episode kernel takes the 20 columns (prodmp walks row-tile blocks: above)"""
+    if mp == "promp":       # (dmp: two images per row tile, the last wide horizon lies lower)
+        check(cfg_for(mp, 2, 20, 512), 3, expect_kernel="k_traj_wide", seed=1)
+    check(cfg_for(mp, 2, 20, 513), 3, expect_kernel="k_traj_rows", seed=1)
+
+
 @pytest.mark.parametrize("B", [1, 64, 1000])
 def test_the_reference_example_with_1000_basis_functions(B):
     """

@@ -195,6 +195,30 @@ def test_fused_closed_loop_equals_the_two_launches_and_the_reference_loop(name, 
         eq(act, ra.astype(np.float32), "actions vs oracle"); eq(q, rq, "q vs oracle"); eq(qd, rqd, "qd vs oracle")
 
 
+def test_a_horizon_beyond_the_fused_kernels_lds_takes_the_separate_launches():
+    """k_phase_fused keeps the T grid times in LDS beside its chunk images: BeerPong-ProMP's closed loop (pipeline form, chunks of four:
+    35 136 bytes of images and 96 of constants) no longer fits the 160 KB from T = 32 153 on, while the trajectory kernel of a per-episode
+    phase holds T up to 39 756.  There the one-launch form declines (MPK_ENOTIMPL) and mpk_trajectory_rollout answers with its
+    separate launches: the bits of the same launches made by hand, mpk_last_kernel naming the trajectory kernel."""
+    pc, bc, tc, dt = CONFIGS["beerpong_promp"][:4]
+    T, B = 32256, 3
+    eng = make_engine(pc, bc, tc, dt, T * dt, device=0)
+    assert eng.num_steps == T
+    params, ip, iv = make_inputs("beerpong_promp", B, seed=2)
+    _, closed = specs("beerpong_promp")
+    q0, qd0 = ip.astype(np.float64), iv.astype(np.float64)
+    q, qd = cu(q0).clone(), cu(qd0).clone()
+    pos, vel, act = eng.trajectory_rollout(params, ip, iv, closed, q, qd)
+    assert eng.last_kernel().startswith("k_traj_phase<promp"), eng.last_kernel()
+    pos2, vel2 = eng.trajectory(params, ip, iv, 0.0)
+    assert eng.last_kernel().startswith("k_traj_phase<promp"), eng.last_kernel()
+    q2, qd2 = cu(q0).clone(), cu(qd0).clone()
+    act2 = eng.pd_rollout(closed, pos2, vel2, q2, qd2)
+    torch.cuda.synchronize()
+    assert torch.isfinite(pos).all() and torch.isfinite(act).all()
+    eq(pos, pos2, "pos"); eq(vel, vel2, "vel"); eq(act, act2, "actions"); eq(q, q2, "q"); eq(qd, qd2, "qd")
+
+
 def _separate_step(eng, params, cond_pos, cond_vel, closed, q, qd, ts, ps, dn, every, mpt, horizon, init_time, gate=None, raw=None):
     """the launches a step consisted of until round 5 (BatchedBlackBox._step_full)"""
     pos, vel = eng.trajectory(params, cond_pos, cond_vel, init_time)

@@ -161,6 +161,51 @@ def test_dmp_first_sample(mode, path, opts, per_episode, learn, mpk_option):
             assert not np.array_equal(pos[:, 0], ip)
 
 
+# MPK_DMP_FIRST_IS_STEP in front of the routes that DMP_PATHS does not reach (mpk_host.cpp traj_common), 2 DoF, at the shortest
+# horizon that takes each: (id, num_basis, T, options, closed loop, reported kernel).  k_traj_wide holds promp / dmp horizons of at
+# most 32 row tiles (T <= 512); the episode-major kernels hold (n_out KP + 1) TS <= 12 288 table floats beside their staging
+# (TS = T rounded to 32 n + 16): the serial kernels' 16 columns up to T = 720, the response route's 2 x 16 up to T = 368
+STEP_ROUTES = [("wide", 20, 20, {}, False, "k_traj_wide<dmp>"), ("wide_declines", 20, 513, {}, False, "k_traj_rows<dmp>"),
+               ("shared_declines", 13, 721, {"dmp_response": 0}, False, "k_traj_phase<dmp"),
+               ("response_declines", 13, 369, {}, True, "<dmp_resp>")]
+
+
+@pytest.mark.parametrize("name,nb,T,opts,closed,kernel", STEP_ROUTES, ids=[r[0] for r in STEP_ROUTES])
+def test_dmp_first_is_step_in_front_of_the_other_routes(name, nb, T, opts, closed, kernel, mpk_option):
+    from fancy_gym_amd import RolloutSpec
+    from tests.test_gpu_edge_cases import cfg_for
+    for k, v in opts.items():
+        mpk_option(k, v)
+    pc, bc, tc, dt, dur = cfg_for("dmp", 2, nb, T)
+    tc = dataclasses.replace(tc, dmp_first_sample="step")
+    B = 5
+    eng, pos, vel, rp, rv, (params, ip, iv) = _run(pc, bc, tc, dt, dur, B, 0.0, False, seed=T)
+    if not closed:
+        assert eng.last_kernel().startswith(kernel), eng.last_kernel()
+    close(pos, rp, "pos", rtol=2e-5); close(vel, rv, "vel", rtol=2e-5)
+    assert not np.array_equal(pos[:, 0], ip)
+    if closed:
+        # the one-launch form declines (MPK_ENOTIMPL): the entry point's separate launches, bit for bit those made by hand
+        spec = RolloutSpec("motor", 2, 1.0, 0.1, -1.0, 1.0, plant="double_integrator", dt=dt)
+        q0 = ip.astype(np.float64)
+        q, qd = torch.tensor(q0, device="cuda"), torch.zeros((B, 2), dtype=torch.float64, device="cuda")
+        p1, v1, a1 = eng.trajectory_rollout(params, ip, iv, spec, q, qd)
+        assert eng.last_kernel().endswith(kernel), eng.last_kernel()
+        p2, v2 = eng.trajectory(params, ip, iv, 0.0)
+        q2, qd2 = torch.tensor(q0, device="cuda"), torch.zeros((B, 2), dtype=torch.float64, device="cuda")
+        a2 = eng.pd_rollout(spec, p2, v2, q2, qd2)
+        torch.cuda.synchronize()
+        assert np.array_equal(p1.cpu().numpy(), pos) and np.array_equal(v1.cpu().numpy(), vel)
+        assert torch.equal(a1, a2) and torch.equal(q, q2) and torch.equal(qd, qd2)
+        # one step shorter, the same call is ONE launch
+        pc, bc, tc, dt, dur = cfg_for("dmp", 2, nb, T - 1)
+        eng = make_engine(pc, bc, dataclasses.replace(tc, dmp_first_sample="step"), dt, dur)
+        params, ip, iv = inputs(pc, bc, tc, B, seed=T)
+        q, qd = torch.tensor(ip.astype(np.float64), device="cuda"), torch.zeros((B, 2), dtype=torch.float64, device="cuda")
+        eng.trajectory_rollout(params, ip, iv, spec, q, qd)
+        assert eng.last_kernel().endswith("<dmp_resp,closed>"), eng.last_kernel()
+
+
 def test_dmp_first_sample_step_equals_init_mode_started_one_step_later():
     """'step' = one Euler step from the boundary state, then the ordinary recurrence: feeding 'init' mode the stepped state
     (the oracle's first 'step' sample) reproduces the 'step' trajectory"""

@@ -46,6 +46,9 @@ EXITS = (
 
 def build(tree, out, extra):
     csrc = os.path.join(tree, "fancy_gym_amd", "csrc")
+    # (a base from before the request struct: its launchers take argument lists)
+    if "struct TrajRequest" not in open(os.path.join(csrc, "mpk_internal.h")).read():
+        extra = extra + ["-DLAUNCH_POSITIONAL_CALLS"]
     cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "--offload-host-only", "-O1", "-std=c++17",
            "-ffp-contract=off", "-rdynamic", "-Wl,--unresolved-symbols=ignore-all", "-I" + os.path.join(tree, "include"), "-I" + csrc] + \
           extra + [REC, "-o", out, "-ldl"]

@@ -6,6 +6,7 @@
 // kernels whose LDS attribute was raised, the return code, the error text and *kernel_name.  No kernel runs and no device is opened
 // (compile with --offload-host-only).  tools/dev/launch_diff.py builds it twice and compares the two record streams.
 //
+//   -DLAUNCH_POSITIONAL_CALLS   the commits before TrajRequest / LaunchSite: launch_phase_fused / launch_traj_rows take argument lists
 //   launch_rec <rollout | fused | rows> <shard 0..7 | all> [--quick]     one line per block (shape, option): case count + hash of its records
 //   launch_rec <unit> <shard> --dump '<block key>'                       every record of that block, one per line
 #include <dlfcn.h>
@@ -81,18 +82,20 @@ void __hipUnregisterFatBinary(void**) {}
 #include "mpk_traj_phase.hip"
 
 namespace mpk {
-// PhaseArgs and RowArgs are aggregate-initialised by launch_traj_rows, which leaves the padding behind init_time_shared to the stack: not
-// part of what a kernel reads, zeroed before the bytes are hashed (found by argument-dependent lookup from rec::launch)
+// PhaseArgs and RowArgs are aggregate-initialised by launch_traj_rows, which leaves the padding behind init_time_shared (RowArgs: also
+// behind B, its last member) to the stack: not part of what a kernel reads, zeroed before the bytes are hashed (found by
+// argument-dependent lookup from rec::launch)
 template <class A>
-static void arg_bytes_no_padding(const A& a) {
+static void arg_bytes_no_padding(const A& a, size_t end) {
     A b;
     std::memcpy(&b, &a, sizeof(b));
     constexpr size_t from = offsetof(A, init_time_shared) + sizeof(float), to = offsetof(A, pos);
     std::memset(reinterpret_cast<char*>(&b) + from, 0, to - from);
+    std::memset(reinterpret_cast<char*>(&b) + end, 0, sizeof(A) - end);
     rec::arg_bytes(reinterpret_cast<const unsigned char(&)[sizeof(A)]>(b));
 }
-static void arg_bytes(const PhaseArgs& a) { arg_bytes_no_padding(a); }
-static void arg_bytes(const RowArgs& a) { arg_bytes_no_padding(a); }
+static void arg_bytes(const PhaseArgs& a) { arg_bytes_no_padding(a, offsetof(PhaseArgs, h_pad) + sizeof(int)); }
+static void arg_bytes(const RowArgs& a) { arg_bytes_no_padding(a, offsetof(RowArgs, B) + sizeof(int)); }
 static std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 }  // namespace mpk
@@ -251,11 +254,28 @@ unsigned long long fused_case(const DevCfg& c, const Tuning& tune, int B, int cu
     if (it) { gd.check_td = 1; gd.tau_b[0] = 0.5; gd.tau_b[1] = 3.0; gd.delay_b[1] = 0.25; gd.raw_params = fake<float>(42); }
     const char* name = "";
     begin_case();
-    const int r = launch_phase_fused(c, fake<float>(1), fake<float>(2), fake<float>(3), it ? 0.3f : 0.0f, lean ? nullptr : fake<float>(4, oo),
-                                     lean ? nullptr : fake<float>(5, oo), lean ? nullptr : fake<float>(6, oo), rc, fake<double>(9), fake<double>(10),
-                                     closed && !rpl ? fake<int32_t>(11) : nullptr, rpl ? &rp : nullptr, gated ? &gd : nullptr,
-                                     lean ? fake<double>(12) : nullptr, lean ? fake<int32_t>(13) : nullptr, fake<int32_t>(14), B, cu, nullptr, &name,
-                                     tune, fake<int>(15));
+    float* const pos = lean ? nullptr : fake<float>(4, oo);
+    float* const vel = lean ? nullptr : fake<float>(5, oo);
+    float* const actions = lean ? nullptr : fake<float>(6, oo);
+    const int32_t* const n_steps = closed && !rpl ? fake<int32_t>(11) : nullptr;
+    double* const ret = lean ? fake<double>(12) : nullptr;
+    int32_t* const seg_out = lean ? fake<int32_t>(13) : nullptr;
+#ifdef LAUNCH_POSITIONAL_CALLS
+    const int r = launch_phase_fused(c, fake<float>(1), fake<float>(2), fake<float>(3), it ? 0.3f : 0.0f, pos, vel, actions, rc, fake<double>(9),
+                                     fake<double>(10), n_steps, rpl ? &rp : nullptr, gated ? &gd : nullptr, ret, seg_out, fake<int32_t>(14), B, cu,
+                                     nullptr, &name, tune, fake<int>(15));
+#else
+    TrajRequest req;
+    req.params = fake<float>(1); req.init_pos = fake<float>(2); req.init_vel = fake<float>(3); req.init_time_shared = it ? 0.3f : 0.0f;
+    req.pos = pos; req.vel = vel; req.actions = actions; req.rc = &rc; req.n_steps = n_steps;
+    // (the state the kernel reads: the closed loop's plant state, else the frozen one)
+    if (closed) { req.q_state = fake<double>(9); req.qd_state = fake<double>(10); }
+    else { req.c_pos = fake<double>(9); req.c_vel = fake<double>(10); }
+    req.rp = rpl ? &rp : nullptr; req.gate = gated ? &gd : nullptr; req.ep.ret = ret; req.ep.seg_out = seg_out; req.B = B;
+    LaunchSite at;
+    at.num_cu = cu; at.tune = tune; at.kernel_name = &name; at.fault = fake<int>(15); at.range_flag = fake<int32_t>(14);
+    const int r = launch_phase_fused(c, req, at);
+#endif
     return finish(r, name, s, text);
 }
 
@@ -265,8 +285,18 @@ unsigned long long rows_case(const DevCfg& c, const Tuning& tune, int B, int cu,
     const int it = k % 3, oo = k / 3 ? 4 : 0;
     const char* name = "";
     begin_case();
+#ifdef LAUNCH_POSITIONAL_CALLS
     const int r = launch_traj_rows(c, fake<float>(1), fake<float>(2), fake<float>(3), it == 2 ? fake<float>(16) : nullptr, it == 1 ? 0.3f : 0.0f,
                                    fake<float>(4, oo), fake<float>(5, oo), fake<int32_t>(14), B, cu, nullptr, &name, tune);
+#else
+    TrajRequest req;
+    req.params = fake<float>(1); req.init_pos = fake<float>(2); req.init_vel = fake<float>(3);
+    req.init_time = it == 2 ? fake<float>(16) : nullptr; req.init_time_shared = it == 1 ? 0.3f : 0.0f;
+    req.pos = fake<float>(4, oo); req.vel = fake<float>(5, oo); req.B = B;
+    LaunchSite at;
+    at.num_cu = cu; at.tune = tune; at.kernel_name = &name; at.range_flag = fake<int32_t>(14);
+    const int r = launch_traj_rows(c, req, at);
+#endif
     // where launch_traj_phase declined (the launch went on to k_traj_rows or its LDS check): which of its exits, by the shape
     if (tune.phase != 0 && !(c.mp_type == MPK_MP_PROMP && c.T < 2) && std::strncmp(name, "k_traj_phase", 12) != 0) {
         const bool prodmp = c.mp_type == MPK_MP_PRODMP;

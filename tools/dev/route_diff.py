@@ -35,8 +35,10 @@ EXITS = (
 def build(tree, out):
     csrc = os.path.join(tree, "fancy_gym_amd", "csrc")
     old = not os.path.exists(os.path.join(csrc, "mpk_traj_route.h"))
+    # (a base from before the request struct: its launchers take argument lists)
+    positional = "struct TrajRequest" not in open(os.path.join(csrc, "mpk_internal.h")).read()
     cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O2", "-std=c++17", "-ffp-contract=off",
-           "-I" + os.path.join(tree, "include"), "-I" + csrc] + (["-DROUTE_OLD_ABI"] if old else []) + \
+           "-I" + os.path.join(tree, "include"), "-I" + csrc] + (["-DROUTE_OLD_ABI"] if old else []) + (["-DROUTE_POSITIONAL_CALLS"] if positional else []) + \
           [STUB, os.path.join(csrc, "mpk_traj_launch.hip"), "-o", out]
     print("[route_diff]", " ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)

@@ -4,7 +4,8 @@
 // main() sweeps launch_traj_shared / launch_episode_return over shapes, call kinds, pointer alignments and options.  No kernel is
 // launched and no device is opened.  tools/dev/route_diff.py builds it twice and compares the two record streams.
 //
-//   -DROUTE_OLD_ABI   the launchers of the commits before TrajRoute (positional flags); normalised to the same record
+//   -DROUTE_OLD_ABI            the launchers of the commits before TrajRoute (positional flags); normalised to the same record
+//   -DROUTE_POSITIONAL_CALLS   the commits before TrajRequest / LaunchSite: launch_traj_shared / launch_episode_return take argument lists
 //   route_stub <shard 0..3 | all>                one line per block (MP, D, T, KP, option): case count + hash of its records
 //   route_stub <shard> --dump '<block key>'      every record of that block, one per line
 #include <cstdio>
@@ -16,6 +17,8 @@
 #include "mpk_tile.h"
 #ifndef ROUTE_OLD_ABI
 #include "mpk_traj_route.h"
+#elif !defined(ROUTE_POSITIONAL_CALLS)
+#define ROUTE_POSITIONAL_CALLS
 #endif
 
 namespace mpk {
@@ -279,11 +282,26 @@ unsigned long long traj_case(const DevCfg& c, const SharedTables& st, const Tuni
     const char* name = "";
     g_err.clear();
     g_call.n = 0;
+    float* const actions = act ? fake<float>(6, oo) : nullptr;
+    const double* const c_pos = act && !closed ? fake<double>(7, 2 * io) : nullptr;
+    const double* const c_vel = act && !closed ? fake<double>(8, 2 * io) : nullptr;
+    double* const q = closed ? fake<double>(9) : nullptr;
+    double* const qd = closed ? fake<double>(10) : nullptr;
+    const int32_t* const n_steps = closed && !rpl ? fake<int32_t>(11) : nullptr;
+#ifdef ROUTE_POSITIONAL_CALLS
     const int r = launch_traj_shared(c, st, fake<float>(1, io), fake<float>(2, io), fake<float>(3, io), fake<float>(4, oo), fake<float>(5, oo),
-                                     act ? fake<float>(6, oo) : nullptr, act ? &rc : nullptr, act && !closed ? fake<double>(7, 2 * io) : nullptr,
-                                     act && !closed ? fake<double>(8, 2 * io) : nullptr, closed ? fake<double>(9) : nullptr,
-                                     closed ? fake<double>(10) : nullptr, closed && !rpl ? fake<int32_t>(11) : nullptr, B, cu, nullptr, &name, tune,
+                                     actions, act ? &rc : nullptr, c_pos, c_vel, q, qd, n_steps, B, cu, nullptr, &name, tune,
                                      rpl ? &rp : nullptr, fake<unsigned>(12), fake<int>(13), gated ? &gd : nullptr);
+#else
+    TrajRequest req;
+    req.params = fake<float>(1, io); req.init_pos = fake<float>(2, io); req.init_vel = fake<float>(3, io);
+    req.pos = fake<float>(4, oo); req.vel = fake<float>(5, oo); req.actions = actions; req.rc = act ? &rc : nullptr;
+    req.c_pos = c_pos; req.c_vel = c_vel; req.q_state = q; req.qd_state = qd; req.n_steps = n_steps;
+    req.rp = rpl ? &rp : nullptr; req.gate = gated ? &gd : nullptr; req.B = B;
+    LaunchSite at;
+    at.num_cu = cu; at.tune = tune; at.kernel_name = &name; at.ticket = fake<unsigned>(12); at.fault = fake<int>(13);
+    const int r = launch_traj_shared(c, st, req, at);
+#endif
     return finish(r, name, s, text);
 }
 
@@ -303,10 +321,25 @@ unsigned long long ep_case(const DevCfg& c, const SharedTables& st, const Tuning
     const char* name = "";
     g_err.clear();
     g_call.n = 0;
-    const int r = launch_episode_return(c, st, fake<float>(1), fake<float>(2), fake<float>(3), rc, fake<double>(9), fake<double>(10),
-                                        rpl ? nullptr : fake<int32_t>(11), rpl ? &rp : nullptr, rwd ? 1 : 0, rwd ? fake<double>(14) : nullptr,
-                                        rpl ? nullptr : fake<int32_t>(15), 190, variant % 3, fake<double>(16), gated ? nullptr : fake<int32_t>(17), B, cu,
+    const double* const goal = rwd ? fake<double>(14) : nullptr;
+    const int32_t* const n_steps = rpl ? nullptr : fake<int32_t>(11);
+    const int32_t* const step0 = rpl ? nullptr : fake<int32_t>(15);
+    int32_t* const seg_out = gated ? nullptr : fake<int32_t>(17);
+#ifdef ROUTE_POSITIONAL_CALLS
+    const int r = launch_episode_return(c, st, fake<float>(1), fake<float>(2), fake<float>(3), rc, fake<double>(9), fake<double>(10), n_steps,
+                                        rpl ? &rp : nullptr, rwd ? 1 : 0, goal, step0, 190, variant % 3, fake<double>(16), seg_out, B, cu,
                                         nullptr, &name, tune, gated ? &gd : nullptr);
+#else
+    TrajRequest req;
+    req.params = fake<float>(1); req.init_pos = fake<float>(2); req.init_vel = fake<float>(3); req.rc = &rc;
+    req.q_state = fake<double>(9); req.qd_state = fake<double>(10); req.n_steps = n_steps;
+    req.rp = rpl ? &rp : nullptr; req.gate = gated ? &gd : nullptr; req.B = B;
+    req.ep.reward = rwd ? 1 : 0; req.ep.goal = goal; req.ep.step0 = step0; req.ep.steps_before_reward = 190; req.ep.agg = variant % 3;
+    req.ep.ret = fake<double>(16); req.ep.seg_out = seg_out;
+    LaunchSite at;
+    at.num_cu = cu; at.tune = tune; at.kernel_name = &name;
+    const int r = launch_episode_return(c, st, req, at);
+#endif
     return finish(r, name, s, text);
 }
 
