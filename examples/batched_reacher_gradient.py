@@ -4,8 +4,9 @@ Gradient ascent on the return of `fancy_ProDMP/LongSimpleReacher-v0`, all on the
 
 Every episode of the batch (its own start pose and goal, drawn by the seeded device reset) gets its own ProDMP parameter vector, and
 Adam climbs the mean return through `BatchedBlackBox.step(params, differentiable=True)`: plan -> PD controller -> clip -> torque
-plant -> SimpleReacher reward -> aggregation forward, and two launches backward -- `mpk_reacher_rollout_vjp` (the rollout's adjoint)
-and `mpk_trajectory_vjp` (the plan's).  `examples/batched_reacher_search.py` climbs the same return without derivatives.
+plant -> SimpleReacher reward -> aggregation forward in the one launch of the plain step (`mpk_episode_return`), and ONE launch
+backward, `mpk_episode_return_vjp`: the plan recomputed, the rollout's adjoint and the plan's transpose without the desired trajectory
+or its gradient in memory.  `examples/batched_reacher_search.py` climbs the same return without derivatives.
 
     python examples/batched_reacher_gradient.py [--envs 4096] [--iters 100] [--lr 0.02] [--seed 0]
 """

@@ -650,8 +650,9 @@ class BatchedBlackBox:
                 and not self.learn_sub_trajectories and (self._n_phase == 0 or self.reward is None)
                 and (not self.do_replanning or self._lockstep is not None))
 
-    def _step_lean(self, params) -> Optional[Dict[str, torch.Tensor]]:
-        """the verbose < 2 step as ONE launch without per-step outputs (mpk_episode_return); None = not available here"""
+    def _step_lean(self, params, differentiable: bool = False) -> Optional[Dict[str, torch.Tensor]]:
+        """the verbose < 2 step as ONE launch without per-step outputs (mpk_episode_return); None = not available here.
+        ``differentiable``: ``rewards`` carries the graph of ONE mpk_episode_return_vjp launch back to ``params``"""
         gate = self._gate(params)
         was_done = self._was_done() if gate is not None else None
         params = self._plan_params(params)
@@ -663,9 +664,11 @@ class BatchedBlackBox:
                                            replan=(self.traj_steps, self.plan_steps, self.done, self.every, int(mpt), self.horizon),
                                            reward=self.reward, goal=self.goal, steps_before_reward=self.steps_before_reward,
                                            aggregation=self.reward_aggregation, init_time=init_time,
-                                           condition=self.condition_on_desired, gate=gate)
+                                           condition=self.condition_on_desired, gate=gate, differentiable=differentiable)
         except NotImplementedError:
-            self._lean_ok = False
+            # (refused before anything ran.  The plain step never gets another try; a refusal of the gradient says nothing about it.)
+            if not differentiable:
+                self._lean_ok = False
             return None
         if self.condition_on_desired:
             self._store_condition(r["cond_pos"], r["cond_vel"])
@@ -715,10 +718,12 @@ class BatchedBlackBox:
 
     def step(self, params, fuse: bool = True, differentiable: bool = False) -> Dict[str, torch.Tensor]:
         """one plan of every episode.  ``differentiable=True`` (reward "simple_reacher"; off by default, and then nothing changes on any
-        path): the step takes the separate launches under autograd -- differentiable ``get_trajectory`` -> differentiable
-        ``reacher_rollout`` -> ``reward_aggregate`` -- so that ``out["rewards"]`` (and ``step_rewards``) carry the graph back to
-        ``params``: the same values, state and integer outputs as ``step(params, fuse=False)``, and a backward of two launches,
-        mpk_reacher_rollout_vjp and mpk_trajectory_vjp.  With replanning the gradient is that of THIS step's reward w.r.t. THIS
+        path): ``out["rewards"]`` carries the graph back to ``params``.  At ``verbose < 2`` with ``fuse=True`` the step is the one
+        mpk_episode_return launch of the plain step -- the same values, state and integer outputs -- and its backward ONE
+        mpk_episode_return_vjp launch.  With ``verbose >= 2`` or ``fuse=False`` (and where the one-launch gradient does not apply) the step
+        takes the separate launches under autograd -- differentiable ``get_trajectory`` -> differentiable ``reacher_rollout`` ->
+        ``reward_aggregate`` -- so that ``step_rewards`` carry the graph too: the same values, state and integer outputs as
+        ``step(params, fuse=False)``, and a backward of two launches, mpk_reacher_rollout_vjp and mpk_trajectory_vjp.  With replanning the gradient is that of THIS step's reward w.r.t. THIS
         step's parameters: the plant state and the condition the plan starts from are constants of the graph, nothing flows into
         earlier steps.  NotImplementedError: another reward, ``pos_limits``, and what ``trajectory`` refuses under autograd (a learned
         tau / delay, per-episode plan times after partial resets)."""
@@ -729,6 +734,8 @@ class BatchedBlackBox:
         return self._add_observations(out, self._obs_start) if self.observations else out
 
     def _refuse_differentiable(self):
+        """what neither gradient path takes -- the one-launch backward of the ``verbose < 2`` step (mpk_episode_return_vjp) nor the two
+        launches of the separate path: both differentiate SimpleReacher's reward through a plan that is linear in its parameters"""
         if self.reward != "simple_reacher":
             raise NotImplementedError(f"step(differentiable=True) is built for reward='simple_reacher' (the torque double integrator), "
                                       f"not for reward={self.reward!r}: HoleReacher's return is discontinuous at collisions")
@@ -747,6 +754,11 @@ class BatchedBlackBox:
         self._obs_start = (self.q.clone(), self.qd.clone()) if self.observations and self.verbose >= 2 else None
         if differentiable:
             with torch.enable_grad():
+                # the default verbosity: mpk_episode_return forward, one mpk_episode_return_vjp launch backward; what that refuses,
+                # verbose >= 2 and fuse=False take the separate launches (two backward)
+                out = self._step_lean(params, differentiable=True) if fuse and self._can_episode_return() else None
+                if out is not None:
+                    return out
                 out = self._step_full(params, fuse=False, differentiable=True)
             if self.verbose < 2:
                 for k in self._PER_STEP:

@@ -1327,6 +1327,59 @@ int mpk_reacher_rollout_vjp(mpk_handle hh, const mpk_rollout_cfg* rc, const floa
                                       g_q, g_qd, g_des_pos, g_des_vel, g_q0, g_qd0, g_goal, B, T, stream, &h->last_kernel);
 }
 
+// mpk_trajectory + mpk_reacher_rollout_vjp + mpk_trajectory_vjp as one launch: the tables of (init_time_shared, T) as mpk_trajectory
+// finds or builds them, nothing of the forward's launch is reused but its inputs
+int mpk_episode_return_vjp(mpk_handle hh, const float* params, const float* init_pos, const float* init_vel, double init_time_shared,
+                           const mpk_rollout_cfg* rc, const double* q0, const double* qd0, const int32_t* n_steps, const int32_t* step0,
+                           const double* goal, int32_t steps_before_reward, int32_t agg, const double* g_ret, const double* g_q,
+                           const double* g_qd, float* g_params, float* g_init_pos, float* g_init_vel, double* g_q0, double* g_qd0,
+                           double* g_goal, double* q_end, double* qd_end, int32_t B, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (B < 0) { set_error("B must be >= 0"); return MPK_EINVAL; }
+    if (agg < MPK_AGG_SUM || agg > MPK_AGG_LAST) { set_error("unknown reward aggregation"); return MPK_EINVAL; }
+    if (h->cfg.learn_tau || h->cfg.learn_delay) {
+        set_error("mpk_episode_return_vjp: a learned tau / delay makes the trajectory non-linear in those two parameters (and they are "
+                  "clipped to their bounds): only shared-phase handles are differentiable");
+        return MPK_ENOTIMPL;
+    }
+    const Tuning tune = effective_tuning(h);
+    const bool dmp = h->cfg.mp_type == MPK_MP_DMP;
+    if (dmp && (h->cfg.dmp_first_sample == MPK_DMP_FIRST_IS_STEP || !dmp_response(h, nullptr, tune))) {
+        set_error("mpk_episode_return_vjp: a DMP handle is differentiable on its response route only (<= 16 DoF, <= 13 basis functions, "
+                  "alpha ds <= 1, dmp_first_sample = init, option \"dmp_response\" not 0)");
+        return MPK_ENOTIMPL;
+    }
+    const DevCfg& dev = dmp ? h->dev_resp : h->dev;
+    if (dev.D > 0) {
+        if (const int lim = episode_return_vjp_limits(dev); lim != MPK_OK) return lim;
+    }
+    if (rc && rc->plant_type != MPK_PLANT_DOUBLE_INTEGRATOR && rc->plant_type >= 0 && rc->plant_type <= 2) {
+        set_error("mpk_episode_return_vjp differentiates the torque double integrator (MPK_PLANT_DOUBLE_INTEGRATOR) only: a static plant "
+                  "has no rollout to transpose, and HoleReacher's direct-velocity plant is not built");
+        return MPK_ENOTIMPL;
+    }
+    RolloutDev rd;
+    int r = fill_rollout(h, rc, &rd);
+    if (r != MPK_OK) return r;
+    if (B == 0 || dev.D == 0) return MPK_OK;
+    if (!g_params && !g_init_pos && !g_init_vel && !g_q0 && !g_qd0 && !g_goal && !q_end && !qd_end) return MPK_OK;
+    if (!params || !init_pos || !init_vel || !q0 || !qd0 || !goal) { set_error("NULL buffer"); return MPK_EINVAL; }
+    MPK_ON_DEVICE(h->cfg.device);
+    SharedTables st;
+    r = get_shared(h, (float)init_time_shared, stream, &st, dmp);
+    if (r != MPK_OK) return r;
+    EpisodeVjpAsk q;
+    q.params = params; q.init_pos = init_pos; q.init_vel = init_vel; q.q0 = q0; q.qd0 = qd0; q.n_steps = n_steps; q.step0 = step0;
+    q.goal = goal; q.steps_before_reward = steps_before_reward; q.agg = agg; q.g_ret = g_ret; q.g_q = g_q; q.g_qd = g_qd;
+    q.g_params = g_params; q.g_init_pos = g_init_pos; q.g_init_vel = g_init_vel; q.g_q0 = g_q0; q.g_qd0 = g_qd0; q.g_goal = g_goal;
+    q.q_end = q_end; q.qd_end = qd_end;
+    std::string name;
+    r = launch_episode_return_vjp(dev, st, rd, q, B, stream, &name);
+    if (r == MPK_OK) report_kernel(h, name.c_str(), false);
+    return r;
+}
+
 int mpk_hole_reacher_rollout(mpk_handle hh, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel, double* q,
                              double* qd, const int32_t* n_steps, const int32_t* step0, const mpk_hole_task* task, const double* hole,
                              float* actions, double* rewards, double* ret, int32_t agg, int32_t* n_exec, uint8_t* collided,

@@ -198,6 +198,25 @@ int launch_reacher_rollout_vjp(const RolloutDev& rc, int D, const float* des_pos
                                int steps_before_reward, const double* g_rewards, const double* g_q, const double* g_qd,
                                float* g_des_pos, float* g_des_vel, double* g_q0, double* g_qd0, double* g_goal, int B, int T,
                                void* stream, const char** kernel_name);
+// mpk_episode_return_vjp (mpk_episode_vjp.hip): mpk_trajectory, launch_reacher_rollout_vjp and launch_traj_vjp composed in one launch --
+// the plan is recomputed from (params, init_pos, init_vel) with the forward's bits, the desired-trajectory gradients never leave the lane.
+// Any upstream gradient and any output may be nullptr (0 / not written).  c, st: the configuration and tables of the launch (a DMP
+// handle: its response configuration).  MPK_ENOTIMPL: more than kMaxD DoF or kMaxKP columns, a plant other than the double integrator, a
+// horizon whose tile checkpoints do not fit the LDS.
+struct EpisodeVjpAsk {
+    const float *params = nullptr, *init_pos = nullptr, *init_vel = nullptr;   // [B, P], [B, D], [B, D]
+    const double *q0 = nullptr, *qd0 = nullptr;                         // [B, D] the state at the start of the plan
+    const int32_t *n_steps = nullptr, *step0 = nullptr;                 // [B]
+    const double* goal = nullptr;                                       // [B, 2]
+    int steps_before_reward = 0, agg = 0;                               // MPK_AGG_*
+    const double *g_ret = nullptr, *g_q = nullptr, *g_qd = nullptr;     // [B], [B, D], [B, D] upstream
+    float *g_params = nullptr, *g_init_pos = nullptr, *g_init_vel = nullptr;
+    double *g_q0 = nullptr, *g_qd0 = nullptr, *g_goal = nullptr;
+    double *q_end = nullptr, *qd_end = nullptr;                         // [B, D] the state after n_steps, from the replay
+};
+int launch_episode_return_vjp(const DevCfg& c, const SharedTables& st, const RolloutDev& rc, const EpisodeVjpAsk& q, int B, void* stream,
+                              std::string* kernel_name);
+int episode_return_vjp_limits(const DevCfg& c);     // MPK_OK, or MPK_ENOTIMPL with the DoF / column / horizon limit in the message
 // mpk_hole_reacher_rollout (mpk_hole.hip): the HoleReacher step loop with its break on collision
 struct HoleLaunch {
     RolloutDev rc;

@@ -16,6 +16,8 @@
 //   mpk_phase_fused.hip  per-episode phase: the fused entry points (actions, closed loop, replanning step, verbose < 2 step, validity gate)
 //   mpk_rollout.hip      rollout kernels
 //   mpk_rollout_vjp.hip  k_reacher_rollout_vjp: the reacher rollout transposed (mpk_reacher_rollout_vjp)
+//   mpk_episode_vjp.hip  k_episode_return_vjp: plan, rollout adjoint and table transpose in one launch (mpk_episode_return_vjp)
+//   mpk_vjp_row.h        the transpose's table rows and transposed input gather, shared by mpk_traj_vjp.hip and mpk_episode_vjp.hip
 //   mpk_hole.hip         HoleReacher: direct-velocity plant, collisions, reward, break on collision
 //   mpk_reacher_env.h    the reacher envs' draw programs and observation row, shared by the three units below
 //   mpk_reset.hip        reacher resets: numpy's generator per episode (mpk_nprng.h), seeded / continued draws
@@ -35,6 +37,7 @@
 #include "mpk_phase_fused.hip"
 #include "mpk_rollout.hip"
 #include "mpk_rollout_vjp.hip"
+#include "mpk_episode_vjp.hip"
 #include "mpk_hole.hip"
 #include "mpk_reset.hip"
 #include "mpk_obs.hip"

@@ -1,5 +1,6 @@
 // k_traj_vjp_tile / k_traj_vjp_generic: the vector-Jacobian product of the shared-phase trajectory map (mpk_trajectory_vjp)
 #include "mpk_tile.h"
+#include "mpk_vjp_row.h"
 
 namespace mpk {
 
@@ -13,11 +14,7 @@ namespace mpk {
 // followed by the transpose of the forward kernels' input gather (x_kind, mpk_tile.h -- the forward's own function, so the packing and
 // its transpose cannot drift apart): column k of DoF d goes to params[b, off + d Kloc + loc], init_pos[b, d] or init_vel[b, d]; the
 // constant goal-offset column and the padding columns go nowhere.
-//   vjp_row      R0 / R1 of one (column, step).  prodmp / dmp response: the table's rows.  promp: the forward's velocity is the forward
-//                difference of its positions times the reciprocal fp32 time step (aux), last row repeating -- R1 = (R0[th] - R0[tl]) aux[t]
-//                from the position rows alone, which is all a lean (k_traj_wide) table holds.
-//   vjp_scatter  the transposed gather of one element.
-//   vjp_zero_uncovered  inputs no column reads (promp: init_vel always, init_pos unless the basis is zero-padded) get an exact 0.
+// (vjp_row, vjp_scatter, vjp_zero_uncovered: mpk_vjp_row.h, shared with mpk_episode_vjp.hip.)
 // Two routes, one arithmetic recipe each (deterministic: an episode's reduction never leaves its workgroup, plain stores, no atomics):
 //   k_traj_vjp_tile     D <= 16, <= 16 columns, on the matrix cores (below).
 //   k_traj_vjp_generic  everything else (the k_traj_wide shapes): one workgroup per episode, one thread per (column, DoF), float64 sum.
@@ -36,40 +33,6 @@ struct VjpArgs {
     int TP;                // T rounded up to 4: the time chunks of the tile route
     int stride;            // floats per (array, episode) gradient image in LDS
 };
-
-template <int MP>
-__device__ __forceinline__ float vjp_row(const VjpArgs& a, int o, int k, int t) {
-    const DevCfg& c = a.c;
-    if (MP == MPK_MP_PROMP) {
-        const float* r = a.A + (size_t)k * a.TS;
-        if (o == 0) return r[t];
-        const int th = t < c.T - 1 ? t + 1 : c.T - 1, tl = t < c.T - 1 ? t : c.T - 2;
-        return (r[th] - r[tl]) * a.aux[t];
-    }
-    return a.A[((size_t)o * c.KP + k) * a.TS + t];
-}
-
-template <int MP>
-__device__ __forceinline__ void vjp_scatter(const DevCfg& c, int k, int b, int d, float v, float* g_params, float* g_init_pos,
-                                            float* g_init_vel) {
-    int loc;
-    const int kind = x_kind<MP>(c, k, &loc);
-    if (kind == XK_PARAM) {
-        if (g_params) g_params[(size_t)b * c.P + c.off + d * c.Kloc + loc] = v;
-    } else if (kind == XK_IPOS) {
-        if (g_init_pos) g_init_pos[(size_t)b * c.D + d] = v;
-    } else if (kind == XK_IVEL) {
-        if (g_init_vel) g_init_vel[(size_t)b * c.D + d] = v;
-    }
-}
-
-template <int MP>
-__device__ __forceinline__ void vjp_zero_uncovered(const DevCfg& c, int b, int d, float* g_init_pos, float* g_init_vel) {
-    if (MP == MPK_MP_PROMP) {
-        if (g_init_vel) g_init_vel[(size_t)b * c.D + d] = 0.0f;
-        if (g_init_pos && c.KT <= c.nb) g_init_pos[(size_t)b * c.D + d] = 0.0f;
-    }
-}
 
 // floats by which episode b's gradient rows start past a 16-byte boundary
 __device__ __forceinline__ int vjp_shift(const float* g, int b, int TD) {
@@ -106,7 +69,7 @@ __global__ void __launch_bounds__(256) k_traj_vjp_tile(const VjpArgs a) {
     for (int i = tid; i < 2 * 16 * TP; i += 256) {                  // t fastest: coalesced table reads
         const int o = i / (16 * TP), r = i - o * 16 * TP;
         const int k = r / TP, t = r - k * TP;
-        sAt[(o * TP + t) * 16 + k] = (t < T && k < c.KT) ? vjp_row<MP>(a, o, k, t) : 0.0f;
+        sAt[(o * TP + t) * 16 + k] = (t < T && k < c.KT) ? vjp_row<MP>(a.c, a.A, a.aux, a.TS, o, k, t) : 0.0f;
     }
     __syncthreads();
     const int col = lane & 15, q = lane >> 4;
@@ -198,11 +161,11 @@ __global__ void __launch_bounds__(256) k_traj_vjp_generic(const VjpArgs a) {
             double s = 0.0;
             if (a.g_pos) {
                 const float* g = a.g_pos + base + d;
-                for (int t = 0; t < T; ++t) s = fma((double)vjp_row<MP>(a, 0, k, t), (double)g[(size_t)t * D], s);
+                for (int t = 0; t < T; ++t) s = fma((double)vjp_row<MP>(a.c, a.A, a.aux, a.TS, 0, k, t), (double)g[(size_t)t * D], s);
             }
             if (a.g_vel) {
                 const float* g = a.g_vel + base + d;
-                for (int t = 0; t < T; ++t) s = fma((double)vjp_row<MP>(a, 1, k, t), (double)g[(size_t)t * D], s);
+                for (int t = 0; t < T; ++t) s = fma((double)vjp_row<MP>(a.c, a.A, a.aux, a.TS, 1, k, t), (double)g[(size_t)t * D], s);
             }
             vjp_scatter<MP>(c, k, b, d, (float)s, a.g_params, a.g_init_pos, a.g_init_vel);
         }

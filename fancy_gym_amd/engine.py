@@ -127,6 +127,33 @@ class _ReacherRolloutFn(torch.autograd.Function):
         return (None,) * 9 + (g_pos, g_vel, g_goal)
 
 
+class _EpisodeReturnFn(torch.autograd.Function):
+    """``TrajectoryEngine.episode_return(differentiable=True)``: forward = a copy of the plan-start (q, qd) and of the step counters and
+    the mpk_episode_return launch as without autograd, backward = ONE mpk_episode_return_vjp launch (plan, rollout adjoint and table
+    transpose fused); the in-place state and the integer outputs carry no graph"""
+
+    @staticmethod
+    def forward(ctx, engine, launch, spec, q, qd, step0, steps_before_reward, aggregation, init_time, params, init_pos, init_vel, goal):
+        ctx.engine, ctx.spec, ctx.sbr, ctx.agg, ctx.init_time = engine, spec, int(steps_before_reward), aggregation, float(init_time)
+        ctx.start = (q.clone(), qd.clone())
+        ctx.step0 = None if step0 is None else step0.clone()      # (a replanning state's traj_steps is advanced by the launch)
+        r = launch()
+        ctx.seg = r["seg_len"]
+        ctx.save_for_backward(params, init_pos, init_vel, goal)
+        return r["ret"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_ret):
+        params, init_pos, init_vel, goal = ctx.saved_tensors
+        need = ctx.needs_input_grad[9:13]
+        g_params, g_ip, g_iv, _, _, g_goal, _, _ = ctx.engine.episode_return_vjp(
+            params, init_pos, init_vel, ctx.spec, ctx.start[0], ctx.start[1], goal, g_ret, n_steps=ctx.seg, step0=ctx.step0,
+            steps_before_reward=ctx.sbr, aggregation=ctx.agg, init_time=ctx.init_time,
+            need=(need[0], need[1], need[2], False, False, need[3], False, False))
+        return (None,) * 9 + (g_params, g_ip, g_iv, g_goal)
+
+
 class _RewardAggregateFn(torch.autograd.Function):
     """``reward_aggregate`` with a backward: the value is the mpk_reward_aggregate launch's, bit for bit; the aggregation is linear, so
     the gradient of the step rewards is g_ret[b] times 1 (sum), 1 / seg (mean) or the last-step indicator (last) for t < seg[b]"""
@@ -574,7 +601,7 @@ class TrajectoryEngine:
                        replan=None, n_steps: Optional[torch.Tensor] = None, reward: Optional[str] = None,
                        goal: Optional[torch.Tensor] = None, step0: Optional[torch.Tensor] = None,
                        steps_before_reward: int = 199, aggregation: str = "sum", init_time: float = 0.0,
-                       condition: bool = False, gate=None):
+                       condition: bool = False, gate=None, differentiable: bool = False):
         """
         One plan of a ``verbose < 2`` step for every episode in ONE launch, nothing per step stored (mpk.h: mpk_episode_return):
         plan + controller + double-integrator plant + reward + reward_aggregation (+ the integer replanning state and the
@@ -582,8 +609,40 @@ class TrajectoryEngine:
         the replanning state) are updated in place.  Returns dict(ret float64 [B], seg_len int32 [B], done uint8 [B] or None,
         cond_pos, cond_vel (or None)).  NotImplementedError where the fused kernel does not apply (per-episode phase, > 16
         columns / DoF, very long horizons): use replan_step / trajectory_rollout + reacher_rollout + reward_aggregate.
+
+        ``differentiable=True`` (reward "simple_reacher", no gate): the same launch on a copy-protected plan-start state, and ``ret``
+        carries a ``grad_fn`` whose backward is ONE mpk_episode_return_vjp launch (``episode_return_vjp``) to ``params``, ``init_pos``,
+        ``init_vel`` and ``goal`` where they require grad; the plan-start state is a constant of that graph, and under replanning the
+        gradient is that of this plan's return w.r.t. this plan's inputs.  NotImplementedError for what mpk_episode_return_vjp refuses (a
+        learned tau / delay, a DMP off its response route, very long horizons) BEFORE anything is launched.  Without the flag nothing
+        changes: inputs that require grad are treated as constants.
         """
         self._refuse_metaworld(spec, "episode_return")
+        if differentiable:
+            if reward != "simple_reacher" or gate is not None:
+                raise NotImplementedError("episode_return(differentiable=True) is built for reward='simple_reacher' without a validity gate")
+            params = torch.as_tensor(params, dtype=torch.float32, device=self.device)
+            if params.dim() == 1:
+                params = params[None]
+            Bn = params.shape[0]
+            init_pos, init_vel = self._f32(init_pos, (Bn, self.num_dof)), self._f32(init_vel, (Bn, self.num_dof))
+            goal = torch.as_tensor(goal, dtype=torch.float64, device=self.device).expand(Bn, 2)
+            if torch.is_grad_enabled() and any(t.requires_grad for t in (params, init_pos, init_vel, goal)):
+                # what the backward would refuse is refused here, before the forward changes the state (B = 0: the checks alone, no launch)
+                _lib.check(self._lib.mpk_episode_return_vjp(self._h, None, None, None, float(init_time), C.byref(spec.c), *([None] * 5),
+                                                            int(steps_before_reward), _lib.AGG_MODES.get(aggregation, 0),
+                                                            *([None] * 11), 0, self._stream()))
+                res = {}
+
+                def launch():
+                    res.update(self.episode_return(params.detach(), init_pos.detach(), init_vel.detach(), spec, q, qd, replan=replan,
+                                                   n_steps=n_steps, reward=reward, goal=goal.detach(), step0=step0,
+                                                   steps_before_reward=steps_before_reward, aggregation=aggregation,
+                                                   init_time=init_time, condition=condition))
+                    return res
+                ret = _EpisodeReturnFn.apply(self, launch, spec, q, qd, replan[0] if replan is not None else step0, steps_before_reward,
+                                             aggregation, init_time, params.contiguous(), init_pos, init_vel, goal.contiguous())
+                return dict(res, ret=ret)
         params = torch.as_tensor(params, dtype=torch.float32, device=self.device)
         if params.dim() == 1:
             params = params[None]
@@ -758,6 +817,68 @@ class TrajectoryEngine:
             self._h, C.byref(spec.c), des_pos.data_ptr(), des_vel.data_ptr(), q0.data_ptr(), qd0.data_ptr(), _dptr(n_steps),
             _dptr(step0), goal.data_ptr(), int(steps_before_reward), _dptr(ups[0]), _dptr(ups[1]), _dptr(ups[2]), _dptr(res[0]),
             _dptr(res[1]), _dptr(res[2]), _dptr(res[3]), _dptr(res[4]), B, T, self._stream()))
+        return tuple(res)
+
+    def episode_return_vjp(self, params, init_pos, init_vel, spec: RolloutSpec, q0: torch.Tensor, qd0: torch.Tensor,
+                           goal: torch.Tensor, g_ret: Optional[torch.Tensor], *, g_q: Optional[torch.Tensor] = None,
+                           g_qd: Optional[torch.Tensor] = None, n_steps: Optional[torch.Tensor] = None,
+                           step0: Optional[torch.Tensor] = None, steps_before_reward: int = 199, aggregation: str = "sum",
+                           init_time: float = 0.0, need: Sequence[bool] = (True, True, True, True, True, True, False, False),
+                           out: Optional[Sequence[Optional[torch.Tensor]]] = None):
+        """
+        The vector-Jacobian product of ``episode_return`` with reward "simple_reacher" (mpk.h: mpk_episode_return_vjp), ONE launch --
+        ``trajectory``, ``reacher_rollout_vjp`` and ``trajectory_vjp`` composed without the plan or its gradient in memory: the gradients
+        of a loss w.r.t. the aggregated reward [B] float64 and the final state (``g_q``, ``g_qd`` [B, D] float64; any of the three may
+        be None = 0) -> (g_params [B, P], g_init_pos, g_init_vel [B, D] float32, g_q0, g_qd0 [B, D], g_goal [B, 2] float64, q_end, qd_end
+        [B, D] float64: the state after ``n_steps`` as the replay finds it, the bits ``episode_return`` leaves in q, qd).  ``q0``, ``qd0``
+        are the state at the START of the plan (episode_return overwrites its q, qd: pass a copy taken before) and ``n_steps`` the
+        executed steps (its ``seg_len``; None = all).  ``need[i]`` False: that output is not computed (None in its place); ``out``:
+        buffers for the needed ones.  NotImplementedError: a learned tau / delay, a DMP off its response route, more than 16 DoF or
+        contraction columns, a plant other than the double integrator, horizons beyond about 2 200 steps.
+        """
+        if getattr(spec, "metaworld", False) or spec.plant != "double_integrator":
+            raise NotImplementedError("episode_return_vjp differentiates the torque double integrator only (plant='double_integrator'): "
+                                      "the metaworld controller runs on a frozen state, HoleReacher's direct-velocity plant is not built")
+        if aggregation not in _lib.AGG_MODES:
+            raise ValueError(f"unknown reward aggregation {aggregation!r}; choose one of {list(_lib.AGG_MODES)}")
+        params = torch.as_tensor(params, dtype=torch.float32, device=self.device).detach()
+        if params.dim() == 1:
+            params = params[None]
+        params = params.contiguous()
+        B, D = params.shape[0], self.num_dof
+        if params.shape[1] != self.num_params:
+            raise ValueError(f"params has {params.shape[1]} entries per episode, expected {self.num_params}")
+        init_pos, init_vel = self._f32(init_pos, (B, D)).detach(), self._f32(init_vel, (B, D)).detach()
+        q0, qd0 = self._f64(q0, (B, D)).detach(), self._f64(qd0, (B, D)).detach()
+        goal = torch.as_tensor(goal, dtype=torch.float64, device=self.device).detach().expand(B, 2).contiguous()
+        ups = []
+        for name, g, shape in (("g_ret", g_ret, (B,)), ("g_q", g_q, (B, D)), ("g_qd", g_qd, (B, D))):
+            if g is not None:
+                g = torch.as_tensor(g, dtype=torch.float64, device=self.device)
+                if tuple(g.shape) != shape:
+                    raise ValueError(f"{name} must be {list(shape)}, got {list(g.shape)}")
+                g = g.detach().contiguous()
+            ups.append(g)
+        if n_steps is not None:
+            n_steps = n_steps.to(device=self.device, dtype=torch.int32).contiguous()
+        if step0 is not None:
+            step0 = step0.to(device=self.device, dtype=torch.int32).contiguous()
+        f32, f64 = torch.float32, torch.float64
+        res = []
+        for i, (shape, dtype) in enumerate((((B, self.num_params), f32), ((B, D), f32), ((B, D), f32), ((B, D), f64), ((B, D), f64),
+                                            ((B, 2), f64), ((B, D), f64), ((B, D), f64))):
+            if not need[i]:
+                res.append(None)
+            elif out is not None and out[i] is not None:
+                if tuple(out[i].shape) != shape or out[i].dtype != dtype or not out[i].is_contiguous() or out[i].device != self.device:
+                    raise ValueError(f"out[{i}] must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+                res.append(out[i])
+            else:
+                res.append(torch.empty(shape, dtype=dtype, device=self.device))
+        _lib.check(self._lib.mpk_episode_return_vjp(
+            self._h, params.data_ptr(), init_pos.data_ptr(), init_vel.data_ptr(), float(init_time), C.byref(spec.c), q0.data_ptr(),
+            qd0.data_ptr(), _dptr(n_steps), _dptr(step0), goal.data_ptr(), int(steps_before_reward), _lib.AGG_MODES[aggregation],
+            _dptr(ups[0]), _dptr(ups[1]), _dptr(ups[2]), *(_dptr(r) for r in res), B, self._stream()))
         return tuple(res)
 
     def hole_reacher_rollout(self, spec: RolloutSpec, des_pos: Optional[torch.Tensor], des_vel: torch.Tensor, q: torch.Tensor,

@@ -951,6 +951,36 @@ int mpk_reacher_rollout_vjp(mpk_handle h, const mpk_rollout_cfg* rc, const float
                             float* g_des_pos, float* g_des_vel, double* g_q0, double* g_qd0, double* g_goal, int32_t B, int32_t T,
                             void* stream);
 
+/*
+ * The gradient of mpk_episode_return's aggregated SimpleReacher reward in ONE launch (appended under ABI 4): exactly the composition of
+ * mpk_trajectory, mpk_reacher_rollout_vjp and mpk_trajectory_vjp above, for a handle with a shared phase, without the desired
+ * trajectory, the step rewards or their gradients ever reaching memory.  The adjoint formulas of mpk_reacher_rollout_vjp are the
+ * specification; the step-reward gradients come from the aggregation, g_r[b, t] = g_ret[b] w_t for t < n_steps[b] with w_t = 1
+ * (MPK_AGG_SUM), 1 / n_steps[b] (MPK_AGG_MEAN) or [t == n_steps[b] - 1] (MPK_AGG_LAST); the parameter gradients follow
+ * mpk_trajectory_vjp (the forward's own input gather transposed, exact zeros for inputs no column reads).
+ *   params, init_pos, init_vel, init_time_shared, rc   as mpk_episode_return: the plan is recomputed from them, with the forward's bits
+ *   q0, qd0      dev double [B, D]     the state at the START of the plan (mpk_episode_return overwrites its q, qd: keep a copy); const
+ *   n_steps, step0, goal, steps_before_reward   as mpk_reacher_rollout_vjp (n_steps: mpk_episode_return's seg_out; NULL = T)
+ *   agg, g_ret   MPK_AGG_*; dev double [B] = d loss / d ret, or NULL = 0
+ *   g_q, g_qd    dev double [B, D] or NULL   d loss / d final state; NULL = 0
+ *   g_params     dev float [B, P]  out;  g_init_pos, g_init_vel  dev float [B, D] out: the float64 sums rounded once
+ *   g_q0, g_qd0  dev double [B, D] out;  g_goal dev double [B, 2] out
+ *   q_end, qd_end   dev double [B, D] out: the state after n_steps as the replay finds it -- the bits mpk_episode_return leaves in q, qd
+ * Any output may be NULL: not written.  An episode with n_steps = 0 has zero parameter gradients and passes g_q, g_qd through.
+ * k_episode_return_vjp<mp, controller[, D]> (mpk_last_kernel): k_reacher_rollout_vjp's lane map, checkpoints, replay and reverse chain;
+ * a lane plans its DoF's desired (pos, vel) of a step from its parameter column and the step's table row with the fp32 fmaf chain of the
+ * forward's matrix-core contraction, and adds the step's desired-trajectory gradient times the same row to 16 float64 column
+ * accumulators, t descending.  One launch on `stream` (plus the table builder when (init_time_shared, T) is not cached, exactly as
+ * mpk_trajectory); nothing is allocated or synchronised, no atomics: the same bits from run to run and for any pointer alignment.
+ * MPK_ENOTIMPL: a learned tau / delay; a DMP handle outside its response route; more than 16 DoF or 16 contraction columns; a plant other
+ * than MPK_PLANT_DOUBLE_INTEGRATOR; a horizon whose checkpoints (1 KB of LDS per 16 steps) do not fit the CU's 160 KB (about 2 200 steps).
+ */
+int mpk_episode_return_vjp(mpk_handle h, const float* params, const float* init_pos, const float* init_vel, double init_time_shared,
+                           const mpk_rollout_cfg* rc, const double* q0, const double* qd0, const int32_t* n_steps, const int32_t* step0,
+                           const double* goal, int32_t steps_before_reward, int32_t agg, const double* g_ret, const double* g_q,
+                           const double* g_qd, float* g_params, float* g_init_pos, float* g_init_vel, double* g_q0, double* g_qd0,
+                           double* g_goal, double* q_end, double* qd_end, int32_t B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
