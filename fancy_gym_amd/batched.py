@@ -58,7 +58,8 @@ class BatchedBlackBox:
                  check_tau_delay: bool = False, reward: Optional[str] = None, steps_before_reward: int = 199,
                  device=None, learn_sub_trajectories: bool = False, reward_aggregation="sum", verbose: int = 2,
                  collision_penalty: float = 100.0, allow_self_collision: bool = False, allow_wall_collision: bool = False,
-                 env_kwargs: Optional[dict] = None, observations: bool = False, rew_fct: str = "simple"):
+                 env_kwargs: Optional[dict] = None, observations: bool = False, rew_fct: str = "simple",
+                 collision_gradient: Optional[str] = None):
         """
         trajectory_generator / tracking_controller: the objects the factories return (``get_trajectory_generator``,
         ``get_controller``).  ``replanning_every = n`` is the schedule ``lambda pos, vel, obs, action, t: t % n == 0``
@@ -111,7 +112,16 @@ class BatchedBlackBox:
         path accepts; the per-episode fallback kernel behind "pd_generic" 1 / D = 1 sums a step's squared actions as a tree: 1e-13
         relative -- mpk.h, mpk_episode_return).  Falls back to the verbose = 2 launches (and drops their arrays)
         where the fused kernel does not apply: sub-trajectories, a device reward together with a learned phase, drifted episodes.
+
+        ``collision_gradient`` (None, the default, or "frozen"): HoleReacher's return is discontinuous where a collision starts or the
+        episode's end moves, so ``step(differentiable=True)`` refuses reward "hole_reacher" unless this says what the gradient should
+        be.  "frozen": the pathwise gradient with each episode's end and collision verdict held at what the forward found -- the
+        collision penalty is a constant, the distance paid on the colliding step still pulls the arm (mpk_hole_reacher_rollout_vjp;
+        rew_fct "simple" and "vel_acc").  Ignored by the other rewards.
         """
+        if collision_gradient not in (None, "frozen"):
+            raise ValueError(f"collision_gradient must be None or 'frozen', got {collision_gradient!r}")
+        self.collision_gradient = collision_gradient
         if rew_fct != "simple" and reward != "hole_reacher":
             raise ValueError(f"rew_fct={rew_fct!r} is HoleReacher's reward function: it needs reward='hole_reacher'")
         _lib.hole_rew_fct(rew_fct, steps_before_reward)        # (refused before anything is built)
@@ -725,8 +735,12 @@ class BatchedBlackBox:
         ``reward_aggregate`` -- so that ``step_rewards`` carry the graph too: the same values, state and integer outputs as
         ``step(params, fuse=False)``, and a backward of two launches, mpk_reacher_rollout_vjp and mpk_trajectory_vjp.  With replanning the gradient is that of THIS step's reward w.r.t. THIS
         step's parameters: the plant state and the condition the plan starts from are constants of the graph, nothing flows into
-        earlier steps.  NotImplementedError: another reward, ``pos_limits``, and what ``trajectory`` refuses under autograd (a learned
-        tau / delay, per-episode plan times after partial resets)."""
+        earlier steps.  Reward "hole_reacher" takes part only with ``collision_gradient="frozen"`` (the constructor's argument): the
+        plain step's two launches under autograd, the same values, state and integer outputs, and a backward of two launches,
+        mpk_hole_reacher_rollout_vjp at the forward's own ``trajectory_length`` / ``is_collided`` and mpk_trajectory_vjp; at
+        ``verbose < 2`` nothing per step is stored.  NotImplementedError: another reward, HoleReacher without that option or with rew_fct
+        "unbounded", ``pos_limits``, and what ``trajectory`` refuses under autograd (a learned tau / delay, per-episode plan times after
+        partial resets)."""
         if differentiable:
             self._refuse_differentiable()
         out = self._step(params, fuse, differentiable)
@@ -735,10 +749,16 @@ class BatchedBlackBox:
 
     def _refuse_differentiable(self):
         """what neither gradient path takes -- the one-launch backward of the ``verbose < 2`` step (mpk_episode_return_vjp) nor the two
-        launches of the separate path: both differentiate SimpleReacher's reward through a plan that is linear in its parameters"""
-        if self.reward != "simple_reacher":
+        launches of the separate path: both differentiate SimpleReacher's reward through a plan that is linear in its parameters --
+        nor HoleReacher's two launches, which differentiate only where ``collision_gradient`` says how"""
+        frozen = self.reward == "hole_reacher" and getattr(self, "collision_gradient", None) == "frozen"
+        if self.reward != "simple_reacher" and not frozen:
             raise NotImplementedError(f"step(differentiable=True) is built for reward='simple_reacher' (the torque double integrator), "
-                                      f"not for reward={self.reward!r}: HoleReacher's return is discontinuous at collisions")
+                                      f"not for reward={self.reward!r}: HoleReacher's return is discontinuous at collisions "
+                                      f"(collision_gradient='frozen' gives its gradient with the episode's end and verdict held)")
+        if frozen and getattr(self, "rew_fct", "simple") == "unbounded":
+            raise NotImplementedError("step(differentiable=True) with collision_gradient='frozen' takes rew_fct 'simple' and 'vel_acc': "
+                                      "'unbounded' pays on the end effector stored at step 180, which may belong to an earlier plan")
         if self.pos_limits is not None:
             raise NotImplementedError("step(differentiable=True) does not take pos_limits: the validity gate ends episodes on a "
                                       "threshold of the plan, which has no derivative")
@@ -752,6 +772,11 @@ class BatchedBlackBox:
     def _step(self, params, fuse: bool, differentiable: bool = False) -> Dict[str, torch.Tensor]:
         self._plans_since_reset += 1
         self._obs_start = (self.q.clone(), self.qd.clone()) if self.observations and self.verbose >= 2 else None
+        if differentiable and self.reward == "hole_reacher":
+            # collision_gradient="frozen": the plan and the rollout under autograd, two launches backward (mpk_hole_reacher_rollout_vjp,
+            # mpk_trajectory_vjp); at verbose < 2 nothing per step is stored, the return's gradient enters the kernel through agg
+            with torch.enable_grad():
+                return self._step_hole(params, differentiable=True)
         if differentiable:
             with torch.enable_grad():
                 # the default verbosity: mpk_episode_return forward, one mpk_episode_return_vjp launch backward; what that refuses,
@@ -813,7 +838,7 @@ class BatchedBlackBox:
         return self._finish(out, seg, valid, was_done)
 
 
-    def _step_hole(self, params) -> Dict[str, torch.Tensor]:
+    def _step_hole(self, params, differentiable: bool = False) -> Dict[str, torch.Tensor]:
         """HoleReacher: the plan, then ONE rollout launch that advances the integer state, executes until the plan ends or the
         arm collides, and commits the break (mpk_hole_reacher_rollout); at verbose < 2 it stores nothing per step.  The plan's
         init_time is the shared clock while the episodes move in lockstep, per episode from the device counters after a partial reset"""
@@ -826,7 +851,7 @@ class BatchedBlackBox:
             self.spec, pos, vel, self.q, self.qd, self.hole, steps_before_reward=self.steps_before_reward,
             replan=(self.traj_steps, self.plan_steps, self.done, self.every, int(mpt), self.horizon),
             condition=self.condition_on_desired, want_actions=full, want_rewards=full, aggregation=self.reward_aggregation,
-            rew_fct=self.rew_fct, reward_state=self._reward_state, **self.hole_task)
+            rew_fct=self.rew_fct, reward_state=self._reward_state, differentiable=differentiable, **self.hole_task)
         if self.condition_on_desired:
             self._store_condition(r["cond_pos"], r["cond_vel"])
         if self.do_replanning and self._lockstep is not None:

@@ -1431,6 +1431,48 @@ int mpk_hole_reacher_rollout2(mpk_handle hh, const mpk_rollout_cfg* rc, const fl
     return launch_hole_rollout(hl, B, T, D, stream, effective_tuning(h));
 }
 
+// the adjoint of mpk_hole_reacher_rollout2 with the episode's end and verdict frozen: nothing of the forward's launch is reused but its
+// inputs and its (n_exec, collided)
+int mpk_hole_reacher_rollout_vjp(mpk_handle hh, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel, const double* q0,
+                                 const double* qd0, const int32_t* n_exec, const int32_t* step0, const mpk_hole_task* task,
+                                 const double* hole, const uint8_t* collided, int32_t agg, const double* g_ret, const double* g_rewards,
+                                 const double* g_q, const double* g_qd, float* g_des_pos, float* g_des_vel, double* g_q0, double* g_qd0,
+                                 double* g_hole, int32_t B, int32_t T, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (B < 0 || T < 0) { set_error("B and T must be >= 0"); return MPK_EINVAL; }
+    if (h->dev.D > kMaxD) {
+        set_error("mpk_hole_reacher_rollout_vjp: " + std::to_string(h->dev.D) + " DoF, the kernel takes at most 16 (one lane per "
+                  "(episode, DoF), the links of a paid step summed inside a wave)");
+        return MPK_ENOTIMPL;
+    }
+    HoleVjpLaunch hl;
+    int r = fill_rollout(h, rc, &hl.rc, true);
+    if (r != MPK_OK) return r;
+    if (!task) { set_error("task is NULL"); return MPK_EINVAL; }
+    if (task->rew_fct < MPK_HOLE_REW_SIMPLE || task->rew_fct > MPK_HOLE_REW_UNBOUNDED) { set_error("unknown rew_fct (MPK_HOLE_REW_*)"); return MPK_EINVAL; }
+    if (task->rew_fct == MPK_HOLE_REW_UNBOUNDED) {
+        set_error("mpk_hole_reacher_rollout_vjp: rew_fct unbounded pays on the end effector stored at step 180, which may belong to an "
+                  "earlier plan: its gradient crosses plans and is not built (simple and vel_acc are)");
+        return MPK_ENOTIMPL;
+    }
+    if (task->rew_fct != MPK_HOLE_REW_SIMPLE && task->steps_before_reward != 199) {
+        set_error("rew_fct vel_acc pays at the reference's step 199: steps_before_reward must be 199");
+        return MPK_EINVAL;
+    }
+    if (agg < MPK_AGG_SUM || agg > MPK_AGG_LAST) { set_error("unknown reward aggregation"); return MPK_EINVAL; }
+    if (B == 0 || h->dev.D == 0) return MPK_OK;
+    if (!g_des_pos && !g_des_vel && !g_q0 && !g_qd0 && !g_hole) return MPK_OK;
+    const bool need_pos = rc->controller_type != MPK_CTRL_VELOCITY, need_vel = rc->controller_type != MPK_CTRL_POSITION;
+    if (!q0 || !qd0 || !hole || (T > 0 && ((need_pos && !des_pos) || (need_vel && !des_vel)))) { set_error("NULL buffer"); return MPK_EINVAL; }
+    hl.des_pos = des_pos; hl.des_vel = des_vel; hl.q0 = q0; hl.qd0 = qd0; hl.n_exec = n_exec; hl.step0 = step0; hl.hole = hole;
+    hl.collided = collided; hl.agg = agg; hl.g_ret = g_ret; hl.g_rewards = g_rewards; hl.g_q = g_q; hl.g_qd = g_qd;
+    hl.g_des_pos = g_des_pos; hl.g_des_vel = g_des_vel; hl.g_q0 = g_q0; hl.g_qd0 = g_qd0; hl.g_hole = g_hole;
+    hl.penalty = task->collision_penalty; hl.steps_before_reward = task->steps_before_reward; hl.rew_fct = task->rew_fct;
+    MPK_ON_DEVICE(h->cfg.device);
+    return launch_hole_rollout_vjp(hl, B, T, h->dev.D, stream, &h->last_kernel);
+}
+
 int mpk_episode_reset(mpk_handle hh, const double* init_q, const double* init_qd, double* q, double* qd,
                       float* cond_pos, float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done,
                       int32_t B, void* stream) {

@@ -240,6 +240,25 @@ struct HoleLaunch {
     double* reward_state = nullptr;         // [B, 2] unbounded's stored end effector (MPK_HOLE_REW_UNBOUNDED only)
 };
 int launch_hole_rollout(const HoleLaunch& h, int B, int T, int D, void* stream, const Tuning& tune);
+// mpk_hole_reacher_rollout_vjp (mpk_hole_vjp.hip): the adjoint of launch_hole_rollout's computation with the episode's end and collision
+// verdict frozen (n_exec, collided: the forward's outputs), one launch; any upstream gradient and any output may be nullptr (0 / not
+// written).  rew_fct: MPK_HOLE_REW_SIMPLE or _VEL_ACC.  MPK_ENOTIMPL: more than kMaxD DoF, a horizon whose tile checkpoints do not fit
+// the LDS.
+struct HoleVjpLaunch {
+    RolloutDev rc;
+    const float *des_pos = nullptr, *des_vel = nullptr;                 // [B, T, D]; the one the controller does not read may be nullptr
+    const double *q0 = nullptr, *qd0 = nullptr;                         // [B, D] the state at the start of the plan
+    const int32_t *n_exec = nullptr, *step0 = nullptr;                  // [B]
+    const double* hole = nullptr;                                       // [B, 3]
+    const uint8_t* collided = nullptr;                                  // [B]
+    int agg = 0;                                                        // MPK_AGG_*
+    const double *g_ret = nullptr, *g_rewards = nullptr, *g_q = nullptr, *g_qd = nullptr;   // [B], [B, T], [B, D], [B, D] upstream
+    float *g_des_pos = nullptr, *g_des_vel = nullptr;
+    double *g_q0 = nullptr, *g_qd0 = nullptr, *g_hole = nullptr;
+    double penalty = 0.0;
+    int steps_before_reward = 0, rew_fct = 0;
+};
+int launch_hole_rollout_vjp(const HoleVjpLaunch& h, int B, int T, int D, void* stream, const char** kernel_name);
 int launch_episode_reset(const double* init_q, const double* init_qd, double* q, double* qd, float* cond_pos,
                          float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done, int B, int D,
                          void* stream);

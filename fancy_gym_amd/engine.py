@@ -127,6 +127,44 @@ class _ReacherRolloutFn(torch.autograd.Function):
         return (None,) * 9 + (g_pos, g_vel, g_goal)
 
 
+class _HoleRolloutFn(torch.autograd.Function):
+    """``TrajectoryEngine.hole_reacher_rollout(differentiable=True)``: forward = a copy of the plan-start (q, qd) and of the step counters
+    and the mpk_hole_reacher_rollout2 launch as without autograd, backward = ONE mpk_hole_reacher_rollout_vjp launch at the forward's own
+    (n_exec, collided) -- the episode's end and verdict are frozen; the actions, the in-place state and the integer outputs carry no
+    graph.  Returns (ret, rewards) -- either may be None --, the launch's dict is left in ``box``"""
+
+    @staticmethod
+    def forward(ctx, engine, launch, box, spec, q, qd, step0, task_kw, aggregation, des_pos, des_vel, hole):
+        ctx.engine, ctx.spec, ctx.task_kw, ctx.agg = engine, spec, task_kw, aggregation
+        ctx.start = (q.clone(), qd.clone())
+        ctx.step0 = None if step0 is None else step0.clone()      # (a replanning state's traj_steps is advanced by the launch)
+        r = launch()
+        box.update(r)
+        ctx.n_exec, ctx.collided = r["n_exec"], r["collided"]
+        ctx.has_pos = des_pos is not None
+        ctx.save_for_backward(*([des_pos] if ctx.has_pos else []), des_vel, hole)
+        ctx.set_materialize_grads(False)
+        outs = tuple(t for t in (r["ret"], r["rewards"]) if t is not None)
+        ctx.which = tuple(k for k in ("ret", "rewards") if r[k] is not None)
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        saved = ctx.saved_tensors
+        des_pos = saved[0] if ctx.has_pos else None
+        des_vel, hole = saved[-2], saved[-1]
+        g = dict(zip(ctx.which, grads))
+        need = ctx.needs_input_grad[9:12]
+        if g.get("ret") is None and g.get("rewards") is None:
+            return (None,) * 12
+        g_pos, g_vel, _, _, g_hole = ctx.engine.hole_reacher_rollout_vjp(
+            ctx.spec, des_pos, des_vel, ctx.start[0], ctx.start[1], hole, n_exec=ctx.n_exec, collided=ctx.collided, step0=ctx.step0,
+            g_rewards=g.get("rewards"), g_ret=g.get("ret"), aggregation=ctx.agg or "sum",
+            need=(bool(need[0]) and ctx.has_pos, need[1], False, False, need[2]), **ctx.task_kw)
+        return (None,) * 9 + (g_pos, g_vel, g_hole)
+
+
 class _EpisodeReturnFn(torch.autograd.Function):
     """``TrajectoryEngine.episode_return(differentiable=True)``: forward = a copy of the plan-start (q, qd) and of the step counters and
     the mpk_episode_return launch as without autograd, backward = ONE mpk_episode_return_vjp launch (plan, rollout adjoint and table
@@ -881,13 +919,82 @@ class TrajectoryEngine:
             _dptr(ups[0]), _dptr(ups[1]), _dptr(ups[2]), *(_dptr(r) for r in res), B, self._stream()))
         return tuple(res)
 
+    def hole_reacher_rollout_vjp(self, spec: RolloutSpec, des_pos: Optional[torch.Tensor], des_vel: Optional[torch.Tensor],
+                                 q0: torch.Tensor, qd0: torch.Tensor, hole: torch.Tensor, *, n_exec: Optional[torch.Tensor],
+                                 collided: Optional[torch.Tensor], step0: Optional[torch.Tensor] = None,
+                                 g_rewards: Optional[torch.Tensor] = None, g_ret: Optional[torch.Tensor] = None,
+                                 aggregation: str = "sum", g_q: Optional[torch.Tensor] = None, g_qd: Optional[torch.Tensor] = None,
+                                 rew_fct: str = "simple", collision_penalty: float = 100.0, steps_before_reward: int = 199,
+                                 need: Sequence[bool] = (True, True, True, True, True),
+                                 out: Optional[Sequence[Optional[torch.Tensor]]] = None):
+        """
+        The vector-Jacobian product of ``hole_reacher_rollout`` with the episode's end and collision verdict frozen (mpk.h:
+        mpk_hole_reacher_rollout_vjp), one launch: the gradients of a loss w.r.t. the step rewards [B, T], their aggregate ``g_ret`` [B]
+        (``aggregation``: how the forward formed it) and the final state (``g_q``, ``g_qd`` [B, D]; float64, any of the four may be
+        None = 0) -> (g_des_pos, g_des_vel float32 [B, T, D], g_q0, g_qd0 float64 [B, D], g_hole float64 [B, 3]).  ``n_exec`` int32 [B]
+        and ``collided`` uint8 [B] are the forward's outputs (None = T / no collision); ``q0``, ``qd0`` the state at the START of the
+        plan (hole_reacher_rollout overwrites its q, qd: pass a copy taken before) and ``step0`` the env step counter there (a
+        replanning forward: a copy of traj_steps before the plan).  The velocity controller reads ``des_vel`` only (``des_pos`` may be
+        None, its gradient is zeros), the position controller the other way round.  ``need[i]`` False: that output is not computed (None
+        in its place); ``out``: buffers for the needed ones.  ValueError: a plant other than 'velocity_direct'.  NotImplementedError:
+        rew_fct 'unbounded', more than 16 DoF, horizons beyond about 2 200 steps.
+        """
+        if spec.plant != "velocity_direct":
+            raise ValueError("hole_reacher_rollout_vjp differentiates plant='velocity_direct' (reacher_rollout_vjp: the double integrator)")
+        if aggregation not in _lib.AGG_MODES:
+            raise ValueError(f"unknown reward aggregation {aggregation!r}; choose one of {list(_lib.AGG_MODES)}")
+        rew = _lib.hole_rew_fct(rew_fct, steps_before_reward)
+        ref = des_vel if des_vel is not None else des_pos
+        if ref is None:
+            raise ValueError("hole_reacher_rollout_vjp needs des_pos or des_vel")
+        B, T, D = ref.shape
+        des = []
+        for t in (des_pos, des_vel):
+            if t is not None:
+                assert t.dtype == torch.float32 and tuple(t.shape) == (B, T, D)
+                t = t.detach().contiguous()
+            des.append(t)
+        q0, qd0 = self._f64(q0, (B, D)).detach(), self._f64(qd0, (B, D)).detach()
+        hole = torch.as_tensor(hole, dtype=torch.float64, device=self.device).detach().expand(B, 3).contiguous()
+        ups = []
+        for name, g, shape in (("g_ret", g_ret, (B,)), ("g_rewards", g_rewards, (B, T)), ("g_q", g_q, (B, D)), ("g_qd", g_qd, (B, D))):
+            if g is not None:
+                g = torch.as_tensor(g, dtype=torch.float64, device=self.device)
+                if tuple(g.shape) != shape:
+                    raise ValueError(f"{name} must be {list(shape)}, got {list(g.shape)}")
+                g = g.detach().contiguous()
+            ups.append(g)
+        if n_exec is not None:
+            n_exec = n_exec.to(device=self.device, dtype=torch.int32).contiguous()
+        if collided is not None:
+            collided = collided.to(device=self.device, dtype=torch.uint8).contiguous()
+        if step0 is not None:
+            step0 = step0.to(device=self.device, dtype=torch.int32).contiguous()
+        res = []
+        for i, (shape, dtype) in enumerate((((B, T, D), torch.float32), ((B, T, D), torch.float32), ((B, D), torch.float64),
+                                            ((B, D), torch.float64), ((B, 3), torch.float64))):
+            if not need[i]:
+                res.append(None)
+            elif out is not None and out[i] is not None:
+                if tuple(out[i].shape) != shape or out[i].dtype != dtype or not out[i].is_contiguous() or out[i].device != self.device:
+                    raise ValueError(f"out[{i}] must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+                res.append(out[i])
+            else:
+                res.append(torch.empty(shape, dtype=dtype, device=self.device))
+        task = _lib.mpk_hole_task(float(collision_penalty), 0, 0, int(steps_before_reward), rew)
+        _lib.check(self._lib.mpk_hole_reacher_rollout_vjp(
+            self._h, C.byref(spec.c), _dptr(des[0]), _dptr(des[1]), q0.data_ptr(), qd0.data_ptr(), _dptr(n_exec), _dptr(step0),
+            C.byref(task), hole.data_ptr(), _dptr(collided), _lib.AGG_MODES[aggregation], _dptr(ups[0]), _dptr(ups[1]), _dptr(ups[2]),
+            _dptr(ups[3]), *(_dptr(r) for r in res), B, T, self._stream()))
+        return tuple(res)
+
     def hole_reacher_rollout(self, spec: RolloutSpec, des_pos: Optional[torch.Tensor], des_vel: torch.Tensor, q: torch.Tensor,
                              qd: torch.Tensor, hole: torch.Tensor, *, collision_penalty: float = 100.0,
                              allow_self_collision: bool = False, allow_wall_collision: bool = False, steps_before_reward: int = 199,
                              n_steps: Optional[torch.Tensor] = None, step0: Optional[torch.Tensor] = None, replan=None,
                              condition: bool = False, want_actions: bool = True, want_rewards: bool = True,
                              aggregation: Optional[str] = "sum", rew_fct: str = "simple",
-                             reward_state: Optional[torch.Tensor] = None):
+                             reward_state: Optional[torch.Tensor] = None, differentiable: bool = False):
         """
         The HoleReacher step loop on the device (mpk.h: mpk_hole_reacher_rollout2; spec.plant 'velocity_direct'): controller, clip,
         direct-velocity plant, collisions, reward, and the break on collision.  q, qd are updated in place.  ``rew_fct`` is the
@@ -898,9 +1005,39 @@ class TrajectoryEngine:
         the break (then n_steps / step0 must be None).  Returns a dict: actions [B, T, D] / rewards [B, T] (or None), ret [B] (or None
         when aggregation is None), n_exec [B] int32, collided / success [B] uint8, and with ``replan`` done (snapshot after the plan)
         plus cond_pos / cond_vel when ``condition``.
+
+        ``differentiable=True`` (rew_fct "simple" / "vel_acc"; off by default, and then nothing changes -- no clone, no ``grad_fn`` even
+        if the inputs require grad): with grad enabled and ``des_pos``, ``des_vel`` or ``hole`` requiring grad the launch is the plain
+        call's -- the same state, integer outputs and values -- on a copy-protected plan-start state, and ``ret`` and ``rewards`` carry a
+        ``grad_fn`` whose backward is ONE mpk_hole_reacher_rollout_vjp launch (``hole_reacher_rollout_vjp``) fed with the forward's own
+        ``n_exec`` / ``collided``: the pathwise gradient with the episode's end and its collision verdict frozen.  The actions and the
+        in-place q, qd carry no graph; the plan-start state is a constant of it.
         """
         if spec.plant != "velocity_direct":
             raise ValueError("hole_reacher_rollout integrates plant='velocity_direct'")
+        if differentiable and rew_fct == "unbounded":
+            raise NotImplementedError("hole_reacher_rollout(differentiable=True): rew_fct='unbounded' pays on the end effector stored at "
+                                      "step 180, which may belong to an earlier plan -- its gradient crosses plans and is not built")
+        if differentiable and torch.is_grad_enabled() and (want_rewards or aggregation is not None) and any(
+                isinstance(t, torch.Tensor) and t.requires_grad for t in (des_pos, des_vel, hole)):
+            kw = dict(collision_penalty=collision_penalty, allow_self_collision=allow_self_collision,
+                      allow_wall_collision=allow_wall_collision, steps_before_reward=steps_before_reward, n_steps=n_steps, step0=step0,
+                      replan=replan, condition=condition, want_actions=want_actions, want_rewards=want_rewards, aggregation=aggregation,
+                      rew_fct=rew_fct, reward_state=reward_state)
+            B = des_vel.shape[0]
+            hole_t = torch.as_tensor(hole, dtype=torch.float64, device=self.device).expand(B, 3).contiguous()
+            dp, dv = (des_pos.contiguous() if des_pos is not None else None), des_vel.contiguous()
+            s0 = replan[0] if replan is not None else step0
+            box = {}
+            outs = _HoleRolloutFn.apply(
+                self, lambda: self.hole_reacher_rollout(spec, None if dp is None else dp.detach(), dv.detach(), q, qd, hole_t.detach(), **kw),
+                box, spec, q, qd, s0, dict(rew_fct=rew_fct, collision_penalty=collision_penalty, steps_before_reward=steps_before_reward),
+                aggregation, dp, dv, hole_t)
+            outs = list(outs)
+            for k in ("ret", "rewards"):
+                if box[k] is not None:
+                    box[k] = outs.pop(0)
+            return box
         B, T, D = des_vel.shape
         assert des_vel.dtype == torch.float32 and (des_pos is None or des_pos.dtype == torch.float32)
         assert q.dtype == torch.float64 and qd.dtype == torch.float64 and q.is_contiguous() and qd.is_contiguous()

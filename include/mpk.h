@@ -981,6 +981,65 @@ int mpk_episode_return_vjp(mpk_handle h, const float* params, const float* init_
                            const double* g_qd, float* g_params, float* g_init_pos, float* g_init_vel, double* g_q0, double* g_qd0,
                            double* g_goal, double* q_end, double* qd_end, int32_t B, void* stream);
 
+/*
+ * The vector-Jacobian product of mpk_hole_reacher_rollout2 with the episode's end and its collision verdict FROZEN (appended under ABI 4):
+ * the step at which an episode ends and whether it collided are piecewise constant in the plan, everything else -- controller, clip,
+ * direct-velocity plant, the squared distance to the hole's bottom, the acceleration and velocity costs -- is smooth, so the pathwise
+ * gradient at fixed (n_exec, collided) is well defined: the collision penalty is a constant, the distance paid on the colliding step
+ * still pulls the arm.  The collision geometry is never evaluated here.  The forward that is transposed, per executed step t < n_exec[b]
+ * with the state (q, qd) before the step and s = step0 + t the env step:
+ *   u  = Kp (des_pos_t - q) + Kd (des_vel_t - qd)     motor;  u = des_pos_t (position), u = des_vel_t (velocity)
+ *   a  = clip(u, lo, hi)          m = (lo <= u) && (u <= hi)    (the derivative of clip; 1 AT a bound: torch.clamp's convention)
+ *   acc = (a - qd) / delta ;  qd' = a ;  q' = q + delta' a
+ *         delta, delta' are the constants the forward's operation used on that step: the float64 dt for the motor controller; for the
+ *         velocity / position controllers delta' = (double)(float)dt always, delta = dt on the episode's first env step (s == 0) and
+ *         (double)(float)dt afterwards (mpk_hole_reacher_rollout: numpy's dtypes)
+ *   c_l = sum_{j<=l} q'_j ;  ee = sum_l (cos c_l, sin c_l) ;  diff = ee - (hole_x, -depth) ;  last = collided[b] && t == n_exec[b] - 1
+ *   MPK_HOLE_REW_SIMPLE    r_t = -P |diff|^2 - 5e-8 sum_d acc_d^2 - collision_penalty last,   P = (s == steps_before_reward || last)
+ *   MPK_HOLE_REW_VEL_ACC   r_t = -1e-4 sum_d qd'_d^2 - 1e-6 sum_d acc_d^2 - P (1 + collision_penalty last) |diff|^2,   P = (s == 199)
+ * Every rounding of the forward -- the float32 action, acc, cost sums and dt * a of the velocity / position controllers, the float64
+ * operations -- is the identity for the derivative, which is evaluated at the forward's own intermediate values: the replay runs the
+ * forward's operations in their dtypes, so a_t, acc_t, m_t and q'_t are the forward's bits; the adjoint arithmetic is float64 without FMA
+ * contraction.  The upstream gradient of a step's reward is
+ *   g_r[b,t] = (g_rewards ? g_rewards[b,t] : 0) + (g_ret ? g_ret[b] w_t : 0)      for t < n_exec[b],
+ *   w_t = 1 (MPK_AGG_SUM), 1 / n_exec[b] (MPK_AGG_MEAN: g_ret[b] / n_exec[b]) or [t == n_exec[b] - 1] (MPK_AGG_LAST)
+ * so a step that stored no step rewards needs no g_rewards.  The adjoint: lq, lqd start as g_q, g_qd; t runs from n_exec[b] - 1 down to 0;
+ * sx_j = sum_{l>=j} -sin c_l, sy_j = sum_{l>=j} cos c_l; W = P (simple), P (1 + collision_penalty last) (vel_acc):
+ *   lq_j  += -2 g_r W (diff_x sx_j + diff_y sy_j) ;  g_hole_x += 2 g_r W diff_x ;  g_hole_depth += -2 g_r W diff_y
+ *   vel_acc:  lqd_d += -2e-4 g_r qd'_d
+ *   lacc_d = 2 c_acc g_r acc_d                       (c_acc = -5e-8 simple, -1e-6 vel_acc)
+ *   la = delta' lq + lqd + lacc / delta ;  lqd = -lacc / delta ;  (lq unchanged) ;  lu = m la
+ *   g_des_pos_t = Kp lu, g_des_vel_t = Kd lu     (position: lu, 0;  velocity: 0, lu)
+ *   motor only:  lq -= Kp lu ;  lqd -= Kd lu
+ * and at the end g_q0 = lq, g_qd0 = lqd.
+ *   rc, des_pos, des_vel, step0, task, hole   as mpk_hole_reacher_rollout2 (rc->plant_type MPK_PLANT_VELOCITY_DIRECT; the velocity
+ *                controller reads des_vel only and des_pos may be NULL, the position controller the other way round; task's
+ *                allow_*_collision are not read)
+ *   q0, qd0      dev double [B, D]     the state at the START of the plan (the forward overwrites its q, qd: keep a copy); const
+ *   n_exec       dev int32 [B] or NULL (= T);  collided dev uint8 [B] or NULL (= 0): the forward's outputs.  With a replanning state the
+ *                forward took step0 from traj_steps BEFORE the plan: pass a copy of it
+ *   agg, g_ret   MPK_AGG_*; dev double [B] = d loss / d ret, or NULL = 0;  g_rewards dev double [B, T] or NULL = 0
+ *   g_q, g_qd    dev double [B, D] or NULL   d loss / d final state; NULL = 0
+ *   g_des_pos, g_des_vel   dev float [B, T, D] out, the float64 result rounded once; rows t >= n_exec[b] are exact zeros, as is the whole
+ *                array of the input the controller does not read; any alignment
+ *   g_q0, g_qd0  dev double [B, D] out;  g_hole dev double [B, 3] out: w.r.t. (x, width, depth), width always 0.
+ * Any output may be NULL: not written.  An episode with n_exec = 0 passes g_q, g_qd through unchanged.
+ * k_hole_rollout_vjp<controller, reward[, 5]> (mpk_last_kernel names the instantiation, e.g. "k_hole_rollout_vjp<motor, simple, 5>";
+ * without the DoF count: run-time D): k_reacher_rollout_vjp's lane map and schedule -- one lane per (episode, DoF), floor(64 / D)
+ * episodes per wave, one wave per workgroup; a forward sweep leaves (q, qd) at every 16-step tile boundary in LDS, the tiles are then
+ * replayed and reversed last to first; the link sums of the at most two paid steps of an episode go through LDS.  No atomics, an episode
+ * never leaves its wave: the same bits from run to run and for any pointer alignment.  Allocates nothing, synchronises nothing, waits
+ * for no other wave.
+ * MPK_EINVAL: rc->plant_type other than MPK_PLANT_VELOCITY_DIRECT, an unknown rew_fct or agg.  MPK_ENOTIMPL: MPK_HOLE_REW_UNBOUNDED (the
+ * end effector it stores at step 180 may belong to an earlier plan: its gradient crosses plans); more than 16 DoF; a horizon whose
+ * checkpoints (1 KB of LDS per 16 steps) do not fit the CU's 160 KB (about 2 200 steps; the message names the largest T).
+ */
+int mpk_hole_reacher_rollout_vjp(mpk_handle h, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel, const double* q0,
+                                 const double* qd0, const int32_t* n_exec, const int32_t* step0, const mpk_hole_task* task,
+                                 const double* hole, const uint8_t* collided, int32_t agg, const double* g_ret, const double* g_rewards,
+                                 const double* g_q, const double* g_qd, float* g_des_pos, float* g_des_vel, double* g_q0, double* g_qd0,
+                                 double* g_hole, int32_t B, int32_t T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
