@@ -59,7 +59,7 @@ class BatchedBlackBox:
                  device=None, learn_sub_trajectories: bool = False, reward_aggregation="sum", verbose: int = 2,
                  collision_penalty: float = 100.0, allow_self_collision: bool = False, allow_wall_collision: bool = False,
                  env_kwargs: Optional[dict] = None, observations: bool = False, rew_fct: str = "simple",
-                 collision_gradient: Optional[str] = None):
+                 collision_gradient: Optional[str] = None, phase_gradient: Optional[str] = None):
         """
         trajectory_generator / tracking_controller: the objects the factories return (``get_trajectory_generator``,
         ``get_controller``).  ``replanning_every = n`` is the schedule ``lambda pos, vel, obs, action, t: t % n == 0``
@@ -118,10 +118,22 @@ class BatchedBlackBox:
         be.  "frozen": the pathwise gradient with each episode's end and collision verdict held at what the forward found -- the
         collision penalty is a constant, the distance paid on the colliding step still pulls the arm (mpk_hole_reacher_rollout_vjp;
         rew_fct "simple" and "vel_acc").  Ignored by the other rewards.
+
+        ``phase_gradient`` (None, the default, or "pathwise"): passed to ``TrajectoryEngine.trajectory`` by ``get_trajectory`` -- with
+        "pathwise" a box with a learned tau / delay (the TableTennis / BeerPong families), or one whose episodes have their own plan
+        clocks after partial resets, keeps the graph from ``des_pos`` / ``des_vel`` to ``params`` (one mpk_trajectory_phase_vjp launch
+        backward; a ProDMP's table indices held, torch.clamp's mask on tau / delay).  NotImplementedError with
+        ``learn_sub_trajectories``.  ``step(differentiable=True)`` is unchanged: its refusals stay.
         """
         if collision_gradient not in (None, "frozen"):
             raise ValueError(f"collision_gradient must be None or 'frozen', got {collision_gradient!r}")
         self.collision_gradient = collision_gradient
+        if phase_gradient not in (None, "pathwise"):
+            raise ValueError(f"phase_gradient must be None or 'pathwise', got {phase_gradient!r}")
+        if phase_gradient is not None and learn_sub_trajectories:
+            raise NotImplementedError("phase_gradient='pathwise' with learn_sub_trajectories is not built: tau also sets the number of "
+                                      "steps a sub-trajectory executes, an integer the pathwise gradient cannot see")
+        self.phase_gradient = phase_gradient
         if rew_fct != "simple" and reward != "hole_reacher":
             raise ValueError(f"rew_fct={rew_fct!r} is HoleReacher's reward function: it needs reward='hole_reacher'")
         _lib.hole_rew_fct(rew_fct, steps_before_reward)        # (refused before anything is built)
@@ -485,11 +497,12 @@ class BatchedBlackBox:
         launches and in-place selects, nothing read back, the same bits as B single-episode wrappers.  (Rows that are done and were
         not reset execute nothing; off the grid they keep the plan of clock 0.)"""
         t = self._plan_time()
+        pg = getattr(self, "phase_gradient", None)
         if not isinstance(t, torch.Tensor) or self.engine.mp_type == "promp" or not self._on_clock_grid():
-            return self.engine.trajectory(params, cond_pos, cond_vel, t)
-        pos, vel = self.engine.trajectory(params, cond_pos, cond_vel, 0.0)
+            return self.engine.trajectory(params, cond_pos, cond_vel, t, phase_gradient=pg)
+        pos, vel = self.engine.trajectory(params, cond_pos, cond_vel, 0.0, phase_gradient=pg)
         for clock in range(self.every, self.horizon, self.every):
-            p, v = self.engine.trajectory(params, cond_pos, cond_vel, float(clock * self.dt))
+            p, v = self.engine.trajectory(params, cond_pos, cond_vel, float(clock * self.dt), phase_gradient=pg)
             own = (self.traj_steps == clock).view(self.B, 1, 1)
             if pos.requires_grad:                     # a differentiable plan: autograd takes no out=
                 pos, vel = torch.where(own, p, pos), torch.where(own, v, vel)

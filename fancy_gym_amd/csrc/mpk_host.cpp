@@ -1473,6 +1473,28 @@ int mpk_hole_reacher_rollout_vjp(mpk_handle hh, const mpk_rollout_cfg* rc, const
     return launch_hole_rollout_vjp(hl, B, T, h->dev.D, stream, &h->last_kernel);
 }
 
+// the transpose of mpk_trajectory's per-episode-phase map (k_traj_phase's shapes), tau / delay included: one k_phase_vjp launch
+int mpk_trajectory_phase_vjp(mpk_handle hh, const float* params, const float* init_pos, const float* init_vel, const float* init_time,
+                             double init_time_shared, const float* g_pos, const float* g_vel, float* g_params, float* g_init_pos,
+                             float* g_init_vel, int32_t B, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (B < 0) { set_error("B must be >= 0"); return MPK_EINVAL; }
+    if (h->cfg.mp_type == MPK_MP_DMP) {
+        set_error("mpk_trajectory_phase_vjp: a DMP with a per-episode phase is an Euler recurrence in the scaled time, which this "
+                  "kernel does not transpose (promp / prodmp only)");
+        return MPK_ENOTIMPL;
+    }
+    if (B == 0 || h->dev.D == 0 || (!g_params && !g_init_pos && !g_init_vel)) return MPK_OK;
+    if (!params || !init_pos || !init_vel) { set_error("NULL buffer"); return MPK_EINVAL; }
+    MPK_ON_DEVICE(h->cfg.device);
+    PhaseVjpLaunch q;
+    q.params = params; q.init_pos = init_pos; q.init_vel = init_vel; q.init_time = init_time; q.init_time_shared = (float)init_time_shared;
+    q.g_pos = g_pos; q.g_vel = g_vel; q.g_params = g_params; q.g_init_pos = g_init_pos; q.g_init_vel = g_init_vel;
+    q.range_flag = h->d_flag; q.B = B;
+    return launch_phase_vjp(h->dev, q, h->num_cu, stream, &h->last_kernel);
+}
+
 int mpk_episode_reset(mpk_handle hh, const double* init_q, const double* init_qd, double* q, double* qd,
                       float* cond_pos, float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done,
                       int32_t B, void* stream) {

@@ -259,6 +259,20 @@ struct HoleVjpLaunch {
     int steps_before_reward = 0, rew_fct = 0;
 };
 int launch_hole_rollout_vjp(const HoleVjpLaunch& h, int B, int T, int D, void* stream, const char** kernel_name);
+// mpk_trajectory_phase_vjp (mpk_phase_vjp.hip): the transpose of the per-episode-phase trajectory map of promp / prodmp (learned tau /
+// delay, per-episode init_time) with prodmp's table indices held and torch.clamp's mask on tau / delay, one launch; either upstream
+// gradient and any output may be nullptr (not read / not written).  MPK_ENOTIMPL: dmp, promp with T = 1, shapes beyond the wave
+// kernel k_traj_phase's (<= kMaxD DoF here).
+struct PhaseVjpLaunch {
+    const float *params = nullptr, *init_pos = nullptr, *init_vel = nullptr;    // [B, P], [B, D], [B, D] the forward's inputs
+    const float* init_time = nullptr;                                           // [B] per episode; nullptr: init_time_shared
+    float init_time_shared = 0.f;
+    const float *g_pos = nullptr, *g_vel = nullptr;                             // [B, T, D] upstream
+    float *g_params = nullptr, *g_init_pos = nullptr, *g_init_vel = nullptr;    // [B, P], [B, D], [B, D]
+    int32_t* range_flag = nullptr;
+    int B = 0;
+};
+int launch_phase_vjp(const DevCfg& c, const PhaseVjpLaunch& q, int num_cu, void* stream, const char** kernel_name);
 int launch_episode_reset(const double* init_q, const double* init_qd, double* q, double* qd, float* cond_pos,
                          float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done, int B, int D,
                          void* stream);

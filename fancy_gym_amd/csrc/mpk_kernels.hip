@@ -20,6 +20,7 @@
 //   mpk_vjp_row.h        the transpose's table rows and transposed input gather, shared by mpk_traj_vjp.hip and mpk_episode_vjp.hip
 //   mpk_hole.hip         HoleReacher: direct-velocity plant, collisions, reward, break on collision
 //   mpk_hole_vjp.hip     k_hole_rollout_vjp: the HoleReacher rollout transposed, end and verdict frozen (mpk_hole_reacher_rollout_vjp)
+//   mpk_phase_vjp.hip    k_phase_vjp: the per-episode-phase trajectory map transposed, tau / delay included (mpk_trajectory_phase_vjp)
 //   mpk_reacher_env.h    the reacher envs' draw programs and observation row, shared by the three units below
 //   mpk_reset.hip        reacher resets: numpy's generator per episode (mpk_nprng.h), seeded / continued draws
 //   mpk_obs.hip          reacher observations: current rows, per-step rows replayed on the stored plan (mpk_plant.h)
@@ -41,6 +42,7 @@
 #include "mpk_episode_vjp.hip"
 #include "mpk_hole.hip"
 #include "mpk_hole_vjp.hip"
+#include "mpk_phase_vjp.hip"
 #include "mpk_reset.hip"
 #include "mpk_obs.hip"
 #include "mpk_autoreset.hip"

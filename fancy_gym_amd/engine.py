@@ -99,6 +99,30 @@ class _TrajectoryFn(torch.autograd.Function):
         return None, None, None, g_params, g_init_pos, g_init_vel
 
 
+class _TrajectoryPhaseFn(torch.autograd.Function):
+    """``TrajectoryEngine.trajectory(..., phase_gradient="pathwise")`` for a per-episode phase (learned tau / delay, per-episode
+    init_time): forward = the plain mpk_trajectory launch, backward = one mpk_trajectory_phase_vjp launch, which recomputes the episode's
+    phase and rows from the forward's inputs (nothing of the forward launch is kept but those); ``init_time`` gets no gradient"""
+
+    @staticmethod
+    def forward(ctx, engine, it_t, it_s, out, params, init_pos, init_vel):
+        ctx.engine, ctx.it_t, ctx.it_s = engine, it_t, it_s
+        ctx.save_for_backward(params, init_pos, init_vel)
+        ctx.set_materialize_grads(False)
+        return engine._trajectory_launch(params, init_pos, init_vel, it_t, it_s, out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_pos, g_vel):
+        need = ctx.needs_input_grad[4:7]
+        if g_pos is None and g_vel is None:
+            return (None,) * 7
+        params, init_pos, init_vel = ctx.saved_tensors
+        g = ctx.engine.trajectory_phase_vjp(params, init_pos, init_vel, g_pos, g_vel, ctx.it_t if ctx.it_t is not None else ctx.it_s,
+                                            need=need)
+        return (None, None, None, None) + tuple(g)
+
+
 class _ReacherRolloutFn(torch.autograd.Function):
     """``TrajectoryEngine.reacher_rollout`` with a backward: forward = a copy of the plan-start (q, qd) and the mpk_reacher_rollout launch
     as without autograd, backward = one mpk_reacher_rollout_vjp launch; the actions and the in-place q, qd carry no graph"""
@@ -332,12 +356,21 @@ class TrajectoryEngine:
         return _lib.get_option(key, self._h)
 
     # ---- hot path ----------------------------------------------------------------------------------------------
-    def trajectory(self, params, init_pos, init_vel, init_time=0.0, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
-                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    def trajectory(self, params, init_pos, init_vel, init_time=0.0, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                   phase_gradient: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """
         params [B, P] -> (pos [B, T, D], vel [B, T, D]) float32 CUDA tensors.  ``init_time`` is a python float shared by
         all episodes, or a tensor [B] of per-episode values.
+
+        ``phase_gradient`` (None, the default, or "pathwise") says what autograd does with a per-episode phase -- a handle with a
+        learned tau / delay, or a per-episode ``init_time`` tensor.  None: such a call refuses under autograd.  "pathwise": it keeps
+        the graph; the forward is the plain launch (same bits, same ``last_kernel``), the backward ONE mpk_trajectory_phase_vjp launch
+        with the convention of mpk.h: a ProDMP's integer table indices are held (so its delay gets exactly 0), tau / delay outside
+        their bounds get exactly 0 (torch.clamp), ``init_time`` gets no gradient.  A shared-phase call with a float ``init_time`` keeps
+        using mpk_trajectory_vjp.  NotImplementedError: a DMP.
         """
+        if phase_gradient not in (None, "pathwise"):
+            raise ValueError(f"phase_gradient must be None or 'pathwise', got {phase_gradient!r}")
         params = torch.as_tensor(params, dtype=torch.float32, device=self.device)
         if params.dim() == 1:
             params = params[None]
@@ -355,6 +388,12 @@ class TrajectoryEngine:
             it_s = float(init_time)
         if torch.is_grad_enabled() and (params.requires_grad or init_pos.requires_grad or init_vel.requires_grad):
             # differentiable: the same forward launch, and one mpk_trajectory_vjp launch as its backward (shared phase only)
+            learned = bool(self.config.learn_tau or self.config.learn_delay)
+            if phase_gradient == "pathwise" and (learned or it_t is not None):
+                if self.mp_type == "dmp":
+                    raise NotImplementedError("trajectory(phase_gradient='pathwise') is built for promp and prodmp: a DMP with a "
+                                              "per-episode phase is an Euler recurrence in the scaled time, which has no adjoint kernel")
+                return _TrajectoryPhaseFn.apply(self, it_t, it_s, out, params, init_pos, init_vel)
             if self.config.learn_tau or self.config.learn_delay:
                 raise NotImplementedError("trajectory() is differentiable for a shared phase only: with a learned tau / delay the "
                                           "trajectory is not linear in those two parameters, and they are clipped to their bounds")
@@ -410,6 +449,57 @@ class TrajectoryEngine:
                 res.append(torch.empty(shape, dtype=torch.float32, device=self.device))
         _lib.check(self._lib.mpk_trajectory_vjp(self._h, _dptr(gs[0]), _dptr(gs[1]), float(init_time), _dptr(res[0]), _dptr(res[1]),
                                                 _dptr(res[2]), B, self._stream()))
+        return res[0], res[1], res[2]
+
+    def trajectory_phase_vjp(self, params, init_pos, init_vel, g_pos: Optional[torch.Tensor], g_vel: Optional[torch.Tensor],
+                             init_time=0.0, *, need: Sequence[bool] = (True, True, True),
+                             out: Optional[Sequence[Optional[torch.Tensor]]] = None
+                             ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """
+        The vector-Jacobian product of ``trajectory`` for a per-episode phase (mpk.h: mpk_trajectory_phase_vjp), one launch: the
+        forward's own inputs (``init_time`` a float or a tensor [B]) and the gradients of a loss w.r.t. pos / vel [B, T, D] (either may
+        be None) -> (g_params [B, P], g_init_pos [B, D], g_init_vel [B, D]) float32 on the device; ``need`` / ``out`` as
+        ``trajectory_vjp``.  The convention is mpk.h's: a ProDMP's table indices held (g_delay = 0), torch.clamp's mask on tau /
+        delay.  NotImplementedError: a DMP, a ProMP with one step, shapes beyond the forward's wave kernel.
+        """
+        ref = g_pos if g_pos is not None else g_vel
+        if ref is None:
+            raise ValueError("trajectory_phase_vjp needs g_pos or g_vel")
+        D, T = self.num_dof, self.num_steps
+        B = ref.shape[0]
+        params = torch.as_tensor(params, dtype=torch.float32, device=self.device)
+        if params.dim() == 1:
+            params = params[None]
+        params = params.detach().contiguous()
+        if params.shape != (B, self.num_params):
+            raise ValueError(f"params must be [{B}, {self.num_params}], got {tuple(params.shape)}")
+        init_pos, init_vel = self._f32(init_pos, (B, D)).detach(), self._f32(init_vel, (B, D)).detach()
+        it_t, it_s = None, 0.0
+        if isinstance(init_time, torch.Tensor) and init_time.dim() > 0:
+            it_t = self._f32(init_time, (B,))
+        else:
+            it_s = float(init_time)
+        gs = []
+        for name, g in (("g_pos", g_pos), ("g_vel", g_vel)):
+            if g is not None:
+                g = torch.as_tensor(g, dtype=torch.float32, device=self.device)
+                if g.shape != (B, T, D):
+                    raise ValueError(f"{name} must be [{B}, {T}, {D}], got {tuple(g.shape)}")
+                g = g.contiguous()
+            gs.append(g)
+        res = []
+        for i, shape in enumerate(((B, self.num_params), (B, D), (B, D))):
+            if not need[i]:
+                res.append(None)
+            elif out is not None and out[i] is not None:
+                if out[i].shape != shape or out[i].dtype != torch.float32 or not out[i].is_contiguous() or out[i].device != self.device:
+                    raise ValueError(f"out[{i}] must be a contiguous float32 tensor of shape {shape} on {self.device}")
+                res.append(out[i])
+            else:
+                res.append(torch.empty(shape, dtype=torch.float32, device=self.device))
+        _lib.check(self._lib.mpk_trajectory_phase_vjp(self._h, params.data_ptr(), init_pos.data_ptr(), init_vel.data_ptr(), _dptr(it_t),
+                                                      it_s, _dptr(gs[0]), _dptr(gs[1]), _dptr(res[0]), _dptr(res[1]), _dptr(res[2]), B,
+                                                      self._stream()))
         return res[0], res[1], res[2]
 
     def check_range(self):

@@ -1040,6 +1040,32 @@ int mpk_hole_reacher_rollout_vjp(mpk_handle h, const mpk_rollout_cfg* rc, const 
                                  const double* g_q, const double* g_qd, float* g_des_pos, float* g_des_vel, double* g_q0, double* g_qd0,
                                  double* g_hole, int32_t B, int32_t T, void* stream);
 
+/*
+ * The vector-Jacobian product of mpk_trajectory for a PER-EPISODE phase -- a handle with learn_tau / learn_delay, or a per-episode
+ * init_time -- of a ProMP or a ProDMP, in ONE launch (appended within ABI 4): gradients of a loss w.r.t. pos / vel [B, T, D] (either
+ * may be NULL: not read) -> g_params [B, P] (the tau / delay columns first, as in params), g_init_pos [B, D], g_init_vel [B, D] (any may
+ * be NULL: not written).  params, init_pos, init_vel, init_time (NULL: init_time_shared) are the forward's own inputs; nothing of the
+ * forward launch is stored, the episode's phase and rows are recomputed with the forward's device functions.  mpk_trajectory_vjp is
+ * untouched and keeps refusing such handles: THIS gradient is a stated convention, the one torch autograd gives the reference's
+ * formulation --
+ *   * held indices: a ProDMP reads its rows at INTEGER table indices rint(max((t - delay) / tau, 0) / scaled_dt); they are constants of
+ *     the graph.  tau still enters through the boundary velocity tau * init_vel and the 1 / tau of vel; the delay enters through the
+ *     indices only, so g_delay = 0.0 exactly.
+ *   * the clamp convention: tau / delay are clipped to their bounds as in the forward; the gradient w.r.t. the raw parameter is that
+ *     w.r.t. the clipped one where lo <= raw <= hi and 0.0 exactly outside (torch.clamp).
+ *   * a ProMP's phase clips likewise: linear d x / d s = 1 on 0 < s < 1, exp d x / d s = -alpha x on s > 0, else 0; its velocity is
+ *     the forward difference over the time grid, transposed as it stands.  init_time gets no gradient.
+ * Outputs no column reads are exact zeros (a disabled block, g_init_vel of a ProMP, g_init_pos of a ProMP without zero padding).
+ * k_phase_vjp<promp | prodmp> (mpk_last_kernel): one wave per episode, lane <-> time step, float64 reduction inside the wave, plain
+ * stores, no atomics: the same bits from run to run and for any alignment of g_pos / g_vel.  A ProDMP episode that leaves the
+ * pre-computed range clamps and raises the range flag as the forward does (mpk_check_range).  Allocates nothing, synchronises nothing.
+ * MPK_ENOTIMPL: a DMP; a ProMP with one time step; shapes beyond the wave kernel of the forward (more than 16 DoF or 16 columns,
+ * DoF x padded columns > 256, more than 320 parameters per episode).
+ */
+int mpk_trajectory_phase_vjp(mpk_handle h, const float* params, const float* init_pos, const float* init_vel,
+                             const float* init_time, double init_time_shared, const float* g_pos, const float* g_vel,
+                             float* g_params, float* g_init_pos, float* g_init_vel, int32_t B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
