@@ -206,6 +206,14 @@ SIGNATURES = {
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mpk_hole_reacher_rollout_vjp": (C.c_int, [_vp, C.POINTER(mpk_rollout_cfg), _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(mpk_hole_task),
                                                _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    # the three rollout adjoints with an upstream gradient of the forward's condition output (g_cond_pos, g_cond_vel after g_qd)
+    "mpk_reacher_rollout_vjp_cond": (C.c_int, [_vp, C.POINTER(mpk_rollout_cfg), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp]),
+    "mpk_episode_return_vjp_cond": (C.c_int, [_vp, _vp, _vp, _vp, _dbl, C.POINTER(mpk_rollout_cfg), _vp, _vp, _vp, _vp, _vp, _i32, _i32,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "mpk_hole_reacher_rollout_vjp_cond": (C.c_int, [_vp, C.POINTER(mpk_rollout_cfg), _vp, _vp, _vp, _vp, _vp, _vp,
+                                                    C.POINTER(mpk_hole_task), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                    _vp, _vp, _i32, _i32, _vp]),
     "mpk_trajectory_phase_vjp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
 }
 

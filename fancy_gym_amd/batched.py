@@ -59,7 +59,8 @@ class BatchedBlackBox:
                  device=None, learn_sub_trajectories: bool = False, reward_aggregation="sum", verbose: int = 2,
                  collision_penalty: float = 100.0, allow_self_collision: bool = False, allow_wall_collision: bool = False,
                  env_kwargs: Optional[dict] = None, observations: bool = False, rew_fct: str = "simple",
-                 collision_gradient: Optional[str] = None, phase_gradient: Optional[str] = None):
+                 collision_gradient: Optional[str] = None, phase_gradient: Optional[str] = None,
+                 replan_gradient: Optional[str] = None):
         """
         trajectory_generator / tracking_controller: the objects the factories return (``get_trajectory_generator``,
         ``get_controller``).  ``replanning_every = n`` is the schedule ``lambda pos, vel, obs, action, t: t % n == 0``
@@ -124,7 +125,26 @@ class BatchedBlackBox:
         clocks after partial resets, keeps the graph from ``des_pos`` / ``des_vel`` to ``params`` (one mpk_trajectory_phase_vjp launch
         backward; a ProDMP's table indices held, torch.clamp's mask on tau / delay).  NotImplementedError with
         ``learn_sub_trajectories``.  ``step(differentiable=True)`` is unchanged: its refusals stay.
+
+        ``replan_gradient`` (None, the default, or "episode"): what ``step(differentiable=True)`` differentiates on a replanning box.
+        None: every plan on its own -- this step's reward w.r.t. this step's parameters, the state and the condition the plan starts
+        from are constants.  "episode": the gradient crosses plan boundaries.  The box keeps graph-carrying twins of the plant state
+        (and, with ``condition_on_desired``, of the stored condition), bit for bit equal to ``q``, ``qd``, ``condition_pos``,
+        ``condition_vel``; plan k starts from the twins plan k - 1 left (without ``condition_on_desired`` its init_pos / init_vel are
+        ``twin.float()``, the cast being the identity for the derivative), so ``rewards`` of plan k reaches the ``params`` of every
+        plan j <= k and the goal / hole, and ``step`` also returns ``end_pos`` / ``end_vel``, float64 [B, D]: the twins after the plan,
+        for a cost on the state (``current_pos`` / ``current_vel`` stay the graph-free state).  Forward values, the in-place state and
+        every integer output are the plain step's, from the same launches; each plan's backward is still the launch(es) of that plan
+        (mpk_episode_return_vjp_cond, or mpk_reacher_rollout_vjp_cond / mpk_hole_reacher_rollout_vjp_cond + mpk_trajectory_vjp).  The
+        chain is cut -- the next plan starts from constants -- by ``reset`` / ``reset_done`` / ``autoreset``, by any step that is not
+        ``differentiable=True``, and by ``get_trajectory`` called on its own.  NOT differentiated: the state given to ``reset``, the
+        observations, the integer schedule (which steps a plan executes, where an episode ends or collides).  Without replanning the
+        option is accepted and changes nothing; every refusal of ``step(differentiable=True)`` stays.
         """
+        if replan_gradient not in (None, "episode"):
+            raise ValueError(f"replan_gradient must be None or 'episode', got {replan_gradient!r}")
+        self.replan_gradient = replan_gradient
+        self._twin = None           # replan_gradient="episode": the graph-carrying twins dict(q, qd[, cond_pos, cond_vel]) of the last plan
         if collision_gradient not in (None, "frozen"):
             raise ValueError(f"collision_gradient must be None or 'frozen', got {collision_gradient!r}")
         self.collision_gradient = collision_gradient
@@ -312,6 +332,7 @@ class BatchedBlackBox:
         separate launches -- the same results.  A partial reset synchronises nothing, so it does not run ``check_range()`` for the
         episodes it ends: call it yourself where a ProDMP plan can leave the table range.  Not with a learned tau / delay (the phase an
         episode freezes at its first plan would have to be re-frozen row by row: not built)."""
+        self._twin = None           # (replan_gradient: any reset cuts the chain)
         drawn = seed is not None or bool(sample)
         explicit = any(x is not None for x in (init_pos, init_vel, goal, hole))
         if mask is not None and not drawn:
@@ -413,6 +434,7 @@ class BatchedBlackBox:
     def _autoreset_launch(self, seeding: dict, mask, observe: bool):
         """the one launch of every partial reset (mpk_reacher_autoreset) and the host bookkeeping that goes with it"""
         self._refuse_partial()
+        self._twin = None
         if self._rng is None and not seeding:
             raise ValueError("a partial reset continues the streams of a seeded reset: call reset(seed=...) first")
         if self._rng is None:
@@ -578,9 +600,33 @@ class BatchedBlackBox:
         return params
 
     def get_trajectory(self, params) -> Dict[str, torch.Tensor]:
+        self._twin = None           # (replan_gradient: a plan asked for on its own cuts the chain)
+        return self._get_trajectory(params)
+
+    def _carry_start(self):
+        """replan_gradient="episode": (init_pos, init_vel, q_in, qd_in) of the next plan -- what the twins of the plan before give (the
+        same bits as ``_plan_condition`` and ``q``, ``qd``), or right after a cut the constants themselves"""
+        tw = self._twin
+        if tw is None:
+            return (*self._plan_condition(), self.q, self.qd)
+        if self.condition_on_desired and tw.get("cond_pos") is not None:
+            return tw["cond_pos"], tw["cond_vel"], tw["q"], tw["qd"]
+        if self.condition_pos is not None:
+            return self.condition_pos, self.condition_vel, tw["q"], tw["qd"]
+        return tw["q"].float(), tw["qd"].float(), tw["q"], tw["qd"]
+
+    def _carry_end(self, out, twins):
+        self._twin = twins
+        out.update(end_pos=twins["q"], end_vel=twins["qd"])
+        return out
+
+    def _get_trajectory(self, params, cond=None) -> Dict[str, torch.Tensor]:
         params = self._plan_params(params)
-        cond_pos = self.condition_pos if self.condition_pos is not None else self.q.float()
-        cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
+        if cond is not None:
+            cond_pos, cond_vel = cond
+        else:
+            cond_pos = self.condition_pos if self.condition_pos is not None else self.q.float()
+            cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
         pos, vel = self._trajectory(params, cond_pos, cond_vel)
         if self.learn_sub_trajectories and self.engine.mp_type == "promp":
             # ProMP's velocity is the forward difference of its positions with the LAST row repeating the one before
@@ -673,13 +719,17 @@ class BatchedBlackBox:
                 and not self.learn_sub_trajectories and (self._n_phase == 0 or self.reward is None)
                 and (not self.do_replanning or self._lockstep is not None))
 
-    def _step_lean(self, params, differentiable: bool = False) -> Optional[Dict[str, torch.Tensor]]:
+    def _step_lean(self, params, differentiable: bool = False, carry: bool = False) -> Optional[Dict[str, torch.Tensor]]:
         """the verbose < 2 step as ONE launch without per-step outputs (mpk_episode_return); None = not available here.
         ``differentiable``: ``rewards`` carries the graph of ONE mpk_episode_return_vjp launch back to ``params``"""
         gate = self._gate(params)
         was_done = self._was_done() if gate is not None else None
         params = self._plan_params(params)
-        cond_pos, cond_vel = self._plan_condition()
+        if carry:
+            cond_pos, cond_vel, q_in, qd_in = self._carry_start()
+        else:
+            cond_pos, cond_vel = self._plan_condition()
+        kw = dict(carry=(q_in, qd_in)) if carry else {}
         init_time = float(self._lockstep * self.dt) if self.do_replanning else 0.0
         mpt = self.max_planning_times if math.isfinite(self.max_planning_times) else 2 ** 31 - 1
         try:
@@ -687,7 +737,7 @@ class BatchedBlackBox:
                                            replan=(self.traj_steps, self.plan_steps, self.done, self.every, int(mpt), self.horizon),
                                            reward=self.reward, goal=self.goal, steps_before_reward=self.steps_before_reward,
                                            aggregation=self.reward_aggregation, init_time=init_time,
-                                           condition=self.condition_on_desired, gate=gate, differentiable=differentiable)
+                                           condition=self.condition_on_desired, gate=gate, differentiable=differentiable, **kw)
         except NotImplementedError:
             # (refused before anything ran.  The plain step never gets another try; a refusal of the gradient says nothing about it.)
             if not differentiable:
@@ -711,9 +761,9 @@ class BatchedBlackBox:
             out.update(valid=valid, invalid_penalty=r["penalty"], terminated=terminated, truncated=truncated)
         if self.reward is not None:
             out["rewards"] = r["ret"]
-        return out
+        return self._carry_end(out, r["carry"]) if carry else out
 
-    def _finish(self, out, seg, valid, was_done) -> Dict[str, torch.Tensor]:
+    def _finish(self, out, seg, valid, was_done, cond=None) -> Dict[str, torch.Tensor]:
         pos, vel = out["des_pos"], out["des_vel"]
         out.update(valid=valid, trajectory_length=seg, done=self.done.bool(), terminated=~valid & ~was_done,
                    truncated=self.done.bool() & valid)
@@ -721,7 +771,8 @@ class BatchedBlackBox:
             # (black_box_wrapper.py:197-203 stores the desired state only inside the break branch -- terminated, truncated, or the
             # replanning schedule.  With sub-trajectories the schedule is never true: a plan that ends before the episode does leaves
             # condition_pos None, and the next one starts from env.current_pos / current_vel -- self.q / self.qd here.)
-            self._store_condition(*self.engine.condition_gather(pos, vel, seg))
+            # (``cond``: the carrying rollout of replan_gradient="episode" has gathered it already -- the same launch on the same plan)
+            self._store_condition(*(cond if cond is not None else self.engine.condition_gather(pos, vel, seg)))
         if self.do_replanning and self._lockstep is not None:
             if self.pos_limits is None:
                 # no validity gate: every episode follows the same integer sequence, which the host can mirror without
@@ -748,7 +799,9 @@ class BatchedBlackBox:
         ``reward_aggregate`` -- so that ``step_rewards`` carry the graph too: the same values, state and integer outputs as
         ``step(params, fuse=False)``, and a backward of two launches, mpk_reacher_rollout_vjp and mpk_trajectory_vjp.  With replanning the gradient is that of THIS step's reward w.r.t. THIS
         step's parameters: the plant state and the condition the plan starts from are constants of the graph, nothing flows into
-        earlier steps.  Reward "hole_reacher" takes part only with ``collision_gradient="frozen"`` (the constructor's argument): the
+        earlier steps -- unless the box was built with ``replan_gradient="episode"`` (the constructor's argument), which carries the
+        graph across plan boundaries and adds ``end_pos`` / ``end_vel`` to the result.
+        Reward "hole_reacher" takes part only with ``collision_gradient="frozen"`` (the constructor's argument): the
         plain step's two launches under autograd, the same values, state and integer outputs, and a backward of two launches,
         mpk_hole_reacher_rollout_vjp at the forward's own ``trajectory_length`` / ``is_collided`` and mpk_trajectory_vjp; at
         ``verbose < 2`` nothing per step is stored.  NotImplementedError: another reward, HoleReacher without that option or with rew_fct
@@ -785,19 +838,23 @@ class BatchedBlackBox:
     def _step(self, params, fuse: bool, differentiable: bool = False) -> Dict[str, torch.Tensor]:
         self._plans_since_reset += 1
         self._obs_start = (self.q.clone(), self.qd.clone()) if self.observations and self.verbose >= 2 else None
+        # replan_gradient="episode": this plan starts from the twins of the one before and leaves its own; any other step cuts the chain
+        carry = differentiable and self.replan_gradient == "episode" and self.do_replanning
+        if not carry:
+            self._twin = None
         if differentiable and self.reward == "hole_reacher":
             # collision_gradient="frozen": the plan and the rollout under autograd, two launches backward (mpk_hole_reacher_rollout_vjp,
             # mpk_trajectory_vjp); at verbose < 2 nothing per step is stored, the return's gradient enters the kernel through agg
             with torch.enable_grad():
-                return self._step_hole(params, differentiable=True)
+                return self._step_hole(params, differentiable=True, carry=carry)
         if differentiable:
             with torch.enable_grad():
                 # the default verbosity: mpk_episode_return forward, one mpk_episode_return_vjp launch backward; what that refuses,
                 # verbose >= 2 and fuse=False take the separate launches (two backward)
-                out = self._step_lean(params, differentiable=True) if fuse and self._can_episode_return() else None
+                out = self._step_lean(params, differentiable=True, carry=carry) if fuse and self._can_episode_return() else None
                 if out is not None:
                     return out
-                out = self._step_full(params, fuse=False, differentiable=True)
+                out = self._step_full(params, fuse=False, differentiable=True, carry=carry)
             if self.verbose < 2:
                 for k in self._PER_STEP:
                     out.pop(k, None)
@@ -814,10 +871,12 @@ class BatchedBlackBox:
                 out.pop(k, None)
         return out
 
-    def _step_full(self, params, fuse: bool = True, differentiable: bool = False) -> Dict[str, torch.Tensor]:
+    def _step_full(self, params, fuse: bool = True, differentiable: bool = False, carry: bool = False) -> Dict[str, torch.Tensor]:
         if fuse and self._can_fuse():
             return self._step_fused(params)
-        out = self.get_trajectory(params)
+        start = self._carry_start() if carry else None
+        # (right after a cut the plan's condition is chosen as without the option)
+        out = self._get_trajectory(params, cond=start[:2] if carry and self._twin is not None else None)
         pos, vel = out["des_pos"], out["des_vel"]
         was_done = self.done.bool()
         self._prev_done_known = False       # (this path changes the done bytes with launches of its own: _was_done copies them next time)
@@ -842,6 +901,14 @@ class BatchedBlackBox:
                 # (a plan that kept its graph -- params.requires_grad_() -- is rolled out as a constant, as before step(differentiable=True)
                 # existed: no clone of the state, no grad_fn on the rewards)
                 pos, vel = pos.detach(), vel.detach()
+            if carry:
+                # (the carrying rollout gathers the condition itself, so that it is an output of the plan's one backward launch)
+                act, rew, twins = self.engine.reacher_rollout(
+                    self.spec, pos, vel, self.q, self.qd, self.goal, n_steps=seg, step0=self.traj_steps - seg,
+                    steps_before_reward=self.steps_before_reward, carry=start[2:],
+                    condition=self.condition_on_desired and not self.learn_sub_trajectories)
+                out.update(step_actions=act, step_rewards=rew, rewards=self._aggregate(rew, seg))
+                return self._carry_end(self._finish(out, seg, valid, was_done, cond=twins.pop("cond", None)), twins)
             act, rew = self.engine.reacher_rollout(self.spec, pos, vel, self.q, self.qd, self.goal, n_steps=seg,
                                                    step0=self.traj_steps - seg,
                                                    steps_before_reward=self.steps_before_reward)
@@ -851,12 +918,16 @@ class BatchedBlackBox:
         return self._finish(out, seg, valid, was_done)
 
 
-    def _step_hole(self, params, differentiable: bool = False) -> Dict[str, torch.Tensor]:
+    def _step_hole(self, params, differentiable: bool = False, carry: bool = False) -> Dict[str, torch.Tensor]:
         """HoleReacher: the plan, then ONE rollout launch that advances the integer state, executes until the plan ends or the
         arm collides, and commits the break (mpk_hole_reacher_rollout); at verbose < 2 it stores nothing per step.  The plan's
         init_time is the shared clock while the episodes move in lockstep, per episode from the device counters after a partial reset"""
         params = self._plan_params(params)
-        cond_pos, cond_vel = self._plan_condition()
+        if carry:
+            cond_pos, cond_vel, q_in, qd_in = self._carry_start()
+        else:
+            cond_pos, cond_vel = self._plan_condition()
+        kw = dict(carry=(q_in, qd_in)) if carry else {}
         pos, vel = self._trajectory(params, cond_pos, cond_vel)
         mpt = self.max_planning_times if math.isfinite(self.max_planning_times) else 2 ** 31 - 1
         full = self.verbose >= 2
@@ -864,7 +935,7 @@ class BatchedBlackBox:
             self.spec, pos, vel, self.q, self.qd, self.hole, steps_before_reward=self.steps_before_reward,
             replan=(self.traj_steps, self.plan_steps, self.done, self.every, int(mpt), self.horizon),
             condition=self.condition_on_desired, want_actions=full, want_rewards=full, aggregation=self.reward_aggregation,
-            rew_fct=self.rew_fct, reward_state=self._reward_state, differentiable=differentiable, **self.hole_task)
+            rew_fct=self.rew_fct, reward_state=self._reward_state, differentiable=differentiable, **kw, **self.hole_task)
         if self.condition_on_desired:
             self._store_condition(r["cond_pos"], r["cond_vel"])
         if self.do_replanning and self._lockstep is not None:
@@ -877,7 +948,7 @@ class BatchedBlackBox:
                    is_success=r["success"].view(torch.bool), current_pos=self.q, current_vel=self.qd)
         if full:
             out.update(des_pos=pos, des_vel=vel, step_actions=r["actions"], step_rewards=r["rewards"])
-        return out
+        return self._carry_end(out, r["carry"]) if carry else out
 
     def _sub_trajectory_advance(self, params: torch.Tensor) -> torch.Tensor:
         """

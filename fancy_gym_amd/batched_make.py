@@ -142,7 +142,7 @@ def resolve_batched_config(id: str, mp_config_override: Optional[dict] = None, *
 
 def make_batched(id: str, num_envs: int, *, device=None, verbose: Optional[int] = None, observations: bool = True,
                  mp_config_override: Optional[dict] = None, collision_gradient: Optional[str] = None,
-                 phase_gradient: Optional[str] = None, **env_kwargs):
+                 phase_gradient: Optional[str] = None, replan_gradient: Optional[str] = None, **env_kwargs):
     """
     The ``BatchedBlackBox`` of ``num_envs`` episodes of the registered MP id ``id`` -- the batched ``_gym.make(id, mp_config_override=...,
     **env_kwargs)``: generator and controller from the factories, everything else from ``resolve_batched_config``.  ``verbose`` as
@@ -150,13 +150,17 @@ def make_batched(id: str, num_envs: int, *, device=None, verbose: Optional[int] 
     stores nothing per step); ``observations`` as ``BatchedBlackBox``'s (on here: an id has an observation); ``collision_gradient`` as
     ``BatchedBlackBox``'s (None or "frozen": what ``step(differentiable=True)`` differentiates on a HoleReacher id; a SimpleReacher id
     accepts and ignores it); ``phase_gradient`` as ``BatchedBlackBox``'s (None or "pathwise": whether ``get_trajectory`` keeps the autograd
-    graph through a learned tau / delay or per-episode plan clocks).
+    graph through a learned tau / delay or per-episode plan clocks); ``replan_gradient`` as ``BatchedBlackBox``'s (None or "episode":
+    whether the gradient of ``step(differentiable=True)`` crosses plan boundaries on a replanning id; an id without replanning accepts
+    and ignores it).
     """
     from .batched import BatchedBlackBox
     if collision_gradient not in (None, "frozen"):
         raise ValueError(f"collision_gradient must be None or 'frozen', got {collision_gradient!r}")
     if phase_gradient not in (None, "pathwise"):
         raise ValueError(f"phase_gradient must be None or 'pathwise', got {phase_gradient!r}")
+    if replan_gradient not in (None, "episode"):
+        raise ValueError(f"replan_gradient must be None or 'episode', got {replan_gradient!r}")
     cfg = resolve_batched_config(id, mp_config_override, **env_kwargs)
     for key in ("id", "base_id", "mp_type", "n_links"):
         cfg.pop(key)
@@ -167,7 +171,8 @@ def make_batched(id: str, num_envs: int, *, device=None, verbose: Optional[int] 
     if verbose is not None:
         cfg["verbose"] = verbose
     return BatchedBlackBox(traj_gen, controller, int(num_envs), device=device, observations=observations,
-                           collision_gradient=collision_gradient, phase_gradient=phase_gradient, **cfg)
+                           collision_gradient=collision_gradient, phase_gradient=phase_gradient, replan_gradient=replan_gradient,
+                           **cfg)
 
 
 def make_batched_vec(id: str, num_envs: int, *, partial_resets: bool = False, **kwargs):

@@ -24,6 +24,8 @@ struct EvjpArgs {
     const double* g_ret;       // [B] or nullptr
     const double* g_q;
     const double* g_qd;
+    const float* g_cond_pos;   // [B, D] or nullptr: upstream of the forward's condition output (row tcond of the plan)
+    const float* g_cond_vel;
     float* g_params;
     float* g_init_pos;
     float* g_init_vel;
@@ -55,10 +57,15 @@ __host__ __device__ inline size_t evjp_lds_bytes(int RS, int NRT) {
 //     with coalesced 16-byte loads one tile ahead of their use, and every step reads its row back with broadcast ds_read_b128: no
 //     per-workgroup copy of the whole table, so a wave's LDS is the checkpoints plus 19 KB and the staging rows and the g_r image of
 //     k_reacher_rollout_vjp are gone.
+//   * An upstream gradient of the forward's condition output (g_cond_pos / g_cond_vel, mpk_episode_return_vjp_cond) is one more
+//     g_des term of row tcond = clamp(n - 1, 0, T - 1): the condition is a copy of the PLAN, whatever the controller reads, so it goes
+//     through R0 / R1 of step tcond into the same accumulators when the chain reaches that step -- its own block, compiled into the GC
+//     instantiations only, outside the CT guards.  An episode that executed nothing still gets row 0.
 // The step-reward gradient is the aggregation's: g_ret (sum), g_ret / n (mean), g_ret at t = n - 1 (last).  No atomics, no waits on
 // other waves.  MP: promp or prodmp rows (a DMP handle arrives as its response rows), CT: the controller, DC: the DoF count compiled
-// in (0: run time).
-template <int MP, int CT, int DC>
+// in (0: run time), GC: an upstream gradient of the condition output is given (mpk_episode_return_vjp_cond with g_cond_pos or g_cond_vel;
+// without one the instantiation is the code it was before the term existed).
+template <int MP, int CT, int DC, bool GC>
 __global__ void __launch_bounds__(64) k_episode_return_vjp(const EvjpArgs a) {
     static_assert(MP != MPK_MP_DMP, "promp / prodmp rows (DMP arrives as its response rows)");
     extern __shared__ __attribute__((aligned(16))) double evjp_smem[];
@@ -99,6 +106,9 @@ __global__ void __launch_bounds__(64) k_episode_return_vjp(const EvjpArgs a) {
     const double gret = have_gr ? a.g_ret[b] : 0.0;
     const double gevery = a.agg == MPK_AGG_MEAN ? gret / (double)(n > 1 ? n : 1) : (a.agg == MPK_AGG_LAST ? 0.0 : gret);
     const int tlast = a.agg == MPK_AGG_LAST ? n - 1 : -1;
+    // the condition output's upstream goes to row tcond = clamp(n - 1, 0, T - 1) of the plan (the forward's rule: nothing executed ->
+    // row 0); it is loaded where the chain reaches that row, so nothing of it is live across the sweep and the replay
+    constexpr bool have_gc = GC;
 
     // ---- the lane's extended parameter column: the forward's gather (every load is requested before the first one is used) ----
     float x[kMaxKP];
@@ -218,6 +228,27 @@ __global__ void __launch_bounds__(64) k_episode_return_vjp(const EvjpArgs a) {
     double gxa[kMaxKP];
 #pragma unroll
     for (int k = 0; k < kMaxKP; ++k) gxa[k] = 0.0;
+    // d loss / d (cond_pos, cond_vel) times the staged tile's row i, for the lanes whose tcond this step is
+    auto cond_term = [&](const int i, const bool mine) {
+        const float auxt = MP == MPK_MP_PROMP ? sAux[i] : 0.0f;
+        const double gcp = (mine && a.g_cond_pos) ? (double)a.g_cond_pos[sidx] : 0.0;
+        const double gcv = (mine && a.g_cond_vel) ? (double)a.g_cond_vel[sidx] : 0.0;
+#pragma unroll
+        for (int k4 = 0; k4 < kMaxKP / 4; ++k4) {
+            if (4 * k4 < KP) {                            // (wave-uniform)
+                const Row4 r = read_row4(i, k4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float r0, r1;
+                    vjp_row_sm<MP>(r.r0[j], r.rh[j], r.rl[j], auxt, &r0, &r1);
+                    if (mine) {
+                        gxa[4 * k4 + j] = fma((double)r0, gcp, gxa[4 * k4 + j]);
+                        gxa[4 * k4 + j] = fma((double)r1, gcv, gxa[4 * k4 + j]);
+                    }
+                }
+            }
+        }
+    };
     double ggx = 0.0, ggy = 0.0;
     double qe = q, qde = qd;                      // the state after n steps (no executed tile: the plan-start state)
     for (int rt = NT - 1; rt >= 0; --rt) {
@@ -307,8 +338,18 @@ __global__ void __launch_bounds__(64) k_episode_return_vjp(const EvjpArgs a) {
                     }
                 }
             }
+            if (have_gc) {                                // (wave-uniform)
+                const bool mine = t == min(max(n - 1, 0), T - 1);
+                if (__any(mine) != 0) cond_term(i, mine);
+            }
         }
         __syncthreads();
+    }
+    if (have_gc && NT == 0 && T > 0) {            // (wave-uniform) nobody executed a step: the loop did not run, every tcond is row 0
+        fetch(0);
+        stage();
+        __syncthreads();
+        cond_term(0, true);
     }
     if (on) {
 #pragma unroll
@@ -366,6 +407,7 @@ int launch_episode_return_vjp(const DevCfg& c, const SharedTables& st, const Rol
     va.At = st.A + (size_t)va.RS * st.TS; va.aux = st.aux;
     va.params = q.params; va.init_pos = q.init_pos; va.init_vel = q.init_vel; va.q0 = q.q0; va.qd0 = q.qd0;
     va.n_steps = q.n_steps; va.step0 = q.step0; va.goal = q.goal; va.g_ret = q.g_ret; va.g_q = q.g_q; va.g_qd = q.g_qd;
+    va.g_cond_pos = q.g_cond_pos; va.g_cond_vel = q.g_cond_vel;
     va.g_params = q.g_params; va.g_init_pos = q.g_init_pos; va.g_init_vel = q.g_init_vel;
     va.g_q0 = q.g_q0; va.g_qd0 = q.g_qd0; va.g_goal = q.g_goal; va.q_end = q.q_end; va.qd_end = q.qd_end;
     va.B = B; va.NRT = (c.T + 15) / 16; va.steps_before_reward = q.steps_before_reward; va.agg = q.agg;
@@ -378,13 +420,17 @@ int launch_episode_return_vjp(const DevCfg& c, const SharedTables& st, const Rol
     const int dc = (D == 2 || D == 5 || D == 7) ? D : 0;
     *kernel_name = std::string("k_episode_return_vjp<") + (c.dmp_resp ? "dmp_resp" : (promp ? "promp" : "prodmp")) + ", " +
                    (ct == MPK_CTRL_MOTOR ? "motor" : (ct == MPK_CTRL_POSITION ? "position" : "velocity")) +
-                   (dc ? ", " + std::to_string(dc) : std::string()) + ">";
-    auto by_d = [&](auto mp_tag, auto ct_tag) -> int {
+                   (dc ? ", " + std::to_string(dc) : std::string()) + ">" + ((q.g_cond_pos || q.g_cond_vel) ? " + cond" : "");
+    auto by_gc = [&](auto mp_tag, auto ct_tag, auto gc_tag) -> int {
         constexpr int MP = decltype(mp_tag)::value, CT = decltype(ct_tag)::value;
-        if (dc == 2) return go(k_episode_return_vjp<MP, CT, 2>);
-        if (dc == 5) return go(k_episode_return_vjp<MP, CT, 5>);
-        if (dc == 7) return go(k_episode_return_vjp<MP, CT, 7>);
-        return go(k_episode_return_vjp<MP, CT, 0>);
+        constexpr bool GC = decltype(gc_tag)::value;
+        if (dc == 2) return go(k_episode_return_vjp<MP, CT, 2, GC>);
+        if (dc == 5) return go(k_episode_return_vjp<MP, CT, 5, GC>);
+        if (dc == 7) return go(k_episode_return_vjp<MP, CT, 7, GC>);
+        return go(k_episode_return_vjp<MP, CT, 0, GC>);
+    };
+    auto by_d = [&](auto mp_tag, auto ct_tag) -> int {
+        return (q.g_cond_pos || q.g_cond_vel) ? by_gc(mp_tag, ct_tag, std::true_type()) : by_gc(mp_tag, ct_tag, std::false_type());
     };
     auto by_ct = [&](auto mp_tag) -> int {
         using std::integral_constant;

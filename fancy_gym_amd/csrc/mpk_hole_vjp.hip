@@ -21,6 +21,8 @@ struct HvjpArgs {
     const double* g_rewards;         // [B, T] or nullptr
     const double* g_q;
     const double* g_qd;
+    const float* g_cond_pos;         // [B, D] or nullptr: upstream of the forward's condition output (row tcond of the plan)
+    const float* g_cond_vel;
     float* g_des_pos;
     float* g_des_vel;
     double* g_q0;
@@ -52,8 +54,10 @@ __host__ __device__ inline size_t hvjp_lds_bytes(int D, int NRT, int rew) {
 // requested one tile ahead (registers -> LDS staging); g_des_pos / g_des_vel of a tile are staged in the same LDS rows and leave as
 // float4 stores on 16-byte boundaries with dword stores for the up to three floats at either end of an episode's run: any pointer
 // alignment takes the same path and gives the same bits.  No atomics, no waits on other waves.  CT: the controller, REW:
-// MPK_HOLE_REW_SIMPLE / _VEL_ACC, DC: the DoF count compiled in (0: run time).
-template <int CT, int REW, int DC>
+// MPK_HOLE_REW_SIMPLE / _VEL_ACC, DC: the DoF count compiled in (0: run time), GC: an upstream gradient of the condition output is given
+// (mpk_hole_reacher_rollout_vjp_cond with g_cond_pos or g_cond_vel; without one the instantiation is the code it was before the term
+// existed).
+template <int CT, int REW, int DC, bool GC>
 __global__ void __launch_bounds__(64) k_hole_rollout_vjp(const HvjpArgs a) {
     extern __shared__ __attribute__((aligned(16))) double hvjp_smem[];
     constexpr bool VA = REW == MPK_HOLE_REW_VEL_ACC;
@@ -102,6 +106,10 @@ __global__ void __launch_bounds__(64) k_hole_rollout_vjp(const HvjpArgs a) {
     const size_t sidx = (size_t)b * D + d;
     double q = a.q0[sidx], qd = a.qd0[sidx];
     double lq = a.g_q ? a.g_q[sidx] : 0.0, lqd = a.g_qd ? a.g_qd[sidx] : 0.0;
+    // the condition output's upstream: the forward copied row tcond = clamp(n - 1, 0, T - 1) of the plan (nothing executed -> row 0),
+    // whatever the controller reads, so g_cond_* joins that row of g_des_* in float64 before the one rounding; it is loaded where the
+    // chain reaches the row: nothing of it is live across the replay
+    constexpr bool have_gc = GC;
 
     // ---- the desired (pos, vel) of a tile: item = lane + 64 k over the wave's E runs of 16 D floats, registers, then LDS ----
     constexpr int KL = DC > 0 ? ((64 / (DC > 0 ? DC : 1)) * 16 * DC + 63) / 64 : 16;
@@ -228,6 +236,10 @@ __global__ void __launch_bounds__(64) k_hole_rollout_vjp(const HvjpArgs a) {
             if (on) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) { stP[elc * SEGS + i * D + d] = 0.0f; stV[elc * SEGS + i * D + d] = 0.0f; }
+                if (have_gc && rt == 0) {                     // (a wave that executed nothing: every episode's tcond is row 0)
+                    stP[elc * SEGS + d] = a.g_cond_pos ? a.g_cond_pos[sidx] : 0.0f;
+                    stV[elc * SEGS + d] = a.g_cond_vel ? a.g_cond_vel[sidx] : 0.0f;
+                }
             }
             store_both(rt);
         }
@@ -330,6 +342,12 @@ __global__ void __launch_bounds__(64) k_hole_rollout_vjp(const HvjpArgs a) {
             } else {
                 gp = 0.0f; gv = (float)lu;
             }
+            if (have_gc && t == min(max(n - 1, 0), T - 1)) {
+                const double gcp = a.g_cond_pos ? (double)a.g_cond_pos[sidx] : 0.0, gcv = a.g_cond_vel ? (double)a.g_cond_vel[sidx] : 0.0;
+                const double kp = CT == MPK_CTRL_MOTOR ? pg * lu : (CT == MPK_CTRL_POSITION ? lu : 0.0);
+                const double kd = CT == MPK_CTRL_MOTOR ? dg * lu : (CT == MPK_CTRL_POSITION ? 0.0 : lu);
+                gp = (float)(kp + gcp); gv = (float)(kd + gcv);
+            }
             if (on && want_rows) { stP[elc * SEGS + i * D + d] = gp; stV[elc * SEGS + i * D + d] = gv; }
         }
         if (want_rows) store_both(rt);
@@ -354,6 +372,7 @@ int launch_hole_rollout_vjp(const HoleVjpLaunch& h, int B, int T, int D, void* s
     HvjpArgs va{};
     va.rc = h.rc; va.des_pos = h.des_pos; va.des_vel = h.des_vel; va.q0 = h.q0; va.qd0 = h.qd0; va.n_exec = h.n_exec; va.step0 = h.step0;
     va.hole = h.hole; va.collided = h.collided; va.g_ret = h.g_ret; va.g_rewards = h.g_rewards; va.g_q = h.g_q; va.g_qd = h.g_qd;
+    va.g_cond_pos = h.g_cond_pos; va.g_cond_vel = h.g_cond_vel;
     va.g_des_pos = h.g_des_pos; va.g_des_vel = h.g_des_vel; va.g_q0 = h.g_q0; va.g_qd0 = h.g_qd0; va.g_hole = h.g_hole;
     va.penalty = h.penalty; va.D = D; va.B = B; va.T = T; va.NRT = (T + 15) / 16; va.steps_before_reward = h.steps_before_reward;
     va.agg = h.agg;
@@ -368,12 +387,22 @@ int launch_hole_rollout_vjp(const HoleVjpLaunch& h, int B, int T, int D, void* s
     const unsigned blocks = (unsigned)(((long)B + E - 1) / E);
     auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(64), lds, stream, va); };
     // names[rew][0: D = 5, 1: run-time D]
-    auto by_rew = [&](auto ct_tag, const char* const (&names)[2][2]) -> int {
+    const bool gc = h.g_cond_pos != nullptr || h.g_cond_vel != nullptr;
+    auto by_gc = [&](auto ct_tag, auto gc_tag, const char* const (&names)[2][2]) -> int {
         constexpr int CT = decltype(ct_tag)::value;
+        constexpr bool GC = decltype(gc_tag)::value;
         const bool va_rew = h.rew_fct == MPK_HOLE_REW_VEL_ACC;
         *kernel_name = names[va_rew ? 1 : 0][D == 5 ? 0 : 1];
-        if (va_rew) return D == 5 ? go(k_hole_rollout_vjp<CT, MPK_HOLE_REW_VEL_ACC, 5>) : go(k_hole_rollout_vjp<CT, MPK_HOLE_REW_VEL_ACC, 0>);
-        return D == 5 ? go(k_hole_rollout_vjp<CT, MPK_HOLE_REW_SIMPLE, 5>) : go(k_hole_rollout_vjp<CT, MPK_HOLE_REW_SIMPLE, 0>);
+        if (va_rew)
+            return D == 5 ? go(k_hole_rollout_vjp<CT, MPK_HOLE_REW_VEL_ACC, 5, GC>) : go(k_hole_rollout_vjp<CT, MPK_HOLE_REW_VEL_ACC, 0, GC>);
+        return D == 5 ? go(k_hole_rollout_vjp<CT, MPK_HOLE_REW_SIMPLE, 5, GC>) : go(k_hole_rollout_vjp<CT, MPK_HOLE_REW_SIMPLE, 0, GC>);
+    };
+    // (the <.., cond> variants are named by appending " + cond" to the name of the plain instantiation)
+    auto by_rew = [&](auto ct_tag, const char* const (&names)[2][2]) -> int {
+        if (!gc) return by_gc(ct_tag, std::false_type(), names);
+        const int r = by_gc(ct_tag, std::true_type(), names);
+        *kernel_name = cond_variant_name(*kernel_name);
+        return r;
     };
     using std::integral_constant;
     static const char* const motor[2][2] = {{"k_hole_rollout_vjp<motor, simple, 5>", "k_hole_rollout_vjp<motor, simple>"},

@@ -13,6 +13,7 @@
 #include <limits>
 #include <map>
 #include <mutex>
+#include <set>
 
 #include "mpk_internal.h"
 
@@ -20,6 +21,14 @@ namespace mpk {
 
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
+
+// (a std::set's nodes do not move: the c_str() a handle's last_kernel points at stays valid)
+const char* cond_variant_name(const char* plain) {
+    static std::mutex m;
+    static std::set<std::string> pool;
+    std::lock_guard<std::mutex> lock(m);
+    return pool.insert(std::string(plain) + " + cond").first->c_str();
+}
 
 #define MPK_HIP(call)                                                                          \
     do {                                                                                       \
@@ -1302,6 +1311,16 @@ int mpk_reacher_rollout_vjp(mpk_handle hh, const mpk_rollout_cfg* rc, const floa
                             int32_t steps_before_reward, const double* g_rewards, const double* g_q, const double* g_qd,
                             float* g_des_pos, float* g_des_vel, double* g_q0, double* g_qd0, double* g_goal, int32_t B, int32_t T,
                             void* stream) {
+    return mpk_reacher_rollout_vjp_cond(hh, rc, des_pos, des_vel, q0, qd0, n_steps, step0, goal, steps_before_reward, g_rewards, g_q, g_qd,
+                                        nullptr, nullptr, g_des_pos, g_des_vel, g_q0, g_qd0, g_goal, B, T, stream);
+}
+
+// ... with an upstream gradient of the forward's condition output (row clamp(n - 1, 0, T - 1) of the plan); both NULL: the entry above
+int mpk_reacher_rollout_vjp_cond(mpk_handle hh, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel, const double* q0,
+                                 const double* qd0, const int32_t* n_steps, const int32_t* step0, const double* goal,
+                                 int32_t steps_before_reward, const double* g_rewards, const double* g_q, const double* g_qd,
+                                 const float* g_cond_pos, const float* g_cond_vel, float* g_des_pos, float* g_des_vel, double* g_q0,
+                                 double* g_qd0, double* g_goal, int32_t B, int32_t T, void* stream) {
     if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
     Handle* h = reinterpret_cast<Handle*>(hh);
     if (B < 0 || T < 0) { set_error("B and T must be >= 0"); return MPK_EINVAL; }
@@ -1324,7 +1343,7 @@ int mpk_reacher_rollout_vjp(mpk_handle hh, const mpk_rollout_cfg* rc, const floa
     if (!q0 || !qd0 || !goal || (T > 0 && (!des_pos || !des_vel))) { set_error("NULL buffer"); return MPK_EINVAL; }
     MPK_ON_DEVICE(h->cfg.device);
     return launch_reacher_rollout_vjp(rd, h->dev.D, des_pos, des_vel, q0, qd0, n_steps, step0, goal, steps_before_reward, g_rewards,
-                                      g_q, g_qd, g_des_pos, g_des_vel, g_q0, g_qd0, g_goal, B, T, stream, &h->last_kernel);
+                                      g_q, g_qd, g_cond_pos, g_cond_vel, g_des_pos, g_des_vel, g_q0, g_qd0, g_goal, B, T, stream, &h->last_kernel);
 }
 
 // mpk_trajectory + mpk_reacher_rollout_vjp + mpk_trajectory_vjp as one launch: the tables of (init_time_shared, T) as mpk_trajectory
@@ -1334,6 +1353,18 @@ int mpk_episode_return_vjp(mpk_handle hh, const float* params, const float* init
                            const double* goal, int32_t steps_before_reward, int32_t agg, const double* g_ret, const double* g_q,
                            const double* g_qd, float* g_params, float* g_init_pos, float* g_init_vel, double* g_q0, double* g_qd0,
                            double* g_goal, double* q_end, double* qd_end, int32_t B, void* stream) {
+    return mpk_episode_return_vjp_cond(hh, params, init_pos, init_vel, init_time_shared, rc, q0, qd0, n_steps, step0, goal,
+                                       steps_before_reward, agg, g_ret, g_q, g_qd, nullptr, nullptr, g_params, g_init_pos, g_init_vel, g_q0,
+                                       g_qd0, g_goal, q_end, qd_end, B, stream);
+}
+
+// ... with an upstream gradient of the forward's condition output (row clamp(n - 1, 0, T - 1) of the plan); both NULL: the entry above
+int mpk_episode_return_vjp_cond(mpk_handle hh, const float* params, const float* init_pos, const float* init_vel, double init_time_shared,
+                                const mpk_rollout_cfg* rc, const double* q0, const double* qd0, const int32_t* n_steps,
+                                const int32_t* step0, const double* goal, int32_t steps_before_reward, int32_t agg, const double* g_ret,
+                                const double* g_q, const double* g_qd, const float* g_cond_pos, const float* g_cond_vel, float* g_params,
+                                float* g_init_pos, float* g_init_vel, double* g_q0, double* g_qd0, double* g_goal, double* q_end,
+                                double* qd_end, int32_t B, void* stream) {
     if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
     Handle* h = reinterpret_cast<Handle*>(hh);
     if (B < 0) { set_error("B must be >= 0"); return MPK_EINVAL; }
@@ -1372,6 +1403,7 @@ int mpk_episode_return_vjp(mpk_handle hh, const float* params, const float* init
     EpisodeVjpAsk q;
     q.params = params; q.init_pos = init_pos; q.init_vel = init_vel; q.q0 = q0; q.qd0 = qd0; q.n_steps = n_steps; q.step0 = step0;
     q.goal = goal; q.steps_before_reward = steps_before_reward; q.agg = agg; q.g_ret = g_ret; q.g_q = g_q; q.g_qd = g_qd;
+    q.g_cond_pos = g_cond_pos; q.g_cond_vel = g_cond_vel;
     q.g_params = g_params; q.g_init_pos = g_init_pos; q.g_init_vel = g_init_vel; q.g_q0 = g_q0; q.g_qd0 = g_qd0; q.g_goal = g_goal;
     q.q_end = q_end; q.qd_end = qd_end;
     std::string name;
@@ -1438,6 +1470,17 @@ int mpk_hole_reacher_rollout_vjp(mpk_handle hh, const mpk_rollout_cfg* rc, const
                                  const double* hole, const uint8_t* collided, int32_t agg, const double* g_ret, const double* g_rewards,
                                  const double* g_q, const double* g_qd, float* g_des_pos, float* g_des_vel, double* g_q0, double* g_qd0,
                                  double* g_hole, int32_t B, int32_t T, void* stream) {
+    return mpk_hole_reacher_rollout_vjp_cond(hh, rc, des_pos, des_vel, q0, qd0, n_exec, step0, task, hole, collided, agg, g_ret, g_rewards,
+                                             g_q, g_qd, nullptr, nullptr, g_des_pos, g_des_vel, g_q0, g_qd0, g_hole, B, T, stream);
+}
+
+// ... with an upstream gradient of the forward's condition output (row clamp(n_exec - 1, 0, T - 1) of the plan); both NULL: the entry above
+int mpk_hole_reacher_rollout_vjp_cond(mpk_handle hh, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel,
+                                      const double* q0, const double* qd0, const int32_t* n_exec, const int32_t* step0,
+                                      const mpk_hole_task* task, const double* hole, const uint8_t* collided, int32_t agg,
+                                      const double* g_ret, const double* g_rewards, const double* g_q, const double* g_qd,
+                                      const float* g_cond_pos, const float* g_cond_vel, float* g_des_pos, float* g_des_vel, double* g_q0,
+                                      double* g_qd0, double* g_hole, int32_t B, int32_t T, void* stream) {
     if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
     Handle* h = reinterpret_cast<Handle*>(hh);
     if (B < 0 || T < 0) { set_error("B and T must be >= 0"); return MPK_EINVAL; }
@@ -1467,6 +1510,7 @@ int mpk_hole_reacher_rollout_vjp(mpk_handle hh, const mpk_rollout_cfg* rc, const
     if (!q0 || !qd0 || !hole || (T > 0 && ((need_pos && !des_pos) || (need_vel && !des_vel)))) { set_error("NULL buffer"); return MPK_EINVAL; }
     hl.des_pos = des_pos; hl.des_vel = des_vel; hl.q0 = q0; hl.qd0 = qd0; hl.n_exec = n_exec; hl.step0 = step0; hl.hole = hole;
     hl.collided = collided; hl.agg = agg; hl.g_ret = g_ret; hl.g_rewards = g_rewards; hl.g_q = g_q; hl.g_qd = g_qd;
+    hl.g_cond_pos = g_cond_pos; hl.g_cond_vel = g_cond_vel;
     hl.g_des_pos = g_des_pos; hl.g_des_vel = g_des_vel; hl.g_q0 = g_q0; hl.g_qd0 = g_qd0; hl.g_hole = g_hole;
     hl.penalty = task->collision_penalty; hl.steps_before_reward = task->steps_before_reward; hl.rew_fct = task->rew_fct;
     MPK_ON_DEVICE(h->cfg.device);

@@ -192,10 +192,14 @@ int launch_reacher_rollout(const RolloutDev& rc, int D, const float* des_pos, co
                            const Tuning& tune, int* fault);
 // mpk_reacher_rollout_vjp (mpk_rollout_vjp.hip): the adjoint of launch_reacher_rollout's computation, one launch; any upstream gradient
 // and any output may be nullptr (0 / not written).  MPK_ENOTIMPL: more than kMaxD DoF, a plant other than the double integrator, a
-// horizon whose tile checkpoints do not fit the LDS.
+// horizon whose tile checkpoints do not fit the LDS.  g_cond_pos / g_cond_vel [B, D]: the upstream of the forward's condition output,
+// added to row clamp(n - 1, 0, T - 1) of g_des_pos / g_des_vel whatever the controller reads; nullptr = 0.
+// the name of a kernel's variant with the condition upstream (GC): `plain` + " + cond", interned -- the pointer stays valid
+const char* cond_variant_name(const char* plain);
 int launch_reacher_rollout_vjp(const RolloutDev& rc, int D, const float* des_pos, const float* des_vel, const double* q0,
                                const double* qd0, const int32_t* n_steps, const int32_t* step0, const double* goal,
                                int steps_before_reward, const double* g_rewards, const double* g_q, const double* g_qd,
+                               const float* g_cond_pos, const float* g_cond_vel,
                                float* g_des_pos, float* g_des_vel, double* g_q0, double* g_qd0, double* g_goal, int B, int T,
                                void* stream, const char** kernel_name);
 // mpk_episode_return_vjp (mpk_episode_vjp.hip): mpk_trajectory, launch_reacher_rollout_vjp and launch_traj_vjp composed in one launch --
@@ -210,6 +214,7 @@ struct EpisodeVjpAsk {
     const double* goal = nullptr;                                       // [B, 2]
     int steps_before_reward = 0, agg = 0;                               // MPK_AGG_*
     const double *g_ret = nullptr, *g_q = nullptr, *g_qd = nullptr;     // [B], [B, D], [B, D] upstream
+    const float *g_cond_pos = nullptr, *g_cond_vel = nullptr;           // [B, D] upstream of the forward's condition output
     float *g_params = nullptr, *g_init_pos = nullptr, *g_init_vel = nullptr;
     double *g_q0 = nullptr, *g_qd0 = nullptr, *g_goal = nullptr;
     double *q_end = nullptr, *qd_end = nullptr;                         // [B, D] the state after n_steps, from the replay
@@ -253,6 +258,7 @@ struct HoleVjpLaunch {
     const uint8_t* collided = nullptr;                                  // [B]
     int agg = 0;                                                        // MPK_AGG_*
     const double *g_ret = nullptr, *g_rewards = nullptr, *g_q = nullptr, *g_qd = nullptr;   // [B], [B, T], [B, D], [B, D] upstream
+    const float *g_cond_pos = nullptr, *g_cond_vel = nullptr;           // [B, D] upstream of the forward's condition output
     float *g_des_pos = nullptr, *g_des_vel = nullptr;
     double *g_q0 = nullptr, *g_qd0 = nullptr, *g_hole = nullptr;
     double penalty = 0.0;

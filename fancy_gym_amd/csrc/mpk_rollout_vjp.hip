@@ -17,6 +17,8 @@ struct RvjpArgs {
     const double* g_rewards;
     const double* g_q;
     const double* g_qd;
+    const float* g_cond_pos;         // [B, D] or nullptr: upstream of the forward's condition output (row tcond of the plan)
+    const float* g_cond_vel;
     float* g_des_pos;
     float* g_des_vel;
     double* g_q0;
@@ -44,8 +46,9 @@ __host__ __device__ inline size_t rvjp_lds_bytes(int D, int NRT) {
 // of a tile are requested one tile ahead of their use (registers -> LDS staging); g_des_pos / g_des_vel of a tile are staged in the
 // same LDS rows and leave as float4 stores on 16-byte boundaries with dword stores for the up to three floats at either end of an
 // episode's run, so any pointer alignment takes the same path and gives the same bits.  No atomics, no waits on other waves.
-// CT: the controller, DC: the DoF count compiled in (0: run time).
-template <int CT, int DC>
+// CT: the controller, DC: the DoF count compiled in (0: run time), GC: an upstream gradient of the condition output is given
+// (mpk_reacher_rollout_vjp_cond with g_cond_pos or g_cond_vel; without one the instantiation is the code it was before the term existed).
+template <int CT, int DC, bool GC>
 __global__ void __launch_bounds__(64) k_reacher_rollout_vjp(const RvjpArgs a) {
     extern __shared__ __attribute__((aligned(16))) double rvjp_smem[];
     const int D = DC > 0 ? DC : a.D, T = a.T, B = a.B, NRT = a.NRT;
@@ -81,6 +84,10 @@ __global__ void __launch_bounds__(64) k_reacher_rollout_vjp(const RvjpArgs a) {
     const size_t sidx = (size_t)b * D + d;
     double q = a.q0[sidx], qd = a.qd0[sidx];
     double lq = a.g_q ? a.g_q[sidx] : 0.0, lqd = a.g_qd ? a.g_qd[sidx] : 0.0;
+    // the condition output's upstream: the forward copied row tcond = clamp(n - 1, 0, T - 1) of the plan (nothing executed -> row 0),
+    // whatever the controller reads, so g_cond_* joins that row of g_des_* in float64 before the one rounding; it is loaded where the
+    // chain reaches the row: nothing of it is live across the replay
+    constexpr bool have_gc = GC;
 
     // ---- the desired (pos, vel) of a tile: item = lane + 64 k over the wave's E runs of 16 D floats, registers, then LDS ----
     constexpr int KL = DC > 0 ? ((64 / (DC > 0 ? DC : 1)) * 16 * DC + 63) / 64 : 16;
@@ -190,6 +197,10 @@ __global__ void __launch_bounds__(64) k_reacher_rollout_vjp(const RvjpArgs a) {
             if (on) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) { stP[elc * SEGS + i * D + d] = 0.0f; stV[elc * SEGS + i * D + d] = 0.0f; }
+                if (have_gc && rt == 0) {                     // (a wave that executed nothing: every episode's tcond is row 0)
+                    stP[elc * SEGS + d] = a.g_cond_pos ? a.g_cond_pos[sidx] : 0.0f;
+                    stV[elc * SEGS + d] = a.g_cond_vel ? a.g_cond_vel[sidx] : 0.0f;
+                }
             }
             store_both(rt);
         }
@@ -272,6 +283,12 @@ __global__ void __launch_bounds__(64) k_reacher_rollout_vjp(const RvjpArgs a) {
             } else {
                 gp = 0.0f; gv = (float)lu;
             }
+            if (have_gc && t == min(max(n - 1, 0), T - 1)) {
+                const double gcp = a.g_cond_pos ? (double)a.g_cond_pos[sidx] : 0.0, gcv = a.g_cond_vel ? (double)a.g_cond_vel[sidx] : 0.0;
+                const double kp = CT == MPK_CTRL_MOTOR ? pg * lu : (CT == MPK_CTRL_POSITION ? lu : 0.0);
+                const double kd = CT == MPK_CTRL_MOTOR ? dg * lu : (CT == MPK_CTRL_POSITION ? 0.0 : lu);
+                gp = (float)(kp + gcp); gv = (float)(kd + gcv);
+            }
             if (on && want_rows) { stP[elc * SEGS + i * D + d] = gp; stV[elc * SEGS + i * D + d] = gv; }
         }
         if (want_rows) store_both(rt);
@@ -288,7 +305,7 @@ __global__ void __launch_bounds__(64) k_reacher_rollout_vjp(const RvjpArgs a) {
 int launch_reacher_rollout_vjp(const RolloutDev& rc, int D, const float* des_pos, const float* des_vel, const double* q0,
                                const double* qd0, const int32_t* n_steps, const int32_t* step0, const double* goal,
                                int steps_before_reward, const double* g_rewards, const double* g_q, const double* g_qd,
-                               float* g_des_pos, float* g_des_vel, double* g_q0, double* g_qd0, double* g_goal, int B, int T,
+                               const float* g_cond_pos, const float* g_cond_vel, float* g_des_pos, float* g_des_vel, double* g_q0, double* g_qd0, double* g_goal, int B, int T,
                                void* stream, const char** kernel_name) {
     if (D < 1 || D > kMaxD) {
         set_error("mpk_reacher_rollout_vjp: at most 16 DoF (one lane per (episode, DoF), the links of a paid step summed inside a wave)");
@@ -300,7 +317,8 @@ int launch_reacher_rollout_vjp(const RolloutDev& rc, int D, const float* des_pos
     }
     RvjpArgs va{};
     va.rc = rc; va.des_pos = des_pos; va.des_vel = des_vel; va.q0 = q0; va.qd0 = qd0; va.n_steps = n_steps; va.step0 = step0;
-    va.goal = goal; va.g_rewards = g_rewards; va.g_q = g_q; va.g_qd = g_qd; va.g_des_pos = g_des_pos; va.g_des_vel = g_des_vel;
+    va.goal = goal; va.g_rewards = g_rewards; va.g_q = g_q; va.g_qd = g_qd; va.g_cond_pos = g_cond_pos;
+    va.g_cond_vel = g_cond_vel; va.g_des_pos = g_des_pos; va.g_des_vel = g_des_vel;
     va.g_q0 = g_q0; va.g_qd0 = g_qd0; va.g_goal = g_goal;
     va.D = D; va.B = B; va.T = T; va.NRT = (T + 15) / 16; va.steps_before_reward = steps_before_reward;
     const size_t lds = rvjp_lds_bytes(D, va.NRT);
@@ -314,13 +332,22 @@ int launch_reacher_rollout_vjp(const RolloutDev& rc, int D, const float* des_pos
     const int E = 64 / D;
     const unsigned blocks = (unsigned)(((long)B + E - 1) / E);
     auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(64), lds, stream, va); };
-    auto by_d = [&](auto ct_tag, const char* n2, const char* n5, const char* n7, const char* n0) -> int {
+    const bool gc = g_cond_pos != nullptr || g_cond_vel != nullptr;
+    auto by_gc = [&](auto ct_tag, auto gc_tag, const char* n2, const char* n5, const char* n7, const char* n0) -> int {
         constexpr int CT = decltype(ct_tag)::value;
-        if (D == 2) { *kernel_name = n2; return go(k_reacher_rollout_vjp<CT, 2>); }
-        if (D == 5) { *kernel_name = n5; return go(k_reacher_rollout_vjp<CT, 5>); }
-        if (D == 7) { *kernel_name = n7; return go(k_reacher_rollout_vjp<CT, 7>); }
+        constexpr bool GC = decltype(gc_tag)::value;
+        if (D == 2) { *kernel_name = n2; return go(k_reacher_rollout_vjp<CT, 2, GC>); }
+        if (D == 5) { *kernel_name = n5; return go(k_reacher_rollout_vjp<CT, 5, GC>); }
+        if (D == 7) { *kernel_name = n7; return go(k_reacher_rollout_vjp<CT, 7, GC>); }
         *kernel_name = n0;
-        return go(k_reacher_rollout_vjp<CT, 0>);
+        return go(k_reacher_rollout_vjp<CT, 0, GC>);
+    };
+    // (the <.., cond> variants are named by appending " + cond" to the name of the plain instantiation)
+    auto by_d = [&](auto ct_tag, const char* n2, const char* n5, const char* n7, const char* n0) -> int {
+        if (!gc) return by_gc(ct_tag, std::false_type(), n2, n5, n7, n0);
+        const int r = by_gc(ct_tag, std::true_type(), n2, n5, n7, n0);
+        *kernel_name = cond_variant_name(*kernel_name);
+        return r;
     };
     using std::integral_constant;
     switch (rc.controller_type) {

@@ -216,6 +216,129 @@ class _EpisodeReturnFn(torch.autograd.Function):
         return (None,) * 9 + (g_params, g_ip, g_iv, g_goal)
 
 
+def _carry_outputs(q, qd, cond_pos, cond_vel):
+    """the differentiable outputs a carrying function adds: clones of what the launch left in q, qd and, where it wrote them, of the
+    condition -- the same bits; the caller's in-place q, qd and the launch's own cond tensors stay graph-free"""
+    outs = [q.clone(), qd.clone()]
+    if cond_pos is not None:
+        outs += [cond_pos.clone(), cond_vel.clone()]
+    return outs
+
+
+class _ReacherRolloutCarryFn(torch.autograd.Function):
+    """``_ReacherRolloutFn`` in its carrying form (``reacher_rollout(carry=...)``): the plan-start state ``q_in``, ``qd_in`` -- float64
+    [B, D] tensors with the bits of q, qd that may carry the graph of earlier plans -- are inputs, and the state after the plan
+    (``q_end``, ``qd_end``) and, with ``condition``, the gathered condition (``cond_pos``, ``cond_vel``: mpk_condition_gather on this plan
+    at ``n_steps``) are differentiable outputs.  The backward is still ONE launch, mpk_reacher_rollout_vjp[_cond], fed with the incoming
+    gradients of the rewards, the end state and the condition (a missing one is passed as NULL); it returns g_q0, g_qd0 for ``q_in``,
+    ``qd_in``.  Returns (rewards, q_end, qd_end[, cond_pos, cond_vel]); the actions are left in ``box``"""
+
+    @staticmethod
+    def forward(ctx, engine, spec, q, qd, n_steps, step0, steps_before_reward, want_actions, out, condition, box, des_pos, des_vel, goal,
+                q_in, qd_in):
+        ctx.engine, ctx.spec, ctx.n_steps, ctx.step0, ctx.sbr = engine, spec, n_steps, step0, int(steps_before_reward)
+        ctx.start = (q.clone(), qd.clone())
+        ctx.save_for_backward(des_pos, des_vel, goal)
+        ctx.set_materialize_grads(False)
+        act, rew = engine._reacher_rollout_launch(spec, des_pos, des_vel, q, qd, goal, n_steps, step0, steps_before_reward,
+                                                  want_actions, out)
+        box["actions"] = act
+        cp = cv = None
+        if condition:
+            T = des_pos.shape[1]
+            seg = n_steps if n_steps is not None else torch.full((des_pos.shape[0],), T, dtype=torch.int32, device=des_pos.device)
+            cp, cv = engine.condition_gather(des_pos, des_vel, seg)
+        box["cond_pos"], box["cond_vel"] = cp, cv
+        ctx.has_cond = condition
+        return (rew, *_carry_outputs(q, qd, cp, cv))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rew, g_qe, g_qde, g_cp=None, g_cv=None):
+        if all(g is None for g in (g_rew, g_qe, g_qde, g_cp, g_cv)):
+            return (None,) * 16
+        des_pos, des_vel, goal = ctx.saved_tensors
+        need = ctx.needs_input_grad[11:16]
+        g_pos, g_vel, g_q0, g_qd0, g_goal = ctx.engine.reacher_rollout_vjp(
+            ctx.spec, des_pos, des_vel, ctx.start[0], ctx.start[1], goal, g_rew, g_q=g_qe, g_qd=g_qde, n_steps=ctx.n_steps,
+            step0=ctx.step0, steps_before_reward=ctx.sbr, need=(need[0], need[1], need[3], need[4], need[2]),
+            g_cond_pos=g_cp, g_cond_vel=g_cv)
+        return (None,) * 11 + (g_pos, g_vel, g_goal, g_q0, g_qd0)
+
+
+class _HoleRolloutCarryFn(torch.autograd.Function):
+    """``_HoleRolloutFn`` in its carrying form (``hole_reacher_rollout(differentiable=True, carry=...)``): ``q_in``, ``qd_in`` -- float64
+    [B, D] tensors with the bits of q, qd that may carry the graph of earlier plans -- are inputs; the state after the plan and, where
+    the launch wrote it, the condition are differentiable outputs.  ONE mpk_hole_reacher_rollout_vjp[_cond] launch backward, at the
+    forward's own (n_exec, collided): an episode that executed nothing hands the gradient of its end state on unchanged.  Returns
+    ([ret][, rewards], q_end, qd_end[, cond_pos, cond_vel]), the launch's dict is left in ``box``"""
+
+    @staticmethod
+    def forward(ctx, engine, launch, box, spec, q, qd, step0, task_kw, aggregation, des_pos, des_vel, hole, q_in, qd_in):
+        ctx.engine, ctx.spec, ctx.task_kw, ctx.agg = engine, spec, task_kw, aggregation
+        ctx.start = (q.clone(), qd.clone())
+        ctx.step0 = None if step0 is None else step0.clone()      # (a replanning state's traj_steps is advanced by the launch)
+        r = launch()
+        box.update(r)
+        ctx.n_exec, ctx.collided = r["n_exec"], r["collided"]
+        ctx.has_pos = des_pos is not None
+        ctx.save_for_backward(*([des_pos] if ctx.has_pos else []), des_vel, hole)
+        ctx.set_materialize_grads(False)
+        ctx.which = tuple(k for k in ("ret", "rewards") if r[k] is not None) + ("q", "qd") + \
+            (("cond_pos", "cond_vel") if r.get("cond_pos") is not None else ())
+        return (*(r[k] for k in ("ret", "rewards") if r[k] is not None), *_carry_outputs(q, qd, r.get("cond_pos"), r.get("cond_vel")))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        saved = ctx.saved_tensors
+        des_pos = saved[0] if ctx.has_pos else None
+        des_vel, hole = saved[-2], saved[-1]
+        g = dict(zip(ctx.which, grads))
+        if all(v is None for v in g.values()):
+            return (None,) * 14
+        need = ctx.needs_input_grad[9:14]
+        g_pos, g_vel, g_q0, g_qd0, g_hole = ctx.engine.hole_reacher_rollout_vjp(
+            ctx.spec, des_pos, des_vel, ctx.start[0], ctx.start[1], hole, n_exec=ctx.n_exec, collided=ctx.collided, step0=ctx.step0,
+            g_rewards=g.get("rewards"), g_ret=g.get("ret"), aggregation=ctx.agg or "sum", g_q=g.get("q"), g_qd=g.get("qd"),
+            need=(bool(need[0]) and ctx.has_pos, need[1], need[3], need[4], need[2]),
+            g_cond_pos=g.get("cond_pos"), g_cond_vel=g.get("cond_vel"), **ctx.task_kw)
+        return (None,) * 9 + (g_pos, g_vel, g_hole, g_q0, g_qd0)
+
+
+class _EpisodeReturnCarryFn(torch.autograd.Function):
+    """``_EpisodeReturnFn`` in its carrying form (``episode_return(differentiable=True, carry=...)``): ``q_in``, ``qd_in`` -- float64
+    [B, D] tensors with the bits of q, qd that may carry the graph of earlier plans -- are inputs; the state after the plan and, where
+    the launch wrote it, the condition are differentiable outputs.  ONE mpk_episode_return_vjp[_cond] launch backward: the incoming
+    gradients of the return, the end state and the condition (a missing one as NULL) -> params, init_pos, init_vel, goal and g_q0,
+    g_qd0 for ``q_in``, ``qd_in``.  Returns (ret, q_end, qd_end[, cond_pos, cond_vel])"""
+
+    @staticmethod
+    def forward(ctx, engine, launch, spec, q, qd, step0, steps_before_reward, aggregation, init_time, params, init_pos, init_vel, goal,
+                q_in, qd_in):
+        ctx.engine, ctx.spec, ctx.sbr, ctx.agg, ctx.init_time = engine, spec, int(steps_before_reward), aggregation, float(init_time)
+        ctx.start = (q.clone(), qd.clone())
+        ctx.step0 = None if step0 is None else step0.clone()      # (a replanning state's traj_steps is advanced by the launch)
+        r = launch()
+        ctx.seg = r["seg_len"]
+        ctx.save_for_backward(params, init_pos, init_vel, goal)
+        ctx.set_materialize_grads(False)
+        return (r["ret"], *_carry_outputs(q, qd, r.get("cond_pos"), r.get("cond_vel")))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_ret, g_qe, g_qde, g_cp=None, g_cv=None):
+        if all(g is None for g in (g_ret, g_qe, g_qde, g_cp, g_cv)):
+            return (None,) * 15
+        params, init_pos, init_vel, goal = ctx.saved_tensors
+        need = ctx.needs_input_grad[9:15]
+        g_params, g_ip, g_iv, g_q0, g_qd0, g_goal, _, _ = ctx.engine.episode_return_vjp(
+            params, init_pos, init_vel, ctx.spec, ctx.start[0], ctx.start[1], goal, g_ret, g_q=g_qe, g_qd=g_qde, n_steps=ctx.seg,
+            step0=ctx.step0, steps_before_reward=ctx.sbr, aggregation=ctx.agg, init_time=ctx.init_time,
+            need=(need[0], need[1], need[2], need[4], need[5], need[3], False, False), g_cond_pos=g_cp, g_cond_vel=g_cv)
+        return (None,) * 9 + (g_params, g_ip, g_iv, g_goal, g_q0, g_qd0)
+
+
 class _RewardAggregateFn(torch.autograd.Function):
     """``reward_aggregate`` with a backward: the value is the mpk_reward_aggregate launch's, bit for bit; the aggregation is linear, so
     the gradient of the step rewards is g_ret[b] times 1 (sum), 1 / seg (mean) or the last-step indicator (last) for t < seg[b]"""
@@ -729,7 +852,7 @@ class TrajectoryEngine:
                        replan=None, n_steps: Optional[torch.Tensor] = None, reward: Optional[str] = None,
                        goal: Optional[torch.Tensor] = None, step0: Optional[torch.Tensor] = None,
                        steps_before_reward: int = 199, aggregation: str = "sum", init_time: float = 0.0,
-                       condition: bool = False, gate=None, differentiable: bool = False):
+                       condition: bool = False, gate=None, differentiable: bool = False, carry=None):
         """
         One plan of a ``verbose < 2`` step for every episode in ONE launch, nothing per step stored (mpk.h: mpk_episode_return):
         plan + controller + double-integrator plant + reward + reward_aggregation (+ the integer replanning state and the
@@ -744,8 +867,16 @@ class TrajectoryEngine:
         gradient is that of this plan's return w.r.t. this plan's inputs.  NotImplementedError for what mpk_episode_return_vjp refuses (a
         learned tau / delay, a DMP off its response route, very long horizons) BEFORE anything is launched.  Without the flag nothing
         changes: inputs that require grad are treated as constants.
+
+        ``carry=(q_in, qd_in)`` (with ``differentiable=True``): the carrying form for gradients that cross plan boundaries.  ``q_in``,
+        ``qd_in`` are float64 [B, D] tensors with the bits of q, qd that may carry the graph of the plans before; the result gains
+        ``carry = dict(q=, qd=[, cond_pos=, cond_vel=])``: clones of what the launch left in q, qd (and of the condition it wrote) that
+        carry this plan's graph -- the backward, still ONE launch (mpk_episode_return_vjp_cond), takes their gradients as g_q, g_qd,
+        g_cond_* and returns g_q0, g_qd0 to ``q_in``, ``qd_in``.  q, qd themselves and ``cond_pos`` / ``cond_vel`` stay graph-free.
         """
         self._refuse_metaworld(spec, "episode_return")
+        if carry is not None and not differentiable:
+            raise ValueError("episode_return(carry=...) is the carrying form of differentiable=True")
         if differentiable:
             if reward != "simple_reacher" or gate is not None:
                 raise NotImplementedError("episode_return(differentiable=True) is built for reward='simple_reacher' without a validity gate")
@@ -755,7 +886,9 @@ class TrajectoryEngine:
             Bn = params.shape[0]
             init_pos, init_vel = self._f32(init_pos, (Bn, self.num_dof)), self._f32(init_vel, (Bn, self.num_dof))
             goal = torch.as_tensor(goal, dtype=torch.float64, device=self.device).expand(Bn, 2)
-            if torch.is_grad_enabled() and any(t.requires_grad for t in (params, init_pos, init_vel, goal)):
+            if carry is not None:
+                q_in, qd_in = (self._f64(t, (Bn, self.num_dof)) for t in carry)
+            if torch.is_grad_enabled() and (carry is not None or any(t.requires_grad for t in (params, init_pos, init_vel, goal))):
                 # what the backward would refuse is refused here, before the forward changes the state (B = 0: the checks alone, no launch)
                 _lib.check(self._lib.mpk_episode_return_vjp(self._h, None, None, None, float(init_time), C.byref(spec.c), *([None] * 5),
                                                             int(steps_before_reward), _lib.AGG_MODES.get(aggregation, 0),
@@ -768,7 +901,12 @@ class TrajectoryEngine:
                                                    steps_before_reward=steps_before_reward, aggregation=aggregation,
                                                    init_time=init_time, condition=condition))
                     return res
-                ret = _EpisodeReturnFn.apply(self, launch, spec, q, qd, replan[0] if replan is not None else step0, steps_before_reward,
+                s0 = replan[0] if replan is not None else step0
+                if carry is not None:
+                    ret, *tw = _EpisodeReturnCarryFn.apply(self, launch, spec, q, qd, s0, steps_before_reward, aggregation, init_time,
+                                                           params.contiguous(), init_pos, init_vel, goal.contiguous(), q_in, qd_in)
+                    return dict(res, ret=ret, carry=dict(zip(("q", "qd", "cond_pos", "cond_vel"), tw)))
+                ret = _EpisodeReturnFn.apply(self, launch, spec, q, qd, s0, steps_before_reward,
                                              aggregation, init_time, params.contiguous(), init_pos, init_vel, goal.contiguous())
                 return dict(res, ret=ret)
         params = torch.as_tensor(params, dtype=torch.float32, device=self.device)
@@ -855,7 +993,7 @@ class TrajectoryEngine:
     def reacher_rollout(self, spec: RolloutSpec, des_pos: torch.Tensor, des_vel: torch.Tensor, q: torch.Tensor,
                         qd: torch.Tensor, goal: torch.Tensor, n_steps: Optional[torch.Tensor] = None,
                         step0: Optional[torch.Tensor] = None, steps_before_reward: int = 199,
-                        want_actions: bool = True, out=None):
+                        want_actions: bool = True, out=None, carry=None, condition: bool = False):
         """
         pd_rollout + SimpleReacherEnv's per-step reward (simple_reacher.py:56-72) on the torque double integrator:
         returns (actions float32 [B, T, D] or None, rewards float64 [B, T]); q, qd are updated in place.
@@ -864,6 +1002,13 @@ class TrajectoryEngine:
         plan-start state (q, qd are cloned first) and ``rewards`` carries a ``grad_fn`` whose backward is ONE mpk_reacher_rollout_vjp
         launch (``reacher_rollout_vjp``); the actions and the in-place q, qd carry no graph.  The plan-start state is a constant of that
         graph.  Otherwise -- no requires_grad, or under no_grad -- nothing changes.
+
+        ``carry=(q_in, qd_in)`` (grad enabled): the carrying form for gradients that cross plan boundaries.  ``q_in``, ``qd_in`` are
+        float64 [B, D] tensors with the bits of q, qd that may carry the graph of the plans before.  Returns (actions, rewards, carry)
+        with ``carry = dict(q=, qd=[, cond_pos=, cond_vel=])``: clones of what the launch left in q, qd that carry this plan's graph
+        and, with ``condition``, clones of the condition gathered from this plan at ``n_steps`` (``condition_gather``, whose own
+        graph-free outputs are ``carry["cond"]``).  The backward is still one launch (mpk_reacher_rollout_vjp_cond) and returns g_q0,
+        g_qd0 to ``q_in``, ``qd_in``.
         """
         self._refuse_metaworld(spec, "reacher_rollout")
         B, T, D = des_pos.shape
@@ -875,6 +1020,17 @@ class TrajectoryEngine:
             n_steps = n_steps.to(device=self.device, dtype=torch.int32).contiguous()
         if step0 is not None:
             step0 = step0.to(device=self.device, dtype=torch.int32).contiguous()
+        if carry is not None:
+            if not torch.is_grad_enabled():
+                raise ValueError("reacher_rollout(carry=...) is the carrying form of the differentiable rollout: it needs grad enabled")
+            q_in, qd_in = (self._f64(t, (B, D)) for t in carry)
+            box = {}
+            rew, *tw = _ReacherRolloutCarryFn.apply(self, spec, q, qd, n_steps, step0, steps_before_reward, want_actions, out,
+                                                    bool(condition), box, des_pos, des_vel, goal, q_in, qd_in)
+            tw = dict(zip(("q", "qd", "cond_pos", "cond_vel"), tw))
+            if condition:
+                tw["cond"] = (box["cond_pos"], box["cond_vel"])
+            return box["actions"], rew, tw
         if torch.is_grad_enabled() and (des_pos.requires_grad or des_vel.requires_grad or goal.requires_grad):
             res = _ReacherRolloutFn.apply(self, spec, q, qd, n_steps, step0, steps_before_reward, want_actions, out, des_pos, des_vel,
                                           goal)
@@ -900,7 +1056,8 @@ class TrajectoryEngine:
                             g_q: Optional[torch.Tensor] = None, g_qd: Optional[torch.Tensor] = None,
                             n_steps: Optional[torch.Tensor] = None, step0: Optional[torch.Tensor] = None,
                             steps_before_reward: int = 199, need: Sequence[bool] = (True, True, True, True, True),
-                            out: Optional[Sequence[Optional[torch.Tensor]]] = None):
+                            out: Optional[Sequence[Optional[torch.Tensor]]] = None,
+                            g_cond_pos: Optional[torch.Tensor] = None, g_cond_vel: Optional[torch.Tensor] = None):
         """
         The vector-Jacobian product of ``reacher_rollout`` (mpk.h: mpk_reacher_rollout_vjp), one launch: the gradients of a loss w.r.t.
         the step rewards [B, T] float64 and the final state (``g_q``, ``g_qd`` [B, D] float64; any of the three may be None = 0) ->
@@ -909,6 +1066,11 @@ class TrajectoryEngine:
         replanning this is the gradient of ONE plan's rewards w.r.t. that plan's trajectory.  ``need[i]`` False: that output is not
         computed (None in its place); ``out``: buffers for the needed ones.  NotImplementedError: more than 16 DoF, a plant other than
         the double integrator (the metaworld controller), horizons beyond about 2 100 steps.
+
+        ``g_cond_pos`` / ``g_cond_vel`` (float32 [B, D], either may be None = 0): the gradient of a loss w.r.t. the condition a
+        replanning forward gathered from this plan -- row ``clamp(n_steps - 1, 0, T - 1)`` of (des_pos, des_vel) -- is added to that row
+        of (g_des_pos, g_des_vel) whatever the controller reads (mpk.h: mpk_reacher_rollout_vjp_cond, the entry taken when either is
+        given).
         """
         if getattr(spec, "metaworld", False) or spec.plant != "double_integrator":
             raise NotImplementedError("reacher_rollout_vjp differentiates the torque double integrator only (plant='double_integrator'): "
@@ -926,6 +1088,7 @@ class TrajectoryEngine:
                     raise ValueError(f"{name} must be {list(shape)}, got {list(g.shape)}")
                 g = g.detach().contiguous()
             ups.append(g)
+        gc = self._cond_upstreams(g_cond_pos, g_cond_vel, B, D)
         if n_steps is not None:
             n_steps = n_steps.to(device=self.device, dtype=torch.int32).contiguous()
         if step0 is not None:
@@ -941,18 +1104,39 @@ class TrajectoryEngine:
                 res.append(out[i])
             else:
                 res.append(torch.empty(shape, dtype=dtype, device=self.device))
-        _lib.check(self._lib.mpk_reacher_rollout_vjp(
-            self._h, C.byref(spec.c), des_pos.data_ptr(), des_vel.data_ptr(), q0.data_ptr(), qd0.data_ptr(), _dptr(n_steps),
-            _dptr(step0), goal.data_ptr(), int(steps_before_reward), _dptr(ups[0]), _dptr(ups[1]), _dptr(ups[2]), _dptr(res[0]),
-            _dptr(res[1]), _dptr(res[2]), _dptr(res[3]), _dptr(res[4]), B, T, self._stream()))
+        head = (self._h, C.byref(spec.c), des_pos.data_ptr(), des_vel.data_ptr(), q0.data_ptr(), qd0.data_ptr(), _dptr(n_steps),
+                _dptr(step0), goal.data_ptr(), int(steps_before_reward), _dptr(ups[0]), _dptr(ups[1]), _dptr(ups[2]))
+        tail = (_dptr(res[0]), _dptr(res[1]), _dptr(res[2]), _dptr(res[3]), _dptr(res[4]), B, T, self._stream())
+        if gc is None:
+            _lib.check(self._lib.mpk_reacher_rollout_vjp(*head, *tail))
+        else:
+            _lib.check(self._lib.mpk_reacher_rollout_vjp_cond(*head, _dptr(gc[0]), _dptr(gc[1]), *tail))
         return tuple(res)
+
+    def _cond_upstreams(self, g_cond_pos, g_cond_vel, B: int, D: int):
+        """the condition upstreams of a ``*_vjp`` product as the ``_cond`` entry points take them: float32 [B, D], contiguous, either may
+        be None; None when neither is given (the plain entry point)"""
+        if g_cond_pos is None and g_cond_vel is None:
+            return None
+        gc = []
+        for name, g in (("g_cond_pos", g_cond_pos), ("g_cond_vel", g_cond_vel)):
+            if g is not None:
+                g = torch.as_tensor(g, device=self.device)
+                if g.dtype != torch.float32:
+                    raise ValueError(f"{name} must be float32 (the dtype of the condition), got {g.dtype}")
+                if tuple(g.shape) != (B, D):
+                    raise ValueError(f"{name} must be {[B, D]}, got {list(g.shape)}")
+                g = g.detach().contiguous()
+            gc.append(g)
+        return gc
 
     def episode_return_vjp(self, params, init_pos, init_vel, spec: RolloutSpec, q0: torch.Tensor, qd0: torch.Tensor,
                            goal: torch.Tensor, g_ret: Optional[torch.Tensor], *, g_q: Optional[torch.Tensor] = None,
                            g_qd: Optional[torch.Tensor] = None, n_steps: Optional[torch.Tensor] = None,
                            step0: Optional[torch.Tensor] = None, steps_before_reward: int = 199, aggregation: str = "sum",
                            init_time: float = 0.0, need: Sequence[bool] = (True, True, True, True, True, True, False, False),
-                           out: Optional[Sequence[Optional[torch.Tensor]]] = None):
+                           out: Optional[Sequence[Optional[torch.Tensor]]] = None,
+                           g_cond_pos: Optional[torch.Tensor] = None, g_cond_vel: Optional[torch.Tensor] = None):
         """
         The vector-Jacobian product of ``episode_return`` with reward "simple_reacher" (mpk.h: mpk_episode_return_vjp), ONE launch --
         ``trajectory``, ``reacher_rollout_vjp`` and ``trajectory_vjp`` composed without the plan or its gradient in memory: the gradients
@@ -963,6 +1147,11 @@ class TrajectoryEngine:
         executed steps (its ``seg_len``; None = all).  ``need[i]`` False: that output is not computed (None in its place); ``out``:
         buffers for the needed ones.  NotImplementedError: a learned tau / delay, a DMP off its response route, more than 16 DoF or
         contraction columns, a plant other than the double integrator, horizons beyond about 2 200 steps.
+
+        ``g_cond_pos`` / ``g_cond_vel`` (float32 [B, D], either may be None = 0): the gradient of a loss w.r.t. the ``cond_pos`` /
+        ``cond_vel`` a replanning ``episode_return(condition=True)`` returned -- row ``clamp(n_steps - 1, 0, T - 1)`` of the plan -- joins
+        the plan's gradient at that row whatever the controller reads (mpk.h: mpk_episode_return_vjp_cond, the entry taken when either
+        is given).
         """
         if getattr(spec, "metaworld", False) or spec.plant != "double_integrator":
             raise NotImplementedError("episode_return_vjp differentiates the torque double integrator only (plant='double_integrator'): "
@@ -987,6 +1176,7 @@ class TrajectoryEngine:
                     raise ValueError(f"{name} must be {list(shape)}, got {list(g.shape)}")
                 g = g.detach().contiguous()
             ups.append(g)
+        gc = self._cond_upstreams(g_cond_pos, g_cond_vel, B, D)
         if n_steps is not None:
             n_steps = n_steps.to(device=self.device, dtype=torch.int32).contiguous()
         if step0 is not None:
@@ -1003,10 +1193,14 @@ class TrajectoryEngine:
                 res.append(out[i])
             else:
                 res.append(torch.empty(shape, dtype=dtype, device=self.device))
-        _lib.check(self._lib.mpk_episode_return_vjp(
-            self._h, params.data_ptr(), init_pos.data_ptr(), init_vel.data_ptr(), float(init_time), C.byref(spec.c), q0.data_ptr(),
-            qd0.data_ptr(), _dptr(n_steps), _dptr(step0), goal.data_ptr(), int(steps_before_reward), _lib.AGG_MODES[aggregation],
-            _dptr(ups[0]), _dptr(ups[1]), _dptr(ups[2]), *(_dptr(r) for r in res), B, self._stream()))
+        head = (self._h, params.data_ptr(), init_pos.data_ptr(), init_vel.data_ptr(), float(init_time), C.byref(spec.c), q0.data_ptr(),
+                qd0.data_ptr(), _dptr(n_steps), _dptr(step0), goal.data_ptr(), int(steps_before_reward), _lib.AGG_MODES[aggregation],
+                _dptr(ups[0]), _dptr(ups[1]), _dptr(ups[2]))
+        tail = (*(_dptr(r) for r in res), B, self._stream())
+        if gc is None:
+            _lib.check(self._lib.mpk_episode_return_vjp(*head, *tail))
+        else:
+            _lib.check(self._lib.mpk_episode_return_vjp_cond(*head, _dptr(gc[0]), _dptr(gc[1]), *tail))
         return tuple(res)
 
     def hole_reacher_rollout_vjp(self, spec: RolloutSpec, des_pos: Optional[torch.Tensor], des_vel: Optional[torch.Tensor],
@@ -1016,7 +1210,8 @@ class TrajectoryEngine:
                                  aggregation: str = "sum", g_q: Optional[torch.Tensor] = None, g_qd: Optional[torch.Tensor] = None,
                                  rew_fct: str = "simple", collision_penalty: float = 100.0, steps_before_reward: int = 199,
                                  need: Sequence[bool] = (True, True, True, True, True),
-                                 out: Optional[Sequence[Optional[torch.Tensor]]] = None):
+                                 out: Optional[Sequence[Optional[torch.Tensor]]] = None,
+                                 g_cond_pos: Optional[torch.Tensor] = None, g_cond_vel: Optional[torch.Tensor] = None):
         """
         The vector-Jacobian product of ``hole_reacher_rollout`` with the episode's end and collision verdict frozen (mpk.h:
         mpk_hole_reacher_rollout_vjp), one launch: the gradients of a loss w.r.t. the step rewards [B, T], their aggregate ``g_ret`` [B]
@@ -1028,6 +1223,11 @@ class TrajectoryEngine:
         None, its gradient is zeros), the position controller the other way round.  ``need[i]`` False: that output is not computed (None
         in its place); ``out``: buffers for the needed ones.  ValueError: a plant other than 'velocity_direct'.  NotImplementedError:
         rew_fct 'unbounded', more than 16 DoF, horizons beyond about 2 200 steps.
+
+        ``g_cond_pos`` / ``g_cond_vel`` (float32 [B, D], either may be None = 0): the gradient of a loss w.r.t. the condition a
+        replanning forward gathered from this plan -- row ``clamp(n_exec - 1, 0, T - 1)`` of (des_pos, des_vel) -- is added to that row
+        of (g_des_pos, g_des_vel) whatever the controller reads: the velocity controller's g_des_pos is then that row and zeros
+        (mpk.h: mpk_hole_reacher_rollout_vjp_cond, the entry taken when either is given).
         """
         if spec.plant != "velocity_direct":
             raise ValueError("hole_reacher_rollout_vjp differentiates plant='velocity_direct' (reacher_rollout_vjp: the double integrator)")
@@ -1054,6 +1254,7 @@ class TrajectoryEngine:
                     raise ValueError(f"{name} must be {list(shape)}, got {list(g.shape)}")
                 g = g.detach().contiguous()
             ups.append(g)
+        gc = self._cond_upstreams(g_cond_pos, g_cond_vel, B, D)
         if n_exec is not None:
             n_exec = n_exec.to(device=self.device, dtype=torch.int32).contiguous()
         if collided is not None:
@@ -1072,10 +1273,14 @@ class TrajectoryEngine:
             else:
                 res.append(torch.empty(shape, dtype=dtype, device=self.device))
         task = _lib.mpk_hole_task(float(collision_penalty), 0, 0, int(steps_before_reward), rew)
-        _lib.check(self._lib.mpk_hole_reacher_rollout_vjp(
-            self._h, C.byref(spec.c), _dptr(des[0]), _dptr(des[1]), q0.data_ptr(), qd0.data_ptr(), _dptr(n_exec), _dptr(step0),
-            C.byref(task), hole.data_ptr(), _dptr(collided), _lib.AGG_MODES[aggregation], _dptr(ups[0]), _dptr(ups[1]), _dptr(ups[2]),
-            _dptr(ups[3]), *(_dptr(r) for r in res), B, T, self._stream()))
+        head = (self._h, C.byref(spec.c), _dptr(des[0]), _dptr(des[1]), q0.data_ptr(), qd0.data_ptr(), _dptr(n_exec), _dptr(step0),
+                C.byref(task), hole.data_ptr(), _dptr(collided), _lib.AGG_MODES[aggregation], _dptr(ups[0]), _dptr(ups[1]), _dptr(ups[2]),
+                _dptr(ups[3]))
+        tail = (*(_dptr(r) for r in res), B, T, self._stream())
+        if gc is None:
+            _lib.check(self._lib.mpk_hole_reacher_rollout_vjp(*head, *tail))
+        else:
+            _lib.check(self._lib.mpk_hole_reacher_rollout_vjp_cond(*head, _dptr(gc[0]), _dptr(gc[1]), *tail))
         return tuple(res)
 
     def hole_reacher_rollout(self, spec: RolloutSpec, des_pos: Optional[torch.Tensor], des_vel: torch.Tensor, q: torch.Tensor,
@@ -1084,7 +1289,7 @@ class TrajectoryEngine:
                              n_steps: Optional[torch.Tensor] = None, step0: Optional[torch.Tensor] = None, replan=None,
                              condition: bool = False, want_actions: bool = True, want_rewards: bool = True,
                              aggregation: Optional[str] = "sum", rew_fct: str = "simple",
-                             reward_state: Optional[torch.Tensor] = None, differentiable: bool = False):
+                             reward_state: Optional[torch.Tensor] = None, differentiable: bool = False, carry=None):
         """
         The HoleReacher step loop on the device (mpk.h: mpk_hole_reacher_rollout2; spec.plant 'velocity_direct'): controller, clip,
         direct-velocity plant, collisions, reward, and the break on collision.  q, qd are updated in place.  ``rew_fct`` is the
@@ -1102,14 +1307,23 @@ class TrajectoryEngine:
         ``grad_fn`` whose backward is ONE mpk_hole_reacher_rollout_vjp launch (``hole_reacher_rollout_vjp``) fed with the forward's own
         ``n_exec`` / ``collided``: the pathwise gradient with the episode's end and its collision verdict frozen.  The actions and the
         in-place q, qd carry no graph; the plan-start state is a constant of it.
+
+        ``carry=(q_in, qd_in)`` (with ``differentiable=True``): the carrying form for gradients that cross plan boundaries.  ``q_in``,
+        ``qd_in`` are float64 [B, D] tensors with the bits of q, qd that may carry the graph of the plans before; the dict gains
+        ``carry = dict(q=, qd=[, cond_pos=, cond_vel=])``: clones of what the launch left in q, qd (and of the condition it wrote) that
+        carry this plan's graph.  The backward is still one launch (mpk_hole_reacher_rollout_vjp_cond) and returns g_q0, g_qd0 to
+        ``q_in``, ``qd_in``; q, qd and ``cond_pos`` / ``cond_vel`` stay graph-free.
         """
         if spec.plant != "velocity_direct":
             raise ValueError("hole_reacher_rollout integrates plant='velocity_direct'")
+        if carry is not None and not differentiable:
+            raise ValueError("hole_reacher_rollout(carry=...) is the carrying form of differentiable=True")
         if differentiable and rew_fct == "unbounded":
             raise NotImplementedError("hole_reacher_rollout(differentiable=True): rew_fct='unbounded' pays on the end effector stored at "
                                       "step 180, which may belong to an earlier plan -- its gradient crosses plans and is not built")
-        if differentiable and torch.is_grad_enabled() and (want_rewards or aggregation is not None) and any(
-                isinstance(t, torch.Tensor) and t.requires_grad for t in (des_pos, des_vel, hole)):
+        if differentiable and torch.is_grad_enabled() and (carry is not None or (
+                (want_rewards or aggregation is not None) and any(
+                    isinstance(t, torch.Tensor) and t.requires_grad for t in (des_pos, des_vel, hole)))):
             kw = dict(collision_penalty=collision_penalty, allow_self_collision=allow_self_collision,
                       allow_wall_collision=allow_wall_collision, steps_before_reward=steps_before_reward, n_steps=n_steps, step0=step0,
                       replan=replan, condition=condition, want_actions=want_actions, want_rewards=want_rewards, aggregation=aggregation,
@@ -1119,14 +1333,22 @@ class TrajectoryEngine:
             dp, dv = (des_pos.contiguous() if des_pos is not None else None), des_vel.contiguous()
             s0 = replan[0] if replan is not None else step0
             box = {}
-            outs = _HoleRolloutFn.apply(
-                self, lambda: self.hole_reacher_rollout(spec, None if dp is None else dp.detach(), dv.detach(), q, qd, hole_t.detach(), **kw),
-                box, spec, q, qd, s0, dict(rew_fct=rew_fct, collision_penalty=collision_penalty, steps_before_reward=steps_before_reward),
-                aggregation, dp, dv, hole_t)
+
+            def launch():
+                return self.hole_reacher_rollout(spec, None if dp is None else dp.detach(), dv.detach(), q, qd, hole_t.detach(), **kw)
+            task_kw = dict(rew_fct=rew_fct, collision_penalty=collision_penalty, steps_before_reward=steps_before_reward)
+            if carry is not None:
+                D = dv.shape[2]
+                q_in, qd_in = (self._f64(t, (B, D)) for t in carry)
+                outs = _HoleRolloutCarryFn.apply(self, launch, box, spec, q, qd, s0, task_kw, aggregation, dp, dv, hole_t, q_in, qd_in)
+            else:
+                outs = _HoleRolloutFn.apply(self, launch, box, spec, q, qd, s0, task_kw, aggregation, dp, dv, hole_t)
             outs = list(outs)
             for k in ("ret", "rewards"):
                 if box[k] is not None:
                     box[k] = outs.pop(0)
+            if carry is not None:
+                box["carry"] = dict(zip(("q", "qd", "cond_pos", "cond_vel"), outs))
             return box
         B, T, D = des_vel.shape
         assert des_vel.dtype == torch.float32 and (des_pos is None or des_pos.dtype == torch.float32)

@@ -982,6 +982,47 @@ int mpk_episode_return_vjp(mpk_handle h, const float* params, const float* init_
                            double* g_goal, double* q_end, double* qd_end, int32_t B, void* stream);
 
 /*
+ * The three rollout adjoints with an upstream gradient of the forward's CONDITION output (added within ABI 4; no existing prototype
+ * changes -- they stand here, beside the adjoints they extend; the HoleReacher forward is specified with mpk_hole_reacher_rollout_vjp
+ * below): the arguments of mpk_episode_return_vjp, mpk_reacher_rollout_vjp and mpk_hole_reacher_rollout_vjp plus, after g_qd,
+ *   g_cond_pos, g_cond_vel   dev float [B, D] or NULL (= 0): d loss / d (cond_pos, cond_vel) of the forward launch
+ * With condition_on_desired a replanning forward (mpk_episode_return / mpk_replan_step with a replan state that has cond_pos,
+ * mpk_hole_reacher_rollout2 likewise; mpk_condition_gather) leaves the desired (pos, vel) of the plan's row
+ *   tcond[b] = clamp(n[b] - 1, 0, T - 1),     n = n_steps / n_exec as the backward is given it (clamped to [0, T]),
+ * in cond_pos / cond_vel: the last executed step, and row 0 for an episode that executed nothing.  The backward adds
+ *   g_des_pos[b, tcond, d] += g_cond_pos[b, d] ;  g_des_vel[b, tcond, d] += g_cond_vel[b, d]
+ * in float64, before the single rounding to float32.  This holds whatever the controller reads: the condition is a copy of the PLAN,
+ * not of what the controller consumed, so a velocity controller's g_des_pos -- all zeros without the term -- then carries g_cond_pos in
+ * row tcond and exact zeros elsewhere (the position controller's g_des_vel likewise); mpk_hole_reacher_rollout_vjp_cond still reads no
+ * des_pos for the velocity controller.  mpk_episode_return_vjp_cond, where the plan's gradient never reaches memory, sends the term
+ * through the R0 / R1 rows of step tcond into the lane's column accumulators, outside the controller's guards.  The term joins when
+ * the reverse chain reaches step tcond (accumulation order t descending); with n = 0 it is the only term.  The plant adjoint (g_q0,
+ * g_qd0), g_goal / g_hole do not see it.
+ * With both pointers NULL every output is bit-identical to the predecessor, which calls its _cond entry with NULL: the same
+ * instantiation as before runs, the term is compiled into a variant of its own (a template flag), which mpk_last_kernel names by
+ * appending " + cond", e.g. "k_reacher_rollout_vjp<motor, 5> + cond".  Everything else is the predecessor's: one launch, no atomics,
+ * an episode never leaves its wave, the same bits from run to run and for any pointer alignment, nothing allocated or synchronised,
+ * and the same MPK_EINVAL / MPK_ENOTIMPL cases.
+ */
+int mpk_episode_return_vjp_cond(mpk_handle h, const float* params, const float* init_pos, const float* init_vel, double init_time_shared,
+                                const mpk_rollout_cfg* rc, const double* q0, const double* qd0, const int32_t* n_steps,
+                                const int32_t* step0, const double* goal, int32_t steps_before_reward, int32_t agg, const double* g_ret,
+                                const double* g_q, const double* g_qd, const float* g_cond_pos, const float* g_cond_vel, float* g_params,
+                                float* g_init_pos, float* g_init_vel, double* g_q0, double* g_qd0, double* g_goal, double* q_end,
+                                double* qd_end, int32_t B, void* stream);
+int mpk_reacher_rollout_vjp_cond(mpk_handle h, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel, const double* q0,
+                                 const double* qd0, const int32_t* n_steps, const int32_t* step0, const double* goal,
+                                 int32_t steps_before_reward, const double* g_rewards, const double* g_q, const double* g_qd,
+                                 const float* g_cond_pos, const float* g_cond_vel, float* g_des_pos, float* g_des_vel, double* g_q0,
+                                 double* g_qd0, double* g_goal, int32_t B, int32_t T, void* stream);
+int mpk_hole_reacher_rollout_vjp_cond(mpk_handle h, const mpk_rollout_cfg* rc, const float* des_pos, const float* des_vel,
+                                      const double* q0, const double* qd0, const int32_t* n_exec, const int32_t* step0,
+                                      const mpk_hole_task* task, const double* hole, const uint8_t* collided, int32_t agg,
+                                      const double* g_ret, const double* g_rewards, const double* g_q, const double* g_qd,
+                                      const float* g_cond_pos, const float* g_cond_vel, float* g_des_pos, float* g_des_vel, double* g_q0,
+                                      double* g_qd0, double* g_hole, int32_t B, int32_t T, void* stream);
+
+/*
  * The vector-Jacobian product of mpk_hole_reacher_rollout2 with the episode's end and its collision verdict FROZEN (appended under ABI 4):
  * the step at which an episode ends and whether it collided are piecewise constant in the plan, everything else -- controller, clip,
  * direct-velocity plant, the squared distance to the hole's bottom, the acceleration and velocity costs -- is smooth, so the pathwise
