@@ -214,6 +214,10 @@ SIGNATURES = {
     "mpk_hole_reacher_rollout_vjp_cond": (C.c_int, [_vp, C.POINTER(mpk_rollout_cfg), _vp, _vp, _vp, _vp, _vp, _vp,
                                                     C.POINTER(mpk_hole_task), _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                     _vp, _vp, _i32, _i32, _vp]),
+    # the closed-form fit of params to demonstrations: shared phase, per-episode phase, the latter's status word
+    "mpk_trajectory_fit": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _vp, _i32, _vp]),
+    "mpk_trajectory_phase_fit": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _vp, _i32, _vp]),
+    "mpk_fit_status": (C.c_int, [_vp, C.POINTER(C.c_int32), _vp]),
     "mpk_trajectory_phase_vjp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
 }
 
@@ -221,10 +225,10 @@ _lib: Optional[C.CDLL] = None
 
 # the files libmpk.so is built from, in the order mpk_source_hash() is defined over (include/mpk.h)
 _ROOT = os.path.dirname(_HERE)
-KERNEL_UNITS = ("mpk_traj_family.hip", "mpk_traj_ring.hip", "mpk_episode.hip", "mpk_episode_vjp.hip", "mpk_traj_launch.hip", "mpk_traj_wide.hip", "mpk_traj_vjp.hip", "mpk_traj_phase.hip",
+KERNEL_UNITS = ("mpk_traj_family.hip", "mpk_traj_ring.hip", "mpk_episode.hip", "mpk_episode_vjp.hip", "mpk_traj_launch.hip", "mpk_traj_wide.hip", "mpk_traj_vjp.hip", "mpk_traj_fit.hip", "mpk_traj_phase.hip",
                 "mpk_phase_fused.hip", "mpk_rollout.hip", "mpk_rollout_vjp.hip", "mpk_hole.hip", "mpk_hole_vjp.hip", "mpk_phase_vjp.hip", "mpk_reset.hip", "mpk_obs.hip", "mpk_autoreset.hip", "mpk_env_step.hip", "mpk_misc.hip")          # translation units of the device code (mpk_traj_family.hip: once per MP type)
 KERNEL_HEADERS = ("mpk_dev.h", "mpk_tile.h", "mpk_traj_tiles.h", "mpk_traj_stream.h", "mpk_traj_flat.h", "mpk_traj_ring.h", "mpk_traj_quad.h",
-                  "mpk_traj_pipe.h", "mpk_traj_route.h", "mpk_reward.h", "mpk_vjp_row.h", "mpk_phase.h", "mpk_trace_reader.h", "mpk_nprng.h", "mpk_plant.h", "mpk_reacher_env.h", "mpk_hole_geom.h")
+                  "mpk_traj_pipe.h", "mpk_traj_route.h", "mpk_reward.h", "mpk_vjp_row.h", "mpk_run_stage.h", "mpk_phase.h", "mpk_trace_reader.h", "mpk_nprng.h", "mpk_plant.h", "mpk_reacher_env.h", "mpk_hole_geom.h")
 SOURCE_FILES = (os.path.join(_ROOT, "include", "mpk.h"), os.path.join(_HERE, "csrc", "mpk_internal.h"),
                 os.path.join(_HERE, "csrc", "mpk_host.cpp")) + \
     tuple(os.path.join(_HERE, "csrc", f) for f in KERNEL_HEADERS + KERNEL_UNITS)

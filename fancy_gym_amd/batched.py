@@ -603,6 +603,14 @@ class BatchedBlackBox:
         self._twin = None           # (replan_gradient: a plan asked for on its own cuts the chain)
         return self._get_trajectory(params)
 
+    def fit_trajectory(self, pos, phase_params=None, reg: float = 1e-9) -> torch.Tensor:
+        """params [B, P] whose plan reproduces the demonstrated positions ``pos`` [B, T, D] best (``TrajectoryEngine.fit_trajectory``:
+        regularised least squares, one launch) from the init_time / init_pos / init_vel ``get_trajectory`` would use now -- so the
+        result can be handed straight to ``step`` / ``get_trajectory``"""
+        cond_pos = self.condition_pos if self.condition_pos is not None else self.q.float()
+        cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
+        return self.engine.fit_trajectory(pos, cond_pos, cond_vel, self._plan_time(), reg=reg, phase_params=phase_params)
+
     def _carry_start(self):
         """replan_gradient="episode": (init_pos, init_vel, q_in, qd_in) of the next plan -- what the twins of the plan before give (the
         same bits as ``_plan_condition`` and ``q``, ``qd``), or right after a cut the constants themselves"""

@@ -221,6 +221,16 @@ struct CacheEntry {
     unsigned long long capture_id = 0;
 };
 
+// mpk_trajectory_fit: the float64 factor of one (init_time, T, reg) beside the handle's tables (fit_factor_build), on the device
+struct FitEntry {
+    bool valid = false;
+    uint32_t key = 0;    // bit pattern of the fp32 init_time
+    int T = 0;
+    double reg = 0.0;
+    double* d_fac = nullptr;
+    uint64_t stamp = 0;
+};
+
 struct Handle {
     mpk_config cfg{};
     HostTables tab;
@@ -256,6 +266,9 @@ struct Handle {
     Tuning tune;                 // per-handle overrides (mpk_set_option); -1 = follow the process-wide default
     float* d_pre = nullptr;      // MPK_DMP_FIRST_IS_STEP: [2][pre_cap] boundary state after the pre-step
     size_t pre_cap = 0;
+    static constexpr int kFitCache = 16;
+    FitEntry fit_cache[kFitCache];
+    int32_t* d_fit_status = nullptr;   // mpk_trajectory_phase_fit: 1 after a launch in which an episode's Gram matrix had no factor
 };
 
 static Tuning effective_tuning(const Handle* h);   // defined beside the option table
@@ -412,6 +425,7 @@ static int upload_times(Handle* h) {
     MPK_HIP(hipMemcpy(h->d_times, h->times.data(), sizeof(float) * T, hipMemcpyHostToDevice));
     for (auto& e : h->cache) { e.valid = false; e.pinned = false; e.deferred = false; }
     for (auto& e : h->cache_resp) { e.valid = false; e.pinned = false; e.deferred = false; }
+    for (auto& e : h->fit_cache) e.valid = false;
     return MPK_OK;
 }
 
@@ -431,6 +445,9 @@ static void free_handle(Handle* h) {
     if (h->h_fault) (void)hipHostFree(h->h_fault);
     if (h->d_idx) (void)hipFree(h->d_idx);
     if (h->d_pre) (void)hipFree(h->d_pre);
+    for (auto& e : h->fit_cache)
+        if (e.d_fac) (void)hipFree(e.d_fac);
+    if (h->d_fit_status) (void)hipFree(h->d_fit_status);
     delete h;
 }
 
@@ -1084,6 +1101,128 @@ int mpk_trajectory_vjp(mpk_handle hh, const float* g_pos, const float* g_vel, do
     if (rc != MPK_OK) return rc;
     return launch_traj_vjp(dmp ? h->dev_resp : h->dev, st, g_pos, g_vel, g_params, g_init_pos, g_init_vel, B, h->num_cu, stream,
                            &h->last_kernel, tune);
+}
+
+// the factor of (init_time, T, reg): cached, or built here from the table's position rows as the device holds them -- a copy back,
+// ONE synchronisation of `stream` per new key
+static int get_fit_factor(Handle* h, const DevCfg& dev, const SharedTables& st, float init_time, double reg, void* stream,
+                          const double** out) {
+    uint32_t key;
+    std::memcpy(&key, &init_time, 4);
+    ++h->stamp;
+    FitEntry* victim = nullptr;
+    for (auto& e : h->fit_cache) {
+        if (e.valid && e.key == key && e.T == dev.T && e.reg == reg) {
+            e.stamp = h->stamp; *out = e.d_fac;
+            return MPK_OK;
+        }
+        if (!victim || (!e.valid && victim->valid) || (e.valid == victim->valid && e.stamp < victim->stamp)) victim = &e;
+    }
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) (void)hipGetLastError();
+    if (cs == hipStreamCaptureStatusActive) {
+        set_error("mpk_trajectory_fit: the factor of this (init_time, reg) is not cached and building it synchronises the stream: call "
+                  "once outside the stream capture first");
+        return MPK_EINVAL;
+    }
+    std::vector<float> rows((size_t)dev.KP * st.TS);
+    MPK_HIP(hipMemcpyAsync(rows.data(), st.A, rows.size() * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    MPK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    std::vector<double> fac((size_t)fit_factor_doubles());
+    const int rc = fit_factor_build(dev, rows.data(), st.TS, reg, fac.data());
+    if (rc != MPK_OK) return rc;
+    victim->valid = false;
+    if (!victim->d_fac) MPK_HIP(hipMalloc((void**)&victim->d_fac, fac.size() * sizeof(double)));
+    // (a reused slot: the copy is ordered behind every earlier launch on this stream that reads it)
+    MPK_HIP(hipMemcpyAsync(victim->d_fac, fac.data(), fac.size() * sizeof(double), hipMemcpyHostToDevice, (hipStream_t)stream));
+    MPK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    victim->valid = true; victim->key = key; victim->T = dev.T; victim->reg = reg; victim->stamp = h->stamp;
+    *out = victim->d_fac;
+    return MPK_OK;
+}
+
+int mpk_trajectory_fit(mpk_handle hh, const float* pos, const float* init_pos, const float* init_vel, const float* init_time,
+                       double init_time_shared, double reg, float* params, int32_t B, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (B < 0) { set_error("B must be >= 0"); return MPK_EINVAL; }
+    if (!(reg > 0.0) || !std::isfinite(reg)) {
+        set_error("mpk_trajectory_fit: reg must be a positive finite number, got " + std::to_string(reg));
+        return MPK_EINVAL;
+    }
+    if (h->cfg.learn_tau || h->cfg.learn_delay || init_time) {
+        set_error(std::string("mpk_trajectory_fit: ") + (init_time ? "a per-episode init_time" : "a learned tau / delay") +
+                  " gives every episode its own phase and its own Gram matrix: that is the per-episode-phase fit "
+                  "(mpk_trajectory_phase_fit), not this shared-phase entry point");
+        return MPK_EINVAL;
+    }
+    const Tuning tune = effective_tuning(h);
+    const bool dmp = h->cfg.mp_type == MPK_MP_DMP;
+    if (dmp && (h->cfg.dmp_first_sample == MPK_DMP_FIRST_IS_STEP || !dmp_response(h, nullptr, tune))) {
+        set_error("mpk_trajectory_fit: a DMP handle is fitted through its response rows only (<= 16 DoF, <= 13 basis functions, alpha ds "
+                  "<= 1, dmp_first_sample = init, option \"dmp_response\" not 0)");
+        return MPK_ENOTIMPL;
+    }
+    const DevCfg& dev = dmp ? h->dev_resp : h->dev;
+    int rc = traj_fit_limits(dev, nullptr, nullptr, nullptr);
+    if (rc != MPK_OK) return rc;
+    if (B == 0 || dev.D == 0) return MPK_OK;
+    if (!pos || !params) { set_error("mpk_trajectory_fit: NULL buffer"); return MPK_EINVAL; }
+    if ((!init_pos || !init_vel) && h->cfg.mp_type != MPK_MP_PROMP) {
+        set_error("mpk_trajectory_fit: init_pos and init_vel are required (only a ProMP may pass NULL: zeros)");
+        return MPK_EINVAL;
+    }
+    MPK_ON_DEVICE(h->cfg.device);
+    SharedTables st;
+    rc = get_shared(h, (float)init_time_shared, stream, &st, dmp);
+    if (rc != MPK_OK) return rc;
+    const double* fac = nullptr;
+    rc = get_fit_factor(h, dev, st, (float)init_time_shared, reg, stream, &fac);
+    if (rc != MPK_OK) return rc;
+    return launch_traj_fit(dev, st, fac, pos, init_pos, init_vel, params, B, h->num_cu, stream, &h->last_kernel);
+}
+
+int mpk_trajectory_phase_fit(mpk_handle hh, const float* pos, const float* phase_params, const float* init_pos, const float* init_vel,
+                             const float* init_time, double init_time_shared, double reg, float* params, int32_t B, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (B < 0) { set_error("B must be >= 0"); return MPK_EINVAL; }
+    if (!(reg > 0.0) || !std::isfinite(reg)) {
+        set_error("mpk_trajectory_phase_fit: reg must be a positive finite number, got " + std::to_string(reg));
+        return MPK_EINVAL;
+    }
+    int rc = phase_fit_limits(h->dev);
+    if (rc != MPK_OK) return rc;
+    const bool learned = h->cfg.learn_tau || h->cfg.learn_delay;
+    if (learned && !phase_params && B > 0) {
+        set_error("mpk_trajectory_phase_fit: this handle learns tau / delay: phase_params [B, n_phase] is required (an input of the fit)");
+        return MPK_EINVAL;
+    }
+    if (B == 0) return MPK_OK;
+    if (!pos || !params) { set_error("mpk_trajectory_phase_fit: NULL buffer"); return MPK_EINVAL; }
+    if ((!init_pos || !init_vel) && h->cfg.mp_type != MPK_MP_PROMP) {
+        set_error("mpk_trajectory_phase_fit: init_pos and init_vel are required (only a ProMP may pass NULL: zeros)");
+        return MPK_EINVAL;
+    }
+    MPK_ON_DEVICE(h->cfg.device);
+    if (!h->d_fit_status) MPK_HIP(hipMalloc((void**)&h->d_fit_status, sizeof(int32_t)));
+    MPK_HIP(hipMemsetAsync(h->d_fit_status, 0, sizeof(int32_t), (hipStream_t)stream));
+    PhaseFitLaunch q;
+    q.pos = pos; q.phase = learned ? phase_params : nullptr; q.init_pos = init_pos; q.init_vel = init_vel; q.init_time = init_time;
+    q.init_time_shared = (float)init_time_shared; q.reg = reg; q.params = params; q.range_flag = h->d_flag; q.status = h->d_fit_status;
+    q.B = B;
+    return launch_phase_fit(h->dev, q, h->num_cu, stream, &h->last_kernel);
+}
+
+int mpk_fit_status(mpk_handle hh, int32_t* not_positive_definite, void* stream) {
+    if (!hh || !not_positive_definite) { set_error("NULL argument"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    *not_positive_definite = 0;
+    if (!h->d_fit_status) return MPK_OK;
+    MPK_ON_DEVICE(h->cfg.device);
+    MPK_HIP(hipMemcpyAsync(not_positive_definite, h->d_fit_status, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    MPK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    return MPK_OK;
 }
 
 int mpk_trajectory_actions(mpk_handle hh, const float* params, const float* init_pos, const float* init_vel,

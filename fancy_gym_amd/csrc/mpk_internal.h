@@ -279,6 +279,31 @@ struct PhaseVjpLaunch {
     int B = 0;
 };
 int launch_phase_vjp(const DevCfg& c, const PhaseVjpLaunch& q, int num_cu, void* stream, const char** kernel_name);
+// mpk_trajectory_fit (mpk_traj_fit.hip): the regularised least-squares fit of the shared-phase map to demonstrated positions, one
+// launch of k_traj_fit_tile.  fac: fit_factor_doubles() device doubles from fit_factor_build -- the Cholesky factor of the fitted columns'
+// Gram matrix plus reg I and the cross term of the given columns, from the float32 position rows [KP][TS] of the launch's table (host
+// copy).  c: the configuration the tables were built for (a DMP handle: its response configuration).  traj_fit_limits: MPK_OK, or
+// MPK_ENOTIMPL with the DoF / column / horizon limit in the message (no HIP call; the outputs may be nullptr).
+int fit_factor_doubles();
+int fit_factor_build(const DevCfg& c, const float* rows, int TS, double reg, double* fac);
+int traj_fit_limits(const DevCfg& c, size_t* lds_out, int* sh_out, int* stride_out);
+// mpk_trajectory_phase_fit (mpk_traj_fit.hip): the same fit for a per-episode phase of promp / prodmp, one launch of k_phase_fit: one
+// wave per episode builds the episode's own Gram matrix, factors it and solves.  phase: the tau / delay columns of params [B, n_phase]
+// (nullptr: none learned).  status: set to 1 by an episode whose Gram + reg I is not positive definite (its params row is NaN).
+// MPK_ENOTIMPL: dmp, shapes beyond the wave kernel k_traj_phase's (phase_fit_limits: no HIP call).
+struct PhaseFitLaunch {
+    const float *pos = nullptr, *phase = nullptr, *init_pos = nullptr, *init_vel = nullptr;
+    const float* init_time = nullptr;
+    float init_time_shared = 0.f;
+    double reg = 0.0;
+    float* params = nullptr;
+    int32_t *range_flag = nullptr, *status = nullptr;
+    int B = 0;
+};
+int phase_fit_limits(const DevCfg& c);
+int launch_phase_fit(const DevCfg& c, const PhaseFitLaunch& q, int num_cu, void* stream, const char** kernel_name);
+int launch_traj_fit(const DevCfg& c, const SharedTables& st, const double* fac, const float* pos, const float* init_pos,
+                    const float* init_vel, float* params, int B, int num_cu, void* stream, const char** kernel_name);
 int launch_episode_reset(const double* init_q, const double* init_qd, double* q, double* qd, float* cond_pos,
                          float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done, int B, int D,
                          void* stream);

@@ -12,6 +12,8 @@
 //   mpk_traj_launch.hip  k_build_shared + plan_traj_shared (kernel selection rule, one function per family) + launch_traj_shared
 //   mpk_traj_wide.hip    k_traj_wide
 //   mpk_traj_vjp.hip     k_traj_vjp_tile / k_traj_vjp_generic: the shared-phase map transposed (mpk_trajectory_vjp)
+//   mpk_run_stage.h      an episode's contiguous run HBM -> LDS image, alignment-shifted, shared by mpk_traj_vjp.hip and mpk_traj_fit.hip
+//   mpk_traj_fit.hip     k_traj_fit_tile: the least-squares fit of the shared-phase map to demonstrations (mpk_trajectory_fit)
 //   mpk_traj_phase.hip   per-episode phase kernels
 //   mpk_phase_fused.hip  per-episode phase: the fused entry points (actions, closed loop, replanning step, verbose < 2 step, validity gate)
 //   mpk_rollout.hip      rollout kernels
@@ -35,6 +37,7 @@
 #include "mpk_traj_launch.hip"
 #include "mpk_traj_wide.hip"
 #include "mpk_traj_vjp.hip"
+#include "mpk_traj_fit.hip"
 #include "mpk_traj_phase.hip"
 #include "mpk_phase_fused.hip"
 #include "mpk_rollout.hip"

@@ -115,8 +115,9 @@ constexpr int kEpSlotInts = 8;                   // per episode slot: executed s
 enum : int { XK_ZERO = 0, XK_PARAM = 1, XK_IPOS = 2, XK_IVEL = 3, XK_ONE = 4 };
 
 // which raw input feeds element k of a DoF's extended parameter column, and its offset inside the DoF's local block
+// (__host__ too: the fit's host side splits the Gram matrix by it, mpk_traj_fit.hip)
 template <int MP>
-__device__ __forceinline__ int x_kind(const DevCfg& c, int k, int* loc) {
+__host__ __device__ __forceinline__ int x_kind(const DevCfg& c, int k, int* loc) {
     // select form (no early returns): this runs in the latency-critical prologue of every trajectory kernel
     const int nb = c.nb;
     if (MP == MPK_MP_PRODMP) {

@@ -1,5 +1,6 @@
 // k_traj_vjp_tile / k_traj_vjp_generic: the vector-Jacobian product of the shared-phase trajectory map (mpk_trajectory_vjp)
 #include "mpk_tile.h"
+#include "mpk_run_stage.h"
 #include "mpk_vjp_row.h"
 
 namespace mpk {
@@ -34,11 +35,6 @@ struct VjpArgs {
     int stride;            // floats per (array, episode) gradient image in LDS
 };
 
-// floats by which episode b's gradient rows start past a 16-byte boundary
-__device__ __forceinline__ int vjp_shift(const float* g, int b, int TD) {
-    return (int)((reinterpret_cast<uintptr_t>(g + (size_t)b * TD) >> 2) & 3u);
-}
-
 // ------------------------------------------------------------------------------------------------------------
 // k_traj_vjp_tile<MP>: v_mfma_f32_16x16x4_f32 with M = contraction column, K = four time steps, N = (episode, DoF) -- the forward's tile
 // with the roles of column and time exchanged.  A workgroup is four waves; a wave walks episode groups of NTW = 16 >> sh episodes (the
@@ -46,7 +42,7 @@ __device__ __forceinline__ int vjp_shift(const float* g, int b, int TD) {
 //   * Tables: staged once per workgroup, TRANSPOSED to [2][TP][16] (column fastest), t >= T and k >= KT zero: the A fragment of a chunk
 //     (lane <-> column lane & 15, step lane >> 4) is 64 consecutive floats -- ds_read_b32 without bank conflicts.
 //   * Gradients: each episode's T * D floats of g_pos (then g_vel) are one contiguous run in HBM: the wave copies them into its LDS
-//     image with 16-byte loads -- the image is shifted by the run's offset from a 16-byte boundary (vjp_shift), so aligned HBM chunks
+//     image with 16-byte loads (stage_run, mpk_run_stage.h) -- the image is shifted by the run's offset from a 16-byte boundary, so aligned HBM chunks
 //     land on aligned LDS chunks whatever the pointer and T * D; up to three floats at either end go as dwords -- and zero-fills the
 //     (TP - T) * D floats behind the run: the tail chunk contracts zeros, nothing is read past T.  A null array is not read at all.
 //     The B fragment of a chunk is (step lane >> 4, tile column) = image[(4 ch + q) D + d] of the lane's episode; images of the
@@ -86,24 +82,7 @@ __global__ void __launch_bounds__(256) k_traj_vjp_tile(const VjpArgs a) {
             for (int arr = 0; arr < 2; ++arr) {
                 const float* src = arr ? a.g_vel : a.g_pos;
                 if (!src) continue;
-                const float* s = src + (size_t)bb * TD;
-                const int shift = vjp_shift(src, bb, TD);
-                float* dst = img + (arr * NTW + e) * a.stride + shift;      // element f of the run at dst[f]
-                const int head = min((4 - shift) & 3, TD);
-                const int n4 = (TD - head) >> 2;
-                const int tail0 = head + 4 * n4;
-                if (lane < head) dst[lane] = s[lane];
-                for (int i0 = lane; i0 < n4; i0 += 256) {                    // four 16-byte loads in flight per lane
-                    f32x4 r4[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (i0 + 64 * u < n4) r4[u] = *reinterpret_cast<const f32x4*>(s + head + 4 * (i0 + 64 * u));
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (i0 + 64 * u < n4) *reinterpret_cast<f32x4*>(dst + head + 4 * (i0 + 64 * u)) = r4[u];
-                }
-                if (tail0 + lane < TD) dst[tail0 + lane] = s[tail0 + lane];
-                if (TD + lane < TP * D) dst[TD + lane] = 0.0f;               // (TP - T) * D <= 48 floats
+                stage_run(img + (arr * NTW + e) * a.stride, src, bb, TD, TP * D, lane);      // mpk_run_stage.h
             }
         }
         // (lanes read what OTHER lanes of the wave wrote: a wave's LDS operations complete in issue order, so the barrier only has to
@@ -115,8 +94,8 @@ __global__ void __launch_bounds__(256) k_traj_vjp_tile(const VjpArgs a) {
         const int bs = lv ? bb : b0;
         const float* ip = img + (lv ? bl * a.stride + q * D + d : 0);
         const float* iv = ip + NTW * a.stride;
-        if (a.g_pos) ip += vjp_shift(a.g_pos, bs, TD);
-        if (a.g_vel) iv += vjp_shift(a.g_vel, bs, TD);
+        if (a.g_pos) ip += run_shift(a.g_pos, bs, TD);
+        if (a.g_vel) iv += run_shift(a.g_vel, bs, TD);
         f32x4 p0 = {0.f, 0.f, 0.f, 0.f}, p1 = p0, v0 = p0, v1 = p0;
         const int D4 = 4 * D;
         int ch = 0;
@@ -199,8 +178,7 @@ int launch_traj_vjp(const DevCfg& c, const SharedTables& st, const float* g_pos,
         va.G = (B + NTW - 1) / NTW;
         va.TP = (c.T + 3) / 4 * 4;
         // a run of T * D floats shifted by up to 3, zero-filled to TP * D; images of a group's episodes 32 / NTW banks apart
-        const long need = (long)va.TP * c.D + 3;
-        const long st_ = (need + 31) / 32 * 32 + (NTW == 1 ? 0 : (32 / NTW > 4 ? 32 / NTW : 4));
+        const long st_ = run_image_stride(va.TP, c.D, NTW);
         const size_t bytes = ((size_t)2 * va.TP * 16 + (size_t)4 * 2 * NTW * st_) * sizeof(float);
         if (bytes > kLdsPerCu) tile = false;        // long horizons: the generic route
         va.stride = (int)st_;

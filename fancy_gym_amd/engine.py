@@ -625,6 +625,90 @@ class TrajectoryEngine:
                                                       self._stream()))
         return res[0], res[1], res[2]
 
+    def fit_trajectory(self, pos, init_pos=None, init_vel=None, init_time=0.0, *, reg: float = 1e-9, phase_params=None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """
+        The closed-form fit of the parameters to demonstrated positions (mpk.h: mpk_trajectory_fit), one launch: ``pos`` [B, T, D] ->
+        ``params`` [B, P] float32 on the device, without an autograd graph.  For episode b the handle defines the affine map
+        ``pos_b(p) = Psi p + c_b`` -- ``p`` the non-phase part of ``params`` in the user's units (scales, relative goal, zero padding,
+        disable_* folded in as ``trajectory`` folds them), ``c_b`` what ``init_pos`` / ``init_vel`` / the goal offset contribute -- and
+        the result is ``argmin_p |Psi p + c_b - pos_b|^2 + reg |p|^2``, solved per DoF in float64.  Positions only; ``reg`` is absolute
+        and must be > 0.  This stands in for mp_pytorch's ``learn_mp_params_from_trajs`` on a batch: ``trajectory(fit_trajectory(y), ...)``
+        is the best reproduction of ``y`` the handle has.
+
+        ``init_pos`` / ``init_vel`` [B, D] are given, not fitted; None only for a ProMP (zeros).  ``init_time`` is one float for the
+        batch.  A handle with a learned tau / delay, or an ``init_time`` tensor [B], gives every episode its own phase
+        (mpk_trajectory_phase_fit, ProMP / ProDMP): each episode's tau / delay are inputs, ``phase_params`` [B, n_phase] in the order
+        they have at the front of ``params``; they are clipped to the handle's bounds as ``trajectory`` clips them and come back
+        unclipped at the front of the result.  There an episode whose Gram matrix plus ``reg`` I is not positive definite in float64
+        gets a NaN row, and ``fit_status()`` says so.  ``phase_params`` on a shared-phase handle is a ValueError.  Every refusal is
+        raised before any launch: ValueError for ``reg <= 0``, wrong shapes, a learned-phase handle without ``phase_params``,
+        ``init_pos=None`` on a ProDMP / DMP; NotImplementedError for more than 16 DoF or 16 table columns, a DMP off its response
+        route and a DMP with a per-episode phase.
+        """
+        reg = float(reg)
+        if not (reg > 0.0) or not np.isfinite(reg):
+            raise ValueError(f"fit_trajectory: reg must be a positive finite number, got {reg!r}")
+        D, T, P = self.num_dof, self.num_steps, self.num_params
+        shape = tuple(pos.shape) if hasattr(pos, "shape") else np.shape(pos)
+        if len(shape) != 3 or shape[1:] != (T, D):
+            raise ValueError(f"fit_trajectory: pos must be [B, {T}, {D}], got {shape}")
+        B = shape[0]
+        n_phase = int(bool(self.config.learn_tau)) + int(bool(self.config.learn_delay))
+        per_episode_time = isinstance(init_time, torch.Tensor) and init_time.dim() > 0
+        if n_phase and phase_params is None:
+            raise ValueError("fit_trajectory: this handle learns " + " and ".join(
+                n for n, on in (("tau", self.config.learn_tau), ("delay", self.config.learn_delay)) if on) +
+                f": pass each episode's values as phase_params [{B}, {n_phase}] (they are inputs of the fit, not fitted)")
+        if not n_phase and phase_params is not None:
+            raise ValueError("fit_trajectory: phase_params given, but this handle has a shared phase (no learned tau / delay)")
+        if (init_pos is None or init_vel is None) and self.mp_type != "promp":
+            raise ValueError(f"fit_trajectory: init_pos / init_vel may be None only for a ProMP, which ignores them; a {self.mp_type} "
+                             "starts from them")
+        for name, x in (("init_pos", init_pos), ("init_vel", init_vel)):
+            xs = None if x is None else (tuple(x.shape) if hasattr(x, "shape") else np.shape(x))
+            if xs is not None and xs not in ((B, D), (D,)):
+                raise ValueError(f"fit_trajectory: {name} must be [{B}, {D}], got {xs}")
+        if out is not None and (tuple(out.shape) != (B, P) or out.dtype != torch.float32 or not out.is_contiguous()
+                                or out.device != self.device):
+            raise ValueError(f"fit_trajectory: out must be a contiguous float32 tensor of shape {(B, P)} on {self.device}")
+        if phase_params is not None:
+            ps = tuple(phase_params.shape) if hasattr(phase_params, "shape") else np.shape(phase_params)
+            if ps != (B, n_phase):
+                raise ValueError(f"fit_trajectory: phase_params must be [{B}, {n_phase}], got {ps}")
+        if per_episode_time and tuple(init_time.shape) != (B,):
+            raise ValueError(f"fit_trajectory: an init_time tensor must be [{B}], got {tuple(init_time.shape)}")
+        if n_phase or per_episode_time:
+            if self.mp_type == "dmp":
+                raise NotImplementedError("fit_trajectory: a DMP with a per-episode phase is an Euler recurrence in the scaled time, "
+                                          "which is not a table the fit could invert (promp / prodmp only)")
+            with torch.no_grad():
+                pos = torch.as_tensor(pos, dtype=torch.float32, device=self.device).detach().contiguous()
+                ip = None if init_pos is None else self._f32(init_pos, (B, D)).detach()
+                iv = None if init_vel is None else self._f32(init_vel, (B, D)).detach()
+                ph = None if not n_phase else self._f32(phase_params, (B, n_phase)).detach()
+                it_t = self._f32(init_time, (B,)) if per_episode_time else None
+                params = out if out is not None else torch.empty((B, P), dtype=torch.float32, device=self.device)
+                _lib.check(self._lib.mpk_trajectory_phase_fit(self._h, pos.data_ptr(), _dptr(ph), _dptr(ip), _dptr(iv), _dptr(it_t),
+                                                              0.0 if per_episode_time else float(init_time), reg, params.data_ptr(),
+                                                              B, self._stream()))
+            return params
+        with torch.no_grad():
+            pos = torch.as_tensor(pos, dtype=torch.float32, device=self.device).detach().contiguous()
+            ip = None if init_pos is None else self._f32(init_pos, (B, D)).detach()
+            iv = None if init_vel is None else self._f32(init_vel, (B, D)).detach()
+            params = out if out is not None else torch.empty((B, P), dtype=torch.float32, device=self.device)
+            _lib.check(self._lib.mpk_trajectory_fit(self._h, pos.data_ptr(), _dptr(ip), _dptr(iv), None, float(init_time), reg,
+                                                    params.data_ptr(), B, self._stream()))
+        return params
+
+    def fit_status(self) -> bool:
+        """synchronise; True if an episode of the last per-episode-phase ``fit_trajectory`` launch had a Gram matrix that is not
+        positive definite in float64 (its params row is NaN)"""
+        flag = C.c_int32(0)
+        _lib.check(self._lib.mpk_fit_status(self._h, C.byref(flag), self._stream()))
+        return bool(flag.value)
+
     def check_range(self):
         """synchronise and raise RuntimeError if a per-episode-phase ProDMP launch left the pre-computed table range"""
         _lib.check(self._lib.mpk_check_range(self._h, self._stream()))

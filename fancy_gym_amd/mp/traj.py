@@ -173,6 +173,81 @@ class MPInterface:
             plt.show()
         return times, basis
 
+    def learn_mp_params_from_trajs(self, times, trajs, reg: float = 1e-9, **kwargs) -> dict:
+        """
+        mp_pytorch's regularised least-squares fit of the parameters to demonstrated position trajectories, on the device
+        (``TrajectoryEngine.fit_trajectory``: one launch for the whole batch).  ``times`` [..., N], ``trajs`` [..., N, D]; returns
+        ``{"params", "init_time", "init_pos", "init_vel"}`` and, for a single demonstration, sets them on the generator as upstream
+        does.  ``init_time`` / ``init_pos`` / ``init_vel`` come from ``kwargs`` when all three are given; otherwise ``init_time`` is
+        ``times[..., 0]``, ``init_pos`` the first sample and ``init_vel`` the first finite difference.  The signature and that
+        defaulting rule are written from recollection of mp_pytorch 0.1.x and, like the rest of the MP arithmetic, are not pinned
+        against it.
+
+        The fit is ``argmin_p |Psi p + c - trajs|^2 + reg |p|^2`` per DoF, ``reg`` absolute and > 0, on the handle's own time grid:
+        the T steps of ``set_duration`` start one ``dt`` after ``init_time``.  With the three given, ``times`` must be that grid
+        (N = T).  With the defaults the first sample IS the initial condition, so N = T + 1 and ``times[..., 1:]`` must be the grid of
+        ``init_time = times[..., 0]``; the fit runs on the samples behind the first.  Any other grid is a ValueError: the fit inverts
+        the map of that grid only.  One ``init_time`` is shared by the batch.  ProMP, ProDMP and a shared-phase DMP; a generator that
+        learns tau / delay has no shared phase (ValueError: ``TrajectoryEngine.fit_trajectory`` takes them as ``phase_params``).
+        """
+        from .._lib import load as _lib_load
+        reg = float(reg)
+        if not (reg > 0.0) or not np.isfinite(reg):
+            raise ValueError(f"learn_mp_params_from_trajs: reg must be a positive finite number, got {reg!r}")
+        if self.duration is None or self.dt is None:
+            raise RuntimeError("set_duration(duration, dt) must be called before parameters can be fitted")
+        if self.learn_tau or self.learn_delay:
+            raise ValueError("learn_mp_params_from_trajs: this generator learns tau / delay, so the batch has no shared phase; pass each "
+                             "episode's values as phase_params to TrajectoryEngine.fit_trajectory")
+
+        def to_np(x):
+            return x.detach().cpu().numpy().astype(np.float32) if isinstance(x, torch.Tensor) else np.asarray(x, np.float32)
+        times = to_np(times)
+        D = self.num_dof
+        tshape = tuple(trajs.shape) if hasattr(trajs, "shape") else np.shape(trajs)
+        if len(tshape) < 2 or tshape[-1] != D or tuple(times.shape) != tshape[:-1]:
+            raise ValueError(f"learn_mp_params_from_trajs: trajs must be [..., T, {D}] and times [..., T], got {tshape} and "
+                             f"{tuple(times.shape)}")
+        given = all(kwargs.get(k) is not None for k in ("init_time", "init_pos", "init_vel"))
+        N, batch = tshape[-2], tshape[:-2]
+        lib = _lib_load()
+        T = lib.mpk_host_times(float(self.duration), float(self.dt), None, 0)
+        if N != T + (0 if given else 1):
+            raise ValueError(f"learn_mp_params_from_trajs: the handle's time grid has {T} steps (duration {self.duration}, dt {self.dt}); "
+                             + (f"with init_time / init_pos / init_vel given trajs needs {T} samples" if given else
+                                f"without them the first sample is the initial condition and trajs needs {T + 1} samples") + f", got {N}")
+        grid = np.empty(T, np.float32)
+        lib.mpk_host_times(float(self.duration), float(self.dt), grid.ctypes.data, T)
+        flat_t = times.reshape(-1, N)
+        it = to_np(kwargs["init_time"]).reshape(-1) if given else flat_t[:, 0]
+        if not np.all(it == it[0]):
+            raise ValueError("learn_mp_params_from_trajs: one init_time is shared by the batch; got different values")
+        it0 = np.float32(it[0])
+        on_grid = flat_t if given else flat_t[:, 1:]
+        if not np.allclose(on_grid, grid[None] + it0, rtol=0.0, atol=1e-3 * float(self.dt)):
+            raise ValueError("learn_mp_params_from_trajs: times is not the handle's own grid for this init_time "
+                             f"(linspace(0, {self.duration}, {T + 1})[1:] + {float(it0)}): the fit inverts the map of that grid only")
+        if isinstance(trajs, torch.Tensor):
+            y = trajs.detach().to(torch.float32).reshape(-1, N, D)
+        else:
+            y = torch.from_numpy(np.ascontiguousarray(np.asarray(trajs, np.float32).reshape(-1, N, D)))
+        B = y.shape[0]
+        if given:
+            ip = torch.from_numpy(to_np(kwargs["init_pos"]).reshape(-1, D)).expand(B, D)
+            iv = torch.from_numpy(to_np(kwargs["init_vel"]).reshape(-1, D)).expand(B, D)
+        else:
+            ip = y[:, 0, :].cpu()
+            iv = ((y[:, 1, :] - y[:, 0, :]) / float(flat_t[0, 1] - flat_t[0, 0])).cpu()
+            y = y[:, 1:, :]
+        eng = self.engine()
+        params = eng.fit_trajectory(y.to(eng.device), ip.to(eng.device), iv.to(eng.device), float(it0), reg=reg)
+        out = {"params": params.reshape(*batch, -1), "init_time": torch.full(batch, float(it0)),
+               "init_pos": ip.reshape(*batch, D).clone(), "init_vel": iv.reshape(*batch, D).clone()}
+        if B == 1:
+            self.set_params(params[0].cpu().numpy())
+            self.set_initial_conditions(float(it0), ip[0].numpy(), iv[0].numpy())
+        return out
+
     def get_traj_pos(self, **_ignored) -> torch.Tensor:
         if self._pos is None:
             self._compute()

@@ -915,6 +915,64 @@ int mpk_trajectory_vjp(mpk_handle h, const float* g_pos, const float* g_vel, dou
                        float* g_params, float* g_init_pos, float* g_init_vel, int32_t B, void* stream);
 
 /*
+ * The closed-form fit of MP parameters to demonstrated positions for a handle with a SHARED phase (added within ABI 4; no existing prototype
+ * changes -- the fit entry points stand here, beside the transpose of the map they invert) -- what
+ * mp_pytorch's MPInterface.learn_mp_params_from_trajs (ProMP / ProDMP / DMP: a regularised least-squares fit; written from
+ * recollection of mp_pytorch 0.1.x, unpinned like the rest of the MP arithmetic) answers on the host.  For episode b the handle
+ * defines the affine map
+ *     pos_b(p) = Psi p + c_b
+ * p: the non-phase part of params in the user's own units (weights_scale, goal_scale, the relative goal, the zero padding and
+ * disable_weights / disable_goal folded in exactly as mpk_trajectory folds them); c_b: what init_pos, init_vel and the constant
+ * goal-offset column contribute; Psi: the launch's own basis table for (init_time_shared, T).  The fit returns, per (episode, DoF),
+ *     p* = argmin_p |Psi p + c_b - y_b|^2 + reg |p|^2 = (Psi^T Psi + reg I)^-1 Psi^T (y_b - c_b)
+ * Positions only (velocities are not fitted, as in mp_pytorch); reg is absolute and must be > 0 (mp_pytorch's default: 1e-9).
+ *   pos        dev float [B, T, D]  the demonstrations y, contiguous; any alignment
+ *   init_pos   dev float [B, D]     given, not fitted; NULL (zeros) is accepted for a ProMP only
+ *   init_vel   dev float [B, D]
+ *   init_time  must be NULL: a per-episode init_time (like a learned tau / delay) is the per-episode-phase fit, MPK_EINVAL here
+ *   params     dev float [B, P]     out
+ * One launch of k_traj_fit_tile<promp | prodmp | dmp_resp> (mpk_last_kernel) on `stream`: the demonstrations are read once and
+ * contracted over time with the table on the matrix cores in float64, and the cross term of the given columns, the two triangular
+ * solves with the Cholesky factor and the scatter into params happen inside the launch, in float64, rounded to float32 once.  No
+ * atomics, an episode never leaves its wave: the same bits from run to run, for any alignment of pos, and whatever else is in the batch.
+ * The Gram matrix (<= 16 x 16, shared by the batch) and its factor are built once per (init_time_shared, T, reg) in float64 from the
+ * float32 rows the forward kernels read and cached beside the handle's tables; the FIRST call with a new key copies those rows back and
+ * synchronises `stream` (MPK_EINVAL inside a stream capture); every later call allocates nothing and synchronises nothing.
+ * MPK_EINVAL: reg <= 0 or not finite; a learned tau / delay or a per-episode init_time; a non-positive Cholesky pivot (the message
+ * names reg).  MPK_ENOTIMPL, before any launch: more than 16 DoF or 16 table columns (the k_traj_wide shapes); a DMP handle outside
+ * its response route (as mpk_trajectory_vjp); a horizon whose demonstration images do not fit the CU's LDS.
+ */
+int mpk_trajectory_fit(mpk_handle h, const float* pos, const float* init_pos, const float* init_vel, const float* init_time,
+                       double init_time_shared, double reg, float* params, int32_t B, void* stream);
+
+/*
+ * The same fit for a PER-EPISODE phase -- a handle with learn_tau / learn_delay (the TableTennis-ProDMP and BeerPong-ProMP families)
+ * and / or a per-episode init_time -- of a ProMP or a ProDMP, in ONE launch (added within ABI 4; mp_pytorch:
+ * learn_mp_params_from_trajs after set_params' tau / delay, per episode).  Each episode's tau / delay are INPUTS, not fitted:
+ *   phase_params   dev float [B, n_phase]  in the order they have at the front of params (tau, then delay); NULL when none is learned
+ *   init_time      dev float [B], or NULL: init_time_shared
+ *   pos, init_pos, init_vel, reg, params: as mpk_trajectory_fit
+ * The kernel clips tau / delay to the handle's bounds exactly as mpk_trajectory does, fits at the clipped values, and copies the
+ * UNCLIPPED input values to the front of the params row -- so mpk_trajectory of the result is the best reproduction at that timing.
+ * Psi_b depends on the episode's phase, so every episode has its own Gram matrix: k_phase_fit<promp | prodmp> (mpk_last_kernel) gives
+ * an episode one wave, lane <-> time step, 64 steps a round; a lane recomputes its row with the forward's device functions (nothing
+ * of a forward launch is needed), the rows are regrouped by parameter (a ProDMP's boundary terms folded in), and the Gram matrix and
+ * Psi^T (y - c) are summed in float64 in a fixed order inside the wave, factored (Cholesky) and solved there.  Plain stores, no atomics
+ * but the forward's range flag: the same bits from run to run and for any alignment of pos.  A ProDMP episode that leaves the
+ * pre-computed range clamps and raises the range flag as the forward does (mpk_check_range).
+ * If an episode's Gram matrix plus reg I is not positive definite in float64 (a pivot <= 0 or NaN), that episode's non-phase params
+ * come back NaN and the launch's status word is set: mpk_fit_status synchronises `stream` and returns it (1: some episode of the LAST
+ * mpk_trajectory_phase_fit launch on this handle had no factor; 0 otherwise).  The first call allocates the status word (not inside a
+ * stream capture); later calls allocate and synchronise nothing.
+ * MPK_EINVAL: reg <= 0 or not finite; a handle that learns tau / delay without phase_params.  MPK_ENOTIMPL, before any launch: a DMP;
+ * shapes beyond the wave kernel of the forward (the limits of mpk_trajectory_phase_vjp: more than 16 DoF or 16 columns, DoF x padded
+ * columns > 256, more than 320 parameters per episode).
+ */
+int mpk_trajectory_phase_fit(mpk_handle h, const float* pos, const float* phase_params, const float* init_pos, const float* init_vel,
+                             const float* init_time, double init_time_shared, double reg, float* params, int32_t B, void* stream);
+int mpk_fit_status(mpk_handle h, int32_t* not_positive_definite, void* stream);
+
+/*
  * The vector-Jacobian product of mpk_reacher_rollout (appended under ABI 4): controller, clip, torque double integrator and
  * SimpleReacher's reward transposed -- the gradient of any scalar loss of the step rewards and the final state w.r.t. the desired
  * trajectory, the plan-start state and the goal, one launch.  The forward it transposes (mpk_reacher_rollout above), per executed step
