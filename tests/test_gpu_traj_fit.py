@@ -11,6 +11,10 @@ RTOL = 1e-5 is the project's rule (tests/test_gpu_trajectory.py); p_f32 is the a
 tests/test_gpu_traj_vjp.py::check with the float32 fit in the float32 einsum's place.  cfg1 and cfg4 additionally compare params by the
 same rule (cfg1's smallest Gram eigenvalue is 3.6; cfg4's, at init_time 0.5, is 4.7e-8 against 7.3, so its params comparison rests on the
 float32 fit's floor -- profiles/r18_traj_fit.md).  Every comparison prints its maxima before it asserts.
+
+The per-episode-phase kernel k_phase_fit<MP, KQ> (section 4): PHASE_KQ lists the rows and the instantiation each takes -- all five, one to
+four right-hand-side slots a lane --; beside them the lane map's round boundaries, the batch wrap-around, the not-positive-definite
+result and the shared route's factor cache (profiles/r19_phase_fit_edges.md).
 """
 import functools
 import os
@@ -255,16 +259,112 @@ def test_refusals_happen_before_any_launch():
 
 
 # ---- 4. per-episode phase: learned tau / delay, per-episode init_time (k_phase_fit) ----------------------------------------------------
+def phase_fit_kq(bc, tc):
+    """the instantiation k_phase_fit<MP, KQ> a configuration takes, by phase_fit_limits' rule (csrc/mpk_traj_fit.hip): a ProMP needs its
+    KT table columns (the basis functions, plus the init_pos column of a zero-padded basis), a ProDMP num_basis + 3 (weights, goal, y_b,
+    v_b); KQ = 1 for a ProMP that needs <= 4, 2 for <= 8, else 4 (at most 16); a lane row holds KS = 4 KQ columns"""
+    prodmp = tc.trajectory_generator_type == "prodmp"
+    need = bc.num_basis + 3 if prodmp else bc.num_basis + int(bc.basis_generator_type == "zero_rbf")
+    assert need <= 16, need
+    return 1 if need <= 4 and not prodmp else (2 if need <= 8 else 4)
+
+
+ROUND_T, ROUND_D = (1, 2, 3, 63, 64, 65, 129), (1, 7)
+
+
+def round_config(kind, D, T):
+    """the lane map's round boundaries: T steps of dt = 0.01 exactly.  ProMP: linear phase, 5 plain RBFs, learned tau (the phase runs to
+    1 at tau = T dt); ProDMP: 4 basis functions, learned tau and delay"""
+    dt = 0.01
+    if kind == "promp":
+        return (O.PhaseCfg("linear", tau=T * dt, learn_tau=True, tau_bound=(0.5 * T * dt, T * dt)),
+                O.BasisCfg("rbf", num_basis=5, basis_bandwidth_factor=3), O.TrajCfg("promp", action_dim=D, weights_scale=0.9), dt, T * dt)
+    return (O.PhaseCfg("exp", tau=1.0, alpha_phase=3.0, learn_tau=True, learn_delay=True, tau_bound=(0.4, 1.0), delay_bound=(0.0, 0.008)),
+            O.BasisCfg("prodmp", num_basis=4, alpha=20, basis_bandwidth_factor=3),
+            O.TrajCfg("prodmp", action_dim=D, weights_scale=0.6, goal_scale=1.2, auto_scale_basis=True), dt, T * dt)
+
+
+# name -> the KQ of k_phase_fit<MP, KQ> the row must take (tests/test_traj_fit_host.py holds it against phase_fit_kq and checks that the
+# table reaches all five instantiations and every count of right-hand-side slots); D x KS = DoF x 4 KQ entries of Psi^T (y - c), 64 a slot
+PHASE_KQ = {
+    "tt_prodmp_70_steps": 2, "tt_prodmp_350_steps": 2, "beerpong_promp": 1, "cfg4_three_clocks": 2,
+    # the learned-phase and phase-vjp tables' rows
+    "promp_5dof_learn_both": 2,                   # zero-padded, tau and delay
+    "prodmp_3dof_learn_tau": 2,                   # the goal fitted, weights_scale and goal_scale
+    "promp_16dof_learn_tau": 1,                   # D = 16: D x KS = 64, one slot exactly full
+    "tt_prodmp_replan": 2,                        # goal_offset given and ignored (the reference's default mode)
+    "promp_exp_learn_both": 2,                    # exp phase, no zero padding: nothing given
+    "prodmp_after_scale_no_weights": 2,           # the goal alone, init_pos joins the scaled goal
+    # new shapes
+    "promp_16_basis_16_dof": 4,                   # D x KS = 256: all four slots of every lane; P = 258
+    "promp_9_basis_5_dof": 4,                     # D x KS = 80: two slots, the second part full
+    "promp_8_basis_9_dof": 2,                     # D x KS = 72
+    "promp_10_basis_11_dof": 4,                   # D x KS = 176: three slots
+    "promp_zero_12_basis_3_dof": 4,               # 13 columns, the padding column given
+    "prodmp_13_basis_16_dof_relative_goal": 4,    # the largest LDS block, D x KS = 256
+    "prodmp_6_basis_three_clocks": 4,             # the smallest KQ-4 ProDMP; per-episode init_time, no learned timing
+    "prodmp_13_basis_1_dof_no_goal": 4,
+    "prodmp_4_basis_12_dof_goal_offset_add": 2,   # the goal-offset column given (mode 'add'); D x KS = 96
+    "promp_round_t5_d3": 2, "prodmp_round_t5_d3": 2,      # the wrap-around test's episodes
+}
+PHASE_KQ.update({f"promp_round_t{T}_d{D}": 2 for T in ROUND_T for D in ROUND_D})
+PHASE_KQ.update({f"prodmp_round_t{T}_d{D}": 2 for T in ROUND_T for D in ROUND_D})
+PHASE_TABLE = [n for n in PHASE_KQ if "_round_t" not in n or n.endswith("_t5_d3")]
+
+
+@functools.lru_cache(maxsize=None)
 def phase_configs():
+    from . import phase_vjp_ref as V
     from .test_gpu_learned_phase import CONFIGS as LP, CONFIGS_ALL
     tt, bp, c4 = LP["tt_prodmp"], LP["beerpong_promp"], CONFIGS_ALL["cfg4_prodmp_replan"]
-    return {
+    clocks = np.array([0.0, 0.4, 0.8], np.float32)
+    out = {
         # name: (pc, bc, tc, dt, duration, per-episode init_time)
         "tt_prodmp_70_steps": tt[:4] + (70 * tt[3], None),            # two lane rounds, the second ragged
         "tt_prodmp_350_steps": tt[:5] + (None,),
         "beerpong_promp": bp[:5] + (None,),
-        "cfg4_three_clocks": c4[:5] + (np.array([0.0, 0.4, 0.8], np.float32),),
+        "cfg4_three_clocks": c4[:5] + (clocks,),
     }
+    for name in ("promp_5dof_learn_both", "prodmp_3dof_learn_tau", "promp_16dof_learn_tau"):
+        out[name] = LP[name][:5] + (None,)
+    out["tt_prodmp_replan"] = LP["tt_prodmp_replan"][:4] + (40 * LP["tt_prodmp_replan"][3], None)
+    for name in ("promp_exp_learn_both", "prodmp_after_scale_no_weights"):
+        out[name] = V.EXTRA[name] + (None,)
+    lin = dict(learn_tau=True, tau_bound=(0.4, 0.6))
+    both = dict(learn_tau=True, learn_delay=True, tau_bound=(0.4, 0.6), delay_bound=(0.0, 0.1))
+    out.update({
+        "promp_16_basis_16_dof": (O.PhaseCfg("linear", tau=0.6, **both), O.BasisCfg("rbf", num_basis=16, basis_bandwidth_factor=3),
+                                  O.TrajCfg("promp", action_dim=16), 0.02, 0.6, None),
+        "promp_9_basis_5_dof": (O.PhaseCfg("linear", tau=0.6, **lin), O.BasisCfg("rbf", num_basis=9, basis_bandwidth_factor=3),
+                                O.TrajCfg("promp", action_dim=5, weights_scale=0.8), 0.02, 0.6, None),
+        "promp_8_basis_9_dof": (O.PhaseCfg("linear", tau=0.6, **lin), O.BasisCfg("rbf", num_basis=8, basis_bandwidth_factor=3),
+                                O.TrajCfg("promp", action_dim=9), 0.02, 0.5, None),
+        "promp_10_basis_11_dof": (O.PhaseCfg("linear", tau=0.6, **lin), O.BasisCfg("rbf", num_basis=10, basis_bandwidth_factor=3),
+                                  O.TrajCfg("promp", action_dim=11), 0.02, 0.6, None),
+        "promp_zero_12_basis_3_dof": (O.PhaseCfg("linear", tau=0.6, learn_delay=True, delay_bound=(0.0, 0.1)),
+                                      O.BasisCfg("zero_rbf", num_basis=12, num_basis_zero_start=1, num_basis_zero_goal=1,
+                                                 basis_bandwidth_factor=3), O.TrajCfg("promp", action_dim=3), 0.02, 0.7, None),
+        "prodmp_13_basis_16_dof_relative_goal": (O.PhaseCfg("exp", tau=0.6, alpha_phase=3.0, **both),
+                                                 O.BasisCfg("prodmp", num_basis=13, alpha=25, basis_bandwidth_factor=3),
+                                                 O.TrajCfg("prodmp", action_dim=16, weights_scale=0.7, goal_scale=1.3, auto_scale_basis=True,
+                                                           relative_goal=True), 0.02, 0.5, None),
+        "prodmp_6_basis_three_clocks": (O.PhaseCfg("exp", tau=1.0, alpha_phase=3.0), O.BasisCfg("prodmp", num_basis=6, alpha=15),
+                                        O.TrajCfg("prodmp", action_dim=3, auto_scale_basis=True), 0.02, 0.6, clocks),
+        "prodmp_13_basis_1_dof_no_goal": (O.PhaseCfg("exp", tau=0.6, alpha_phase=3.0, **lin),
+                                          O.BasisCfg("prodmp", num_basis=13, alpha=25, basis_bandwidth_factor=3),
+                                          O.TrajCfg("prodmp", action_dim=1, auto_scale_basis=True, disable_goal=True), 0.02, 0.7, None),
+        "prodmp_4_basis_12_dof_goal_offset_add": (O.PhaseCfg("exp", tau=0.6, alpha_phase=3.0, **lin),
+                                                  O.BasisCfg("prodmp", num_basis=4, alpha=15, basis_bandwidth_factor=2),
+                                                  O.TrajCfg("prodmp", action_dim=12, goal_scale=0.8, goal_offset_mode="add",
+                                                            goal_offset=-0.7), 0.02, 0.5, None),
+    })
+    for kind in ("promp", "prodmp"):
+        out[f"{kind}_round_t5_d3"] = round_config(kind, 3, 5) + (None,)
+        for T in ROUND_T:
+            for D in ROUND_D:
+                out[f"{kind}_round_t{T}_d{D}"] = round_config(kind, D, T) + (None,)
+    assert set(out) == set(PHASE_KQ)
+    return out
 
 
 def phase_values(pc, B, rng):
@@ -286,6 +386,25 @@ def phase_values(pc, B, rng):
     return np.stack(cols, axis=1).astype(np.float32) if cols else np.zeros((B, 0), np.float32)
 
 
+class FirstStepDesign(R.Design):
+    """a one-step ProMP.  The oracle's finite-difference velocity needs two steps, so this is the first step of the two-step grid of the
+    same configuration: the same first time (asserted), hence the same phase and row"""
+
+    def __init__(self, pc, bc, tc, dt, duration, init_time=0.0, phase=()):
+        assert O.num_steps(duration, dt) == 1 and tc.trajectory_generator_type == "promp"
+        assert np.array_equal(O.make_times(duration, dt, init_time), O.make_times(2 * dt, dt, init_time)[:1])
+        super().__init__(pc, bc, tc, dt, 2 * dt, init_time, phase)
+        self.Psi = np.ascontiguousarray(self.Psi[:, :1])
+        self.Psi.setflags(write=False)
+        self.T = 1
+
+    def offset(self, init_pos, init_vel):
+        return super().offset(init_pos, init_vel)[:, :1]
+
+    def forward(self, params, init_pos, init_vel):
+        return super().forward(params, init_pos, init_vel)[:, :1]
+
+
 @functools.lru_cache(maxsize=None)
 def phase_case(name, B, seed=0):
     """per episode: its own design (the oracle at that episode's tau / delay / init_time), demonstration and CPU fits"""
@@ -293,9 +412,10 @@ def phase_case(name, B, seed=0):
     rng = np.random.default_rng(100 + seed + B)
     phase = phase_values(pc, B, rng)
     it = None if clocks is None else clocks[np.arange(B) % len(clocks)]
+    one_step = tc.trajectory_generator_type == "promp" and O.num_steps(duration, dt) == 1
     eps = []
     for b in range(B):
-        ds = R.Design(pc, bc, tc, dt, duration, 0.0 if it is None else float(it[b]), phase[b])
+        ds = (FirstStepDesign if one_step else R.Design)(pc, bc, tc, dt, duration, 0.0 if it is None else float(it[b]), phase[b])
         y, ip, iv, _ = R.demonstrations(ds, 1, 1000 * seed + 10 * B + b)
         c = ds.offset(ip, iv)
         eps.append(dict(ds=ds, y=y, ip=ip, iv=iv, c=c, p64=R.fit64(ds, y, c, REG), p32=R.fit32(ds, y, c, REG)))
@@ -333,7 +453,7 @@ def phase_check(cs, params, what):
 
 
 @pytest.mark.parametrize("B", [1, 3, 9])
-@pytest.mark.parametrize("name", ["tt_prodmp_70_steps", "tt_prodmp_350_steps", "beerpong_promp", "cfg4_three_clocks"])
+@pytest.mark.parametrize("name", PHASE_TABLE)
 def test_per_episode_phase_fit_matches_the_float64_fit(name, B):
     eng = phase_engine(name)
     cs = phase_case(name, B)
@@ -349,7 +469,18 @@ def test_per_episode_phase_fit_matches_the_float64_fit(name, B):
 def test_per_episode_phase_fit_properties():
     """equal bits from two launches and from views 1, 2, 3 floats into a larger buffer; a NaN stays in its episode; the forward of the
     fit is what the fit promised (positions at the clipped timing reproduce the reference's reconstruction)"""
-    name = "tt_prodmp_70_steps"
+    phase_fit_properties("tt_prodmp_70_steps")
+
+
+@pytest.mark.parametrize("name", ["promp_9_basis_5_dof", "prodmp_13_basis_16_dof_relative_goal"])
+def test_per_episode_phase_fit_properties_of_sixteen_column_rows(name):
+    """the same properties where a lane row has 16 columns (KQ = 4), ProMP and ProDMP: the forward's per-episode kernel takes these
+    handles too"""
+    assert PHASE_KQ[name] == 4
+    phase_fit_properties(name)
+
+
+def phase_fit_properties(name):
     eng = phase_engine(name)
     cs = phase_case(name, 9)
     first = phase_fit(eng, cs)
@@ -391,6 +522,157 @@ def test_per_episode_phase_refusals():
     with pytest.raises(NotImplementedError, match="Euler recurrence"):
         dmp.fit_trajectory(y, z, z, torch.zeros(2, device="cuda"))
     assert dmp.last_kernel() == ""
+
+
+def test_per_episode_phase_limits_are_refused_before_any_launch():
+    """beyond the wave kernel's shapes: NotImplementedError with the limit in the message, nothing launched; an empty batch on a
+    learned-phase handle is an empty result, nothing launched either"""
+    tau = dict(learn_tau=True, tau_bound=(0.4, 0.6))
+    wide = {
+        "17 ProMP basis functions": (O.PhaseCfg("linear", tau=0.6, **tau), O.BasisCfg("rbf", num_basis=17), O.TrajCfg("promp", action_dim=3),
+                                     "<= 16 columns"),
+        "14 ProDMP basis functions": (O.PhaseCfg("exp", tau=0.6, **tau), O.BasisCfg("prodmp", num_basis=14, alpha=25),
+                                      O.TrajCfg("prodmp", action_dim=3), "<= 16 columns"),
+        "17 DoF": (O.PhaseCfg("linear", tau=0.6, **tau), O.BasisCfg("rbf", num_basis=3), O.TrajCfg("promp", action_dim=17), "<= 16 DoF"),
+    }
+    for what, (pc, bc, tc, limit) in wide.items():
+        eng = make_engine(pc, bc, tc, 0.02, 0.6)
+        D = tc.action_dim
+        y, z = torch.zeros((2, eng.num_steps, D), device="cuda"), torch.zeros((2, D), device="cuda")
+        before = eng.last_kernel()
+        with pytest.raises(NotImplementedError, match=limit):
+            eng.fit_trajectory(y, z, z, phase_params=torch.full((2, 1), 0.5, device="cuda"))
+        assert eng.last_kernel() == before, what
+    name = "promp_9_basis_5_dof"
+    eng = phase_engine(name)
+    empty = eng.fit_trajectory(torch.zeros((0, eng.num_steps, 5), device="cuda"), torch.zeros((0, 5), device="cuda"),
+                               torch.zeros((0, 5), device="cuda"), phase_params=torch.zeros((0, 1), device="cuda"))
+    assert tuple(empty.shape) == (0, eng.num_params) and empty.dtype == torch.float32 and eng.last_kernel() == ""
+
+
+@pytest.mark.parametrize("D", ROUND_D)
+@pytest.mark.parametrize("T", ROUND_T)
+@pytest.mark.parametrize("kind", ["promp", "prodmp"])
+def test_per_episode_phase_fit_at_the_round_boundaries(kind, T, D):
+    """lane <-> time step, 64 steps a round: one step, a round less one, a full round, a round and one, two rounds and one.  With fewer
+    steps than fitted columns (5) reg decides, as in the shared table's under-determined rows"""
+    name = f"{kind}_round_t{T}_d{D}"
+    eng = phase_engine(name)
+    cs = phase_case(name, 3)
+    assert eng.num_steps == T == cs["eps"][0]["ds"].T
+    params = phase_fit(eng, cs)
+    torch.cuda.synchronize()
+    assert eng.last_kernel() == f"k_phase_fit<{kind}>", eng.last_kernel()
+    phase_check(cs, params, f"{name} B=3")
+    assert eng.fit_status() is False
+    eng.check_range()
+
+
+@pytest.mark.parametrize("name", ["promp_round_t5_d3", "prodmp_round_t5_d3"])
+def test_per_episode_batch_wraps_around_the_grid(name):
+    """every wave of the capped grid (four waves a workgroup, at most 8 workgroups per CU) takes at least two episodes, the last trip
+    part full.  The batch is the 9 reference-checked episodes of the parity test, tiled: an episode never leaves its wave and its sums
+    run in a fixed order, so every row has the bits it has in the 9-episode launch"""
+    B = 2 * 4 * 8 * torch.cuda.get_device_properties(0).multi_processor_count + 3
+    eng = phase_engine(name)
+    cs = phase_case(name, 9)
+    small = phase_fit(eng, cs)
+    idx = np.arange(B) % 9
+    big = eng.fit_trajectory(dev(cs["y"][idx]), dev(cs["ip"][idx]), dev(cs["iv"][idx]), 0.0, reg=REG, phase_params=dev(cs["phase"][idx]))
+    assert tuple(big.shape) == (B, eng.num_params) and eng.fit_status() is False
+    same = (bits(big) == bits(small)[torch.from_numpy(idx).cuda()]).all(dim=1)
+    assert bool(same.all()), f"{int((~same).sum())} of {B} rows differ, the first at {int((~same).nonzero()[0])}"
+
+
+NPD_REG = 1e-300
+
+
+def npd_config():
+    """a ProMP (linear phase, 8 plain RBFs, 3 DoF) of 12 steps without learned timing: the per-episode init_time tensor selects the phase.
+    init_time = 0 gives 12 distinct rows (smallest Gram eigenvalue 5e-2); init_time = 1e6 clips the phase to 1 at every step: 12 equal
+    rows, a Gram matrix of rank 1.  (With 5 steps the ordinary episodes' 8 x 8 Gram matrix would have rank 5 and no factor either.)"""
+    T, dt = 12, 0.01
+    return (O.PhaseCfg("linear", tau=T * dt), O.BasisCfg("rbf", num_basis=8, basis_bandwidth_factor=3), O.TrajCfg("promp", action_dim=3),
+            dt, T * dt)
+
+
+def test_an_episode_without_a_factor_is_flagged_and_stays_alone():
+    """16 ordinary episodes interleaved with 16 whose Gram matrix has rank 1, at reg = 1e-300 (which the first addition absorbs): pivots
+    1 .. 7 of the deficient ones are rounding residue of either sign.  The float64 emulation of the kernel's order
+    (tests/test_traj_fit_host.py::test_the_rank_one_gram_matrix_loses_a_pivot) loses pivot 2 (-1.8e-48 after 1.2e-63 and 2.2e-62); the
+    device's rounding may differ, so: fit_status() is True exactly if a row carries a NaN; a row that carries one is NaN throughout;
+    the ordinary episodes have the bits they have without the deficient ones beside them, and match their float64 fit; the next launch
+    clears the flag; and the deficient episodes (all 16 see the same matrix) were flagged"""
+    pc, bc, tc, dt, duration = npd_config()
+    eng = make_engine(pc, bc, tc, dt, duration)
+    ds = R.Design(pc, bc, tc, dt, duration, 0.0)
+    n = 16
+    y, ip, iv, _ = R.demonstrations(ds, 2 * n, 77)
+    c = ds.offset(ip[:n], iv[:n])
+    cs = dict(y=y[:n], p64=R.fit64(ds, y[:n], c, NPD_REG), p32=R.fit32(ds, y[:n], c, NPD_REG))
+    order = np.arange(2 * n).reshape(2, n).T.reshape(-1)              # ordinary 0, deficient 0, ordinary 1, ...
+    clock = np.where(order < n, 0.0, 1e6).astype(np.float32)
+    mixed = eng.fit_trajectory(dev(y[order]), dev(ip[order]), dev(iv[order]), dev(clock), reg=NPD_REG)
+    torch.cuda.synchronize()
+    assert eng.last_kernel() == "k_phase_fit<promp>"
+    status = eng.fit_status()
+    alone = eng.fit_trajectory(dev(y[:n]), dev(ip[:n]), dev(iv[:n]), torch.zeros(n, device="cuda"), reg=NPD_REG)
+    status_alone = eng.fit_status()
+    nan = torch.isnan(mixed).cpu().numpy()
+    flagged = nan.any(axis=1)
+    print(f"[fit] not positive definite: fit_status {status}, rows with a NaN {np.flatnonzero(flagged).tolist()}, "
+          f"flag after the ordinary launch {status_alone}")
+    assert status is bool(flagged.any())                               # flag and rows agree
+    assert (nan.all(axis=1) == flagged).all()                          # a flagged row is whole
+    assert not flagged[0::2].any()
+    assert torch.equal(bits(mixed[0::2]), bits(alone))                 # ordinary episodes are untouched
+    check("npd_ordinary", ds, cs, alone, "ordinary episodes at reg 1e-300")
+    assert status_alone is False                                       # the flag is cleared
+    assert flagged[1::2].all(), "the rank-1 episodes kept seven positive pivots on this device: the path was not reached"
+
+
+def test_the_factor_cache_evicts_and_rebuilds():
+    """get_fit_factor keeps 16 factors keyed by (init_time, T, reg) and reuses the oldest slot's device buffer: 18 keys evict the first,
+    which then comes back with the bits it had, the bits a fresh handle gives; a new grid with the same step count invalidates all"""
+    name = "cfg2_prodmp"
+    pc, bc, tc, dt, duration = config(name)[:5]
+    cs = case(name, 3, 3)
+    y, ip, iv = dev(cs["y"]), dev(cs["ip"]), dev(cs["iv"])
+    eng = engine_for(name)
+
+    def run(e, it=0.0, reg=REG):
+        return e.fit_trajectory(y, ip, iv, it, reg=reg)
+    first = run(eng)
+    fresh = run(engine_for(name))
+    assert torch.equal(bits(first), bits(fresh))
+    regs = [REG * (1 + i) for i in range(18)]
+    seen = [run(eng, reg=r) for r in regs]
+    assert torch.equal(bits(seen[0]), bits(first)) and not torch.equal(bits(seen[17]), bits(first))
+    assert torch.equal(bits(run(eng, reg=regs[0])), bits(first))
+    assert torch.equal(bits(run(eng, reg=regs[17])), bits(seen[17]))
+    assert torch.equal(bits(run(engine_for(name), reg=regs[17])), bits(seen[17]))
+    clocks = [0.02 * i for i in range(18)]
+    seen = [run(eng, it=t) for t in clocks]
+    assert torch.equal(bits(seen[0]), bits(first)) and not torch.equal(bits(seen[17]), bits(first))
+    assert torch.equal(bits(run(eng, it=clocks[0])), bits(first))
+    assert torch.equal(bits(run(eng, it=clocks[17])), bits(seen[17]))
+    assert torch.equal(bits(run(engine_for(name), it=clocks[17])), bits(seen[17]))
+    # another grid of the same 100 steps: the key (init_time, T, reg) is the cached one, the factor is not
+    eng.set_duration(0.5 * duration, 0.5 * dt)
+    assert eng.num_steps == cs["y"].shape[1]
+    other = run(eng)
+    assert torch.equal(bits(other), bits(run(make_engine(pc, bc, tc, 0.5 * dt, 0.5 * duration)))) and not torch.equal(bits(other), bits(first))
+    eng.set_duration(duration, dt)
+    assert torch.equal(bits(run(eng)), bits(first))
+    # ... and another horizon (50 steps of the first grid) and back
+    eng.set_duration(0.5 * duration, dt)
+    short = y[:, :eng.num_steps].contiguous()
+    assert short.shape[1] == 50
+    assert torch.equal(bits(eng.fit_trajectory(short, ip, iv, 0.0, reg=REG)),
+                       bits(make_engine(pc, bc, tc, dt, 0.5 * duration).fit_trajectory(short, ip, iv, 0.0, reg=REG)))
+    eng.set_duration(duration, dt)
+    assert torch.equal(bits(run(eng)), bits(first))
+    assert eng.last_kernel() == "k_traj_fit_tile<prodmp>"
 
 
 # ---- 5. the layers above the engine -----------------------------------------------------------------------------------------------------

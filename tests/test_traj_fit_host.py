@@ -1,7 +1,10 @@
 """
 The closed-form trajectory fit without a GPU: the NumPy reference of tests/trajectory_fit_ref.py is a fit, the public surface exists, and
-fit_trajectory / learn_mp_params_from_trajs refuse bad arguments before anything touches a device.
+fit_trajectory / learn_mp_params_from_trajs refuse bad arguments before anything touches a device.  The per-episode-phase table
+of tests/test_gpu_traj_fit.py: the instantiations of k_phase_fit it reaches, its CPU fits, and the kernel's Cholesky order emulated in
+float64 for the rank-deficient batch.
 """
+import dataclasses
 import inspect
 import os
 import re
@@ -193,3 +196,109 @@ def test_learn_mp_params_from_trajs_refuses_before_any_device_work():
     fresh = get_trajectory_generator("prodmp", 3, get_basis_generator("prodmp", get_phase_generator("exp"), num_basis=4))
     with pytest.raises(RuntimeError, match="set_duration"):
         fresh.learn_mp_params_from_trajs(times, trajs, **given)
+
+
+# ---- 4. the per-episode-phase table (tests/test_gpu_traj_fit.py) without a device -----------------------------------------------------------
+def test_the_phase_table_reaches_every_instantiation_and_slot_count():
+    """k_phase_fit<MP, KQ> has five instantiations; a lane owns up to four entries of Psi^T (y - c), 64 a slot: the rows of the device
+    table take the KQ the table states (phase_fit_limits' rule), cover all five, and fill two, three and four slots"""
+    from tests import test_gpu_traj_fit as F
+    cfgs = F.phase_configs()
+    assert set(cfgs) == set(F.PHASE_KQ) and set(F.PHASE_TABLE) <= set(cfgs)
+    pairs, sizes = set(), []
+    for name in F.PHASE_TABLE:
+        pc, bc, tc = cfgs[name][:3]
+        kq = F.phase_fit_kq(bc, tc)
+        assert kq == F.PHASE_KQ[name], (name, kq)
+        n_rhs, P = tc.action_dim * 4 * kq, O.num_params(pc, bc, tc)
+        assert tc.action_dim <= 16 and n_rhs <= 256 and P <= 320, (name, n_rhs, P)      # the launcher's limits
+        pairs.add((tc.trajectory_generator_type, kq))
+        sizes.append(n_rhs)
+    for name in set(cfgs) - set(F.PHASE_TABLE):
+        assert F.phase_fit_kq(*cfgs[name][1:3]) == F.PHASE_KQ[name] == 2, name           # the round-boundary grid
+    assert pairs == {("promp", 1), ("promp", 2), ("promp", 4), ("prodmp", 2), ("prodmp", 4)}
+    for lo, hi in ((64, 128), (128, 192), (192, 256)):
+        assert any(lo < n <= hi for n in sizes), (lo, hi, sorted(sizes))
+    assert 64 in sizes and 256 in sizes                                                  # a slot exactly full, all four full
+    assert O.num_params(*cfgs["promp_16_basis_16_dof"][:3]) == 258
+    # the two switch rows take the branches their names say
+    assert cfgs["prodmp_4_basis_12_dof_goal_offset_add"][2].goal_offset_mode == "add"
+    assert cfgs["tt_prodmp_replan"][2].goal_offset_mode == "ignore" and cfgs["tt_prodmp_replan"][2].goal_offset == 1.0
+
+
+def test_the_cpu_fits_of_every_phase_row_are_finite():
+    """both CPU fits of every row (3 episodes: timing outside, inside and on the bounds), and the horizon each round-boundary row names"""
+    from tests import test_gpu_traj_fit as F
+    for name in F.PHASE_KQ:
+        cs = F.phase_case(name, 3)
+        for e in cs["eps"]:
+            assert np.isfinite(e["p64"]).all() and np.isfinite(e["p32"]).all() and np.isfinite(e["y"]).all(), name
+            assert e["p32"].dtype == np.float32
+        if "_round_t" in name:
+            assert cs["eps"][0]["ds"].T == int(name.split("_t")[1].split("_")[0]), name
+
+
+def fma(a, b, c):
+    """a b + c rounded once (exact rational arithmetic, then the correctly rounded conversion)"""
+    from fractions import Fraction
+    if not (np.isfinite(a) and np.isfinite(b) and np.isfinite(c)):
+        return a * b + c
+    return float(Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c)))
+
+
+def emulated_pivots(rows32, reg):
+    """k_phase_fit's order in float64 on float32 rows [T, K]: a Gram entry is the fma chain over ascending steps, reg joins the
+    diagonal, then the column Cholesky with fma(-L[i][k], L[j][k], s) over ascending k and a division by sqrt(pivot).  Returns the
+    pivots; NaN behind the first that is not positive"""
+    T, K = rows32.shape
+    e = rows32.astype(np.float64)
+    M = np.zeros((K, K))
+    for i in range(K):
+        for j in range(i + 1):
+            acc = 0.0
+            for s in range(T):
+                acc = fma(e[s, i], e[s, j], acc)
+            M[i, j] = acc + reg if i == j else acc
+    pivots = []
+    for j in range(K):
+        col = np.zeros(K)
+        for i in range(j, K):
+            s = M[i, j]
+            for k in range(j):
+                s = fma(-M[i, k], M[j, k], s)
+            col[i] = s
+        pivots.append(col[j])
+        ljj = np.sqrt(col[j]) if col[j] > 0.0 else float("nan")
+        M[j, j] = 1.0 / ljj
+        M[j + 1:, j] = col[j + 1:] / ljj
+    return np.array(pivots)
+
+
+def test_the_rank_one_gram_matrix_loses_a_pivot():
+    """the mixed batch of test_an_episode_without_a_factor_is_flagged_and_stays_alone, in the kernel's order on the CPU: an ordinary
+    episode keeps eight pivots above its smallest eigenvalue; an episode whose phase is clipped at every step has equal rows, a Gram
+    matrix of rank 1, and loses a pivot to rounding (here the third: -1.8e-48 after 1.2e-63 and 2.2e-62).  With 5 steps the ordinary
+    episodes would lose one too (8 columns, rank 5: pivot 3 = -1.2e-9), hence 12 steps"""
+    from tests import test_gpu_traj_fit as F
+    pc, bc, tc, dt, duration = F.npd_config()
+    reg = F.NPD_REG
+    assert np.float64(1.0) + reg == 1.0
+    ordinary = R.Design(pc, bc, tc, dt, duration, 0.0)
+    with np.errstate(all="ignore"):                      # (the float32 grid collapses at 1e6: the oracle's velocity divides by zero)
+        clipped = R.Design(pc, bc, tc, dt, duration, 1e6)
+    assert ordinary.T == 12 and ordinary.Kloc == 8
+    piv = emulated_pivots(ordinary.Psi[0].astype(np.float32), reg)
+    ev = np.linalg.eigvalsh(ordinary.Psi[0].T @ ordinary.Psi[0])
+    print(f"ordinary: pivots {piv.min():.3e} .. {piv.max():.3e}, eigenvalues {ev[0]:.3e} .. {ev[-1]:.3e}")
+    assert (piv >= 0.999 * ev[0]).all() and ev[0] > 1e-2
+    rows = clipped.Psi[0].astype(np.float32)
+    assert (rows == rows[0]).all() and (rows[0] > 0).all()
+    piv = emulated_pivots(rows, reg)
+    lost = np.flatnonzero(~(piv > 0.0))
+    print("rank 1: pivots " + " ".join(f"{p:.3e}" for p in piv))
+    assert piv[0] > 0.0 and lost.size and lost[0] >= 1
+    diag = 12.0 * rows[0].astype(np.float64) ** 2
+    assert (np.abs(piv[1:lost[0] + 1]) <= 1e-12 * diag[1:lost[0] + 1]).all()      # residue, not signal
+    # ... and five steps against eight columns leave the ordinary episodes without a factor as well
+    short = R.Design(dataclasses.replace(pc, tau=0.05), bc, tc, dt, 0.05, 0.0)
+    assert short.T == 5 and not (emulated_pivots(short.Psi[0].astype(np.float32), reg) > 0.0).all()
