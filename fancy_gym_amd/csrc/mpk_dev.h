@@ -19,6 +19,69 @@ namespace mpk {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
+// np.sum of the contiguous vector at(0) .. at(D - 1) of element type T in the order numpy adds it (pairwise_sum of numpy's
+// loops_utils.h.src, at most 128 entries): fewer than 8 entries from 0 in index order; from 8 on eight accumulators r[j] = x[j],
+// r[j] += x[8 i + j] over the whole blocks of eight, ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the remaining D % 8
+// entries in index order.  The reference's rewards are such sums over the links (sum(acc ** 2), sum(vel ** 2), sum(action ** 2)), so
+// from 8 links on the index order misses its bits (tests/test_gpu_link_counts.py).  MD > 0: the compile-time bound of D, every
+// loop unrolled, at(d) may index registers; with MD < 8 nothing but the in-order loop exists -- the operations the two- and five-link
+// instantiations had before this function.  MD == 0: D only at run time (at most 128), the loops stay loops.
+template <int MD, typename T, typename F>
+__device__ __forceinline__ T np_sum(const int D, F at) {
+    static_assert(MD >= 0 && MD <= 128, "numpy adds blocks of at most 128 entries this way");
+    if constexpr (MD > 0 && MD < 8) {
+        T s = (T)0;
+#pragma unroll
+        for (int d = 0; d < MD; ++d)
+            if (d < D) s = s + at(d);
+        return s;
+    } else if constexpr (MD > 0) {
+        T x[MD];                          // every entry evaluated once, whichever branch adds it
+#pragma unroll
+        for (int d = 0; d < MD; ++d) x[d] = d < D ? at(d) : (T)0;
+        if (D < 8) {
+            T s = (T)0;
+#pragma unroll
+            for (int d = 0; d < 7; ++d)
+                if (d < D) s = s + x[d];
+            return s;
+        }
+        T r[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = x[j];
+#pragma unroll
+        for (int i = 8; i + 8 <= MD; i += 8) {
+            if (i + 8 <= D) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) r[j] = r[j] + x[i + j];
+            }
+        }
+        T s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        const int whole = D & ~7;
+#pragma unroll
+        for (int d = 8; d < MD; ++d)
+            if (d >= whole && d < D) s = s + x[d];
+        return s;
+    } else {
+        if (D < 8) {
+            T s = (T)0;
+            for (int d = 0; d < D; ++d) s = s + at(d);
+            return s;
+        }
+        T r[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = at(j);
+        int i = 8;
+        for (; i + 8 <= D; i += 8) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r[j] = r[j] + at(i + j);
+        }
+        T s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < D; ++i) s = s + at(i);
+        return s;
+    }
+}
+
 // Development build only (-DMPK_TRACE): wave 0 of workgroup `MPK_TRACE_BLOCK` stamps the shader clock at labelled points
 // of a kernel into a device array that tools/dev/trace_kernel.py prints -- the per-phase timeline of ONE wave.
 #ifdef MPK_TRACE

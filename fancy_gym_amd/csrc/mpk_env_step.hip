@@ -75,13 +75,12 @@ __global__ void __launch_bounds__(kEnvStepBlock) k_reacher_env_step(const EnvSte
         bool hit = false, succ = false;
         if constexpr (KIND == kEnvStepSimple) {
             // base_reacher_torque.py:25-26 for a float32 action: numpy keeps the Python float dt weak, dt * action is float32;
-            // reward_ctrl = (action ** 2).sum() adds in float32 in index order (simple_reacher.py:68)
-            float c32 = 0.0f;
+            // reward_ctrl = (action ** 2).sum() adds in float32 in numpy's order (simple_reacher.py:68; np_sum, mpk_dev.h)
+            const float c32 = np_sum<MD, float>(D, [&](int d) { const float a32 = (float)u[d]; return a32 * a32; });
 #pragma unroll
             for (int d = 0; d < MD; ++d) {
                 if (d >= D) continue;
                 const float a32 = (float)u[d];
-                c32 = c32 + a32 * a32;
                 qd[d] = qd[d] + (double)(dt32 * a32);
                 q[d] = q[d] + dt * qd[d];
             }
@@ -143,7 +142,7 @@ __global__ void __launch_bounds__(kEnvStepBlock) k_reacher_env_step(const EnvSte
                     coll_cost = hit ? dist_cost : 0.0;
                     succ = dist < 0.005 && !hit;
                 }
-                r = ((dist_cost * -1.0 + vel_cost * -1e-4) + acc_cost * -1e-6) + coll_cost * -a.penalty;
+                r = hole_vel_acc_reward(dist_cost, vel_cost, acc_cost, coll_cost, a.penalty);
             } else if constexpr (KIND == MPK_HOLE_REW_UNBOUNDED) {
                 // hr_unbounded_reward.py:32-58: store the end effector at step 180 or on collision, pay at step 199 or on collision
                 double* e = a.reward_state + 2 * (size_t)b;

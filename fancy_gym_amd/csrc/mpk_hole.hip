@@ -140,8 +140,7 @@ __global__ void __launch_bounds__(64 * kHoleWpb) k_hole_rollout(const HoleArgs a
                 coll_cost = hit ? dist_cost : 0.0;          // collided * collision_dist^2, collision_dist = this step's dist
                 succ = dist < 0.005 && !hit;
             }
-            // (the fifth feature, time_cost, has factor 0)
-            r = ((dist_cost * -1.0 + vel_cost * -1e-4) + acc_cost * -1e-6) + coll_cost * -a.penalty;
+            r = hole_vel_acc_reward(dist_cost, vel_cost, acc_cost, coll_cost, a.penalty);
         } else if constexpr (REW == MPK_HOLE_REW_UNBOUNDED) {
             // hr_unbounded_reward.py:32-58: store the end effector at step 180 or on collision, pay at step 199 or on collision.  The
             // stored one lives in reward_state, not in registers (the kernel is at the occupancy-2 limit): step 180 and step 199 may

@@ -74,24 +74,26 @@ __device__ __forceinline__ bool hole_link_hits_wall(double c, double s, double x
 }
 
 // vel_acc's sum(qd^2) (hr_dist_vel_acc_reward.py:54) in numpy's dtypes: qd is the action, float32 for the velocity / position
-// controllers from the first step on (f32), float64 for the motor controller; np.sum adds in order
+// controllers from the first step on (f32), float64 for the motor controller; in numpy's order of additions (np_sum, mpk_dev.h)
 template <int MD>
 __device__ __forceinline__ double hole_vel_cost(bool f32, int D, const double* qd) {
-    if (f32) {
-        float c32 = 0.0f;
-#pragma unroll
-        for (int d = 0; d < MD; ++d) {
-            if (d >= D) continue;
-            const float v = (float)qd[d];
-            c32 = c32 + v * v;
-        }
-        return (double)c32;
-    }
-    double c = 0.0;
-#pragma unroll
-    for (int d = 0; d < MD; ++d)
-        if (d < D) c = c + qd[d] * qd[d];
-    return c;
+    if (f32)
+        return (double)np_sum<MD, float>(D, [&](int d) { const float v = (float)qd[d]; return v * v; });
+    return np_sum<MD, double>(D, [&](int d) { return qd[d] * qd[d]; });
+}
+
+// vel_acc's np.dot(reward_features, reward_factors) (hr_dist_vel_acc_reward.py:57-58) over (dist_cost, vel_cost, acc_cost,
+// collision_cost, time_cost) x (-1, -1e-4, -1e-6, -penalty, 0).  np.dot of five float64 entries is the BLAS's ddot, whose loop over
+// so short a vector is `dot += x[i] * y[i]` compiled to fused multiply-adds: ONE rounding per entry, in index order.  A step without
+// a distance term still has two non-zero products here (velocity and acceleration), so the fusing shows in the last bit: every such
+// reward of the reference fixtures (3 .. 16 links) is this chain's, and one in five to eight of them is not the sum of separately
+// rounded products.  (simple and unbounded have one non-zero product on such a step: either way of adding gives their bits.)
+__device__ __forceinline__ double hole_vel_acc_reward(double dist_cost, double vel_cost, double acc_cost, double coll_cost,
+                                                      double penalty) {
+    double r = dist_cost * -1.0;
+    r = fma(vel_cost, -1e-4, r);
+    r = fma(acc_cost, -1e-6, r);
+    return fma(coll_cost, -penalty, r);     // (the fifth feature, time_cost, has factor 0 and is 0)
 }
 
 __device__ __noinline__ double hole_unbounded_dist_reward(double dist, bool hit, bool up, double ey) {

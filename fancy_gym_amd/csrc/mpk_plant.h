@@ -38,29 +38,33 @@ __device__ __forceinline__ void hole_control(int ctrl, int D, const double* g, c
 // the direct-velocity plant (base_reacher_direct.py:26-28) and its control cost sum(acc^2), in numpy's dtypes: the velocity / position
 // controllers hand over a float32 action, which becomes the state qd -- from the episode's second step on (f32: env step > 0)
 // acc = (a - qd) / dt and dt * qd are float32 operations (numpy casts the Python float dt to float32), and np.sum(acc ** 2) adds in
-// float32; the first step subtracts from the float64 start velocity.  The motor controller's action is float64 throughout.
+// float32; the first step subtracts from the float64 start velocity.  The motor controller's action is float64 throughout.  Either
+// sum in numpy's order of additions (np_sum, mpk_dev.h).
 template <int MD>
 __device__ __forceinline__ double hole_plant_step(int ctrl, bool f32, int D, double dt, float dt32, const double* u, double* q,
                                                   double* qd) {
+    // (the sums read u and the velocity the step found: before the state moves)
     if (f32) {
-        float c32 = 0.0f;
+        const float c32 = np_sum<MD, float>(D, [&](int d) {
+            const float acc = ((float)u[d] - (float)qd[d]) / dt32;
+            return acc * acc;
+        });
 #pragma unroll
         for (int d = 0; d < MD; ++d) {
             if (d >= D) continue;
             const float a32 = (float)u[d];
-            const float acc = (a32 - (float)qd[d]) / dt32;
-            c32 = c32 + acc * acc;
             qd[d] = (double)a32;
             q[d] = q[d] + (double)(dt32 * a32);
         }
         return (double)c32;
     }
-    double acc_cost = 0.0;
+    const double acc_cost = np_sum<MD, double>(D, [&](int d) {
+        const double acc = (u[d] - qd[d]) / dt;
+        return acc * acc;
+    });
 #pragma unroll
     for (int d = 0; d < MD; ++d) {
         if (d >= D) continue;
-        const double acc = (u[d] - qd[d]) / dt;
-        acc_cost = acc_cost + acc * acc;
         qd[d] = u[d];
         q[d] = ctrl == MPK_CTRL_MOTOR ? q[d] + dt * qd[d] : q[d] + (double)(dt32 * (float)u[d]);
     }

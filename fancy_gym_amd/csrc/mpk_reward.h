@@ -43,7 +43,8 @@ __device__ __forceinline__ void sincos_lean(double x, double* sn, double* cs) {
 
 // SimpleReacherEnv's reward of ONE (episode, step) item (simple_reacher.py:56-72; unit links: base_reacher.py:19,97-104) from the
 // plant positions qv[0 .. D) after the step and the clipped actions uv[0 .. D): cumulative joint angles, end effector, control
-// cost, every sum left to right as numpy adds.  DC > 0: the link count compiled in, the sin / cos evaluations (independent chains
+// cost; the end effector's sums are np.cumsum's (index order), the control cost is np.sum's: index order below 8 links, eight
+// accumulators from there on (np_sum, mpk_dev.h).  DC > 0: the link count compiled in, the sin / cos evaluations (independent chains
 // of ~20 dependent float64 operations each) unrolled side by side -- an A/B knob (MPK_RW_DC), off: measured slower than the
 // run-time loop.  Same operations either way: same bits.
 #ifndef MPK_RW_CHAINS
@@ -90,6 +91,7 @@ __device__ __forceinline__ double reacher_reward_item(const double* qv, const do
                                                       const double gx, const double gy) {
     double ex = 0.0, ey = 0.0, ctrl = 0.0;
     if constexpr (DC > 0) {
+        static_assert(DC < 8, "from 8 entries on numpy does not add in index order: take np_sum for the control cost");
         double ang[DC];
         bool big = false;
 #pragma unroll
@@ -137,8 +139,8 @@ __device__ __forceinline__ double reacher_reward_item(const double* qv, const do
             sincos_lean(ang, &sn, &cs);
             ex = dd == 0 ? cs : ex + cs;
             ey = dd == 0 ? sn : ey + sn;
-            ctrl = dd == 0 ? uv[dd * kRwCol] * uv[dd * kRwCol] : ctrl + uv[dd * kRwCol] * uv[dd * kRwCol];
         }
+        ctrl = np_sum<0, double>(D, [&](int dd) { const double u_ = uv[dd * kRwCol]; return u_ * u_; });
     }
     double rdist = 0.0;
     if (dist_on) {
@@ -149,7 +151,7 @@ __device__ __forceinline__ double reacher_reward_item(const double* qv, const do
 }
 
 // The same item where the reference adds no distance term (simple_reacher.py:62-63: `if self._steps >= self.steps_before_reward`,
-// 199 of an episode's 200 steps at the reference's setting, :31): 0 - sum(action ** 2), the sum left to right -- the control cost of
+// 199 of an episode's 200 steps at the reference's setting, :31): 0 - sum(action ** 2), the sum in numpy's order -- the control cost of
 // reacher_reward_item operation for operation, so a pass may take either function for an item with dist_on == false: same bits.
 // Round 5: the pass ran the D sin / cos chains for every item and dropped 199 of 200 results behind a run-time predicate the compiler
 // cannot hoist (review of round 4); now a pass evaluates them only when at least one of its 64 items is past steps_before_reward.
@@ -162,10 +164,14 @@ __device__ __forceinline__ double reacher_ctrl_item(const double* uv, const int 
         double u_[DC];
 #pragma unroll
         for (int dd = 0; dd < DC; ++dd) u_[dd] = uv[dd * kRwCol];
+        if constexpr (DC < 8) {
 #pragma unroll
-        for (int dd = 0; dd < DC; ++dd) ctrl = dd == 0 ? u_[dd] * u_[dd] : ctrl + u_[dd] * u_[dd];
+            for (int dd = 0; dd < DC; ++dd) ctrl = dd == 0 ? u_[dd] * u_[dd] : ctrl + u_[dd] * u_[dd];
+        } else {
+            ctrl = np_sum<DC, double>(DC, [&](int dd) { return u_[dd] * u_[dd]; });
+        }
     } else {
-        for (int dd = 0; dd < D; ++dd) ctrl = dd == 0 ? uv[dd * kRwCol] * uv[dd * kRwCol] : ctrl + uv[dd * kRwCol] * uv[dd * kRwCol];
+        ctrl = np_sum<0, double>(D, [&](int dd) { const double u = uv[dd * kRwCol]; return u * u; });
     }
     return 0.0 - ctrl;
 }

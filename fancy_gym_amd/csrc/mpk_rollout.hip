@@ -352,6 +352,7 @@ __global__ void __launch_bounds__(HW ? 384 : 256) k_pd_rollout_tiles(const PdArg
                 if (p >= rw_npass) break;
                 double r;
                 if constexpr (DC > 0) {
+                    static_assert(DC < 8, "from 8 entries on numpy does not add in index order: take np_sum");
                     double ctrl = 0.0;
 #pragma unroll
                     for (int dd = 0; dd < DC; ++dd) ctrl = dd == 0 ? lu[p][dd] * lu[p][dd] : ctrl + lu[p][dd] * lu[p][dd];

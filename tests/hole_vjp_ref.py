@@ -110,19 +110,33 @@ def rnd(x):
     return x + (x.float().double() - x).detach()
 
 
-def _sum32(x):
-    """np.sum of a float32 row (fewer than 8 entries: left to right), every addition rounded"""
-    s = x[:, 0]
-    for d in range(1, x.shape[1]):
-        s = rnd(s + x[:, d])
+def _np_sum(x, add):
+    """np.sum of every row of x [B, n] in the order numpy adds a contiguous vector (oracle/mp_oracle.py: np_sum_rows): in index order
+    below 8 entries; from 8 on eight accumulators over the whole blocks of eight, combined pairwise, then the remainder in order"""
+    n = x.shape[1]
+    if n < 8:
+        s = x[:, 0]
+        for d in range(1, n):
+            s = add(s, x[:, d])
+        return s
+    r = [x[:, j] for j in range(8)]
+    i = 8
+    while i + 8 <= n:
+        r = [add(r[j], x[:, i + j]) for j in range(8)]
+        i += 8
+    s = add(add(add(r[0], r[1]), add(r[2], r[3])), add(add(r[4], r[5]), add(r[6], r[7])))
+    for d in range(i, n):
+        s = add(s, x[:, d])
     return s
+
+
+def _sum32(x):
+    """np.sum of a float32 row, every addition rounded to float32"""
+    return _np_sum(x, lambda a, b: rnd(a + b))
 
 
 def _sum64(x):
-    s = x[:, 0]
-    for d in range(1, x.shape[1]):
-        s = s + x[:, d]
-    return s
+    return _np_sum(x, lambda a, b: a + b)
 
 
 def torch_rollout(c, des_pos, des_vel, q0, qd0, hole):

@@ -108,6 +108,26 @@ def rows(c, idx):
     return out
 
 
+def _np_sum(x):
+    """np.sum of every row of x [B, n] in the order numpy adds a contiguous vector (oracle.np_sum_rows, in torch): in index order
+    below 8 entries; from 8 on eight accumulators over the whole blocks of eight, combined pairwise, then the remainder in order"""
+    n = x.shape[1]
+    if n < 8:
+        s = x[:, 0]
+        for d in range(1, n):
+            s = s + x[:, d]
+        return s
+    r = [x[:, j] for j in range(8)]
+    i = 8
+    while i + 8 <= n:
+        r = [r[j] + x[:, i + j] for j in range(8)]
+        i += 8
+    s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]))
+    for d in range(i, n):
+        s = s + x[:, d]
+    return s
+
+
 def torch_rollout(c, des_pos, des_vel, q0, qd0, goal):
     """oracle.reacher_rollout restated in float64 torch ops (same operations in the same order): rewards [B, T], final q, qd, and the
     per-step controller output u and distance (for the input conditions)"""
@@ -132,9 +152,7 @@ def torch_rollout(c, des_pos, des_vel, q0, qd0, goal):
         ey = torch.cumsum(torch.sin(ang), dim=1)[:, -1]
         dx, dy = ex - goal[:, 0], ey - goal[:, 1]
         dist = torch.sqrt(dx * dx + dy * dy)
-        ctrl = a[:, 0] * a[:, 0]
-        for d in range(1, D):
-            ctrl = ctrl + a[:, d] * a[:, d]
+        ctrl = _np_sum(a * a)
         r = torch.where(s0 + t >= c["sbr"], 0.0 - dist, torch.zeros_like(dist)) - ctrl
         rewards.append(torch.where(live, r, torch.zeros_like(r)))
         qd = torch.where(live[:, None], qd_n, qd)
