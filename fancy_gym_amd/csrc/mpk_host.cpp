@@ -1225,6 +1225,30 @@ int mpk_fit_status(mpk_handle hh, int32_t* not_positive_definite, void* stream) 
     return MPK_OK;
 }
 
+// the trajectory's standard deviation under a Gaussian over the non-phase parameters: the tables of (init_time_shared, T) as
+// mpk_trajectory_vjp builds or reuses them, one launch
+int mpk_trajectory_std(mpk_handle hh, const float* params_L, double init_time_shared, float* pos_std, float* vel_std, int32_t B,
+                       void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!params_L) { set_error("mpk_trajectory_std: NULL params_L"); return MPK_EINVAL; }
+    if (B < 1) { set_error("mpk_trajectory_std: B must be >= 1"); return MPK_EINVAL; }
+    if (!pos_std && !vel_std) { set_error("mpk_trajectory_std: pos_std and vel_std are both NULL: nothing to compute"); return MPK_EINVAL; }
+    if (h->cfg.learn_tau || h->cfg.learn_delay) {
+        set_error("mpk_trajectory_std: a learned tau / delay gives every episode its own phase and its own table: only shared-phase "
+                  "handles have a standard-deviation kernel");
+        return MPK_ENOTIMPL;
+    }
+    int rc = traj_std_limits(h->dev, nullptr, nullptr, nullptr);
+    if (rc != MPK_OK) return rc;
+    if (h->dev.D == 0) return MPK_OK;
+    MPK_ON_DEVICE(h->cfg.device);
+    SharedTables st;
+    rc = get_shared(h, (float)init_time_shared, stream, &st);
+    if (rc != MPK_OK) return rc;
+    return launch_traj_std(h->dev, st, params_L, pos_std, vel_std, B, h->num_cu, stream, &h->last_kernel);
+}
+
 int mpk_trajectory_actions(mpk_handle hh, const float* params, const float* init_pos, const float* init_vel,
                            double init_time_shared, const mpk_rollout_cfg* rc, const double* c_pos,
                            const double* c_vel, float* pos, float* vel, float* actions, int32_t B, void* stream) {

@@ -304,6 +304,14 @@ int phase_fit_limits(const DevCfg& c);
 int launch_phase_fit(const DevCfg& c, const PhaseFitLaunch& q, int num_cu, void* stream, const char** kernel_name);
 int launch_traj_fit(const DevCfg& c, const SharedTables& st, const double* fac, const float* pos, const float* init_pos,
                     const float* init_vel, float* params, int B, int num_cu, void* stream, const char** kernel_name);
+// mpk_trajectory_std (mpk_traj_std.hip): the standard deviation of the shared-phase trajectory under a Gaussian over the non-phase
+// parameters given by its lower-triangular factor params_L [B, Pl, Pl], Pl = D Kloc -- the norm of the table row times L, one launch of
+// k_traj_std_tile; either output may be nullptr (not computed, not written).  traj_std_limits: MPK_OK, or MPK_ENOTIMPL with the reason in
+// the message -- a DMP, more than kMaxD DoF or kMaxKP columns, a horizon whose tables and output images do not fit the LDS (no HIP call;
+// the outputs may be nullptr).
+int traj_std_limits(const DevCfg& c, size_t* lds_out, int* pitch_out, int* image_out);
+int launch_traj_std(const DevCfg& c, const SharedTables& st, const float* params_L, float* pos_std, float* vel_std, int B, int num_cu,
+                    void* stream, const char** kernel_name);
 int launch_episode_reset(const double* init_q, const double* init_qd, double* q, double* qd, float* cond_pos,
                          float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done, int B, int D,
                          void* stream);

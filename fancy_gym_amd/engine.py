@@ -709,6 +709,93 @@ class TrajectoryEngine:
         _lib.check(self._lib.mpk_fit_status(self._h, C.byref(flag), self._stream()))
         return bool(flag.value)
 
+    def _num_phase_params(self) -> int:
+        return int(bool(self.config.learn_tau)) + int(bool(self.config.learn_delay))
+
+    def trajectory_std(self, params_L, init_time: float = 0.0, *, pos: bool = True, vel: bool = True,
+                       out: Optional[Sequence[Optional[torch.Tensor]]] = None
+                       ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """
+        The trajectory's standard deviation under a Gaussian over the parameters (mpk.h: mpk_trajectory_std), one launch:
+        ``params_L`` [B, Pl, Pl] -> ``(pos_std, vel_std)`` [B, T, D] float32 on the device, None for a disabled one, without an autograd
+        graph.  ``params_L`` is the lower-triangular factor of the covariance of the non-phase parameters (Pl = ``num_params`` of a
+        shared-phase handle), in the user's units and in the order they have in ``params`` -- a policy's ``scale_tril``; its strict
+        upper triangle is never read.  ``pos_std[b, t, d]`` is the norm of the map's row times ``L_b`` (the factor form: non-negative
+        by construction, exact zeros for ``L = 0``); ``init_pos`` / ``init_vel`` are deterministic and contribute nothing.  This stands
+        in for mp_pytorch's ``get_traj_pos_std`` / ``get_traj_vel_std`` on a batch.  ``out``: a pair of buffers to write into (None for
+        one to be allocated).  Every refusal is raised before any launch: ValueError for a shape other than [B, Pl, Pl], a wrong
+        ``out``, ``pos = vel = False``; NotImplementedError for a handle that learns tau / delay, a DMP, and more than 16 DoF or 16
+        table columns.
+        """
+        if not pos and not vel:
+            raise ValueError("trajectory_std: pos and vel are both False: nothing to compute")
+        if self.config.learn_tau or self.config.learn_delay:
+            raise NotImplementedError("trajectory_std: a learned tau / delay gives every episode its own phase; only shared-phase "
+                                      "handles have a standard-deviation kernel")
+        if self.mp_type == "dmp":
+            raise NotImplementedError("trajectory_std: a DMP has no probabilistic interface (promp / prodmp only)")
+        D, T, Pl = self.num_dof, self.num_steps, self.num_params
+        if D > 16:
+            raise NotImplementedError(f"trajectory_std: at most 16 DoF and 16 table columns (this handle: {D} DoF)")
+        shape = tuple(params_L.shape) if hasattr(params_L, "shape") else np.shape(params_L)
+        if len(shape) != 3 or shape[0] < 1 or shape[1:] != (Pl, Pl):
+            raise ValueError(f"trajectory_std: params_L must be [B, {Pl}, {Pl}] (the factor of the {Pl} non-phase parameters' covariance), "
+                             f"got {shape}")
+        B = shape[0]
+        if out is not None and len(out) != 2:
+            raise ValueError("trajectory_std: out must be a pair (pos_std, vel_std) of tensors or None")
+        res = []
+        for i, want in enumerate((pos, vel)):
+            buf = out[i] if out is not None else None
+            if not want:
+                res.append(None)
+            elif buf is not None:
+                if tuple(buf.shape) != (B, T, D) or buf.dtype != torch.float32 or not buf.is_contiguous() or buf.device != self.device:
+                    raise ValueError(f"trajectory_std: out[{i}] must be a contiguous float32 tensor of shape {(B, T, D)} on {self.device}")
+                res.append(buf)
+            else:
+                res.append(False)
+        with torch.no_grad():
+            L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
+            res = [torch.empty((B, T, D), dtype=torch.float32, device=self.device) if r is False else r for r in res]
+            _lib.check(self._lib.mpk_trajectory_std(self._h, L.data_ptr(), float(init_time), _dptr(res[0]), _dptr(res[1]), B,
+                                                    self._stream()))
+        return res[0], res[1]
+
+    def sample_trajectories(self, params, params_L, init_pos, init_vel, init_time: float = 0.0, *, num_samples: int,
+                            generator: Optional[torch.Generator] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """
+        ``num_samples`` trajectories per episode from the Gaussian ``N(params, L L^T)`` over the non-phase parameters: ``(pos, vel)``
+        [B, S, T, D] float32 on the device, without an autograd graph.  ``eps ~ N(0, I)`` [B, S, Pl] is drawn with torch on the device
+        (``generator``: a device generator, for reproducible draws), the sampled parameters are ``params[:, None] + eps @ tril(L)^T``
+        on the non-phase part (tau / delay, where learned, stay as given), and ONE ``trajectory`` launch over the B S rows evaluates
+        them; every sample of an episode starts from that episode's ``init_pos`` / ``init_vel``.
+        """
+        S = int(num_samples)
+        if S < 1:
+            raise ValueError(f"sample_trajectories: num_samples must be >= 1, got {num_samples!r}")
+        D, P = self.num_dof, self.num_params
+        n_phase = self._num_phase_params()
+        Pl = P - n_phase
+        pshape = tuple(params.shape) if hasattr(params, "shape") else np.shape(params)
+        if len(pshape) != 2 or pshape[1] != P:
+            raise ValueError(f"sample_trajectories: params must be [B, {P}], got {pshape}")
+        B = pshape[0]
+        lshape = tuple(params_L.shape) if hasattr(params_L, "shape") else np.shape(params_L)
+        if lshape != (B, Pl, Pl):
+            raise ValueError(f"sample_trajectories: params_L must be [{B}, {Pl}, {Pl}], got {lshape}")
+        with torch.no_grad():
+            mean = torch.as_tensor(params, dtype=torch.float32, device=self.device).detach()
+            L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach()
+            eps = torch.randn((B, S, Pl), dtype=torch.float32, device=self.device, generator=generator)
+            full = mean[:, None, :].repeat(1, S, 1)
+            full[:, :, n_phase:] += eps @ torch.tril(L).transpose(1, 2)
+            ip = self._f32(init_pos, (B, D))[:, None, :].expand(B, S, D).reshape(B * S, D)
+            iv = self._f32(init_vel, (B, D))[:, None, :].expand(B, S, D).reshape(B * S, D)
+            pos, vel = self._trajectory_launch(full.reshape(B * S, P), ip.contiguous(), iv.contiguous(), None, float(init_time), None)
+        T = pos.shape[1]
+        return pos.view(B, S, T, D), vel.view(B, S, T, D)
+
     def check_range(self):
         """synchronise and raise RuntimeError if a per-episode-phase ProDMP launch left the pre-computed table range"""
         _lib.check(self._lib.mpk_check_range(self._h, self._stream()))

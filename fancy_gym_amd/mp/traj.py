@@ -95,11 +95,14 @@ class MPInterface:
         self.init_time = None
         self.init_pos = None
         self.init_vel = None
+        self.params_L = None
         self._clear()
 
     def _clear(self):
         self._pos = None
         self._vel = None
+        self._pos_std = None
+        self._vel_std = None
 
     def set_duration(self, duration: Optional[float], dt: float, include_init_time: bool = False):
         if include_init_time:
@@ -257,6 +260,62 @@ class MPInterface:
         if self._vel is None:
             self._compute()
         return self._vel
+
+    # ---- the probabilistic half (mp_pytorch's ProbabilisticMPInterface, ProMP / ProDMP; recollected from 0.1.x, unpinned) -------
+    def set_mp_params_variances(self, params_L):
+        """``params_L`` [Pl, Pl]: the lower-triangular Cholesky factor of the covariance of the Pl non-phase parameters, in the
+        order ``set_params`` takes them.  None forgets it, as ``reset()`` does."""
+        if self.mp_type == "dmp":
+            raise NotImplementedError("a DMP has no probabilistic interface (ProMP / ProDMP only)")
+        if params_L is not None:
+            if isinstance(params_L, torch.Tensor):
+                params_L = params_L.detach().cpu().numpy()
+            params_L = np.asarray(params_L, dtype=np.float32)
+            Pl = self._num_local_params
+            if params_L.shape == (1, Pl, Pl):
+                params_L = params_L[0]
+            if params_L.shape != (Pl, Pl):
+                raise ValueError(f"params_L must be [{Pl}, {Pl}], got {params_L.shape}")
+            params_L = np.ascontiguousarray(params_L)
+        self.params_L = params_L
+        self._clear()
+
+    def _compute_std(self):
+        if self.mp_type == "dmp":
+            raise NotImplementedError("a DMP has no probabilistic interface (ProMP / ProDMP only)")
+        if self.params_L is None:
+            raise RuntimeError("set_mp_params_variances(params_L) first")
+        it = self.init_time if self.init_time is not None else 0.0
+        pos_std, vel_std = self.engine().trajectory_std(self.params_L[None], it)
+        # one episode, CPU tensors: what get_traj_pos hands out
+        self._pos_std, self._vel_std = pos_std[0].cpu(), vel_std[0].cpu()
+
+    def get_traj_pos_std(self, **_ignored) -> torch.Tensor:
+        """[T, D]: the standard deviation of ``get_traj_pos`` under ``N(params, L L^T)`` (``TrajectoryEngine.trajectory_std``)"""
+        if self._pos_std is None:
+            self._compute_std()
+        return self._pos_std
+
+    def get_traj_vel_std(self, **_ignored) -> torch.Tensor:
+        if self._vel_std is None:
+            self._compute_std()
+        return self._vel_std
+
+    def sample_trajectories(self, num_smp: int = 1, generator: Optional[torch.Generator] = None):
+        """``(pos, vel)`` [num_smp, T, D]: trajectories of parameters drawn from ``N(params, L L^T)``
+        (``TrajectoryEngine.sample_trajectories``), CPU tensors"""
+        if self.mp_type == "dmp":
+            raise NotImplementedError("a DMP has no probabilistic interface (ProMP / ProDMP only)")
+        assert self.params is not None, "set_params() first"
+        if self.params_L is None:
+            raise RuntimeError("set_mp_params_variances(params_L) first")
+        D = self.num_dof
+        ip = self.init_pos if self.init_pos is not None else np.zeros(D, np.float32)
+        iv = self.init_vel if self.init_vel is not None else np.zeros(D, np.float32)
+        it = self.init_time if self.init_time is not None else 0.0
+        pos, vel = self.engine().sample_trajectories(self._full_params()[None], self.params_L[None], ip[None], iv[None], it,
+                                                     num_samples=num_smp, generator=generator)
+        return pos[0].cpu(), vel[0].cpu()
 
 
 class ProMP(MPInterface):

@@ -973,6 +973,38 @@ int mpk_trajectory_phase_fit(mpk_handle h, const float* pos, const float* phase_
 int mpk_fit_status(mpk_handle h, int32_t* not_positive_definite, void* stream);
 
 /*
+ * The trajectory's standard deviation under a Gaussian over the MP parameters, for a handle with a SHARED phase (added within ABI 4; no
+ * existing prototype changes) -- what mp_pytorch's ProbabilisticMPInterface (ProMP / ProDMP: set_mp_params_variances(params_L),
+ * get_traj_pos_std, get_traj_vel_std) answers on the host.  The params_L convention -- the Cholesky factor of the covariance of the
+ * non-phase parameters, in the order they have in params -- is written from recollection of mp_pytorch 0.1.x and is unpinned like the
+ * rest of the MP arithmetic.
+ *   params_L   dev float [B, Pl, Pl]  contiguous, any alignment; Pl = D * Kloc, the non-phase parameters in the order they have in
+ *                                     params (DoF-major).  The lower-triangular factor of the weight covariance Sigma_b = L_b L_b^T, in the
+ *                                     user's own units: weights_scale, goal_scale, the zero padding and disable_weights / disable_goal
+ *                                     are folded in exactly as mpk_trajectory folds them.  The strict upper triangle is never read.
+ *   pos_std    dev float [B, T, D]    out; either output may be NULL: not computed and not written
+ *   vel_std    dev float [B, T, D]    out
+ * With the shared-phase map pos[b, t, d] = sum_k R0[k][t] x[b, d][k] (mpk_trajectory_vjp above) and X_{b,d}[k][j] = L_b[d Kloc + loc(k), j]
+ * for the table columns k that are read from params, 0 for every other column (init_pos, init_vel and the goal offset are
+ * deterministic and contribute nothing),
+ *     pos_std[b, t, d] = sqrt(sum_j (sum_k R0[k][t] X_{b,d}[k][j])^2)
+ * and vel_std the same with R1 (a ProMP's R1 is the forward difference of its position rows, as in mpk_trajectory).  This is the FACTOR
+ * form -- the norm of the table row times L, non-negative by construction -- and never the quadratic form r^T (L L^T) r, which cancels
+ * where Sigma is rank deficient.  Finite input gives finite, non-negative output; L = 0 gives exact zeros.
+ * One launch of k_traj_std_tile<promp | prodmp> (mpk_last_kernel) on `stream`, plus the table builder when (init_time_shared, T) is not
+ * cached, exactly as mpk_trajectory_vjp; nothing is allocated or synchronised.  One wave per episode on the matrix cores, no atomics,
+ * an episode never leaves its wave: the same bits from run to run, for any alignment of the three pointers, and whatever else is in
+ * the batch.
+ * MPK_EINVAL: a NULL handle or params_L, B < 1, both outputs NULL (and vel_std of a ProMP with a single time step).  MPK_ENOTIMPL,
+ * before any launch: a handle that learns tau / delay (a per-episode phase); a DMP (mp_pytorch's DMP has no probabilistic interface);
+ * more than 16 DoF or 16 table columns (the k_traj_wide shapes); a horizon whose tables and output images do not fit the CU's LDS --
+ * 8 KP pitch + 32 (T D + 3) bytes <= 163 840, KP the table columns rounded up to 4, pitch = T rounded up to 16 (+ 16 if that is a
+ * multiple of 32): about 250 steps at 16 DoF and 16 columns, 560 at 7 DoF and 8 columns.
+ */
+int mpk_trajectory_std(mpk_handle h, const float* params_L, double init_time_shared, float* pos_std, float* vel_std, int32_t B,
+                       void* stream);
+
+/*
  * The vector-Jacobian product of mpk_reacher_rollout (appended under ABI 4): controller, clip, torque double integrator and
  * SimpleReacher's reward transposed -- the gradient of any scalar loss of the step rewards and the final state w.r.t. the desired
  * trajectory, the plan-start state and the goal, one launch.  The forward it transposes (mpk_reacher_rollout above), per executed step
