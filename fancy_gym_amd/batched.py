@@ -611,6 +611,16 @@ class BatchedBlackBox:
         cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
         return self.engine.fit_trajectory(pos, cond_pos, cond_vel, self._plan_time(), reg=reg, phase_params=phase_params)
 
+    def condition(self, params, params_L, obs_steps, obs_pos=None, obs_std=None, *, obs_vel=None, obs_vel_std=None, out=None):
+        """``(params, params_L)`` of the Gaussian ``N(params, L L^T)`` conditioned on observed points of the plan
+        (``TrajectoryEngine.condition``: the ProMP operation, one launch) from the init_time / init_pos / init_vel ``get_trajectory``
+        would use now -- so the posterior mean can be handed straight to ``step`` / ``get_trajectory`` and the pair to
+        ``TrajectoryEngine.sample_trajectories``"""
+        cond_pos = self.condition_pos if self.condition_pos is not None else self.q.float()
+        cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
+        return self.engine.condition(params, params_L, obs_steps, obs_pos, obs_std, cond_pos, cond_vel, self._plan_time(),
+                                     obs_vel=obs_vel, obs_vel_std=obs_vel_std, out=out)
+
     def _carry_start(self):
         """replan_gradient="episode": (init_pos, init_vel, q_in, qd_in) of the next plan -- what the twins of the plan before give (the
         same bits as ``_plan_condition`` and ``q``, ``qd``), or right after a cut the constants themselves"""

@@ -1249,6 +1249,68 @@ int mpk_trajectory_std(mpk_handle hh, const float* params_L, double init_time_sh
     return launch_traj_std(h->dev, st, params_L, pos_std, vel_std, B, h->num_cu, stream, &h->last_kernel);
 }
 
+// the Gaussian over the non-phase parameters conditioned on observed trajectory points: every refusal before any launch, the tables of
+// (init_time_shared, T) as mpk_trajectory_std builds or reuses them, one launch; obs_steps is copied into the launch arguments
+int mpk_trajectory_condition(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                             double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
+                             const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, float* params_out,
+                             float* params_L_out, int32_t B, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!params || !params_L || !params_out || !params_L_out) {
+        set_error("mpk_trajectory_condition: NULL params, params_L, params_out or params_L_out");
+        return MPK_EINVAL;
+    }
+    if (B < 1) { set_error("mpk_trajectory_condition: B must be >= 1"); return MPK_EINVAL; }
+    if (M < 1 || M > MPK_COND_MAX_STEPS || !obs_steps) {
+        set_error("mpk_trajectory_condition: M must be 1.." + std::to_string(MPK_COND_MAX_STEPS) + " observed steps (obs_steps: a host "
+                  "array of M step indices), got " + std::to_string(M));
+        return MPK_EINVAL;
+    }
+    for (int m = 0; m < M; ++m) {
+        if (obs_steps[m] < 0 || obs_steps[m] >= h->dev.T || (m > 0 && obs_steps[m] <= obs_steps[m - 1])) {
+            set_error("mpk_trajectory_condition: obs_steps must be strictly increasing step indices in [0, " + std::to_string(h->dev.T) +
+                      "); obs_steps[" + std::to_string(m) + "] = " + std::to_string(obs_steps[m]));
+            return MPK_EINVAL;
+        }
+    }
+    if (!obs_pos && !obs_pos_std && !obs_vel && !obs_vel_std) {
+        set_error("mpk_trajectory_condition: obs_pos and obs_vel are both NULL: nothing is observed");
+        return MPK_EINVAL;
+    }
+    if (!obs_pos != !obs_pos_std || !obs_vel != !obs_vel_std) {
+        set_error("mpk_trajectory_condition: observed values and their standard deviations come in pairs (obs_pos with obs_pos_std, "
+                  "obs_vel with obs_vel_std)");
+        return MPK_EINVAL;
+    }
+    if (h->cfg.learn_tau || h->cfg.learn_delay) {
+        set_error("mpk_trajectory_condition: a learned tau / delay gives every episode its own phase and its own table: only shared-phase "
+                  "handles have a conditioning kernel");
+        return MPK_ENOTIMPL;
+    }
+    int rc = traj_cond_limits(h->dev, M, nullptr, nullptr, nullptr);
+    if (rc != MPK_OK) return rc;
+    if (h->dev.D * h->dev.Kloc < 1) { set_error("mpk_trajectory_condition: the handle has no non-phase parameters"); return MPK_EINVAL; }
+    if (obs_vel && h->cfg.mp_type == MPK_MP_PROMP && h->dev.T < 2) {
+        set_error("promp needs at least two time steps for the finite-difference velocity");
+        return MPK_EINVAL;
+    }
+    if ((!init_pos || !init_vel) && h->cfg.mp_type != MPK_MP_PROMP) {
+        set_error("mpk_trajectory_condition: init_pos and init_vel are required (only a ProMP may pass NULL: zeros)");
+        return MPK_EINVAL;
+    }
+    MPK_ON_DEVICE(h->cfg.device);
+    SharedTables st;
+    rc = get_shared(h, (float)init_time_shared, stream, &st);
+    if (rc != MPK_OK) return rc;
+    CondLaunch q;
+    q.params = params; q.params_L = params_L; q.init_pos = init_pos; q.init_vel = init_vel;
+    q.steps = obs_steps; q.M = M; q.init_time = (float)init_time_shared;
+    q.obs_pos = obs_pos; q.obs_pos_std = obs_pos_std; q.obs_vel = obs_vel; q.obs_vel_std = obs_vel_std;
+    q.params_out = params_out; q.params_L_out = params_L_out; q.B = B;
+    return launch_traj_condition(h->dev, st, q, h->num_cu, stream, &h->last_kernel);
+}
+
 int mpk_trajectory_actions(mpk_handle hh, const float* params, const float* init_pos, const float* init_vel,
                            double init_time_shared, const mpk_rollout_cfg* rc, const double* c_pos,
                            const double* c_vel, float* pos, float* vel, float* actions, int32_t B, void* stream) {

@@ -312,6 +312,23 @@ int launch_traj_fit(const DevCfg& c, const SharedTables& st, const double* fac, 
 int traj_std_limits(const DevCfg& c, size_t* lds_out, int* pitch_out, int* image_out);
 int launch_traj_std(const DevCfg& c, const SharedTables& st, const float* params_L, float* pos_std, float* vel_std, int B, int num_cu,
                     void* stream, const char** kernel_name);
+// mpk_trajectory_condition (mpk_traj_condition.hip): the Gaussian N(params, L L^T) over the non-phase parameters conditioned on observed
+// positions / velocities at M shared steps -- a sequential square-root measurement update of the factor in float64, one launch of
+// k_traj_condition, one wave per episode.  steps: HOST, validated by the caller (strictly increasing, in [0, T)); either observation
+// pair may be nullptr; the outputs may be the inputs.  traj_cond_limits: MPK_OK, or MPK_ENOTIMPL with the reason in the message -- a DMP,
+// more than kMaxD DoF or kMaxKP columns, a Pl whose float64 triangle and work vectors exceed the LDS with one wave per workgroup (no HIP
+// call; the outputs may be nullptr).
+struct CondLaunch {
+    const float *params = nullptr, *params_L = nullptr, *init_pos = nullptr, *init_vel = nullptr;
+    const int32_t* steps = nullptr;                                     // HOST [M]
+    int M = 0;
+    float init_time = 0.f;                                              // the tables' (init_time_shared)
+    const float *obs_pos = nullptr, *obs_pos_std = nullptr, *obs_vel = nullptr, *obs_vel_std = nullptr;   // [B, M, D]
+    float *params_out = nullptr, *params_L_out = nullptr;
+    int B = 0;
+};
+int traj_cond_limits(const DevCfg& c, int M, size_t* lds_out, int* waves_out, int* wave_doubles_out);
+int launch_traj_condition(const DevCfg& c, const SharedTables& st, const CondLaunch& q, int num_cu, void* stream, const char** kernel_name);
 int launch_episode_reset(const double* init_q, const double* init_qd, double* q, double* qd, float* cond_pos,
                          float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done, int B, int D,
                          void* stream);

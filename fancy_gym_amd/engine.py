@@ -762,6 +762,91 @@ class TrajectoryEngine:
                                                     self._stream()))
         return res[0], res[1]
 
+    def condition(self, params, params_L, obs_steps, obs_pos=None, obs_std=None, init_pos=None, init_vel=None,
+                  init_time: float = 0.0, *, obs_vel=None, obs_vel_std=None,
+                  out: Optional[Sequence[torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """
+        The Gaussian ``N(params, L L^T)`` over the parameters conditioned on observed trajectory points (mpk.h:
+        mpk_trajectory_condition), one launch: ``(params_post, params_L_post)`` [B, P], [B, Pl, Pl] float32 on the device, without an
+        autograd graph.  ``obs_steps``: a host sequence of M <= 32 strictly increasing step indices in [0, T), shared by the batch;
+        ``obs_pos`` / ``obs_vel`` [B, M, D]: the observed positions / velocities at those steps (either may be None, not both);
+        ``obs_std`` / ``obs_vel_std``: their standard deviations, a scalar, [M], [M, D] or [B, M, D], broadcast to [B, M, D].  A standard
+        deviation of ``+inf`` (or NaN, or a negative one) skips that (episode, step, DoF) -- this is how some DoFs, or some episodes,
+        only are observed -- and 0 is exact conditioning (more exact observations of a DoF than it has free parameters are the
+        caller's error: unspecified, never a fault).  The update is sequential and in the factor form (float64, rounded once): the
+        posterior factor is lower triangular with a non-negative diagonal and an exactly zero upper triangle, a valid ``scale_tril``
+        even where the posterior covariance is singular; ``params_L``'s strict upper triangle is never read.  This stands in for
+        conditioning an mp_pytorch ProMP on via-points, for a ProMP and a shared-phase ProDMP alike.  ``init_pos`` / ``init_vel``
+        [B, D] are deterministic; None only for a ProMP (zeros).  ``out=(params, params_L)`` gives the in-place form (any pair of
+        contiguous float32 buffers of the right shapes).  Every refusal is raised before any launch: ValueError for wrong shapes, no
+        observation at all, values without standard deviations, bad steps, ``init_pos=None`` on a ProDMP; NotImplementedError for a
+        handle that learns tau / delay, a DMP, more than 16 DoF or 16 table columns, and a Pl whose float64 triangle exceeds a CU's LDS.
+        """
+        if self.config.learn_tau or self.config.learn_delay:
+            raise NotImplementedError("condition: a learned tau / delay gives every episode its own phase; only shared-phase handles "
+                                      "have a conditioning kernel")
+        if self.mp_type == "dmp":
+            raise NotImplementedError("condition: a DMP has no probabilistic interface (promp / prodmp only)")
+        D, T, P = self.num_dof, self.num_steps, self.num_params
+        if D > 16:
+            raise NotImplementedError(f"condition: at most 16 DoF and 16 table columns (this handle: {D} DoF)")
+        pshape = tuple(params.shape) if hasattr(params, "shape") else np.shape(params)
+        if len(pshape) != 2 or pshape[0] < 1 or pshape[1] != P:
+            raise ValueError(f"condition: params must be [B, {P}], got {pshape}")
+        B = pshape[0]
+        lshape = tuple(params_L.shape) if hasattr(params_L, "shape") else np.shape(params_L)
+        if lshape != (B, P, P):
+            raise ValueError(f"condition: params_L must be [{B}, {P}, {P}] (the factor of the {P} non-phase parameters' covariance), "
+                             f"got {lshape}")
+        steps = np.asarray(list(obs_steps))
+        if steps.ndim != 1 or (steps.size and not np.issubdtype(steps.dtype, np.integer)):
+            raise ValueError(f"condition: obs_steps must be a sequence of ints, got {obs_steps!r}")
+        steps = np.ascontiguousarray(steps, dtype=np.int32)
+        M = int(steps.size)
+        if obs_pos is None and obs_vel is None:
+            raise ValueError("condition: obs_pos and obs_vel are both None: nothing is observed")
+        for val, sd, names in ((obs_pos, obs_std, ("obs_pos", "obs_std")), (obs_vel, obs_vel_std, ("obs_vel", "obs_vel_std"))):
+            if (val is None) != (sd is None):
+                raise ValueError(f"condition: {names[0]} and {names[1]} come in pairs (observed values with their standard deviations)")
+        if (init_pos is None or init_vel is None) and self.mp_type != "promp":
+            raise ValueError(f"condition: init_pos / init_vel may be None only for a ProMP, which ignores them; a {self.mp_type} "
+                             "starts from them")
+        if out is not None:
+            if len(out) != 2:
+                raise ValueError("condition: out must be a pair (params, params_L) of tensors")
+            for i, (buf, shape) in enumerate(zip(out, ((B, P), (B, P, P)))):
+                if (not isinstance(buf, torch.Tensor) or tuple(buf.shape) != shape or buf.dtype != torch.float32
+                        or not buf.is_contiguous() or buf.device != self.device):
+                    raise ValueError(f"condition: out[{i}] must be a contiguous float32 tensor of shape {shape} on {self.device}")
+
+        def bcast(x, name):
+            t = torch.as_tensor(x, dtype=torch.float32, device=self.device).detach()
+            if t.dim() == 1 and t.shape[0] == M:                    # [M]: one value per step
+                t = t[:, None]
+            try:
+                return t.expand((B, M, D)).contiguous()
+            except RuntimeError:
+                raise ValueError(f"condition: {name} does not broadcast to [{B}, {M}, {D}], got {tuple(t.shape)}") from None
+        with torch.no_grad():
+            mean = torch.as_tensor(params, dtype=torch.float32, device=self.device).detach().contiguous()
+            L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
+            ip = None if init_pos is None else self._f32(init_pos, (B, D)).detach()
+            iv = None if init_vel is None else self._f32(init_vel, (B, D)).detach()
+            yp = None if obs_pos is None else bcast(obs_pos, "obs_pos")
+            sp = None if obs_pos is None else bcast(obs_std, "obs_std")
+            yv = None if obs_vel is None else bcast(obs_vel, "obs_vel")
+            sv = None if obs_vel is None else bcast(obs_vel_std, "obs_vel_std")
+            if out is not None:
+                mean_out, L_out = out
+            else:
+                mean_out = torch.empty((B, P), dtype=torch.float32, device=self.device)
+                L_out = torch.empty((B, P, P), dtype=torch.float32, device=self.device)
+            _lib.check(self._lib.mpk_trajectory_condition(
+                self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time),
+                steps.ctypes.data_as(C.POINTER(C.c_int32)), M, _dptr(yp), _dptr(sp), _dptr(yv), _dptr(sv), mean_out.data_ptr(),
+                L_out.data_ptr(), B, self._stream()))
+        return mean_out, L_out
+
     def sample_trajectories(self, params, params_L, init_pos, init_vel, init_time: float = 0.0, *, num_samples: int,
                             generator: Optional[torch.Generator] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """

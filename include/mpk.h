@@ -1005,6 +1005,64 @@ int mpk_trajectory_std(mpk_handle h, const float* params_L, double init_time_sha
                        void* stream);
 
 /*
+ * A Gaussian over the MP parameters conditioned on observed trajectory points, for a handle with a SHARED phase (added within ABI 4; no
+ * existing prototype changes) -- the operation a Probabilistic MP is named after: what mp_pytorch's ProMP answers on the host by
+ * conditioning its weight distribution on via-points (written from recollection of mp_pytorch 0.1.x and of Paraschos et al., unpinned
+ * like the rest of the MP arithmetic), here for a ProMP and for a shared-phase ProDMP alike, whose trajectory is affine in the
+ * parameters too.  The params_L convention is the unpinned one of mpk_trajectory_std: the lower-triangular factor of the covariance of
+ * the Pl = D * Kloc non-phase parameters, in the order they have in params and in the user's own units (weights_scale, goal_scale, the
+ * relative goal, the zero padding and disable_weights / disable_goal folded in exactly as mpk_trajectory folds them).
+ *   params        dev float [B, P]       the prior mean (P = Pl: a shared-phase handle has no other parameters)
+ *   params_L      dev float [B, Pl, Pl]  the prior factor, Sigma_b = L_b L_b^T; the strict upper triangle is never read
+ *   init_pos      dev float [B, D]       given, deterministic; NULL (zeros) is accepted for a ProMP only
+ *   init_vel      dev float [B, D]
+ *   obs_steps     HOST int32 [M]         the observed step indices t_m, shared by the batch: 1 <= M <= MPK_COND_MAX_STEPS, strictly
+ *                                        increasing, in [0, T).  Validated here and copied into the launch arguments: a captured graph
+ *                                        keeps its steps
+ *   obs_pos, obs_pos_std   dev float [B, M, D] each, or both NULL: observed positions and their standard deviations
+ *   obs_vel, obs_vel_std   dev float [B, M, D] each, or both NULL: observed velocities and their standard deviations
+ *   params_out    dev float [B, P]       out, the posterior mean;   may be params
+ *   params_L_out  dev float [B, Pl, Pl]  out, the posterior factor; may be params_L.  Lower triangular with a non-negative diagonal
+ *                                        (given one), the strict upper triangle written as exact zeros: a valid scale_tril
+ * A scalar observation (o, m, d) -- o = 0 a position, 1 a velocity; step t_m; DoF d -- of the parameters w ~ N(mu, L L^T) reads
+ *     y = h . w + c + eps,  eps ~ N(0, sigma^2),   h[d Kloc + loc(k)] = R_o[k][t_m] for the table columns k read from params, else 0,
+ * c what the other columns contribute (init_pos, init_vel, the constant goal-offset column: the forward's value at zero parameters), R_o
+ * the launch's own table (mpk_trajectory_vjp above; a ProMP's velocity rows -- the forward difference of two position rows over dt --
+ * are re-evaluated in float64 for the observed steps: differencing the float32 table would amplify its rounding 20 to 50 times).  The scalar observations are applied one after the other -- m ascending; within a
+ * step the positions, d ascending, then the velocities, d ascending -- each by Carlson's square-root measurement update in its
+ * lower-triangular form, in float64:
+ *     v = L^T h ;   b_n = sigma^2,  b_j = b_{j+1} + v_j^2  (j = n - 1 .. 0, n = (d + 1) Kloc: v_j = 0 beyond) ;   s = b_0
+ *     r = y - c - h . mu
+ *     w = 0 ;  for j = n - 1 .. 0:   L'[:, j] = L[:, j] sqrt(b_{j+1} / b_j) - w v_j / sqrt(b_{j+1} b_j) ;   w += L[:, j] v_j
+ *              (b_j == 0: the column stays;  b_{j+1} == 0 < b_j: the column becomes 0;  sqrt(b_{j+1} b_j) is evaluated as
+ *              sqrt(b_{j+1}) sqrt(b_j): the b of far-off RBF columns are ~1e-200 and their product would underflow)
+ *     mu' = mu + w (r / s)
+ * This is the FACTOR form: L L^T is never formed and no two covariances are subtracted, so the posterior factor is defined and lower
+ * triangular even where the posterior covariance is singular -- which it is by construction as soon as sigma is small.  In exact
+ * arithmetic the result equals the batch formula mu + Sigma H^T (H Sigma H^T + R)^-1 (y - H mu - c), Sigma - Sigma H^T (H Sigma H^T +
+ * R)^-1 H Sigma and does not depend on the order.  Everything is rounded to float32 once, on the way out.
+ * Skipping: a standard deviation of +inf, NaN or a negative one skips that scalar observation -- this is how a caller observes some DoFs,
+ * or some episodes, only -- and so does s == 0 (nothing to learn: the prior has no variance there and sigma = 0).  A skipped observation
+ * changes nothing: an episode whose observations are all skipped comes back bit for bit (its strict upper triangle as zeros).
+ * sigma = 0 is exact conditioning.  Asking a DoF for more exact observations than it has free parameters is the caller's error: the
+ * result is then unspecified (it never faults); no status word reports it.
+ * One launch of k_traj_condition<promp | prodmp> (mpk_last_kernel) on `stream`, plus the table builder when (init_time_shared, T) is not
+ * cached, exactly as mpk_trajectory_std; nothing is allocated or synchronised.  One wave per episode, no atomics, an episode never
+ * leaves its wave and is read completely before it is written: the same bits from run to run, for any alignment of the pointers, alone
+ * or in a batch.
+ * MPK_EINVAL: a NULL handle, params, params_L or output; B < 1; M outside 1..MPK_COND_MAX_STEPS; steps not strictly increasing or outside
+ * [0, T); no observation array at all; a value array without its standard deviations or the reverse; obs_vel for a ProMP with a single
+ * time step; init_pos / init_vel NULL for a ProDMP.  MPK_ENOTIMPL, before any launch: a handle that learns tau / delay (a per-episode
+ * phase); a DMP; more than 16 DoF or 16 table columns; a Pl whose float64 triangle and work vectors exceed a CU's LDS with one wave per
+ * workgroup -- 8 (Pl (Pl + 1) / 2 + 4 Pl) + 16 M KT bytes <= 163 840: Pl = 160 (16 DoF x 10) runs, Pl = 256 does not.
+ */
+#define MPK_COND_MAX_STEPS 32
+int mpk_trajectory_condition(mpk_handle h, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                             double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
+                             const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, float* params_out,
+                             float* params_L_out, int32_t B, void* stream);
+
+/*
  * The vector-Jacobian product of mpk_reacher_rollout (appended under ABI 4): controller, clip, torque double integrator and
  * SimpleReacher's reward transposed -- the gradient of any scalar loss of the step rewards and the final state w.r.t. the desired
  * trajectory, the plan-start state and the goal, one launch.  The forward it transposes (mpk_reacher_rollout above), per executed step
