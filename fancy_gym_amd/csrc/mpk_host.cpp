@@ -1311,6 +1311,86 @@ int mpk_trajectory_condition(mpk_handle hh, const float* params, const float* pa
     return launch_traj_condition(h->dev, st, q, h->num_cu, stream, &h->last_kernel);
 }
 
+// the log-likelihood of conditioning's observations under N(params, L L^T) and its gradient: the refusals of mpk_trajectory_condition
+// plus the observation count, every one before any launch; the tables as above; one launch.  grad: the _vjp entry
+static int trajectory_log_prob_entry(const char* fn, mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
+                                     const float* init_vel, double init_time_shared, const int32_t* obs_steps, int32_t M,
+                                     const float* obs_pos, const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std,
+                                     bool grad, double* log_prob, const double* g, float* g_params, float* g_params_L, int32_t B,
+                                     void* stream) {
+    const std::string name(fn);
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!params || !params_L) { set_error(name + ": NULL params or params_L"); return MPK_EINVAL; }
+    if (!grad && !log_prob) { set_error(name + ": NULL log_prob"); return MPK_EINVAL; }
+    if (grad && !g) { set_error(name + ": NULL g"); return MPK_EINVAL; }
+    if (grad && !g_params && !g_params_L) { set_error(name + ": g_params and g_params_L are both NULL: nothing to compute"); return MPK_EINVAL; }
+    if (B < 1) { set_error(name + ": B must be >= 1"); return MPK_EINVAL; }
+    if (M < 1 || M > MPK_COND_MAX_STEPS || !obs_steps) {
+        set_error(name + ": M must be 1.." + std::to_string(MPK_COND_MAX_STEPS) + " observed steps (obs_steps: a host array of M step "
+                  "indices), got " + std::to_string(M));
+        return MPK_EINVAL;
+    }
+    for (int m = 0; m < M; ++m) {
+        if (obs_steps[m] < 0 || obs_steps[m] >= h->dev.T || (m > 0 && obs_steps[m] <= obs_steps[m - 1])) {
+            set_error(name + ": obs_steps must be strictly increasing step indices in [0, " + std::to_string(h->dev.T) + "); obs_steps[" +
+                      std::to_string(m) + "] = " + std::to_string(obs_steps[m]));
+            return MPK_EINVAL;
+        }
+    }
+    if (!obs_pos && !obs_pos_std && !obs_vel && !obs_vel_std) {
+        set_error(name + ": obs_pos and obs_vel are both NULL: nothing is observed");
+        return MPK_EINVAL;
+    }
+    if (!obs_pos != !obs_pos_std || !obs_vel != !obs_vel_std) {
+        set_error(name + ": observed values and their standard deviations come in pairs (obs_pos with obs_pos_std, obs_vel with "
+                  "obs_vel_std)");
+        return MPK_EINVAL;
+    }
+    if (h->cfg.learn_tau || h->cfg.learn_delay) {
+        set_error(name + ": a learned tau / delay gives every episode its own phase and its own table: only shared-phase handles have a "
+                  "likelihood kernel");
+        return MPK_ENOTIMPL;
+    }
+    int rc = traj_log_prob_limits(h->dev, M, (obs_pos ? 1 : 0) + (obs_vel ? 1 : 0), nullptr, nullptr, nullptr);
+    if (rc != MPK_OK) return rc;
+    if (h->dev.D * h->dev.Kloc < 1) { set_error(name + ": the handle has no non-phase parameters"); return MPK_EINVAL; }
+    if (obs_vel && h->cfg.mp_type == MPK_MP_PROMP && h->dev.T < 2) {
+        set_error("promp needs at least two time steps for the finite-difference velocity");
+        return MPK_EINVAL;
+    }
+    if ((!init_pos || !init_vel) && h->cfg.mp_type != MPK_MP_PROMP) {
+        set_error(name + ": init_pos and init_vel are required (only a ProMP may pass NULL: zeros)");
+        return MPK_EINVAL;
+    }
+    MPK_ON_DEVICE(h->cfg.device);
+    SharedTables st;
+    rc = get_shared(h, (float)init_time_shared, stream, &st);
+    if (rc != MPK_OK) return rc;
+    LogProbLaunch q;
+    q.params = params; q.params_L = params_L; q.init_pos = init_pos; q.init_vel = init_vel;
+    q.steps = obs_steps; q.M = M; q.init_time = (float)init_time_shared;
+    q.obs_pos = obs_pos; q.obs_pos_std = obs_pos_std; q.obs_vel = obs_vel; q.obs_vel_std = obs_vel_std;
+    q.grad = grad; q.log_prob = log_prob; q.g = g; q.g_params = g_params; q.g_params_L = g_params_L; q.B = B;
+    return launch_traj_log_prob(h->dev, st, q, h->num_cu, stream, &h->last_kernel);
+}
+
+int mpk_trajectory_log_prob(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                            double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
+                            const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, double* log_prob, int32_t B,
+                            void* stream) {
+    return trajectory_log_prob_entry("mpk_trajectory_log_prob", hh, params, params_L, init_pos, init_vel, init_time_shared, obs_steps, M,
+                                     obs_pos, obs_pos_std, obs_vel, obs_vel_std, false, log_prob, nullptr, nullptr, nullptr, B, stream);
+}
+
+int mpk_trajectory_log_prob_vjp(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                                double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
+                                const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, const double* g, float* g_params,
+                                float* g_params_L, int32_t B, void* stream) {
+    return trajectory_log_prob_entry("mpk_trajectory_log_prob_vjp", hh, params, params_L, init_pos, init_vel, init_time_shared, obs_steps,
+                                     M, obs_pos, obs_pos_std, obs_vel, obs_vel_std, true, nullptr, g, g_params, g_params_L, B, stream);
+}
+
 int mpk_trajectory_actions(mpk_handle hh, const float* params, const float* init_pos, const float* init_vel,
                            double init_time_shared, const mpk_rollout_cfg* rc, const double* c_pos,
                            const double* c_vel, float* pos, float* vel, float* actions, int32_t B, void* stream) {

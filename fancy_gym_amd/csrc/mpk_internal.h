@@ -329,6 +329,28 @@ struct CondLaunch {
 };
 int traj_cond_limits(const DevCfg& c, int M, size_t* lds_out, int* waves_out, int* wave_doubles_out);
 int launch_traj_condition(const DevCfg& c, const SharedTables& st, const CondLaunch& q, int num_cu, void* stream, const char** kernel_name);
+// mpk_trajectory_log_prob / _vjp (mpk_traj_log_prob.hip): the log-likelihood of conditioning's scalar observations under N(params, L L^T)
+// by a dense float64 Cholesky factorisation of their n x n covariance, and its gradient w.r.t. params and params_L -- one launch of
+// k_traj_log_prob each, one wave per episode, the gradient launch recomputing everything from the inputs.  steps: HOST, validated by the
+// caller; either observation pair may be nullptr.  grad = false: log_prob [B] is written; grad = true: g [B] is read and g_params /
+// g_params_L (either may be nullptr) are written.  traj_log_prob_limits: MPK_OK, or MPK_ENOTIMPL with the reason in the message -- a DMP,
+// more than kMaxD DoF or kMaxKP columns, more than MPK_LOGPROB_MAX_OBS candidate observations (M D narr, narr the observation arrays
+// given), float64 images that exceed the LDS with one wave per workgroup (no HIP call; the outputs may be nullptr).
+struct LogProbLaunch {
+    const float *params = nullptr, *params_L = nullptr, *init_pos = nullptr, *init_vel = nullptr;
+    const int32_t* steps = nullptr;                                     // HOST [M]
+    int M = 0;
+    float init_time = 0.f;                                              // the tables' (init_time_shared)
+    const float *obs_pos = nullptr, *obs_pos_std = nullptr, *obs_vel = nullptr, *obs_vel_std = nullptr;   // [B, M, D]
+    bool grad = false;
+    double* log_prob = nullptr;                                         // [B]
+    const double* g = nullptr;                                          // [B]
+    float *g_params = nullptr, *g_params_L = nullptr;
+    int B = 0;
+};
+int traj_log_prob_limits(const DevCfg& c, int M, int narr, size_t* lds_out, int* waves_out, int* wave_doubles_out);
+int launch_traj_log_prob(const DevCfg& c, const SharedTables& st, const LogProbLaunch& q, int num_cu, void* stream,
+                         const char** kernel_name);
 int launch_episode_reset(const double* init_q, const double* init_qd, double* q, double* qd, float* cond_pos,
                          float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done, int B, int D,
                          void* stream);

@@ -1,6 +1,7 @@
 // k_traj_condition: a Gaussian over the MP parameters conditioned on observed trajectory points (mpk_trajectory_condition)
 #include "mpk_tile.h"
 #include "mpk_vjp_row.h"
+#include "mpk_cond_rows.h"
 
 namespace mpk {
 
@@ -66,41 +67,12 @@ struct CondArgs {
     int steps[kCondMaxObs];
 };
 
-// what lanes of the wave wrote to LDS is read by other lanes: a wave's LDS operations complete in issue order, so only the compiler has
-// to be kept from moving them across
-__device__ __forceinline__ void cond_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // (i, j) of the packed lower triangle's entry p = i (i + 1) / 2 + j, j <= i
 __device__ __forceinline__ void cond_unpack(int p, int* i_out, int* j_out) {
     int i = (int)((__builtin_sqrtf(8.0f * (float)p + 1.0f) - 1.0f) * 0.5f);
     while (i * (i + 1) / 2 > p) --i;
     while ((i + 1) * (i + 2) / 2 <= p) ++i;
     *i_out = i; *j_out = p - i * (i + 1) / 2;
-}
-
-// a ProMP's velocity row (column k < nb, step t) in float64: ws (phi_k(x_th) - phi_k(x_tl)) aux[t] with the forward's fp32 reciprocal
-// time step aux and k_build_shared's phase and normalised RBFs (direct exponentials: its recurrence only saves time)
-__device__ __forceinline__ double cond_promp_vel_row(const DevCfg& c, const float* aux, float init_time, int k, int t) {
-    const int th = t < c.T - 1 ? t + 1 : c.T - 1, tl = t < c.T - 1 ? t : c.T - 2;
-    const double* cen = c.tab;
-    const double* bw = c.tab + c.n_total;
-    double phi[2];
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        const double x = phase_f64(c, c.base_times[e ? tl : th] + init_time, c.tau, c.delay, ExpLiteral());
-        double sum = 0.0;
-        for (int i = 0; i < c.n_total; ++i) {
-            const double dx = x - cen[i];
-            sum += exp_nonpos(-(dx * dx * bw[i]) * 0.5);
-        }
-        const double dx = x - cen[c.zs + k];
-        const double ek = exp_nonpos(-(dx * dx * bw[c.zs + k]) * 0.5);
-        phi[e] = c.n_total > 1 ? div_pos(ek, sum) : 1.0;
-    }
-    return (phi[0] - phi[1]) * (double)c.ws * (double)aux[t];
 }
 
 // NS: rows per lane, ceil(Pl / 64)

@@ -123,6 +123,26 @@ class _TrajectoryPhaseFn(torch.autograd.Function):
         return (None, None, None, None) + tuple(g)
 
 
+class _TrajectoryLogProbFn(torch.autograd.Function):
+    """``TrajectoryEngine.trajectory_log_prob`` with a backward: forward = the mpk_trajectory_log_prob launch as without autograd,
+    backward = one mpk_trajectory_log_prob_vjp launch, which recomputes the factorisation from the forward's inputs (nothing of the
+    forward launch is kept but those); the observations and the initial conditions get no gradient"""
+
+    @staticmethod
+    def forward(ctx, engine, steps, inputs, init_time, params, params_L):
+        ctx.engine, ctx.steps, ctx.inputs, ctx.init_time = engine, steps, inputs, init_time
+        ctx.save_for_backward(params, params_L)
+        return engine._log_prob_launch(params, params_L, steps, inputs, init_time)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        params, params_L = ctx.saved_tensors
+        g_params, g_L = ctx.engine._log_prob_vjp_launch(g, params, params_L, ctx.steps, ctx.inputs, ctx.init_time,
+                                                        ctx.needs_input_grad[4:6])
+        return None, None, None, None, g_params, g_L
+
+
 class _ReacherRolloutFn(torch.autograd.Function):
     """``TrajectoryEngine.reacher_rollout`` with a backward: forward = a copy of the plan-start (q, qd) and the mpk_reacher_rollout launch
     as without autograd, backward = one mpk_reacher_rollout_vjp launch; the actions and the in-place q, qd carry no graph"""
@@ -782,35 +802,9 @@ class TrajectoryEngine:
         observation at all, values without standard deviations, bad steps, ``init_pos=None`` on a ProDMP; NotImplementedError for a
         handle that learns tau / delay, a DMP, more than 16 DoF or 16 table columns, and a Pl whose float64 triangle exceeds a CU's LDS.
         """
-        if self.config.learn_tau or self.config.learn_delay:
-            raise NotImplementedError("condition: a learned tau / delay gives every episode its own phase; only shared-phase handles "
-                                      "have a conditioning kernel")
-        if self.mp_type == "dmp":
-            raise NotImplementedError("condition: a DMP has no probabilistic interface (promp / prodmp only)")
-        D, T, P = self.num_dof, self.num_steps, self.num_params
-        if D > 16:
-            raise NotImplementedError(f"condition: at most 16 DoF and 16 table columns (this handle: {D} DoF)")
-        pshape = tuple(params.shape) if hasattr(params, "shape") else np.shape(params)
-        if len(pshape) != 2 or pshape[0] < 1 or pshape[1] != P:
-            raise ValueError(f"condition: params must be [B, {P}], got {pshape}")
-        B = pshape[0]
-        lshape = tuple(params_L.shape) if hasattr(params_L, "shape") else np.shape(params_L)
-        if lshape != (B, P, P):
-            raise ValueError(f"condition: params_L must be [{B}, {P}, {P}] (the factor of the {P} non-phase parameters' covariance), "
-                             f"got {lshape}")
-        steps = np.asarray(list(obs_steps))
-        if steps.ndim != 1 or (steps.size and not np.issubdtype(steps.dtype, np.integer)):
-            raise ValueError(f"condition: obs_steps must be a sequence of ints, got {obs_steps!r}")
-        steps = np.ascontiguousarray(steps, dtype=np.int32)
-        M = int(steps.size)
-        if obs_pos is None and obs_vel is None:
-            raise ValueError("condition: obs_pos and obs_vel are both None: nothing is observed")
-        for val, sd, names in ((obs_pos, obs_std, ("obs_pos", "obs_std")), (obs_vel, obs_vel_std, ("obs_vel", "obs_vel_std"))):
-            if (val is None) != (sd is None):
-                raise ValueError(f"condition: {names[0]} and {names[1]} come in pairs (observed values with their standard deviations)")
-        if (init_pos is None or init_vel is None) and self.mp_type != "promp":
-            raise ValueError(f"condition: init_pos / init_vel may be None only for a ProMP, which ignores them; a {self.mp_type} "
-                             "starts from them")
+        B, steps = self._obs_checks("condition", "a conditioning kernel", params, params_L, obs_steps, obs_pos, obs_std, init_pos,
+                                    init_vel, obs_vel, obs_vel_std)
+        D, P, M = self.num_dof, self.num_params, int(steps.size)
         if out is not None:
             if len(out) != 2:
                 raise ValueError("condition: out must be a pair (params, params_L) of tensors")
@@ -820,13 +814,7 @@ class TrajectoryEngine:
                     raise ValueError(f"condition: out[{i}] must be a contiguous float32 tensor of shape {shape} on {self.device}")
 
         def bcast(x, name):
-            t = torch.as_tensor(x, dtype=torch.float32, device=self.device).detach()
-            if t.dim() == 1 and t.shape[0] == M:                    # [M]: one value per step
-                t = t[:, None]
-            try:
-                return t.expand((B, M, D)).contiguous()
-            except RuntimeError:
-                raise ValueError(f"condition: {name} does not broadcast to [{B}, {M}, {D}], got {tuple(t.shape)}") from None
+            return self._obs_bcast("condition", x, name, B, M)
         with torch.no_grad():
             mean = torch.as_tensor(params, dtype=torch.float32, device=self.device).detach().contiguous()
             L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
@@ -846,6 +834,156 @@ class TrajectoryEngine:
                 steps.ctypes.data_as(C.POINTER(C.c_int32)), M, _dptr(yp), _dptr(sp), _dptr(yv), _dptr(sv), mean_out.data_ptr(),
                 L_out.data_ptr(), B, self._stream()))
         return mean_out, L_out
+
+    def _obs_checks(self, fn, kernel, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std):
+        """the refusals ``condition`` and ``trajectory_log_prob`` / ``_vjp`` share, all before anything touches the device (what only
+        the library can judge -- the steps' range and order -- is refused by the launch's own checks, still before any launch);
+        returns (B, steps int32 [M])"""
+        if self.config.learn_tau or self.config.learn_delay:
+            raise NotImplementedError(f"{fn}: a learned tau / delay gives every episode its own phase; only shared-phase handles have "
+                                      f"{kernel}")
+        if self.mp_type == "dmp":
+            raise NotImplementedError(f"{fn}: a DMP has no probabilistic interface (promp / prodmp only)")
+        D, P = self.num_dof, self.num_params
+        if D > 16:
+            raise NotImplementedError(f"{fn}: at most 16 DoF and 16 table columns (this handle: {D} DoF)")
+        pshape = tuple(params.shape) if hasattr(params, "shape") else np.shape(params)
+        if len(pshape) != 2 or pshape[0] < 1 or pshape[1] != P:
+            raise ValueError(f"{fn}: params must be [B, {P}], got {pshape}")
+        B = pshape[0]
+        lshape = tuple(params_L.shape) if hasattr(params_L, "shape") else np.shape(params_L)
+        if lshape != (B, P, P):
+            raise ValueError(f"{fn}: params_L must be [{B}, {P}, {P}] (the factor of the {P} non-phase parameters' covariance), "
+                             f"got {lshape}")
+        steps = np.asarray(list(obs_steps))
+        if steps.ndim != 1 or (steps.size and not np.issubdtype(steps.dtype, np.integer)):
+            raise ValueError(f"{fn}: obs_steps must be a sequence of ints, got {obs_steps!r}")
+        steps = np.ascontiguousarray(steps, dtype=np.int32)
+        if obs_pos is None and obs_vel is None:
+            raise ValueError(f"{fn}: obs_pos and obs_vel are both None: nothing is observed")
+        for val, sd, names in ((obs_pos, obs_std, ("obs_pos", "obs_std")), (obs_vel, obs_vel_std, ("obs_vel", "obs_vel_std"))):
+            if (val is None) != (sd is None):
+                raise ValueError(f"{fn}: {names[0]} and {names[1]} come in pairs (observed values with their standard deviations)")
+        if (init_pos is None or init_vel is None) and self.mp_type != "promp":
+            raise ValueError(f"{fn}: init_pos / init_vel may be None only for a ProMP, which ignores them; a {self.mp_type} starts from "
+                             "them")
+        return B, steps
+
+    def _log_prob_checks(self, fn, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std):
+        """the refusals of ``trajectory_log_prob`` / ``trajectory_log_prob_vjp`` -- ``condition``'s, plus the steps (here, so that no
+        refusal needs the handle), the observation count and the inputs that have no gradient; returns (B, steps int32 [M])"""
+        B, steps = self._obs_checks(fn, "a likelihood kernel", params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, obs_vel,
+                                    obs_vel_std)
+        D = self.num_dof
+        if not 1 <= steps.size <= 32:
+            raise ValueError(f"{fn}: M must be 1..32 observed steps, got {steps.size}")
+        if steps[0] < 0 or steps[-1] >= self.num_steps or (np.diff(steps) <= 0).any():
+            raise ValueError(f"{fn}: obs_steps must be strictly increasing step indices in [0, {self.num_steps}), got "
+                             f"{steps.tolist()}")
+        n_obs = int(steps.size) * D * ((obs_pos is not None) + (obs_vel is not None))
+        if n_obs > _lib.MPK_LOGPROB_MAX_OBS:
+            raise NotImplementedError(f"{fn}: at most {_lib.MPK_LOGPROB_MAX_OBS} scalar observations per episode (steps x DoF x the "
+                                      f"observation arrays given = {n_obs}); the whole-trajectory likelihood has no kernel here")
+        if torch.is_grad_enabled():
+            for name, t in (("init_pos", init_pos), ("init_vel", init_vel), ("obs_pos", obs_pos), ("obs_std", obs_std),
+                            ("obs_vel", obs_vel), ("obs_vel_std", obs_vel_std)):
+                if isinstance(t, torch.Tensor) and t.requires_grad:
+                    raise NotImplementedError(f"{fn}: {name} requires grad, but the likelihood has a gradient w.r.t. params and params_L "
+                                              "only; detach it")
+        return B, steps
+
+    def _obs_bcast(self, fn, x, name, B, M):
+        """observed values or standard deviations -- a scalar, [M], [M, D] or [B, M, D] -- as a contiguous float32 [B, M, D] on the device"""
+        t = torch.as_tensor(x, dtype=torch.float32, device=self.device).detach()
+        if t.dim() == 1 and t.shape[0] == M:                        # [M]: one value per step
+            t = t[:, None]
+        try:
+            return t.expand((B, M, self.num_dof)).contiguous()
+        except RuntimeError:
+            raise ValueError(f"{fn}: {name} does not broadcast to [{B}, {M}, {self.num_dof}], got {tuple(t.shape)}") from None
+
+    def _log_prob_inputs(self, fn, B, M, obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std):
+        """(init_pos, init_vel, obs_pos, obs_std, obs_vel, obs_vel_std) as contiguous float32 device tensors or None, the standard
+        deviations broadcast to [B, M, D] as ``condition`` broadcasts them"""
+        D = self.num_dof
+
+        def bcast(x, name):
+            return self._obs_bcast(fn, x, name, B, M)
+        with torch.no_grad():
+            return (None if init_pos is None else self._f32(init_pos, (B, D)).detach(),
+                    None if init_vel is None else self._f32(init_vel, (B, D)).detach(),
+                    None if obs_pos is None else bcast(obs_pos, "obs_pos"), None if obs_pos is None else bcast(obs_std, "obs_std"),
+                    None if obs_vel is None else bcast(obs_vel, "obs_vel"),
+                    None if obs_vel is None else bcast(obs_vel_std, "obs_vel_std"))
+
+    def _log_prob_launch(self, mean, L, steps, inputs, init_time):
+        ip, iv, yp, sp, yv, sv = inputs
+        out = torch.empty((mean.shape[0],), dtype=torch.float64, device=self.device)
+        _lib.check(self._lib.mpk_trajectory_log_prob(
+            self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time), steps.ctypes.data_as(C.POINTER(C.c_int32)),
+            int(steps.size), _dptr(yp), _dptr(sp), _dptr(yv), _dptr(sv), out.data_ptr(), mean.shape[0], self._stream()))
+        return out
+
+    def _log_prob_vjp_launch(self, g, mean, L, steps, inputs, init_time, need):
+        ip, iv, yp, sp, yv, sv = inputs
+        B, P = mean.shape
+        g = torch.as_tensor(g, dtype=torch.float64, device=self.device).detach()
+        if tuple(g.shape) != (B,):
+            raise ValueError(f"trajectory_log_prob_vjp: g must be [{B}], got {tuple(g.shape)}")
+        g = g.contiguous()
+        g_mean = torch.empty((B, P), dtype=torch.float32, device=self.device) if need[0] else None
+        g_L = torch.empty((B, P, P), dtype=torch.float32, device=self.device) if need[1] else None
+        if g_mean is None and g_L is None:
+            return None, None
+        _lib.check(self._lib.mpk_trajectory_log_prob_vjp(
+            self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time), steps.ctypes.data_as(C.POINTER(C.c_int32)),
+            int(steps.size), _dptr(yp), _dptr(sp), _dptr(yv), _dptr(sv), g.data_ptr(), _dptr(g_mean), _dptr(g_L), B, self._stream()))
+        return g_mean, g_L
+
+    def trajectory_log_prob(self, params, params_L, obs_steps, obs_pos=None, obs_std=None, init_pos=None, init_vel=None,
+                            init_time: float = 0.0, *, obs_vel=None, obs_vel_std=None) -> torch.Tensor:
+        """
+        The log-likelihood of observed trajectory points under the Gaussian ``N(params, L L^T)`` over the parameters (mpk.h:
+        mpk_trajectory_log_prob), one launch: [B] float64 on the device.  The observations are ``condition``'s, argument by argument:
+        ``obs_steps`` a host sequence of strictly increasing step indices shared by the batch, ``obs_pos`` / ``obs_vel`` [B, M, D] with
+        ``obs_std`` / ``obs_vel_std`` (a scalar, [M], [M, D] or [B, M, D]); a standard deviation of ``+inf``, NaN or a negative one
+        removes that (episode, step, DoF).  With the n that remain, ``log N(y; H mu + c, A A^T + diag(sigma^2))``, ``A = H tril(L)``, by
+        a dense float64 Cholesky factorisation of the n x n covariance: n = 0 gives exactly 0.0, a singular covariance gives NaN for that
+        episode alone.  At most 64 scalar observations per episode (steps x DoF x arrays given).  When ``params`` or ``params_L``
+        requires grad the result carries the autograd graph: its backward is ONE mpk_trajectory_log_prob_vjp launch, which recomputes
+        the factorisation from the inputs; a mean or factor expanded from one shared row gets the sum over the batch through torch as
+        usual.  There is no gradient w.r.t. ``init_pos``, ``init_vel`` or the observations: a tensor among them that requires grad is
+        a NotImplementedError, not a silent cut.  ``params_L``'s strict upper triangle is never read.  Refusals are ``condition``'s,
+        raised before any launch, plus NotImplementedError for more than 64 observations.
+        """
+        B, steps = self._log_prob_checks("trajectory_log_prob", params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel,
+                                         obs_vel, obs_vel_std)
+        inputs = self._log_prob_inputs("trajectory_log_prob", B, int(steps.size), obs_pos, obs_std, init_pos, init_vel, obs_vel,
+                                       obs_vel_std)
+        mean = torch.as_tensor(params, dtype=torch.float32, device=self.device)
+        L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device)
+        if torch.is_grad_enabled() and (mean.requires_grad or L.requires_grad):
+            return _TrajectoryLogProbFn.apply(self, steps, inputs, float(init_time), mean.contiguous(), L.contiguous())
+        return self._log_prob_launch(mean.detach().contiguous(), L.detach().contiguous(), steps, inputs, init_time)
+
+    def trajectory_log_prob_vjp(self, g, params, params_L, obs_steps, obs_pos=None, obs_std=None, init_pos=None, init_vel=None,
+                                init_time: float = 0.0, *, obs_vel=None, obs_vel_std=None,
+                                need: Sequence[bool] = (True, True)) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """
+        The vector-Jacobian product of ``trajectory_log_prob`` (mpk.h: mpk_trajectory_log_prob_vjp), one launch: ``g`` [B] float64, the
+        gradient of a loss w.r.t. the log-likelihoods -> ``(g_params [B, P], g_params_L [B, Pl, Pl])`` float32 on the device, without
+        an autograd graph.  The other arguments are ``trajectory_log_prob``'s.  ``g_params_L``'s strict upper triangle is exact zeros,
+        and so are the rows of a DoF none of whose observations remain; an episode whose covariance is singular gets NaN rows.
+        ``need[i]`` False: that output is not computed (None in its place).
+        """
+        B, steps = self._log_prob_checks("trajectory_log_prob_vjp", params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel,
+                                         obs_vel, obs_vel_std)
+        inputs = self._log_prob_inputs("trajectory_log_prob_vjp", B, int(steps.size), obs_pos, obs_std, init_pos, init_vel, obs_vel,
+                                       obs_vel_std)
+        with torch.no_grad():
+            mean = torch.as_tensor(params, dtype=torch.float32, device=self.device).detach().contiguous()
+            L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
+            return self._log_prob_vjp_launch(g, mean, L, steps, inputs, init_time, need)
 
     def sample_trajectories(self, params, params_L, init_pos, init_vel, init_time: float = 0.0, *, num_samples: int,
                             generator: Optional[torch.Generator] = None) -> Tuple[torch.Tensor, torch.Tensor]:

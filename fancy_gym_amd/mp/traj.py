@@ -301,6 +301,59 @@ class MPInterface:
             self._compute_std()
         return self._vel_std
 
+    def _observations_on_grid(self, fn, times, pos, std, vel, vel_std):
+        """what ``condition_on_observations`` and ``log_prob_of_observations`` hand to the engine: the observation times mapped to steps
+        of the current grid (ascending; a time that is no step, or two at one step: ValueError), the rows reordered with them and
+        broadcast to [1, M, D], and the stored initial conditions: (steps, pos, std, vel, vel_std, init_pos, init_vel, init_time)"""
+        from .._lib import load as _lib_load
+
+        def to_np(x):
+            return x.detach().cpu().numpy().astype(np.float32) if isinstance(x, torch.Tensor) else np.asarray(x, np.float32)
+        times = np.atleast_1d(to_np(times))
+        if times.ndim != 1 or times.size < 1:
+            raise ValueError(f"{fn}: times must be [M] with M >= 1, got {times.shape}")
+        M, D = times.size, self.num_dof
+        lib = _lib_load()
+        T = lib.mpk_host_times(float(self.duration), float(self.dt), None, 0)
+        grid = np.empty(T, np.float32)
+        lib.mpk_host_times(float(self.duration), float(self.dt), grid.ctypes.data, T)
+        it = np.float32(self.init_time if self.init_time is not None else 0.0)
+        grid = grid + it
+        steps = np.abs(grid[None, :] - times[:, None]).argmin(axis=1)
+        off = np.abs(grid[steps] - times)
+        if not (off <= 1e-3 * float(self.dt)).all():
+            bad = int(np.argmax(off))
+            raise ValueError(f"{fn}: time {float(times[bad])} is no step of the grid (init_time {float(it)} + "
+                             f"linspace(0, {self.duration}, {T + 1})[1:]; the nearest step is {float(grid[steps[bad]])})")
+        order = np.argsort(steps, kind="stable")
+        steps = steps[order]
+        if (np.diff(steps) == 0).any():
+            raise ValueError(f"{fn}: two observations at the same time; give each step once")
+
+        def rows(x, name, full):
+            if x is None:
+                return None
+            x = to_np(x)
+            if full and x.shape != (M, D):
+                raise ValueError(f"{fn}: {name} must be [{M}, {D}], got {x.shape}")
+            if x.ndim == 1 and x.shape[0] == M:
+                x = x[:, None]
+            try:
+                x = np.broadcast_to(x, (M, D))
+            except ValueError:
+                raise ValueError(f"{fn}: {name} does not broadcast to [{M}, {D}], got {x.shape}") from None
+            return np.ascontiguousarray(x[order])[None]
+        if pos is None and vel is None:
+            raise ValueError(f"{fn}: pos and vel are both None: nothing is observed")
+        if (pos is None) != (std is None) or (vel is None) != (vel_std is None):
+            raise ValueError(f"{fn}: observed values and their standard deviations come in pairs (pos with std, "
+                             "vel with vel_std)")
+        yp, sp = rows(pos, "pos", True), rows(std, "std", False)
+        yv, sv = rows(vel, "vel", True), rows(vel_std, "vel_std", False)
+        ip = self.init_pos if self.init_pos is not None else np.zeros(D, np.float32)
+        iv = self.init_vel if self.init_vel is not None else np.zeros(D, np.float32)
+        return [int(s) for s in steps], yp, sp, yv, sv, ip[None], iv[None], float(it)
+
     def condition_on_observations(self, times, pos, std, vel=None, vel_std=None):
         """
         Condition the stored Gaussian ``N(params, L L^T)`` on observed points (``TrajectoryEngine.condition``: the ProMP operation,
@@ -321,59 +374,35 @@ class MPInterface:
         if self.learn_tau or self.learn_delay:
             raise NotImplementedError("condition_on_observations: this generator learns tau / delay, so the grid's phase is not shared; "
                                       "only shared-phase generators have a conditioning kernel")
-        from .._lib import load as _lib_load
-
-        def to_np(x):
-            return x.detach().cpu().numpy().astype(np.float32) if isinstance(x, torch.Tensor) else np.asarray(x, np.float32)
-        times = np.atleast_1d(to_np(times))
-        if times.ndim != 1 or times.size < 1:
-            raise ValueError(f"condition_on_observations: times must be [M] with M >= 1, got {times.shape}")
-        M, D = times.size, self.num_dof
-        lib = _lib_load()
-        T = lib.mpk_host_times(float(self.duration), float(self.dt), None, 0)
-        grid = np.empty(T, np.float32)
-        lib.mpk_host_times(float(self.duration), float(self.dt), grid.ctypes.data, T)
-        it = np.float32(self.init_time if self.init_time is not None else 0.0)
-        grid = grid + it
-        steps = np.abs(grid[None, :] - times[:, None]).argmin(axis=1)
-        off = np.abs(grid[steps] - times)
-        if not (off <= 1e-3 * float(self.dt)).all():
-            bad = int(np.argmax(off))
-            raise ValueError(f"condition_on_observations: time {float(times[bad])} is no step of the grid (init_time {float(it)} + "
-                             f"linspace(0, {self.duration}, {T + 1})[1:]; the nearest step is {float(grid[steps[bad]])})")
-        order = np.argsort(steps, kind="stable")
-        steps = steps[order]
-        if (np.diff(steps) == 0).any():
-            raise ValueError("condition_on_observations: two observations at the same time; give each step once")
-
-        def rows(x, name, full):
-            if x is None:
-                return None
-            x = to_np(x)
-            if full and x.shape != (M, D):
-                raise ValueError(f"condition_on_observations: {name} must be [{M}, {D}], got {x.shape}")
-            if x.ndim == 1 and x.shape[0] == M:
-                x = x[:, None]
-            try:
-                x = np.broadcast_to(x, (M, D))
-            except ValueError:
-                raise ValueError(f"condition_on_observations: {name} does not broadcast to [{M}, {D}], got {x.shape}") from None
-            return np.ascontiguousarray(x[order])[None]
-        if pos is None and vel is None:
-            raise ValueError("condition_on_observations: pos and vel are both None: nothing is observed")
-        if (pos is None) != (std is None) or (vel is None) != (vel_std is None):
-            raise ValueError("condition_on_observations: observed values and their standard deviations come in pairs (pos with std, "
-                             "vel with vel_std)")
-        yp, sp = rows(pos, "pos", True), rows(std, "std", False)
-        yv, sv = rows(vel, "vel", True), rows(vel_std, "vel_std", False)
-        ip = self.init_pos if self.init_pos is not None else np.zeros(D, np.float32)
-        iv = self.init_vel if self.init_vel is not None else np.zeros(D, np.float32)
-        mean, L = self.engine().condition(self.params.reshape(1, -1), self.params_L[None], [int(s) for s in steps], yp, sp, ip[None],
-                                          iv[None], float(it), obs_vel=yv, obs_vel_std=sv)
+        steps, yp, sp, yv, sv, ip, iv, it = self._observations_on_grid("condition_on_observations", times, pos, std, vel, vel_std)
+        mean, L = self.engine().condition(self.params.reshape(1, -1), self.params_L[None], steps, yp, sp, ip, iv, it, obs_vel=yv,
+                                          obs_vel_std=sv)
         self.params = np.ascontiguousarray(mean[0].cpu().numpy().reshape(self.params.shape))
         self.params_L = np.ascontiguousarray(L[0].cpu().numpy())
         self._clear()
         return self.params, self.params_L
+
+    def log_prob_of_observations(self, times, pos, std, vel=None, vel_std=None) -> float:
+        """
+        The log-likelihood of observed points under the stored Gaussian ``N(params, L L^T)`` plus observation noise
+        (``TrajectoryEngine.trajectory_log_prob``, one launch), a float.  The arguments are ``condition_on_observations``'s, with its
+        mapping of times to steps of the current grid; nothing stored changes.  At most 64 scalar observations (times x DoF, twice
+        that with velocities).  Needs ``set_params`` and ``set_mp_params_variances`` first.
+        """
+        if self.mp_type == "dmp":
+            raise NotImplementedError("a DMP has no probabilistic interface (ProMP / ProDMP only)")
+        assert self.params is not None, "set_params() first"
+        if self.params_L is None:
+            raise RuntimeError("set_mp_params_variances(params_L) first")
+        if self.duration is None or self.dt is None:
+            raise RuntimeError("set_duration(duration, dt) must be called before observations can be placed on its grid")
+        if self.learn_tau or self.learn_delay:
+            raise NotImplementedError("log_prob_of_observations: this generator learns tau / delay, so the grid's phase is not shared; "
+                                      "only shared-phase generators have a likelihood kernel")
+        steps, yp, sp, yv, sv, ip, iv, it = self._observations_on_grid("log_prob_of_observations", times, pos, std, vel, vel_std)
+        lp = self.engine().trajectory_log_prob(self.params.reshape(1, -1), self.params_L[None], steps, yp, sp, ip, iv, it, obs_vel=yv,
+                                               obs_vel_std=sv)
+        return float(lp[0])
 
     def sample_trajectories(self, num_smp: int = 1, generator: Optional[torch.Generator] = None):
         """``(pos, vel)`` [num_smp, T, D]: trajectories of parameters drawn from ``N(params, L L^T)``

@@ -1063,6 +1063,60 @@ int mpk_trajectory_condition(mpk_handle h, const float* params, const float* par
                              float* params_L_out, int32_t B, void* stream);
 
 /*
+ * The log-likelihood of observed trajectory points under a Gaussian over the MP parameters, and its gradient, for a handle with a SHARED
+ * phase (added within ABI 4; no existing prototype changes) -- what a maximum-likelihood fit of a ProMP, the recognition of a movement
+ * and the likelihood objectives of episodic RL with mp_pytorch (the trajectory distribution at a few selected steps scored under a
+ * policy's loc / scale_tril; written from recollection, unpinned like the rest of the MP arithmetic) need.  params, params_L, init_pos,
+ * init_vel, obs_steps, M and the four observation arrays are mpk_trajectory_condition's, with its conventions, and so are the scalar
+ * observations (o, m, d): the same h, c and sigma, the same order (m ascending; within a step the positions, d ascending, then the
+ * velocities, d ascending), the same rule that a standard deviation of +inf, NaN or a negative one removes that observation.  With the n
+ * observations that remain:
+ *     A = H tril(L)            [n, Pl]   (row i = L^T h_i; zero from column (d_i + 1) Kloc on)
+ *     S = A A^T + diag(sigma^2)  [n, n]
+ *     r = y - c - H mu
+ *     log_prob = -1/2 r^T S^-1 r - 1/2 log det S - (n / 2) log 2 pi
+ * S is formed as A A^T, never through L L^T; S, its Cholesky factor C, the solves and the logarithm are float64, and log_prob leaves as
+ * float64.  This is a DENSE factorisation of the n x n observation covariance, another algorithm than conditioning's sequential update.
+ * n = 0 (everything skipped) gives exactly 0.0.  A Cholesky pivot that is not > 0 -- S singular: sigma = 0 on a direction the prior
+ * gives no variance, or n > Pl at sigma = 0 -- makes that episode's log_prob NaN, and in the gradient launch every entry of its g_params
+ * row and of the lower triangle of its g_params_L; no other episode changes, and no status word reports it: a NaN row reports itself.
+ *   log_prob    dev double [B]          out
+ * mpk_trajectory_log_prob_vjp: for an upstream gradient g [B] of a loss w.r.t. log_prob,
+ *     alpha = S^-1 r
+ *     g_params[off + .] = g H^T alpha
+ *     g_params_L        = g tril(H^T (alpha alpha^T - S^-1) A)
+ * accumulated in float64 and rounded to float32 once.  H has at most Kloc non-zeros per row, so H^T (.) fills the rows d Kloc + loc(k);
+ * the rows of a DoF none of whose observations remain are exact zeros, and so is everything of an episode with n = 0.  The strict upper
+ * triangle of g_params_L is written as exact zeros; the strict upper triangle of params_L is never read.  There is no gradient w.r.t. the
+ * observations, their standard deviations or init_pos / init_vel.
+ *   g           dev double [B]
+ *   g_params    dev float [B, P]        out, or NULL (not computed); entries outside the local block are 0
+ *   g_params_L  dev float [B, Pl, Pl]   out, or NULL (not computed); not both NULL
+ * The gradient launch recomputes A, S and C from the inputs, as mpk_episode_return_vjp recomputes its plan: nothing is kept between the
+ * two launches.  Each entry is one launch of k_traj_log_prob<promp | prodmp> (the gradient: k_traj_log_prob<promp | prodmp, grad>;
+ * mpk_last_kernel) on `stream`, plus the table builder when (init_time_shared, T) is not cached; nothing is allocated or synchronised.
+ * One wave per episode, no atomics, an episode never leaves its wave: the same bits from run to run, for any alignment of the pointers,
+ * alone or in a batch; no index depends on a value that is read, so non-finite inputs never fault.
+ * MPK_EINVAL: as mpk_trajectory_condition (a NULL handle, params, params_L, log_prob or g, or both gradient outputs; B < 1; M outside
+ * 1..MPK_COND_MAX_STEPS; steps not strictly increasing or outside [0, T); no observation array at all; a value array without its
+ * standard deviations or the reverse; obs_vel for a ProMP with a single time step; init_pos / init_vel NULL for a ProDMP).
+ * MPK_ENOTIMPL, before any launch: a handle that learns tau / delay; a DMP; more than 16 DoF or 16 table columns; more candidate
+ * observations than a wave has lanes, nmax = M * D * (the observation arrays given: 1 or 2) > MPK_LOGPROB_MAX_OBS; float64 images that
+ * exceed a CU's LDS with one wave per workgroup -- 8 (nmax (Pl | 1) + nmax (nmax + 1) / 2 + 3 nmax) + 16 M KT + 64 bytes <= 163 840:
+ * Pl = 160 with 64 observations runs (100 608 + 16 M KT + 64 bytes).  The whole-trajectory likelihood, n >> Pl, wants the Pl x Pl form
+ * (the Cholesky factor of I + A^T R^-1 A) and is a different kernel: not built.
+ */
+#define MPK_LOGPROB_MAX_OBS 64
+int mpk_trajectory_log_prob(mpk_handle h, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                            double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
+                            const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, double* log_prob, int32_t B,
+                            void* stream);
+int mpk_trajectory_log_prob_vjp(mpk_handle h, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                                double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
+                                const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, const double* g, float* g_params,
+                                float* g_params_L, int32_t B, void* stream);
+
+/*
  * The vector-Jacobian product of mpk_reacher_rollout (appended under ABI 4): controller, clip, torque double integrator and
  * SimpleReacher's reward transposed -- the gradient of any scalar loss of the step rewards and the final state w.r.t. the desired
  * trajectory, the plan-start state and the goal, one launch.  The forward it transposes (mpk_reacher_rollout above), per executed step
