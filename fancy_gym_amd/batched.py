@@ -630,6 +630,14 @@ class BatchedBlackBox:
         return self.engine.trajectory_log_prob(params, params_L, obs_steps, obs_pos, obs_std, cond_pos.detach(), cond_vel.detach(),
                                                self._plan_time(), obs_vel=obs_vel, obs_vel_std=obs_vel_std)
 
+    def demonstration_log_prob(self, params, params_L, pos, obs_std):
+        """the log-likelihood [B] float64 of whole demonstrations ``pos`` [B, T, D] of the plan under the Gaussian ``N(params, L L^T)``
+        (``TrajectoryEngine.demonstration_log_prob``, one launch; differentiable w.r.t. ``params`` and ``params_L``) from the
+        init_time / init_pos / init_vel ``get_trajectory`` would use now, as ``trajectory_log_prob`` takes them"""
+        cond_pos = self.condition_pos if self.condition_pos is not None else self.q.float()
+        cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
+        return self.engine.demonstration_log_prob(params, params_L, pos, obs_std, cond_pos.detach(), cond_vel.detach(), self._plan_time())
+
     def _carry_start(self):
         """replan_gradient="episode": (init_pos, init_vel, q_in, qd_in) of the next plan -- what the twins of the plan before give (the
         same bits as ``_plan_condition`` and ``q``, ``qd``), or right after a cut the constants themselves"""

@@ -1,0 +1,552 @@
+// k_demo_log_prob: the log-likelihood of WHOLE demonstrations [B, T, D] under a Gaussian over the MP parameters, and its gradient
+// (mpk_demonstration_log_prob, mpk_demonstration_log_prob_vjp) -- the information (Pl x Pl) form, for n >> Pl
+#include "mpk_tile.h"
+#include "mpk_vjp_row.h"
+#include "mpk_cond_rows.h"
+
+namespace mpk {
+
+// ------------------------------------------------------------------------------------------------------------
+// Notation is mpk_traj_log_prob.hip's: w ~ N(mu, L L^T) over the Pl = D Kloc non-phase parameters; the observation (t, d) reads
+// y = psi_t . w_d + c_td + eps, eps ~ N(0, sigma_td^2), psi_t the POSITION table row of step t on the parameter columns (the values
+// cond_obs_row<MP>(.., o = 0, k, t) gives k_traj_log_prob), c what init_pos / init_vel / the goal offset contribute.  An observation is
+// kept when 0 < sigma < +inf (+inf, NaN, negative: removed -- missing samples, prefixes).  With w = 1 / sigma^2 on kept entries and 0
+// elsewhere, n the number kept, r = y - c - psi . mu_d:
+//     G_d = sum_t w_td psi_t psi_t^T  [Kloc x Kloc]    q_d = sum_t w_td psi_t r_td    s = sum w r^2    lsig = sum over kept of log sigma^2
+//     M = I + tril(L)^T blockdiag(G_d) tril(L) = C C^T      v = tril(L)^T q      z = C^-1 v
+//     log_prob = -1/2 (s - z.z) - 1/2 (lsig + 2 sum log C_ii) - n / 2 log 2 pi
+// which is log N(y; H mu + c, A A^T + diag(sigma^2)), A = H tril(L), by the Woodbury identity and the determinant lemma: the n x n
+// covariance (700 x 700 for 7 DoF x 100 steps) is never formed, and neither is L L^T.  Gradients for an upstream g, with x = M^-1 v,
+// X = G tril(L), gm = q - X x (= H^T S^-1 r):
+//     g_params[off + .] = g gm        g_params_L = g tril(gm (tril(L)^T gm)^T - X M^-1)
+// k_demo_log_prob<MP, NS, GRAD>: one wave per episode, `waves` of them a workgroup (sized at launch from the LDS the images need), all
+// float64, NS = ceil(Pl / 64) rows or columns per lane.
+//   * The T position rows [T][KT] are staged once per workgroup (cond_obs_row, o = 0), and the table column of every local parameter
+//     (kof, the inverse of x_kind), as k_traj_log_prob stages them.
+//   * In chunks of tc steps: lane <-> (t, d), pos and obs_std read coalesced; w and r go to an LDS image [tc][D] each, s / lsig / n stay
+//     in the lane (summed over the wave by a fixed xor ladder at the end).  Then lane <-> packed entry (d, k >= l) of the Gram matrices and
+//     lane <-> row of q, each a chain over the chunk's steps in ascending t.
+//   * Per DoF d: the Kloc rows of tril(L)'s block d to a float32 LDS image (entries j <= row only: the strict upper triangle is never
+//     read); X_d = G_d tril(L)[rows of d] [Kloc][ld] with lane <-> column; v += that block's part of tril(L)^T q; the rank-Kloc update
+//     of the packed lower triangle of M, row by row with lane <-> column.  A DoF with nothing kept is skipped: G_d = 0, q_d = 0.
+//   * A left-looking Cholesky in place (lane <-> row), the forward substitution with z in registers, two xor-ladder sums.  GRAD = false
+//     ends here.
+//   * GRAD: back substitution -> x; tril(L) x row by row (lane <-> column, an xor-ladder sum per row); gm; u = tril(L)^T gm (lane <->
+//     column); then per DoF X_d again, its Kloc rows solved against C (forward, backward; lane <-> row of the system, the Kloc right-hand
+//     sides in the LDS image), and that DoF's rows of g_params_L leave: g (gm_row u_j - W[k][j]) for j <= row, exact 0 for j > row, exact
+//     0 for the rows of a DoF with nothing kept.  There is never a Pl x Pl image besides the packed C, so the backward fits wherever the
+//     forward does; nothing is kept from the forward launch.
+// n = 0: exactly 0.0 and zero gradients.  A sigma == 0 cannot be expressed in this form: the episode's log_prob, its g_params local block
+// and the lower triangle of its g_params_L are NaN (mpk_trajectory_log_prob takes exact observations); so is an episode with a pivot that is
+// not > 0 (non-finite input).  No atomics, an episode never leaves its wave, nothing depends on an address, and no index depends on a value
+// that is read: the same bits from run to run, for any alignment, alone or in a batch; non-finite inputs never fault.
+// LDS per wave: 8 (Pl (Pl + 1) / 2 + D Kloc^2 + 2 Pl + max(Kloc ld, 2 tc D)) + 4 Kloc ld + 64 bytes, ld = Pl | 1; per workgroup 8 T KT + 64.
+// ------------------------------------------------------------------------------------------------------------
+constexpr int kDemoSlots = 4;                                       // rows / columns per lane at most (NS = ceil(Pl / 64))
+
+struct DemoLogProbArgs {
+    DevCfg c;
+    const float* A;        // [n_out][KP][TS] (k_build_shared)
+    const float* aux;      // [TS]
+    int TS;
+    float init_time;       // the tables' (init_time_shared)
+    const float* params;   // [B, P]
+    const float* L;        // [B, Pl, Pl]; the lower triangle is read
+    const float* init_pos; // [B, D] or nullptr (promp: zeros)
+    const float* init_vel;
+    const float* pos;      // [B, T, D] the demonstrations
+    const float* sd;       // [B, T, D] their standard deviations
+    double* log_prob;      // [B] out (forward)
+    const double* g;       // [B] the upstream gradient (GRAD)
+    float* g_params;       // [B, P] out or nullptr (GRAD)
+    float* g_L;            // [B, Pl, Pl] out or nullptr (GRAD)
+    int B, Pl;
+    int ld;                // words between the rows of the X and L images (odd)
+    int tc;                // steps per chunk of the accumulation
+    int scratch;           // float64 words of the X image / the chunk's w and r images: max(Kloc ld, 2 tc D)
+    int waves;             // per workgroup
+    int wave_doubles;      // float64 words of LDS per wave
+};
+
+// the sum over the wave by a fixed xor ladder: the same bits in every lane
+__device__ __forceinline__ double demo_wave_sum(double x) {
+#pragma unroll
+    for (int sh = 32; sh >= 1; sh >>= 1) x += __shfl_xor(x, sh, 64);
+    return x;
+}
+
+// element j (wave-uniform) of a vector held as lane + 64 s: every lane gets it
+template <int NS>
+__device__ __forceinline__ double demo_bcast(const double (&x)[NS], int j) {
+    const int sj = j >> 6;
+    double v = x[0];
+#pragma unroll
+    for (int s = 1; s < NS; ++s) v = sj == s ? x[s] : v;
+    return __shfl(v, j & 63, 64);
+}
+
+// the rows of tril(L)'s block d as a float32 LDS image [Kloc][ld] (entries j <= row; exact 0 beyond), and X_d = G_d tril(L)[rows of d]
+// [Kloc][ld] in float64 (columns < (d + 1) Kloc; exact 0 beyond): lane <-> column
+template <int NS>
+__device__ __forceinline__ void demo_stage_block(const float* Lb, const double* Gd, float* sL, double* sX, int d, int Kloc, int Pl, int ld,
+                                                 int lane) {
+    for (int l = 0; l < Kloc; ++l) {
+        const int row = d * Kloc + l;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int j = lane + 64 * s;
+            if (j < Pl) sL[l * ld + j] = j <= row ? Lb[(size_t)row * Pl + j] : 0.0f;
+        }
+    }
+    cond_wave_sync();
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int j = lane + 64 * s;
+        if (j < Pl) {
+            for (int k = 0; k < Kloc; ++k) {
+                double acc = 0.0;
+                for (int l = 0; l < Kloc; ++l) acc = __builtin_fma(Gd[k * Kloc + l], (double)sL[l * ld + j], acc);
+                sX[k * ld + j] = acc;
+            }
+        }
+    }
+    cond_wave_sync();
+}
+
+template <int MP, int NS, bool GRAD>
+__global__ void __launch_bounds__(256) k_demo_log_prob(const DemoLogProbArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double demo_smem[];
+    const DevCfg& c = a.c;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = wave_of(tid);
+    const int D = c.D, Kloc = c.Kloc, Pl = a.Pl, T = c.T, KT = c.KT, ld = a.ld, tc = a.tc;
+    const int KK = Kloc * Kloc, Kt2 = Kloc * (Kloc + 1) / 2;
+    double* sC = demo_smem + (size_t)wave * a.wave_doubles;         // packed lower triangle: M, then its Cholesky factor C
+    double* sG = sC + Pl * (Pl + 1) / 2;                            // [D][Kloc][Kloc] the Gram matrices
+    double* sq = sG + D * KK;                                       // [Pl] q
+    double* sy = sq + Pl;                                           // [Pl] mu, then tril(L) x, then gm
+    double* sX = sy + Pl;                                           // [Kloc][ld] X_d, then X_d M^-1; the accumulation's w | r [tc][D]
+    float* sL = (float*)(sX + a.scratch);                           // [Kloc][ld] the rows of tril(L)'s block d
+    int* snd = (int*)(sL + ((Kloc * ld + 1) & ~1));                 // [D] kept observations per DoF
+    double* rows = demo_smem + (size_t)a.waves * a.wave_doubles;    // [T][KT]
+    int* kof = (int*)(rows + T * KT);                               // [Kloc] the table column read from local parameter l, or -1
+    for (int i = tid; i < T * KT; i += blockDim.x) {
+        const int t = i / KT, k = i - t * KT;
+        rows[i] = cond_obs_row<MP>(c, a.A, a.aux, a.TS, a.init_time, 0, k, t);
+    }
+    if (tid < Kloc) {
+        int found = -1;
+        for (int k = 0; k < KT; ++k) {
+            int loc;
+            if (x_kind<MP>(c, k, &loc) == XK_PARAM && loc == tid) found = k;
+        }
+        kof[tid] = found;
+    }
+    __syncthreads();
+    const double nan = __builtin_nan("");
+    for (int b = blockIdx.x * a.waves + wave; b < a.B; b += gridDim.x * a.waves) {
+        const float* Lb = a.L + (size_t)b * Pl * Pl;
+        for (int i = lane; i < D * KK; i += 64) sG[i] = 0.0;
+        for (int i = lane; i < Pl; i += 64) {
+            sq[i] = 0.0;
+            sy[i] = (double)a.params[(size_t)b * c.P + c.off + i];
+        }
+        if (lane < D) snd[lane] = 0;
+        cond_wave_sync();
+        // ---- w, r, then G, q over the steps, a chunk at a time
+        double s_l = 0.0, lsig_l = 0.0;
+        int n_l = 0;
+        bool zero_l = false;
+        double* sw = sX;
+        double* sr = sX + tc * D;
+        for (int t0 = 0; t0 < T; t0 += tc) {
+            const int nt = T - t0 < tc ? T - t0 : tc;
+            for (int e = lane; e < nt * D; e += 64) {               // lane <-> (t, d): coalesced
+                const int tt = e / D, d = e - tt * D;
+                const size_t at = ((size_t)b * T + t0) * D + e;
+                const double sig = (double)a.sd[at], yv = (double)a.pos[at];
+                const bool keep = sig > 0.0 && sig != __builtin_inf();   // +inf, NaN, negative: not observed
+                zero_l = zero_l || sig == 0.0;
+                const double* hr = rows + (t0 + tt) * KT;
+                double cc = 0.0, hmu = 0.0;
+                for (int k = 0; k < KT; ++k) {
+                    int loc;
+                    const int kind = x_kind<MP>(c, k, &loc);
+                    const double hk = hr[k];
+                    if (kind == XK_PARAM) {
+                        hmu = __builtin_fma(hk, sy[d * Kloc + loc], hmu);
+                    } else if (kind == XK_IPOS) {
+                        if (a.init_pos) cc = __builtin_fma(hk, (double)a.init_pos[(size_t)b * D + d], cc);
+                    } else if (kind == XK_IVEL) {
+                        if (a.init_vel) cc = __builtin_fma(hk, (double)a.init_vel[(size_t)b * D + d], cc);
+                    } else if (kind == XK_ONE) {
+                        cc += hk;
+                    }
+                }
+                const double r = keep ? yv - cc - hmu : 0.0;
+                const double w = keep ? 1.0 / (sig * sig) : 0.0;
+                sw[e] = w;
+                sr[e] = r;
+                if (keep) {
+                    s_l = __builtin_fma(w * r, r, s_l);
+                    lsig_l += log(sig * sig);
+                    ++n_l;
+                }
+            }
+            cond_wave_sync();
+            for (int e = lane; e < D * Kt2; e += 64) {              // lane <-> (d, k >= l)
+                const int d = e / Kt2, rem = e - d * Kt2;
+                int k = 0;
+                while ((k + 1) * (k + 2) / 2 <= rem) ++k;
+                const int l = rem - k * (k + 1) / 2;
+                const int ck = kof[k], cl = kof[l];
+                double acc = sG[d * KK + k * Kloc + l];
+                if (ck >= 0 && cl >= 0) {
+                    for (int tt = 0; tt < nt; ++tt) {
+                        const double* hr = rows + (t0 + tt) * KT;
+                        acc = __builtin_fma(sw[tt * D + d] * hr[ck], hr[cl], acc);
+                    }
+                }
+                sG[d * KK + k * Kloc + l] = acc;
+                sG[d * KK + l * Kloc + k] = acc;
+            }
+            for (int row = lane; row < Pl; row += 64) {             // lane <-> row of q
+                const int d = row / Kloc, ck = kof[row - d * Kloc];
+                double acc = sq[row];
+                if (ck >= 0) {
+                    for (int tt = 0; tt < nt; ++tt) acc = __builtin_fma(sw[tt * D + d] * sr[tt * D + d], rows[(t0 + tt) * KT + ck], acc);
+                }
+                sq[row] = acc;
+            }
+            if (lane < D) {
+                int cnt = snd[lane];
+                for (int tt = 0; tt < nt; ++tt) cnt += sw[tt * D + lane] > 0.0 ? 1 : 0;
+                snd[lane] = cnt;
+            }
+            cond_wave_sync();
+        }
+        const double ssum = demo_wave_sum(s_l), lsig = demo_wave_sum(lsig_l);
+        int n = n_l;
+#pragma unroll
+        for (int sh = 32; sh >= 1; sh >>= 1) n += __shfl_xor(n, sh, 64);
+        n = __builtin_amdgcn_readfirstlane(n);
+        bool bad = __ballot(zero_l) != 0ull;                        // (wave-uniform) a sigma == 0, or a pivot that was not > 0
+        double rr[NS], dg[NS];                                      // lane + 64 s <-> row i: v_i -> z_i -> x_i; C[i][i]
+#pragma unroll
+        for (int s = 0; s < NS; ++s) { rr[s] = 0.0; dg[s] = 1.0; }
+        if (n > 0 && !bad) {
+            // ---- M = I + sum_d tril(L)_d^T G_d tril(L)_d (packed lower triangle), v = tril(L)^T q
+            for (int i = lane; i < Pl * (Pl + 1) / 2; i += 64) sC[i] = 0.0;
+            cond_wave_sync();
+            for (int i = lane; i < Pl; i += 64) sC[i * (i + 1) / 2 + i] = 1.0;
+            cond_wave_sync();
+            for (int d = 0; d < D; ++d) {
+                if (__builtin_amdgcn_readfirstlane(snd[d]) == 0) continue;
+                const int jm = (d + 1) * Kloc;
+                demo_stage_block<NS>(Lb, sG + d * KK, sL, sX, d, Kloc, Pl, ld, lane);
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const int j = lane + 64 * s;
+                    if (j < jm) {
+                        for (int l = 0; l < Kloc; ++l) rr[s] = __builtin_fma((double)sL[l * ld + j], sq[d * Kloc + l], rr[s]);
+                    }
+                }
+                for (int i = 0; i < jm; ++i) {
+                    const int base = i * (i + 1) / 2;
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        const int j = lane + 64 * s;
+                        if (j <= i) {
+                            double acc = sC[base + j];
+                            for (int l = 0; l < Kloc; ++l) acc = __builtin_fma((double)sL[l * ld + i], sX[l * ld + j], acc);
+                            sC[base + j] = acc;
+                        }
+                    }
+                }
+                cond_wave_sync();
+            }
+            // ---- M = C C^T in place, left-looking (lane + 64 s <-> row)
+            for (int jc = 0; jc < Pl; ++jc) {
+                const double* cj = sC + jc * (jc + 1) / 2;
+                double sv[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const int i = lane + 64 * s;
+                    sv[s] = 0.0;
+                    if (i >= jc && i < Pl) {
+                        const int mine = i * (i + 1) / 2;
+                        // four accumulators in a fixed order: with one wave on a CU a single chain waits out every LDS round trip
+                        double x0 = sC[mine + jc], x1 = 0.0, x2 = 0.0, x3 = 0.0;
+                        int k = 0;
+                        for (; k + 3 < jc; k += 4) {
+                            x0 = __builtin_fma(-sC[mine + k], cj[k], x0);
+                            x1 = __builtin_fma(-sC[mine + k + 1], cj[k + 1], x1);
+                            x2 = __builtin_fma(-sC[mine + k + 2], cj[k + 2], x2);
+                            x3 = __builtin_fma(-sC[mine + k + 3], cj[k + 3], x3);
+                        }
+                        for (; k < jc; ++k) x0 = __builtin_fma(-sC[mine + k], cj[k], x0);
+                        sv[s] = (x0 + x1) + (x2 + x3);
+                    }
+                }
+                const double piv = demo_bcast<NS>(sv, jc);
+                const bool ok = piv > 0.0;                          // (wave-uniform) a NaN is not
+                bad = bad || !ok;
+                const double root = ok ? sqrt(piv) : nan;
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const int i = lane + 64 * s;
+                    if (i >= jc && i < Pl) sC[i * (i + 1) / 2 + jc] = i == jc ? root : sv[s] / root;
+                }
+                cond_wave_sync();
+            }
+            // ---- z = C^-1 v (column by column)
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const int i = lane + 64 * s;
+                if (i < Pl) dg[s] = sC[i * (i + 1) / 2 + i];
+            }
+            for (int j = 0; j < Pl; ++j) {
+                const double zj = demo_bcast<NS>(rr, j) / demo_bcast<NS>(dg, j);
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const int i = lane + 64 * s;
+                    if (i == j) rr[s] = zj;
+                    else if (i > j && i < Pl) rr[s] = __builtin_fma(-sC[i * (i + 1) / 2 + j], zj, rr[s]);
+                }
+            }
+        }
+        const bool live = n > 0 && !bad;                            // (wave-uniform)
+        if (!GRAD) {
+            double zz = 0.0, lg = 0.0;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const int i = lane + 64 * s;
+                if (i < Pl) { zz = __builtin_fma(rr[s], rr[s], zz); lg += log(dg[s]); }
+            }
+            const double quad = ssum - demo_wave_sum(zz);
+            const double logs = demo_wave_sum(lg);
+            double lp = 0.0;
+            if (bad) lp = nan;
+            else if (n > 0) lp = -0.5 * quad - 0.5 * lsig - logs - (double)n * 0.91893853320467274178;   // 1/2 log 2 pi
+            if (lane == 0) a.log_prob[b] = lp;
+        } else {
+            const double gb = a.g[b];
+            double u[NS];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) u[s] = 0.0;
+            if (live) {
+                // ---- x = C^-T z (row by row from the last)
+                for (int j = Pl - 1; j >= 0; --j) {
+                    const double xj = demo_bcast<NS>(rr, j) / demo_bcast<NS>(dg, j);
+                    const double* cj = sC + j * (j + 1) / 2;
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        const int i = lane + 64 * s;
+                        if (i == j) rr[s] = xj;
+                        else if (i < j) rr[s] = __builtin_fma(-cj[i], xj, rr[s]);
+                    }
+                }
+                // ---- tril(L) x, row by row (lane <-> column), over mu's place
+                for (int row = 0; row < Pl; ++row) {
+                    double part = 0.0;
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        const int j = lane + 64 * s;
+                        if (j <= row) part = __builtin_fma((double)Lb[(size_t)row * Pl + j], rr[s], part);
+                    }
+                    const double tot = demo_wave_sum(part);
+                    if (lane == 0) sy[row] = tot;
+                }
+                cond_wave_sync();
+                // ---- gm = q - G (tril(L) x), in its place
+                double gm[NS];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const int row = lane + 64 * s;
+                    gm[s] = 0.0;
+                    if (row < Pl) {
+                        const int d = row / Kloc, k = row - d * Kloc;
+                        double acc = 0.0;
+                        for (int l = 0; l < Kloc; ++l) acc = __builtin_fma(sG[d * KK + k * Kloc + l], sy[d * Kloc + l], acc);
+                        gm[s] = sq[row] - acc;
+                    }
+                }
+                cond_wave_sync();
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    const int row = lane + 64 * s;
+                    if (row < Pl) sy[row] = gm[s];
+                }
+                cond_wave_sync();
+                // ---- u = tril(L)^T gm (lane <-> column)
+                for (int row = 0; row < Pl; ++row) {
+                    const double gr = sy[row];
+#pragma unroll
+                    for (int s = 0; s < NS; ++s) {
+                        const int j = lane + 64 * s;
+                        if (j <= row) u[s] = __builtin_fma((double)Lb[(size_t)row * Pl + j], gr, u[s]);
+                    }
+                }
+            }
+            if (a.g_params) {
+                for (int p = lane; p < c.P; p += 64) {
+                    const int row = p - c.off;
+                    float out = 0.0f;
+                    if (row >= 0 && row < Pl) {
+                        if (bad) out = (float)nan;
+                        else if (n > 0 && snd[row / Kloc] > 0) out = (float)(gb * sy[row]);
+                    }
+                    a.g_params[(size_t)b * c.P + p] = out;
+                }
+            }
+            if (a.g_L) {
+                float* Go = a.g_L + (size_t)b * Pl * Pl;
+                for (int d = 0; d < D; ++d) {
+                    const bool any = live && __builtin_amdgcn_readfirstlane(snd[d]) > 0;   // (wave-uniform)
+                    if (any) {
+                        // ---- W = X_d M^-1: the Kloc rows of X_d against C, forward then backward (lane + 64 s <-> row of the system)
+                        demo_stage_block<NS>(Lb, sG + d * KK, sL, sX, d, Kloc, Pl, ld, lane);
+                        for (int j = 0; j < Pl; ++j) {
+                            const double cjj = sC[j * (j + 1) / 2 + j];
+                            if (lane < Kloc) sX[lane * ld + j] = sX[lane * ld + j] / cjj;
+                            cond_wave_sync();
+#pragma unroll
+                            for (int s = 0; s < NS; ++s) {
+                                const int i = lane + 64 * s;
+                                if (i > j && i < Pl) {
+                                    const double cij = sC[i * (i + 1) / 2 + j];
+                                    for (int k = 0; k < Kloc; ++k) sX[k * ld + i] = __builtin_fma(-cij, sX[k * ld + j], sX[k * ld + i]);
+                                }
+                            }
+                            cond_wave_sync();
+                        }
+                        for (int j = Pl - 1; j >= 0; --j) {
+                            const double* cj = sC + j * (j + 1) / 2;
+                            const double cjj = cj[j];
+                            if (lane < Kloc) sX[lane * ld + j] = sX[lane * ld + j] / cjj;
+                            cond_wave_sync();
+#pragma unroll
+                            for (int s = 0; s < NS; ++s) {
+                                const int i = lane + 64 * s;
+                                if (i < j) {
+                                    const double cji = cj[i];
+                                    for (int k = 0; k < Kloc; ++k) sX[k * ld + i] = __builtin_fma(-cji, sX[k * ld + j], sX[k * ld + i]);
+                                }
+                            }
+                            cond_wave_sync();
+                        }
+                    }
+                    // ---- this DoF's rows leave, rounded once
+                    for (int k = 0; k < Kloc; ++k) {
+                        const int row = d * Kloc + k;
+                        const double gr = any ? sy[row] : 0.0;
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) {
+                            const int j = lane + 64 * s;
+                            if (j < Pl) {
+                                float out = 0.0f;
+                                if (j <= row) {
+                                    if (bad) out = (float)nan;
+                                    else if (any) out = (float)(gb * (gr * u[s] - sX[k * ld + j]));
+                                }
+                                Go[(size_t)row * Pl + j] = out;
+                            }
+                        }
+                    }
+                    cond_wave_sync();
+                }
+            }
+        }
+        cond_wave_sync();                                           // the images are free again
+    }
+}
+
+#ifndef MPK_DEVICE_ONLY
+// the shapes the kernel takes; MPK_ENOTIMPL with the limit in the message otherwise (no HIP call)
+int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* wave_doubles_out, int* tc_out, int* scratch_out) {
+    if (c.mp_type == MPK_MP_DMP || c.dmp_resp) {
+        set_error("mpk_demonstration_log_prob: a DMP has no probabilistic interface (promp / prodmp only)");
+        return MPK_ENOTIMPL;
+    }
+    if (c.D > kMaxD || c.KP > kMaxKP) {
+        set_error("mpk_demonstration_log_prob: at most " + std::to_string(kMaxD) + " DoF and " + std::to_string(kMaxKP) +
+                  " table columns (this handle: " + std::to_string(c.D) + " DoF, " + std::to_string(c.KT) +
+                  " columns); the k_traj_wide shapes have no kernel here");
+        return MPK_ENOTIMPL;
+    }
+    const size_t Pl = (size_t)c.D * c.Kloc;
+    if (Pl > (size_t)64 * kDemoSlots) {
+        set_error("mpk_demonstration_log_prob: at most " + std::to_string(64 * kDemoSlots) + " non-phase parameters (this handle: " +
+                  std::to_string(c.D) + " DoF x " + std::to_string(c.Kloc) + " = " + std::to_string(Pl) + ")");
+        return MPK_ENOTIMPL;
+    }
+    const size_t ld = Pl | 1;
+    size_t tc = (size_t)c.Kloc * ld / (2 * (size_t)(c.D > 0 ? c.D : 1));
+    if (tc < 32) tc = 32;
+    if (tc > (size_t)c.T) tc = c.T > 0 ? c.T : 1;
+    const size_t xw = (size_t)c.Kloc * ld, ch = 2 * tc * c.D;
+    const size_t scratch = xw > ch ? xw : ch;
+    const size_t wave_doubles = Pl * (Pl + 1) / 2 + (size_t)c.D * c.Kloc * c.Kloc + 2 * Pl + scratch + (xw + 1) / 2 + 8;
+    const size_t shared = (size_t)c.T * c.KT * sizeof(double) + 64;
+    if (wave_doubles * sizeof(double) + shared > kLdsPerCu) {
+        set_error("mpk_demonstration_log_prob: the float64 images of " + std::to_string(Pl) + " parameters and " + std::to_string(c.T) +
+                  " steps (" + std::to_string(wave_doubles * sizeof(double) + shared) + " bytes with one wave per workgroup) do not "
+                  "fit the CU's " + std::to_string(kLdsPerCu) + " bytes of LDS");
+        return MPK_ENOTIMPL;
+    }
+    // the waves per workgroup (<= 4) that put the most waves on a CU; the larger workgroup on a tie (the tables are staged once each)
+    int best = 1;
+    size_t best_on_cu = 0;
+    for (int w = 1; w <= 4; ++w) {
+        const size_t bytes = w * wave_doubles * sizeof(double) + shared;
+        if (bytes > kLdsPerCu) break;
+        const size_t on_cu = w * (kLdsPerCu / bytes);
+        if (on_cu >= best_on_cu) { best = w; best_on_cu = on_cu; }
+    }
+    if (lds_out) *lds_out = best * wave_doubles * sizeof(double) + shared;
+    if (waves_out) *waves_out = best;
+    if (wave_doubles_out) *wave_doubles_out = (int)wave_doubles;
+    if (tc_out) *tc_out = (int)tc;
+    if (scratch_out) *scratch_out = (int)scratch;
+    return MPK_OK;
+}
+
+template <int MP, bool GRAD>
+static int launch_demo_log_prob_mp(const DemoLogProbArgs& la, int ns, int blocks, size_t lds, void* stream) {
+    auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(64 * la.waves), lds, stream, la); };
+    switch (ns) {
+        case 1: return go(k_demo_log_prob<MP, 1, GRAD>);
+        case 2: return go(k_demo_log_prob<MP, 2, GRAD>);
+        case 3: return go(k_demo_log_prob<MP, 3, GRAD>);
+        default: return go(k_demo_log_prob<MP, 4, GRAD>);
+    }
+}
+
+int launch_demo_log_prob(const DevCfg& c, const SharedTables& st, const DemoLogProbLaunch& q, int num_cu, void* stream,
+                         const char** kernel_name) {
+    DemoLogProbArgs la{};
+    size_t lds = 0;
+    const int rc = demo_log_prob_limits(c, &lds, &la.waves, &la.wave_doubles, &la.tc, &la.scratch);
+    if (rc != MPK_OK) return rc;
+    const bool promp = c.mp_type == MPK_MP_PROMP;
+    la.c = c; la.A = st.A; la.aux = st.aux; la.TS = st.TS; la.init_time = q.init_time;
+    la.params = q.params; la.L = q.params_L; la.init_pos = q.init_pos; la.init_vel = q.init_vel;
+    la.pos = q.pos; la.sd = q.obs_std;
+    la.log_prob = q.log_prob; la.g = q.g; la.g_params = q.g_params; la.g_L = q.g_params_L;
+    la.B = q.B; la.Pl = c.D * c.Kloc; la.ld = la.Pl | 1;
+    const int per_cu = (int)(kLdsPerCu / lds) < 1 ? 1 : ((int)(kLdsPerCu / lds) > 8 ? 8 : (int)(kLdsPerCu / lds));
+    const long units = ((long)q.B + la.waves - 1) / la.waves;
+    const int blocks = (int)(units < (long)num_cu * per_cu ? units : (long)num_cu * per_cu);
+    const int ns = (la.Pl + 63) / 64;
+    if (q.grad) {
+        *kernel_name = promp ? "k_demo_log_prob<promp, grad>" : "k_demo_log_prob<prodmp, grad>";
+        return promp ? launch_demo_log_prob_mp<MPK_MP_PROMP, true>(la, ns, blocks, lds, stream)
+                     : launch_demo_log_prob_mp<MPK_MP_PRODMP, true>(la, ns, blocks, lds, stream);
+    }
+    *kernel_name = promp ? "k_demo_log_prob<promp>" : "k_demo_log_prob<prodmp>";
+    return promp ? launch_demo_log_prob_mp<MPK_MP_PROMP, false>(la, ns, blocks, lds, stream)
+                 : launch_demo_log_prob_mp<MPK_MP_PRODMP, false>(la, ns, blocks, lds, stream);
+}
+#endif  // MPK_DEVICE_ONLY
+
+}  // namespace mpk

@@ -1391,6 +1391,57 @@ int mpk_trajectory_log_prob_vjp(mpk_handle hh, const float* params, const float*
                                      M, obs_pos, obs_pos_std, obs_vel, obs_vel_std, true, nullptr, g, g_params, g_params_L, B, stream);
 }
 
+// the log-likelihood of whole demonstrations under N(params, L L^T) in the information form, and its gradient: every refusal before any
+// launch; the tables as above; one launch.  grad: the _vjp entry
+static int demonstration_log_prob_entry(const char* fn, mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
+                                        const float* init_vel, double init_time_shared, const float* pos, const float* obs_std, bool grad,
+                                        double* log_prob, const double* g, float* g_params, float* g_params_L, int32_t B, void* stream) {
+    const std::string name(fn);
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!params || !params_L) { set_error(name + ": NULL params or params_L"); return MPK_EINVAL; }
+    if (!pos || !obs_std) { set_error(name + ": NULL pos or obs_std"); return MPK_EINVAL; }
+    if (!grad && !log_prob) { set_error(name + ": NULL log_prob"); return MPK_EINVAL; }
+    if (grad && !g) { set_error(name + ": NULL g"); return MPK_EINVAL; }
+    if (grad && !g_params && !g_params_L) { set_error(name + ": g_params and g_params_L are both NULL: nothing to compute"); return MPK_EINVAL; }
+    if (B < 1) { set_error(name + ": B must be >= 1"); return MPK_EINVAL; }
+    if (h->cfg.learn_tau || h->cfg.learn_delay) {
+        set_error(name + ": a learned tau / delay gives every episode its own phase and its own table: only shared-phase handles have a "
+                  "likelihood kernel");
+        return MPK_ENOTIMPL;
+    }
+    int rc = demo_log_prob_limits(h->dev, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc != MPK_OK) return rc;
+    if (h->dev.D * h->dev.Kloc < 1) { set_error(name + ": the handle has no non-phase parameters"); return MPK_EINVAL; }
+    if ((!init_pos || !init_vel) && h->cfg.mp_type != MPK_MP_PROMP) {
+        set_error(name + ": init_pos and init_vel are required (only a ProMP may pass NULL: zeros)");
+        return MPK_EINVAL;
+    }
+    MPK_ON_DEVICE(h->cfg.device);
+    SharedTables st;
+    rc = get_shared(h, (float)init_time_shared, stream, &st);
+    if (rc != MPK_OK) return rc;
+    DemoLogProbLaunch q;
+    q.params = params; q.params_L = params_L; q.init_pos = init_pos; q.init_vel = init_vel; q.init_time = (float)init_time_shared;
+    q.pos = pos; q.obs_std = obs_std;
+    q.grad = grad; q.log_prob = log_prob; q.g = g; q.g_params = g_params; q.g_params_L = g_params_L; q.B = B;
+    return launch_demo_log_prob(h->dev, st, q, h->num_cu, stream, &h->last_kernel);
+}
+
+int mpk_demonstration_log_prob(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                               double init_time_shared, const float* pos, const float* obs_std, double* log_prob, int32_t B,
+                               void* stream) {
+    return demonstration_log_prob_entry("mpk_demonstration_log_prob", hh, params, params_L, init_pos, init_vel, init_time_shared, pos,
+                                        obs_std, false, log_prob, nullptr, nullptr, nullptr, B, stream);
+}
+
+int mpk_demonstration_log_prob_vjp(mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
+                                   const float* init_vel, double init_time_shared, const float* pos, const float* obs_std, const double* g,
+                                   float* g_params, float* g_params_L, int32_t B, void* stream) {
+    return demonstration_log_prob_entry("mpk_demonstration_log_prob_vjp", hh, params, params_L, init_pos, init_vel, init_time_shared, pos,
+                                        obs_std, true, nullptr, g, g_params, g_params_L, B, stream);
+}
+
 int mpk_trajectory_actions(mpk_handle hh, const float* params, const float* init_pos, const float* init_vel,
                            double init_time_shared, const mpk_rollout_cfg* rc, const double* c_pos,
                            const double* c_vel, float* pos, float* vel, float* actions, int32_t B, void* stream) {

@@ -351,6 +351,26 @@ struct LogProbLaunch {
 int traj_log_prob_limits(const DevCfg& c, int M, int narr, size_t* lds_out, int* waves_out, int* wave_doubles_out);
 int launch_traj_log_prob(const DevCfg& c, const SharedTables& st, const LogProbLaunch& q, int num_cu, void* stream,
                          const char** kernel_name);
+// mpk_demonstration_log_prob / _vjp (mpk_demo_log_prob.hip): the log-likelihood of whole demonstrations pos [B, T, D] with standard
+// deviations obs_std [B, T, D] under N(params, L L^T) in the information form -- the Gram matrices G_d, M = I + tril(L)^T G tril(L)
+// = C C^T [Pl x Pl] -- and its gradient w.r.t. params and params_L: one launch of k_demo_log_prob each, one wave per episode, the
+// gradient launch recomputing everything from the inputs.  grad = false: log_prob [B] is written; grad = true: g [B] is read and
+// g_params / g_params_L (either may be nullptr) are written.  demo_log_prob_limits: MPK_OK, or MPK_ENOTIMPL with the limit in the
+// message -- a DMP, more than kMaxD DoF or kMaxKP columns, Pl > 64 x 4, float64 images that exceed the LDS with one wave per workgroup
+// (no HIP call; the outputs may be nullptr).
+struct DemoLogProbLaunch {
+    const float *params = nullptr, *params_L = nullptr, *init_pos = nullptr, *init_vel = nullptr;
+    float init_time = 0.f;                                              // the tables' (init_time_shared)
+    const float *pos = nullptr, *obs_std = nullptr;                     // [B, T, D]
+    bool grad = false;
+    double* log_prob = nullptr;                                         // [B]
+    const double* g = nullptr;                                          // [B]
+    float *g_params = nullptr, *g_params_L = nullptr;
+    int B = 0;
+};
+int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* wave_doubles_out, int* tc_out, int* scratch_out);
+int launch_demo_log_prob(const DevCfg& c, const SharedTables& st, const DemoLogProbLaunch& q, int num_cu, void* stream,
+                         const char** kernel_name);
 int launch_episode_reset(const double* init_q, const double* init_qd, double* q, double* qd, float* cond_pos,
                          float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done, int B, int D,
                          void* stream);

@@ -18,7 +18,8 @@
 //   mpk_traj_std.hip     k_traj_std_tile: the trajectory's standard deviation from the factor of a weight covariance (mpk_trajectory_std)
 //   mpk_traj_condition.hip   k_traj_condition: a Gaussian over the parameters conditioned on observed points (mpk_trajectory_condition)
 //   mpk_traj_log_prob.hip    k_traj_log_prob: the log-likelihood of observed points under that Gaussian and its gradient (mpk_trajectory_log_prob)
-//   mpk_cond_rows.h      the observed steps' float64 table rows and the wave-level LDS ordering, shared by the two units above
+//   mpk_demo_log_prob.hip    k_demo_log_prob: the log-likelihood of whole demonstrations in the Pl x Pl form and its gradient (mpk_demonstration_log_prob)
+//   mpk_cond_rows.h      the observed steps' float64 table rows and the wave-level LDS ordering, shared by the three units above
 //   mpk_traj_phase.hip   per-episode phase kernels
 //   mpk_phase_fused.hip  per-episode phase: the fused entry points (actions, closed loop, replanning step, verbose < 2 step, validity gate)
 //   mpk_rollout.hip      rollout kernels
@@ -46,6 +47,7 @@
 #include "mpk_traj_std.hip"
 #include "mpk_traj_condition.hip"
 #include "mpk_traj_log_prob.hip"
+#include "mpk_demo_log_prob.hip"
 #include "mpk_traj_phase.hip"
 #include "mpk_phase_fused.hip"
 #include "mpk_rollout.hip"

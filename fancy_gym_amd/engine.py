@@ -143,6 +143,25 @@ class _TrajectoryLogProbFn(torch.autograd.Function):
         return None, None, None, None, g_params, g_L
 
 
+class _DemonstrationLogProbFn(torch.autograd.Function):
+    """``TrajectoryEngine.demonstration_log_prob`` with a backward: forward = the mpk_demonstration_log_prob launch as without autograd,
+    backward = one mpk_demonstration_log_prob_vjp launch, which recomputes the Gram matrices and the factorisation from the forward's
+    inputs; the demonstrations, their standard deviations and the initial conditions get no gradient"""
+
+    @staticmethod
+    def forward(ctx, engine, inputs, init_time, params, params_L):
+        ctx.engine, ctx.inputs, ctx.init_time = engine, inputs, init_time
+        ctx.save_for_backward(params, params_L)
+        return engine._demo_log_prob_launch(params, params_L, inputs, init_time)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        params, params_L = ctx.saved_tensors
+        g_params, g_L = ctx.engine._demo_log_prob_vjp_launch(g, params, params_L, ctx.inputs, ctx.init_time, ctx.needs_input_grad[3:5])
+        return None, None, None, g_params, g_L
+
+
 class _ReacherRolloutFn(torch.autograd.Function):
     """``TrajectoryEngine.reacher_rollout`` with a backward: forward = a copy of the plan-start (q, qd) and the mpk_reacher_rollout launch
     as without autograd, backward = one mpk_reacher_rollout_vjp launch; the actions and the in-place q, qd carry no graph"""
@@ -984,6 +1003,98 @@ class TrajectoryEngine:
             mean = torch.as_tensor(params, dtype=torch.float32, device=self.device).detach().contiguous()
             L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
             return self._log_prob_vjp_launch(g, mean, L, steps, inputs, init_time, need)
+
+    def _demo_checks(self, fn, params, params_L, pos, obs_std, init_pos, init_vel):
+        """the refusals of ``demonstration_log_prob`` / ``demonstration_log_prob_vjp`` -- ``trajectory_log_prob``'s (``_obs_checks``)
+        plus the demonstrations' shape and the inputs that have no gradient, all before anything touches the device; returns B"""
+        if pos is None or obs_std is None:
+            raise ValueError(f"{fn}: pos and obs_std are both required (the demonstrations with their standard deviations)")
+        B, _ = self._obs_checks(fn, "a likelihood kernel", params, params_L, (), pos, obs_std, init_pos, init_vel, None, None)
+        T, D = self.num_steps, self.num_dof
+        shape = tuple(pos.shape) if hasattr(pos, "shape") else np.shape(pos)
+        if shape != (B, T, D):
+            raise ValueError(f"{fn}: pos must be [{B}, {T}, {D}] (whole demonstrations on the handle's {T} steps), got {shape}")
+        if torch.is_grad_enabled():
+            for name, t in (("init_pos", init_pos), ("init_vel", init_vel), ("pos", pos), ("obs_std", obs_std)):
+                if isinstance(t, torch.Tensor) and t.requires_grad:
+                    raise NotImplementedError(f"{fn}: {name} requires grad, but the likelihood has a gradient w.r.t. params and params_L "
+                                              "only; detach it")
+        return B
+
+    def _demo_inputs(self, fn, B, pos, obs_std, init_pos, init_vel):
+        """(init_pos, init_vel, pos, obs_std) as contiguous float32 device tensors (the first two or None), obs_std broadcast to
+        [B, T, D] as ``condition`` broadcasts its standard deviations"""
+        D, T = self.num_dof, self.num_steps
+        with torch.no_grad():
+            return (None if init_pos is None else self._f32(init_pos, (B, D)).detach(),
+                    None if init_vel is None else self._f32(init_vel, (B, D)).detach(),
+                    self._f32(pos, (B, T, D)).detach(), self._obs_bcast(fn, obs_std, "obs_std", B, T))
+
+    def _demo_log_prob_launch(self, mean, L, inputs, init_time):
+        ip, iv, y, sd = inputs
+        out = torch.empty((mean.shape[0],), dtype=torch.float64, device=self.device)
+        _lib.check(self._lib.mpk_demonstration_log_prob(
+            self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time), y.data_ptr(), sd.data_ptr(), out.data_ptr(),
+            mean.shape[0], self._stream()))
+        return out
+
+    def _demo_log_prob_vjp_launch(self, g, mean, L, inputs, init_time, need):
+        ip, iv, y, sd = inputs
+        B, P = mean.shape
+        g = torch.as_tensor(g, dtype=torch.float64, device=self.device).detach()
+        if tuple(g.shape) != (B,):
+            raise ValueError(f"demonstration_log_prob_vjp: g must be [{B}], got {tuple(g.shape)}")
+        g = g.contiguous()
+        g_mean = torch.empty((B, P), dtype=torch.float32, device=self.device) if need[0] else None
+        g_L = torch.empty((B, P, P), dtype=torch.float32, device=self.device) if need[1] else None
+        if g_mean is None and g_L is None:
+            return None, None
+        _lib.check(self._lib.mpk_demonstration_log_prob_vjp(
+            self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time), y.data_ptr(), sd.data_ptr(), g.data_ptr(),
+            _dptr(g_mean), _dptr(g_L), B, self._stream()))
+        return g_mean, g_L
+
+    def demonstration_log_prob(self, params, params_L, pos, obs_std, init_pos=None, init_vel=None,
+                               init_time: float = 0.0) -> torch.Tensor:
+        """
+        The log-likelihood of WHOLE demonstrations under the Gaussian ``N(params, L L^T)`` over the parameters (mpk.h:
+        mpk_demonstration_log_prob), one launch: [B] float64 on the device.  ``pos`` [B, T, D]: the demonstrated positions on the
+        handle's own T steps; ``obs_std`` a scalar, [D], [T, D] or [B, T, D].  An entry is kept when ``0 < sigma < inf``: ``+inf``,
+        NaN or a negative one removes that (episode, step, DoF) -- missing samples, or a prefix of the movement.  Every kept entry is
+        an observation of ``trajectory_log_prob``'s kind, ``log N(y; H mu + c, A A^T + diag(sigma^2))``, but evaluated in the
+        information form: the Gram matrices of the basis per DoF and the Cholesky factor of the ``Pl x Pl`` matrix
+        ``I + tril(L)^T G tril(L)``, all float64 -- ``T D`` may be in the thousands.  No entry kept gives exactly 0.0.  ``sigma == 0``
+        cannot be expressed in this form: that episode is NaN (use ``trajectory_log_prob`` for exact observations).  When ``params``
+        or ``params_L`` requires grad the result carries the autograd graph: its backward is ONE mpk_demonstration_log_prob_vjp
+        launch, which recomputes everything from the inputs; a mean or factor expanded from one shared row gets the sum over the
+        batch through torch as usual.  There is no gradient w.r.t. ``pos``, ``obs_std``, ``init_pos`` or ``init_vel``: a tensor among
+        them that requires grad is a NotImplementedError, not a silent cut.  ``params_L``'s strict upper triangle is never read.
+        Refusals are ``trajectory_log_prob``'s, raised before any launch (shapes, a learned tau / delay, a DMP, more than 16 DoF,
+        ``init_pos`` / ``init_vel`` None on a ProDMP), plus ValueError for a ``pos`` that is not [B, T, D] with T the handle's steps.
+        """
+        B = self._demo_checks("demonstration_log_prob", params, params_L, pos, obs_std, init_pos, init_vel)
+        inputs = self._demo_inputs("demonstration_log_prob", B, pos, obs_std, init_pos, init_vel)
+        mean = torch.as_tensor(params, dtype=torch.float32, device=self.device)
+        L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device)
+        if torch.is_grad_enabled() and (mean.requires_grad or L.requires_grad):
+            return _DemonstrationLogProbFn.apply(self, inputs, float(init_time), mean.contiguous(), L.contiguous())
+        return self._demo_log_prob_launch(mean.detach().contiguous(), L.detach().contiguous(), inputs, init_time)
+
+    def demonstration_log_prob_vjp(self, g, params, params_L, pos, obs_std, init_pos=None, init_vel=None, init_time: float = 0.0, *,
+                                   need: Sequence[bool] = (True, True)) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """
+        The vector-Jacobian product of ``demonstration_log_prob`` (mpk.h: mpk_demonstration_log_prob_vjp), one launch: ``g`` [B]
+        float64, the gradient of a loss w.r.t. the log-likelihoods -> ``(g_params [B, P], g_params_L [B, Pl, Pl])`` float32 on the
+        device, without an autograd graph.  The other arguments are ``demonstration_log_prob``'s.  ``g_params_L``'s strict upper
+        triangle is exact zeros, and so are the rows of a DoF none of whose entries remain; an episode with a ``sigma == 0`` gets NaN
+        rows (use ``trajectory_log_prob`` for exact observations).  ``need[i]`` False: that output is not computed (None in its place).
+        """
+        B = self._demo_checks("demonstration_log_prob_vjp", params, params_L, pos, obs_std, init_pos, init_vel)
+        inputs = self._demo_inputs("demonstration_log_prob_vjp", B, pos, obs_std, init_pos, init_vel)
+        with torch.no_grad():
+            mean = torch.as_tensor(params, dtype=torch.float32, device=self.device).detach().contiguous()
+            L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
+            return self._demo_log_prob_vjp_launch(g, mean, L, inputs, init_time, need)
 
     def sample_trajectories(self, params, params_L, init_pos, init_vel, init_time: float = 0.0, *, num_samples: int,
                             generator: Optional[torch.Generator] = None) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -1104,7 +1104,8 @@ int mpk_trajectory_condition(mpk_handle h, const float* params, const float* par
  * observations than a wave has lanes, nmax = M * D * (the observation arrays given: 1 or 2) > MPK_LOGPROB_MAX_OBS; float64 images that
  * exceed a CU's LDS with one wave per workgroup -- 8 (nmax (Pl | 1) + nmax (nmax + 1) / 2 + 3 nmax) + 16 M KT + 64 bytes <= 163 840:
  * Pl = 160 with 64 observations runs (100 608 + 16 M KT + 64 bytes).  The whole-trajectory likelihood, n >> Pl, wants the Pl x Pl form
- * (the Cholesky factor of I + A^T R^-1 A) and is a different kernel: not built.
+ * (the Cholesky factor of I + A^T R^-1 A) and is a different kernel: not built into these two entries -- it is
+ * mpk_demonstration_log_prob, below.
  */
 #define MPK_LOGPROB_MAX_OBS 64
 int mpk_trajectory_log_prob(mpk_handle h, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
@@ -1115,6 +1116,55 @@ int mpk_trajectory_log_prob_vjp(mpk_handle h, const float* params, const float* 
                                 double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
                                 const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, const double* g, float* g_params,
                                 float* g_params_L, int32_t B, void* stream);
+
+/*
+ * The log-likelihood of WHOLE demonstrations under a Gaussian over the MP parameters, and its gradient, for a handle with a SHARED phase
+ * (added within ABI 4; no existing prototype changes): every step of every DoF is an observation, n = T D >> Pl, so the likelihood is
+ * evaluated in the information (Pl x Pl) form -- what learning a ProMP's mean and scale_tril by maximum likelihood from recorded
+ * trajectories, ranking demonstrations and scoring an observed prefix of a movement need.  params, params_L, init_pos and init_vel are
+ * mpk_trajectory_log_prob's.  The observation (t, d) reads y = psi_t . w_d + c_td + eps, eps ~ N(0, sigma_td^2): psi_t the position table
+ * row of step t on the parameter columns (the very values mpk_trajectory_log_prob reads), c what init_pos / init_vel / the goal offset
+ * contribute.
+ *   pos         dev float [B, T, D]     the demonstrated positions on the handle's own steps
+ *   obs_std     dev float [B, T, D]     sigma; an observation is kept when 0 < sigma < +inf: +inf, NaN or a negative one removes it
+ *                                       (missing samples; a prefix is the rest at +inf)
+ * With w = 1 / sigma^2 on kept entries and 0 elsewhere, n the number kept and r = y - c - psi . mu_d:
+ *     G_d = sum_t w_td psi_t psi_t^T  [Kloc x Kloc]     G = blockdiag(G_d)
+ *     q_d = sum_t w_td psi_t r_td     s = sum w r^2     lsig = sum over kept of log sigma^2
+ *     M   = I + tril(L)^T G tril(L) = C C^T             v = tril(L)^T q     z = C^-1 v
+ *     log_prob = -1/2 (s - z.z) - 1/2 (lsig + 2 sum log C_ii) - (n / 2) log 2 pi
+ * which equals log N(y; H mu + c, A A^T + diag(sigma^2)), A = H tril(L), by the Woodbury identity and the matrix determinant lemma; all
+ * float64; L L^T is never formed and neither is the n x n covariance.  n = 0 gives exactly 0.0.  sigma == 0 cannot be expressed in this
+ * form: that episode's log_prob is NaN, and in the gradient launch the local block of its g_params row and the lower triangle of its
+ * g_params_L; use mpk_trajectory_log_prob for exact observations.  A Cholesky pivot that is not > 0 (M is positive definite for finite
+ * inputs, so this needs a non-finite one) does the same.  No other episode changes.
+ *   log_prob    dev double [B]          out
+ * mpk_demonstration_log_prob_vjp: for an upstream gradient g [B], with x = M^-1 v, X = G tril(L), gm = q - X x (= H^T S^-1 r),
+ *     g_params[off + .] = g gm
+ *     g_params_L        = g tril(gm (tril(L)^T gm)^T - X M^-1)
+ * accumulated in float64 and rounded to float32 once.  The strict upper triangle of g_params_L is written as exact zeros, and so are the
+ * rows of a DoF none of whose observations remain and everything of an episode with n = 0; the strict upper triangle of params_L is
+ * never read.  There is no gradient w.r.t. pos, obs_std or init_pos / init_vel.
+ *   g           dev double [B]
+ *   g_params    dev float [B, P]        out, or NULL (not computed); entries outside the local block are 0
+ *   g_params_L  dev float [B, Pl, Pl]   out, or NULL (not computed); not both NULL
+ * The gradient launch recomputes G, M and C from the inputs: nothing is kept between the two launches.  Each entry is one launch of
+ * k_demo_log_prob<promp | prodmp> (the gradient: k_demo_log_prob<promp | prodmp, grad>; mpk_last_kernel) on `stream`, plus the table
+ * builder when (init_time_shared, T) is not cached; nothing is allocated or synchronised.  One wave per episode, no atomics, fixed
+ * summation orders: the same bits from run to run, for any alignment of the pointers, alone or in a batch; no index depends on a value
+ * that is read, so non-finite inputs never fault.
+ * MPK_EINVAL: a NULL handle, params, params_L, pos, obs_std, log_prob or g, or both gradient outputs; B < 1; init_pos / init_vel NULL
+ * for a ProDMP.  MPK_ENOTIMPL, before any launch: a handle that learns tau / delay; a DMP; more than 16 DoF or 16 table columns;
+ * Pl > 256 (64 x 4); float64 images that exceed a CU's LDS with one wave per workgroup --
+ * 8 (Pl (Pl + 1) / 2 + D Kloc^2 + 2 Pl + max(Kloc (Pl | 1), 2 tc D)) + 4 Kloc (Pl | 1) + 64 + 8 T KT + 64 bytes <= 163 840, tc the
+ * steps per chunk of the accumulation: Pl = 160 (16 DoF x 10, 30 steps) runs, forward and backward, with one wave on a CU.
+ * Not built: velocities as observations, correlated noise, learned tau / delay, gradients to the observations.
+ */
+int mpk_demonstration_log_prob(mpk_handle h, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                               double init_time_shared, const float* pos, const float* obs_std, double* log_prob, int32_t B, void* stream);
+int mpk_demonstration_log_prob_vjp(mpk_handle h, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                               double init_time_shared, const float* pos, const float* obs_std, const double* g,
+                               float* g_params, float* g_params_L, int32_t B, void* stream);
 
 /*
  * The vector-Jacobian product of mpk_reacher_rollout (appended under ABI 4): controller, clip, torque double integrator and
