@@ -638,6 +638,15 @@ class BatchedBlackBox:
         cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
         return self.engine.demonstration_log_prob(params, params_L, pos, obs_std, cond_pos.detach(), cond_vel.detach(), self._plan_time())
 
+    def condition_on_demonstration(self, params, params_L, pos, obs_std, *, out=None):
+        """``(params, params_L)`` of the Gaussian ``N(params, L L^T)`` conditioned on whole demonstrations ``pos`` [B, T, D] of the plan
+        (``TrajectoryEngine.condition_on_demonstration``, one launch; ``obs_std = inf`` removes an entry, so a prefix is the rest at
+        ``inf``) from the init_time / init_pos / init_vel ``get_trajectory`` would use now, as ``condition`` takes them"""
+        cond_pos = self.condition_pos if self.condition_pos is not None else self.q.float()
+        cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
+        return self.engine.condition_on_demonstration(params, params_L, pos, obs_std, cond_pos.detach(), cond_vel.detach(),
+                                                      self._plan_time(), out=out)
+
     def _carry_start(self):
         """replan_gradient="episode": (init_pos, init_vel, q_in, qd_in) of the next plan -- what the twins of the plan before give (the
         same bits as ``_plan_condition`` and ``q``, ``qd``), or right after a cut the constants themselves"""

@@ -1,8 +1,6 @@
 // k_demo_log_prob: the log-likelihood of WHOLE demonstrations [B, T, D] under a Gaussian over the MP parameters, and its gradient
 // (mpk_demonstration_log_prob, mpk_demonstration_log_prob_vjp) -- the information (Pl x Pl) form, for n >> Pl
-#include "mpk_tile.h"
-#include "mpk_vjp_row.h"
-#include "mpk_cond_rows.h"
+#include "mpk_demo_gram.h"
 
 namespace mpk {
 
@@ -42,76 +40,13 @@ namespace mpk {
 // that is read: the same bits from run to run, for any alignment, alone or in a batch; non-finite inputs never fault.
 // LDS per wave: 8 (Pl (Pl + 1) / 2 + D Kloc^2 + 2 Pl + max(Kloc ld, 2 tc D)) + 4 Kloc ld + 64 bytes, ld = Pl | 1; per workgroup 8 T KT + 64.
 // ------------------------------------------------------------------------------------------------------------
-constexpr int kDemoSlots = 4;                                       // rows / columns per lane at most (NS = ceil(Pl / 64))
-
-struct DemoLogProbArgs {
-    DevCfg c;
-    const float* A;        // [n_out][KP][TS] (k_build_shared)
-    const float* aux;      // [TS]
-    int TS;
-    float init_time;       // the tables' (init_time_shared)
-    const float* params;   // [B, P]
-    const float* L;        // [B, Pl, Pl]; the lower triangle is read
-    const float* init_pos; // [B, D] or nullptr (promp: zeros)
-    const float* init_vel;
-    const float* pos;      // [B, T, D] the demonstrations
-    const float* sd;       // [B, T, D] their standard deviations
+// the arguments both kernels of the information form read (mpk_demo_gram.h), and this one's own
+struct DemoLogProbArgs : DemoGramArgs {
     double* log_prob;      // [B] out (forward)
     const double* g;       // [B] the upstream gradient (GRAD)
     float* g_params;       // [B, P] out or nullptr (GRAD)
     float* g_L;            // [B, Pl, Pl] out or nullptr (GRAD)
-    int B, Pl;
-    int ld;                // words between the rows of the X and L images (odd)
-    int tc;                // steps per chunk of the accumulation
-    int scratch;           // float64 words of the X image / the chunk's w and r images: max(Kloc ld, 2 tc D)
-    int waves;             // per workgroup
-    int wave_doubles;      // float64 words of LDS per wave
 };
-
-// the sum over the wave by a fixed xor ladder: the same bits in every lane
-__device__ __forceinline__ double demo_wave_sum(double x) {
-#pragma unroll
-    for (int sh = 32; sh >= 1; sh >>= 1) x += __shfl_xor(x, sh, 64);
-    return x;
-}
-
-// element j (wave-uniform) of a vector held as lane + 64 s: every lane gets it
-template <int NS>
-__device__ __forceinline__ double demo_bcast(const double (&x)[NS], int j) {
-    const int sj = j >> 6;
-    double v = x[0];
-#pragma unroll
-    for (int s = 1; s < NS; ++s) v = sj == s ? x[s] : v;
-    return __shfl(v, j & 63, 64);
-}
-
-// the rows of tril(L)'s block d as a float32 LDS image [Kloc][ld] (entries j <= row; exact 0 beyond), and X_d = G_d tril(L)[rows of d]
-// [Kloc][ld] in float64 (columns < (d + 1) Kloc; exact 0 beyond): lane <-> column
-template <int NS>
-__device__ __forceinline__ void demo_stage_block(const float* Lb, const double* Gd, float* sL, double* sX, int d, int Kloc, int Pl, int ld,
-                                                 int lane) {
-    for (int l = 0; l < Kloc; ++l) {
-        const int row = d * Kloc + l;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int j = lane + 64 * s;
-            if (j < Pl) sL[l * ld + j] = j <= row ? Lb[(size_t)row * Pl + j] : 0.0f;
-        }
-    }
-    cond_wave_sync();
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int j = lane + 64 * s;
-        if (j < Pl) {
-            for (int k = 0; k < Kloc; ++k) {
-                double acc = 0.0;
-                for (int l = 0; l < Kloc; ++l) acc = __builtin_fma(Gd[k * Kloc + l], (double)sL[l * ld + j], acc);
-                sX[k * ld + j] = acc;
-            }
-        }
-    }
-    cond_wave_sync();
-}
 
 template <int MP, int NS, bool GRAD>
 __global__ void __launch_bounds__(256) k_demo_log_prob(const DemoLogProbArgs a) {
@@ -119,152 +54,31 @@ __global__ void __launch_bounds__(256) k_demo_log_prob(const DemoLogProbArgs a) 
     const DevCfg& c = a.c;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = wave_of(tid);
-    const int D = c.D, Kloc = c.Kloc, Pl = a.Pl, T = c.T, KT = c.KT, ld = a.ld, tc = a.tc;
-    const int KK = Kloc * Kloc, Kt2 = Kloc * (Kloc + 1) / 2;
-    double* sC = demo_smem + (size_t)wave * a.wave_doubles;         // packed lower triangle: M, then its Cholesky factor C
-    double* sG = sC + Pl * (Pl + 1) / 2;                            // [D][Kloc][Kloc] the Gram matrices
-    double* sq = sG + D * KK;                                       // [Pl] q
-    double* sy = sq + Pl;                                           // [Pl] mu, then tril(L) x, then gm
-    double* sX = sy + Pl;                                           // [Kloc][ld] X_d, then X_d M^-1; the accumulation's w | r [tc][D]
-    float* sL = (float*)(sX + a.scratch);                           // [Kloc][ld] the rows of tril(L)'s block d
-    int* snd = (int*)(sL + ((Kloc * ld + 1) & ~1));                 // [D] kept observations per DoF
-    double* rows = demo_smem + (size_t)a.waves * a.wave_doubles;    // [T][KT]
-    int* kof = (int*)(rows + T * KT);                               // [Kloc] the table column read from local parameter l, or -1
-    for (int i = tid; i < T * KT; i += blockDim.x) {
-        const int t = i / KT, k = i - t * KT;
-        rows[i] = cond_obs_row<MP>(c, a.A, a.aux, a.TS, a.init_time, 0, k, t);
-    }
-    if (tid < Kloc) {
-        int found = -1;
-        for (int k = 0; k < KT; ++k) {
-            int loc;
-            if (x_kind<MP>(c, k, &loc) == XK_PARAM && loc == tid) found = k;
-        }
-        kof[tid] = found;
-    }
-    __syncthreads();
+    const int D = c.D, Kloc = c.Kloc, Pl = a.Pl, ld = a.ld;
+    const int KK = Kloc * Kloc;
+    const DemoImages im = demo_images(a, demo_smem, wave);
+    double* sC = im.sC;                                             // packed lower triangle: M, then its Cholesky factor C
+    double* sG = im.sG;                                             // [D][Kloc][Kloc] the Gram matrices
+    double* sq = im.sq;                                             // [Pl] q
+    double* sy = im.sy;                                             // [Pl] mu, then tril(L) x, then gm
+    double* sX = im.sX;                                             // [Kloc][ld] X_d, then X_d M^-1; the accumulation's w | r [tc][D]
+    float* sL = im.sL;                                              // [Kloc][ld] the rows of tril(L)'s block d
+    int* snd = im.snd;                                              // [D] kept observations per DoF
+    demo_stage_tables<MP>(a, im, tid);                              // rows [T][KT], kof [Kloc]
     const double nan = __builtin_nan("");
     for (int b = blockIdx.x * a.waves + wave; b < a.B; b += gridDim.x * a.waves) {
         const float* Lb = a.L + (size_t)b * Pl * Pl;
-        for (int i = lane; i < D * KK; i += 64) sG[i] = 0.0;
-        for (int i = lane; i < Pl; i += 64) {
-            sq[i] = 0.0;
-            sy[i] = (double)a.params[(size_t)b * c.P + c.off + i];
-        }
-        if (lane < D) snd[lane] = 0;
-        cond_wave_sync();
-        // ---- w, r, then G, q over the steps, a chunk at a time
-        double s_l = 0.0, lsig_l = 0.0;
-        int n_l = 0;
-        bool zero_l = false;
-        double* sw = sX;
-        double* sr = sX + tc * D;
-        for (int t0 = 0; t0 < T; t0 += tc) {
-            const int nt = T - t0 < tc ? T - t0 : tc;
-            for (int e = lane; e < nt * D; e += 64) {               // lane <-> (t, d): coalesced
-                const int tt = e / D, d = e - tt * D;
-                const size_t at = ((size_t)b * T + t0) * D + e;
-                const double sig = (double)a.sd[at], yv = (double)a.pos[at];
-                const bool keep = sig > 0.0 && sig != __builtin_inf();   // +inf, NaN, negative: not observed
-                zero_l = zero_l || sig == 0.0;
-                const double* hr = rows + (t0 + tt) * KT;
-                double cc = 0.0, hmu = 0.0;
-                for (int k = 0; k < KT; ++k) {
-                    int loc;
-                    const int kind = x_kind<MP>(c, k, &loc);
-                    const double hk = hr[k];
-                    if (kind == XK_PARAM) {
-                        hmu = __builtin_fma(hk, sy[d * Kloc + loc], hmu);
-                    } else if (kind == XK_IPOS) {
-                        if (a.init_pos) cc = __builtin_fma(hk, (double)a.init_pos[(size_t)b * D + d], cc);
-                    } else if (kind == XK_IVEL) {
-                        if (a.init_vel) cc = __builtin_fma(hk, (double)a.init_vel[(size_t)b * D + d], cc);
-                    } else if (kind == XK_ONE) {
-                        cc += hk;
-                    }
-                }
-                const double r = keep ? yv - cc - hmu : 0.0;
-                const double w = keep ? 1.0 / (sig * sig) : 0.0;
-                sw[e] = w;
-                sr[e] = r;
-                if (keep) {
-                    s_l = __builtin_fma(w * r, r, s_l);
-                    lsig_l += log(sig * sig);
-                    ++n_l;
-                }
-            }
-            cond_wave_sync();
-            for (int e = lane; e < D * Kt2; e += 64) {              // lane <-> (d, k >= l)
-                const int d = e / Kt2, rem = e - d * Kt2;
-                int k = 0;
-                while ((k + 1) * (k + 2) / 2 <= rem) ++k;
-                const int l = rem - k * (k + 1) / 2;
-                const int ck = kof[k], cl = kof[l];
-                double acc = sG[d * KK + k * Kloc + l];
-                if (ck >= 0 && cl >= 0) {
-                    for (int tt = 0; tt < nt; ++tt) {
-                        const double* hr = rows + (t0 + tt) * KT;
-                        acc = __builtin_fma(sw[tt * D + d] * hr[ck], hr[cl], acc);
-                    }
-                }
-                sG[d * KK + k * Kloc + l] = acc;
-                sG[d * KK + l * Kloc + k] = acc;
-            }
-            for (int row = lane; row < Pl; row += 64) {             // lane <-> row of q
-                const int d = row / Kloc, ck = kof[row - d * Kloc];
-                double acc = sq[row];
-                if (ck >= 0) {
-                    for (int tt = 0; tt < nt; ++tt) acc = __builtin_fma(sw[tt * D + d] * sr[tt * D + d], rows[(t0 + tt) * KT + ck], acc);
-                }
-                sq[row] = acc;
-            }
-            if (lane < D) {
-                int cnt = snd[lane];
-                for (int tt = 0; tt < nt; ++tt) cnt += sw[tt * D + lane] > 0.0 ? 1 : 0;
-                snd[lane] = cnt;
-            }
-            cond_wave_sync();
-        }
-        const double ssum = demo_wave_sum(s_l), lsig = demo_wave_sum(lsig_l);
-        int n = n_l;
-#pragma unroll
-        for (int sh = 32; sh >= 1; sh >>= 1) n += __shfl_xor(n, sh, 64);
-        n = __builtin_amdgcn_readfirstlane(n);
-        bool bad = __ballot(zero_l) != 0ull;                        // (wave-uniform) a sigma == 0, or a pivot that was not > 0
+        // ---- w, r, then G, q over the steps, a chunk at a time (mpk_demo_gram.h)
+        const DemoSums sm = demo_accumulate<MP, true>(a, im, b, lane);
+        const double ssum = sm.s, lsig = sm.lsig;
+        const int n = sm.n;
+        bool bad = sm.zero;                                         // (wave-uniform) a sigma == 0, or a pivot that was not > 0
         double rr[NS], dg[NS];                                      // lane + 64 s <-> row i: v_i -> z_i -> x_i; C[i][i]
 #pragma unroll
         for (int s = 0; s < NS; ++s) { rr[s] = 0.0; dg[s] = 1.0; }
         if (n > 0 && !bad) {
             // ---- M = I + sum_d tril(L)_d^T G_d tril(L)_d (packed lower triangle), v = tril(L)^T q
-            for (int i = lane; i < Pl * (Pl + 1) / 2; i += 64) sC[i] = 0.0;
-            cond_wave_sync();
-            for (int i = lane; i < Pl; i += 64) sC[i * (i + 1) / 2 + i] = 1.0;
-            cond_wave_sync();
-            for (int d = 0; d < D; ++d) {
-                if (__builtin_amdgcn_readfirstlane(snd[d]) == 0) continue;
-                const int jm = (d + 1) * Kloc;
-                demo_stage_block<NS>(Lb, sG + d * KK, sL, sX, d, Kloc, Pl, ld, lane);
-#pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    const int j = lane + 64 * s;
-                    if (j < jm) {
-                        for (int l = 0; l < Kloc; ++l) rr[s] = __builtin_fma((double)sL[l * ld + j], sq[d * Kloc + l], rr[s]);
-                    }
-                }
-                for (int i = 0; i < jm; ++i) {
-                    const int base = i * (i + 1) / 2;
-#pragma unroll
-                    for (int s = 0; s < NS; ++s) {
-                        const int j = lane + 64 * s;
-                        if (j <= i) {
-                            double acc = sC[base + j];
-                            for (int l = 0; l < Kloc; ++l) acc = __builtin_fma((double)sL[l * ld + i], sX[l * ld + j], acc);
-                            sC[base + j] = acc;
-                        }
-                    }
-                }
-                cond_wave_sync();
-            }
+            demo_build_M<NS>(a, im, Lb, lane, rr);
             // ---- M = C C^T in place, left-looking (lane + 64 s <-> row)
             for (int jc = 0; jc < Pl; ++jc) {
                 const double* cj = sC + jc * (jc + 1) / 2;
@@ -462,21 +276,24 @@ __global__ void __launch_bounds__(256) k_demo_log_prob(const DemoLogProbArgs a) 
 }
 
 #ifndef MPK_DEVICE_ONLY
-// the shapes the kernel takes; MPK_ENOTIMPL with the limit in the message otherwise (no HIP call)
-int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* wave_doubles_out, int* tc_out, int* scratch_out) {
+// the shapes the kernels of the information form take; MPK_ENOTIMPL with the limit in the message, under the entry's name fn, otherwise
+// (no HIP call)
+int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* wave_doubles_out, int* tc_out, int* scratch_out,
+                         const char* fn) {
+    const std::string name(fn);
     if (c.mp_type == MPK_MP_DMP || c.dmp_resp) {
-        set_error("mpk_demonstration_log_prob: a DMP has no probabilistic interface (promp / prodmp only)");
+        set_error(name + ": a DMP has no probabilistic interface (promp / prodmp only)");
         return MPK_ENOTIMPL;
     }
     if (c.D > kMaxD || c.KP > kMaxKP) {
-        set_error("mpk_demonstration_log_prob: at most " + std::to_string(kMaxD) + " DoF and " + std::to_string(kMaxKP) +
+        set_error(name + ": at most " + std::to_string(kMaxD) + " DoF and " + std::to_string(kMaxKP) +
                   " table columns (this handle: " + std::to_string(c.D) + " DoF, " + std::to_string(c.KT) +
                   " columns); the k_traj_wide shapes have no kernel here");
         return MPK_ENOTIMPL;
     }
     const size_t Pl = (size_t)c.D * c.Kloc;
     if (Pl > (size_t)64 * kDemoSlots) {
-        set_error("mpk_demonstration_log_prob: at most " + std::to_string(64 * kDemoSlots) + " non-phase parameters (this handle: " +
+        set_error(name + ": at most " + std::to_string(64 * kDemoSlots) + " non-phase parameters (this handle: " +
                   std::to_string(c.D) + " DoF x " + std::to_string(c.Kloc) + " = " + std::to_string(Pl) + ")");
         return MPK_ENOTIMPL;
     }
@@ -489,7 +306,7 @@ int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* 
     const size_t wave_doubles = Pl * (Pl + 1) / 2 + (size_t)c.D * c.Kloc * c.Kloc + 2 * Pl + scratch + (xw + 1) / 2 + 8;
     const size_t shared = (size_t)c.T * c.KT * sizeof(double) + 64;
     if (wave_doubles * sizeof(double) + shared > kLdsPerCu) {
-        set_error("mpk_demonstration_log_prob: the float64 images of " + std::to_string(Pl) + " parameters and " + std::to_string(c.T) +
+        set_error(name + ": the float64 images of " + std::to_string(Pl) + " parameters and " + std::to_string(c.T) +
                   " steps (" + std::to_string(wave_doubles * sizeof(double) + shared) + " bytes with one wave per workgroup) do not "
                   "fit the CU's " + std::to_string(kLdsPerCu) + " bytes of LDS");
         return MPK_ENOTIMPL;

@@ -1442,6 +1442,59 @@ int mpk_demonstration_log_prob_vjp(mpk_handle hh, const float* params, const flo
                                         obs_std, true, nullptr, g, g_params, g_params_L, B, stream);
 }
 
+// N(params, L L^T) conditioned on whole demonstrations in the information form: mpk_demonstration_log_prob's validation, refusals and
+// tables; one launch
+int mpk_demonstration_condition(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                                double init_time_shared, const float* pos, const float* obs_std, float* params_out,
+                                float* params_L_out, int32_t B, void* stream) {
+    const std::string name("mpk_demonstration_condition");
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!params || !params_L || !params_out || !params_L_out) { set_error(name + ": NULL params or params_L, in or out"); return MPK_EINVAL; }
+    if (!pos || !obs_std) { set_error(name + ": NULL pos or obs_std"); return MPK_EINVAL; }
+    if (B < 1) { set_error(name + ": B must be >= 1"); return MPK_EINVAL; }
+    if (h->cfg.learn_tau || h->cfg.learn_delay) {
+        set_error(name + ": a learned tau / delay gives every episode its own phase and its own table: only shared-phase handles have a "
+                  "conditioning kernel");
+        return MPK_ENOTIMPL;
+    }
+    int rc = demo_log_prob_limits(h->dev, nullptr, nullptr, nullptr, nullptr, nullptr, name.c_str());
+    if (rc != MPK_OK) return rc;
+    if (h->dev.D * h->dev.Kloc < 1) { set_error(name + ": the handle has no non-phase parameters"); return MPK_EINVAL; }
+    if ((!init_pos || !init_vel) && h->cfg.mp_type != MPK_MP_PROMP) {
+        set_error(name + ": init_pos and init_vel are required (only a ProMP may pass NULL: zeros)");
+        return MPK_EINVAL;
+    }
+    MPK_ON_DEVICE(h->cfg.device);
+    SharedTables st;
+    rc = get_shared(h, (float)init_time_shared, stream, &st);
+    if (rc != MPK_OK) return rc;
+    DemoCondLaunch q;
+    q.params = params; q.params_L = params_L; q.init_pos = init_pos; q.init_vel = init_vel; q.init_time = (float)init_time_shared;
+    q.pos = pos; q.obs_std = obs_std; q.params_out = params_out; q.params_L_out = params_L_out; q.B = B;
+    return launch_demo_condition(h->dev, st, q, h->num_cu, stream, &h->last_kernel);
+}
+
+// the launch plan of mpk_demonstration_condition for B episodes on this handle's device: no HIP call
+int mpk_demonstration_condition_plan(mpk_handle hh, int32_t B, int32_t* blocks, int32_t* waves, int32_t* lds_bytes) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (B < 1) { set_error("mpk_demonstration_condition_plan: B must be >= 1"); return MPK_EINVAL; }
+    if (h->cfg.learn_tau || h->cfg.learn_delay) {
+        set_error("mpk_demonstration_condition_plan: a learned tau / delay gives every episode its own phase and its own table: only "
+                  "shared-phase handles have a conditioning kernel");
+        return MPK_ENOTIMPL;
+    }
+    int nb = 0, nw = 0;
+    size_t lds = 0;
+    const int rc = demo_condition_launch_plan(h->dev, B, h->num_cu, &nb, &nw, &lds);
+    if (rc != MPK_OK) return rc;
+    if (blocks) *blocks = nb;
+    if (waves) *waves = nw;
+    if (lds_bytes) *lds_bytes = (int32_t)lds;
+    return MPK_OK;
+}
+
 int mpk_trajectory_actions(mpk_handle hh, const float* params, const float* init_pos, const float* init_vel,
                            double init_time_shared, const mpk_rollout_cfg* rc, const double* c_pos,
                            const double* c_vel, float* pos, float* vel, float* actions, int32_t B, void* stream) {

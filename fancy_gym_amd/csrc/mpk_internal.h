@@ -368,9 +368,25 @@ struct DemoLogProbLaunch {
     float *g_params = nullptr, *g_params_L = nullptr;
     int B = 0;
 };
-int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* wave_doubles_out, int* tc_out, int* scratch_out);
+int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* wave_doubles_out, int* tc_out, int* scratch_out,
+                         const char* fn = "mpk_demonstration_log_prob");
 int launch_demo_log_prob(const DevCfg& c, const SharedTables& st, const DemoLogProbLaunch& q, int num_cu, void* stream,
                          const char** kernel_name);
+// mpk_demonstration_condition (mpk_demo_condition.hip): N(params, L L^T) conditioned on the kept entries of whole demonstrations, in the
+// same information form -- M = K^T K from the last row (the reverse Cholesky), L' = tril(L) K^-1, mu' = mu + L' K^-T v: one launch of
+// k_demo_condition, one wave per episode, k_demo_log_prob's images and workgroups (demo_log_prob_limits refuses under this entry's name).
+// The outputs may be the inputs.  demo_condition_launch_plan: the workgroups, waves per workgroup and LDS bytes a launch of B episodes
+// takes (no HIP call; any output may be nullptr).
+struct DemoCondLaunch {
+    const float *params = nullptr, *params_L = nullptr, *init_pos = nullptr, *init_vel = nullptr;
+    float init_time = 0.f;                                              // the tables' (init_time_shared)
+    const float *pos = nullptr, *obs_std = nullptr;                     // [B, T, D]
+    float *params_out = nullptr, *params_L_out = nullptr;
+    int B = 0;
+};
+int demo_condition_launch_plan(const DevCfg& c, int B, int num_cu, int* blocks_out, int* waves_out, size_t* lds_out);
+int launch_demo_condition(const DevCfg& c, const SharedTables& st, const DemoCondLaunch& q, int num_cu, void* stream,
+                          const char** kernel_name);
 int launch_episode_reset(const double* init_q, const double* init_qd, double* q, double* qd, float* cond_pos,
                          float* cond_vel, int32_t* traj_steps, int32_t* plan_steps, uint8_t* done, int B, int D,
                          void* stream);

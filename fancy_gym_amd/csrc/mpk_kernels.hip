@@ -19,7 +19,9 @@
 //   mpk_traj_condition.hip   k_traj_condition: a Gaussian over the parameters conditioned on observed points (mpk_trajectory_condition)
 //   mpk_traj_log_prob.hip    k_traj_log_prob: the log-likelihood of observed points under that Gaussian and its gradient (mpk_trajectory_log_prob)
 //   mpk_demo_log_prob.hip    k_demo_log_prob: the log-likelihood of whole demonstrations in the Pl x Pl form and its gradient (mpk_demonstration_log_prob)
-//   mpk_cond_rows.h      the observed steps' float64 table rows and the wave-level LDS ordering, shared by the three units above
+//   mpk_demo_condition.hip   k_demo_condition: the Gaussian conditioned on whole demonstrations in the same form (mpk_demonstration_condition)
+//   mpk_demo_gram.h      the Gram accumulation and the packed M of the information form, shared by the two units above
+//   mpk_cond_rows.h      the observed steps' float64 table rows and the wave-level LDS ordering, shared by the five units above
 //   mpk_traj_phase.hip   per-episode phase kernels
 //   mpk_phase_fused.hip  per-episode phase: the fused entry points (actions, closed loop, replanning step, verbose < 2 step, validity gate)
 //   mpk_rollout.hip      rollout kernels
@@ -48,6 +50,7 @@
 #include "mpk_traj_condition.hip"
 #include "mpk_traj_log_prob.hip"
 #include "mpk_demo_log_prob.hip"
+#include "mpk_demo_condition.hip"
 #include "mpk_traj_phase.hip"
 #include "mpk_phase_fused.hip"
 #include "mpk_rollout.hip"

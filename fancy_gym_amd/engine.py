@@ -1096,6 +1096,56 @@ class TrajectoryEngine:
             L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
             return self._demo_log_prob_vjp_launch(g, mean, L, inputs, init_time, need)
 
+    def condition_on_demonstration(self, params, params_L, pos, obs_std, init_pos=None, init_vel=None, init_time: float = 0.0, *,
+                                   out: Optional[Sequence[torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """
+        The Gaussian ``N(params, L L^T)`` over the parameters conditioned on WHOLE demonstrations (mpk.h:
+        mpk_demonstration_condition), one launch: ``(params_post, params_L_post)`` [B, P], [B, Pl, Pl] float32 on the device, without
+        an autograd graph.  ``pos`` [B, T, D] and ``obs_std`` (a scalar, [D], [T, D] or [B, T, D]) are ``demonstration_log_prob``'s: an
+        entry is kept when ``0 < sigma < inf``, so an observed prefix of a movement is the rest at ``inf`` and missing samples are
+        ``inf`` one by one.  This is the information form of that likelihood -- the Gram matrices of the basis per DoF, the ``Pl x Pl``
+        matrix ``M = I + tril(L)^T G tril(L)`` factored from its last row, ``L' = tril(L) K^-1`` -- where ``condition`` applies at most
+        32 shared steps one scalar at a time: T D may be in the thousands.  The posterior factor is lower triangular with a
+        non-negative diagonal and an exactly zero upper triangle, a valid ``scale_tril``; ``params_L``'s strict upper triangle is never
+        read.  No entry kept returns the prior bit for bit.  ``sigma == 0`` cannot be expressed in this form: that episode's mean and
+        the lower triangle of its factor are NaN (``condition`` takes exact observations); non-finite inputs do the same and stay
+        inside their episode.  ``out=(params, params_L)`` gives the in-place form, validated as ``condition`` validates it.  A
+        ``params`` or ``params_L`` that requires grad is detached: there is no gradient through the posterior.  Refusals are
+        ``demonstration_log_prob``'s, raised before any launch.
+        """
+        fn = "condition_on_demonstration"
+        with torch.no_grad():                                       # (nothing here has a gradient: _demo_checks need not refuse one)
+            B = self._demo_checks(fn, params, params_L, pos, obs_std, init_pos, init_vel)
+        P = self.num_params
+        if out is not None:
+            if len(out) != 2:
+                raise ValueError(f"{fn}: out must be a pair (params, params_L) of tensors")
+            for i, (buf, shape) in enumerate(zip(out, ((B, P), (B, P, P)))):
+                if (not isinstance(buf, torch.Tensor) or tuple(buf.shape) != shape or buf.dtype != torch.float32
+                        or not buf.is_contiguous() or buf.device != self.device):
+                    raise ValueError(f"{fn}: out[{i}] must be a contiguous float32 tensor of shape {shape} on {self.device}")
+        ip, iv, y, sd = self._demo_inputs(fn, B, pos, obs_std, init_pos, init_vel)
+        with torch.no_grad():
+            mean = torch.as_tensor(params, dtype=torch.float32, device=self.device).detach().contiguous()
+            L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
+            if out is not None:
+                mean_out, L_out = out
+            else:
+                mean_out = torch.empty((B, P), dtype=torch.float32, device=self.device)
+                L_out = torch.empty((B, P, P), dtype=torch.float32, device=self.device)
+            _lib.check(self._lib.mpk_demonstration_condition(
+                self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time), y.data_ptr(), sd.data_ptr(),
+                mean_out.data_ptr(), L_out.data_ptr(), B, self._stream()))
+        return mean_out, L_out
+
+    def condition_on_demonstration_plan(self, B: int) -> Tuple[int, int, int]:
+        """``(workgroups, waves per workgroup, LDS bytes per workgroup)`` of a ``condition_on_demonstration`` launch of ``B`` episodes
+        (mpk.h: mpk_demonstration_condition_plan; nothing is launched): wave w of workgroup g takes the episodes ``g waves + w``,
+        ``+ workgroups waves``, ..."""
+        nb, nw, lds = C.c_int32(), C.c_int32(), C.c_int32()
+        _lib.check(self._lib.mpk_demonstration_condition_plan(self._h, int(B), C.byref(nb), C.byref(nw), C.byref(lds)))
+        return nb.value, nw.value, lds.value
+
     def sample_trajectories(self, params, params_L, init_pos, init_vel, init_time: float = 0.0, *, num_samples: int,
                             generator: Optional[torch.Generator] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """

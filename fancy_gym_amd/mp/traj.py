@@ -404,14 +404,9 @@ class MPInterface:
                                                obs_vel_std=sv)
         return float(lp[0])
 
-    def log_prob_of_trajectories(self, pos, std) -> torch.Tensor:
-        """
-        The log-likelihood of whole demonstrations under the stored Gaussian ``N(params, L L^T)`` plus observation noise
-        (``TrajectoryEngine.demonstration_log_prob``, one launch for all of them): ``pos`` [N, T, D] (or [T, D]: one demonstration) on
-        the current grid's T steps, ``std`` a scalar, [D], [T, D] or [N, T, D] (``inf`` removes an entry: missing samples, a prefix;
-        0 is not expressible here -- ``log_prob_of_observations`` takes exact observations).  Returns [N] float64 on the CPU; nothing
-        stored changes.  Needs ``set_params`` and ``set_mp_params_variances`` first.
-        """
+    def _demonstrations_on_grid(self, fn, kernel, pos, std):
+        """what ``log_prob_of_trajectories`` and ``condition_on_trajectories`` hand to the engine after their common refusals: the stored
+        mean and factor repeated per demonstration, ``pos`` as float32 [N, T, D], ``std``, the initial conditions repeated, init_time"""
         if self.mp_type == "dmp":
             raise NotImplementedError("a DMP has no probabilistic interface (ProMP / ProDMP only)")
         assert self.params is not None, "set_params() first"
@@ -420,26 +415,49 @@ class MPInterface:
         if self.duration is None or self.dt is None:
             raise RuntimeError("set_duration(duration, dt) must be called before demonstrations can be placed on its grid")
         if self.learn_tau or self.learn_delay:
-            raise NotImplementedError("log_prob_of_trajectories: this generator learns tau / delay, so the grid's phase is not shared; "
-                                      "only shared-phase generators have a likelihood kernel")
+            raise NotImplementedError(f"{fn}: this generator learns tau / delay, so the grid's phase is not shared; "
+                                      f"only shared-phase generators have {kernel}")
         D = self.num_dof
         y = pos.detach().cpu().numpy() if isinstance(pos, torch.Tensor) else np.asarray(pos)
         y = np.asarray(y, np.float32)
         if y.ndim == 2:
             y = y[None]
         if y.ndim != 3 or y.shape[2] != D:
-            raise ValueError(f"log_prob_of_trajectories: pos must be [N, T, {D}] or [T, {D}], got {y.shape}")
+            raise ValueError(f"{fn}: pos must be [N, T, {D}] or [T, {D}], got {y.shape}")
         N = y.shape[0]
         sd = std.detach().cpu().numpy() if isinstance(std, torch.Tensor) else np.asarray(std)
         sd = np.asarray(sd, np.float32)
         ip = self.init_pos if self.init_pos is not None else np.zeros(D, np.float32)
         iv = self.init_vel if self.init_vel is not None else np.zeros(D, np.float32)
         it = self.init_time if self.init_time is not None else 0.0
-        P = self.params.size
-        lp = self.engine().demonstration_log_prob(np.repeat(self.params.reshape(1, -1), N, 0), np.repeat(self.params_L[None], N, 0),
-                                                  np.ascontiguousarray(y), sd, np.repeat(np.asarray(ip, np.float32)[None], N, 0),
-                                                  np.repeat(np.asarray(iv, np.float32)[None], N, 0), float(it))
+        return (np.repeat(self.params.reshape(1, -1), N, 0), np.repeat(self.params_L[None], N, 0), np.ascontiguousarray(y), sd,
+                np.repeat(np.asarray(ip, np.float32)[None], N, 0), np.repeat(np.asarray(iv, np.float32)[None], N, 0), float(it))
+
+    def log_prob_of_trajectories(self, pos, std) -> torch.Tensor:
+        """
+        The log-likelihood of whole demonstrations under the stored Gaussian ``N(params, L L^T)`` plus observation noise
+        (``TrajectoryEngine.demonstration_log_prob``, one launch for all of them): ``pos`` [N, T, D] (or [T, D]: one demonstration) on
+        the current grid's T steps, ``std`` a scalar, [D], [T, D] or [N, T, D] (``inf`` removes an entry: missing samples, a prefix;
+        0 is not expressible here -- ``log_prob_of_observations`` takes exact observations).  Returns [N] float64 on the CPU; nothing
+        stored changes.  Needs ``set_params`` and ``set_mp_params_variances`` first.
+        """
+        args = self._demonstrations_on_grid("log_prob_of_trajectories", "a likelihood kernel", pos, std)      # (refusals before the engine)
+        lp = self.engine().demonstration_log_prob(*args)
         return lp.detach().cpu()
+
+    def condition_on_trajectories(self, pos, std):
+        """
+        Condition the stored Gaussian ``N(params, L L^T)`` on whole demonstrations (``TrajectoryEngine.condition_on_demonstration``,
+        one launch for all of them) WITHOUT replacing it: ``pos`` [N, T, D] (or [T, D]: one demonstration) on the current grid's T
+        steps, ``std`` a scalar, [D], [T, D] or [N, T, D] (``inf`` removes an entry: missing samples; a prefix is the rest at ``inf``;
+        0 is not expressible here -- ``condition_on_observations`` takes exact observations).  Returns ``(params [N, P], params_L
+        [N, Pl, Pl])`` float32 on the CPU, one posterior per demonstration, each from the stored prior -- the E-step of EM over N
+        demonstrations; ``set_params`` / ``set_mp_params_variances`` with row n make posterior n the stored one.  Needs ``set_params``
+        and ``set_mp_params_variances`` first.
+        """
+        args = self._demonstrations_on_grid("condition_on_trajectories", "a conditioning kernel", pos, std)    # (refusals before the engine)
+        mean, L = self.engine().condition_on_demonstration(*args)
+        return mean.detach().cpu(), L.detach().cpu()
 
     def sample_trajectories(self, num_smp: int = 1, generator: Optional[torch.Generator] = None):
         """``(pos, vel)`` [num_smp, T, D]: trajectories of parameters drawn from ``N(params, L L^T)``

@@ -1167,6 +1167,43 @@ int mpk_demonstration_log_prob_vjp(mpk_handle h, const float* params, const floa
                                float* g_params, float* g_params_L, int32_t B, void* stream);
 
 /*
+ * A Gaussian over the MP parameters conditioned on WHOLE demonstrations, for a handle with a SHARED phase (added within ABI 4; no existing
+ * prototype changes): the posterior of w ~ N(mu, L L^T) given the kept entries of pos -- an observed prefix of a movement with the rest at
+ * sigma = +inf, or a whole noisy demonstration with missing samples, the E-step of EM for a ProMP.  Every argument up to obs_std is
+ * mpk_demonstration_log_prob's, with its rule that an entry is kept when 0 < sigma < +inf, and so are G_d, q, M and v:
+ *     M = I + tril(L)^T G tril(L) = K^T K     K lower triangular: the reverse (UL) Cholesky, from the bottom-right corner
+ *     L'  = tril(L) K^-1                      lower triangular times lower triangular: diag L'_ii = L_ii / K_ii, no second factorisation
+ *     mu' = mu + L' (K^-T v)
+ * so that L' L'^T = tril(L) M^-1 tril(L)^T and mu' = mu + tril(L) M^-1 v, the batch formula Sigma - Sigma H^T S^-1 H Sigma,
+ * mu + Sigma H^T S^-1 r by the Woodbury identity; all float64, each output rounded to float32 once (mu' from the float64 L');
+ * L L^T is never formed and no two covariances are subtracted.
+ *   params_out    dev float [B, P]       out, the posterior mean;   may be params.  Entries outside the local block are copied
+ *   params_L_out  dev float [B, Pl, Pl]  out, the posterior factor; may be params_L (row i depends on row i of params_L only and is
+ *                                        read before it is written).  Lower triangular with a non-negative diagonal (given one), the
+ *                                        strict upper triangle written as exact zeros: a valid scale_tril
+ * The strict upper triangle of params_L is never read.  An episode with nothing kept comes back bit for bit (params copied, tril(L)
+ * copied).  sigma == 0 cannot be expressed in this form: that episode's local block of params_out and the lower triangle of its
+ * params_L_out are NaN, the upper triangle stays exact zero; use mpk_trajectory_condition for exact observations.  A pivot of K that is
+ * not > 0, or a K^-T v that is not finite (either needs a non-finite input), does the same.  No other episode changes.  An exactly zero
+ * column of tril(L) gives an exactly zero column of L'; an all-zero L returns params unchanged.
+ * One launch of k_demo_condition<promp | prodmp> (mpk_last_kernel) on `stream`, plus the table builder when (init_time_shared, T) is not
+ * cached; nothing is allocated or synchronised.  One wave per episode, no atomics, fixed summation orders: the same bits from run to
+ * run, for any alignment of the pointers, alone or in a batch; no index depends on a value that is read, so non-finite inputs never
+ * fault.
+ * MPK_EINVAL: a NULL handle, params, params_L, pos, obs_std or output; B < 1; init_pos / init_vel NULL for a ProDMP.  MPK_ENOTIMPL, before
+ * any launch, exactly where mpk_demonstration_log_prob refuses: a handle that learns tau / delay; a DMP; more than 16 DoF or 16 table
+ * columns; Pl > 256 (64 x 4); float64 images that exceed a CU's LDS with one wave per workgroup -- the kernel uses that entry's images
+ * and nothing else, so Pl = 160 (16 DoF x 10) runs and Pl = 256 does not.
+ * mpk_demonstration_condition_plan: the launch plan for B episodes, without any HIP call -- workgroups, waves (episodes in flight) per
+ * workgroup, LDS bytes per workgroup; any output may be NULL.  A workgroup's wave takes episodes b, b + blocks * waves, ...
+ * Not built: gradients through the posterior, velocities as observations, correlated noise, learned tau / delay.
+ */
+int mpk_demonstration_condition(mpk_handle h, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                                double init_time_shared, const float* pos, const float* obs_std, float* params_out,
+                                float* params_L_out, int32_t B, void* stream);
+int mpk_demonstration_condition_plan(mpk_handle h, int32_t B, int32_t* blocks, int32_t* waves, int32_t* lds_bytes);
+
+/*
  * The vector-Jacobian product of mpk_reacher_rollout (appended under ABI 4): controller, clip, torque double integrator and
  * SimpleReacher's reward transposed -- the gradient of any scalar loss of the step rewards and the final state w.r.t. the desired
  * trajectory, the plan-start state and the goal, one launch.  The forward it transposes (mpk_reacher_rollout above), per executed step
