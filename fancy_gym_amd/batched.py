@@ -638,6 +638,14 @@ class BatchedBlackBox:
         cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
         return self.engine.demonstration_log_prob(params, params_L, pos, obs_std, cond_pos.detach(), cond_vel.detach(), self._plan_time())
 
+    def demonstration_log_prob_given_timing(self, params, params_L, pos, obs_std):
+        """``demonstration_log_prob`` for a learned tau / delay (``TrajectoryEngine.demonstration_log_prob_given_timing``, one launch):
+        every episode at the tau / delay in front of its ``params`` row, the Gaussian over the non-phase parameters"""
+        cond_pos = self.condition_pos if self.condition_pos is not None else self.q.float()
+        cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
+        return self.engine.demonstration_log_prob_given_timing(params, params_L, pos, obs_std, cond_pos.detach(), cond_vel.detach(),
+                                                               self._plan_time())
+
     def condition_on_demonstration(self, params, params_L, pos, obs_std, *, out=None):
         """``(params, params_L)`` of the Gaussian ``N(params, L L^T)`` conditioned on whole demonstrations ``pos`` [B, T, D] of the plan
         (``TrajectoryEngine.condition_on_demonstration``, one launch; ``obs_std = inf`` removes an entry, so a prefix is the rest at
@@ -646,6 +654,14 @@ class BatchedBlackBox:
         cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
         return self.engine.condition_on_demonstration(params, params_L, pos, obs_std, cond_pos.detach(), cond_vel.detach(),
                                                       self._plan_time(), out=out)
+
+    def condition_on_demonstration_given_timing(self, params, params_L, pos, obs_std, *, out=None):
+        """``condition_on_demonstration`` for a learned tau / delay (``TrajectoryEngine.condition_on_demonstration_given_timing``, one
+        launch): every episode at the tau / delay in front of its ``params`` row, which come back as given"""
+        cond_pos = self.condition_pos if self.condition_pos is not None else self.q.float()
+        cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
+        return self.engine.condition_on_demonstration_given_timing(params, params_L, pos, obs_std, cond_pos.detach(), cond_vel.detach(),
+                                                                   self._plan_time(), out=out)
 
     def _carry_start(self):
         """replan_gradient="episode": (init_pos, init_vel, q_in, qd_in) of the next plan -- what the twins of the plan before give (the

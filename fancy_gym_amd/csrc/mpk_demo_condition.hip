@@ -63,7 +63,7 @@ __device__ __forceinline__ double demo_row_dot(const X* x, const double* sC, int
     return (x0 + x1) + (x2 + x3);
 }
 
-template <int MP, int NS>
+template <int MP, int NS, bool PHASE>
 __global__ void __launch_bounds__(256) k_demo_condition(const DemoCondArgs a) {
     extern __shared__ __attribute__((aligned(16))) double demo_cond_smem[];
     const DevCfg& c = a.c;
@@ -75,12 +75,17 @@ __global__ void __launch_bounds__(256) k_demo_condition(const DemoCondArgs a) {
     double* smu = im.sq;                                            // [Pl] q, then mu'
     const double* sy = im.sy;                                       // [Pl] mu
     float* srow = im.sL;                                            // [Pl] row i of tril(L)
-    demo_stage_tables<MP>(a, im, tid);
+    if (PHASE) {
+        phase_rows_stage<MP>(c, im.sK, im.sBT, tid, (int)blockDim.x);
+        __syncthreads();
+    } else {
+        demo_stage_tables<MP>(a, im, tid);
+    }
     const double nan = __builtin_nan("");
     for (int b = blockIdx.x * a.waves + wave; b < a.B; b += gridDim.x * a.waves) {
         const float* Lb = a.L + (size_t)b * Pl * Pl;
         float* Lo = a.L_out + (size_t)b * Pl * Pl;
-        const DemoSums sm = demo_accumulate<MP, false>(a, im, b, lane);
+        const DemoSums sm = demo_accumulate<MP, false, PHASE>(a, im, b, lane);
         const int n = sm.n;
         bool bad = sm.zero;                                         // (wave-uniform) a sigma == 0, a pivot that was not > 0, a t not finite
         double rr[NS], dg[NS];                                      // lane + 64 s <-> row i: v_i -> t_i; K[i][i]
@@ -237,10 +242,19 @@ __global__ void __launch_bounds__(256) k_demo_condition(const DemoCondArgs a) {
 
 #ifndef MPK_DEVICE_ONLY
 // the launch plan: k_demo_log_prob's images and workgroups (demo_log_prob_limits), refusals under this entry's name
-static int demo_condition_plan(const DevCfg& c, int B, int num_cu, DemoCondArgs* la, size_t* lds_out, int* blocks_out) {
+static int demo_condition_plan(const DevCfg& c, bool phase, const char* fn, int B, int num_cu, DemoCondArgs* la, size_t* lds_out,
+                               int* blocks_out) {
     size_t lds = 0;
-    const int rc = demo_log_prob_limits(c, &lds, &la->waves, &la->wave_doubles, &la->tc, &la->scratch, "mpk_demonstration_condition");
-    if (rc != MPK_OK) return rc;
+    if (phase) {
+        DemoPlan plan;
+        const int rc = demo_phase_limits(c, &plan, fn);
+        if (rc != MPK_OK) return rc;
+        demo_plan_args(plan, la);
+        lds = plan.lds;
+    } else {
+        const int rc = demo_log_prob_limits(c, &lds, &la->waves, &la->wave_doubles, &la->tc, &la->scratch, fn);
+        if (rc != MPK_OK) return rc;
+    }
     const int per_cu = (int)(kLdsPerCu / lds) < 1 ? 1 : ((int)(kLdsPerCu / lds) > 8 ? 8 : (int)(kLdsPerCu / lds));
     const long units = ((long)B + la->waves - 1) / la->waves;
     *blocks_out = (int)(units < (long)num_cu * per_cu ? units : (long)num_cu * per_cu);
@@ -248,11 +262,12 @@ static int demo_condition_plan(const DevCfg& c, int B, int num_cu, DemoCondArgs*
     return MPK_OK;
 }
 
-int demo_condition_launch_plan(const DevCfg& c, int B, int num_cu, int* blocks_out, int* waves_out, size_t* lds_out) {
+int demo_condition_launch_plan(const DevCfg& c, int B, int num_cu, int* blocks_out, int* waves_out, size_t* lds_out, bool phase) {
     DemoCondArgs la{};
     size_t lds = 0;
     int blocks = 0;
-    const int rc = demo_condition_plan(c, B, num_cu, &la, &lds, &blocks);
+    const int rc = demo_condition_plan(c, phase, phase ? "mpk_demonstration_phase_plan" : "mpk_demonstration_condition", B, num_cu, &la,
+                                       &lds, &blocks);
     if (rc != MPK_OK) return rc;
     if (blocks_out) *blocks_out = blocks;
     if (waves_out) *waves_out = la.waves;
@@ -260,14 +275,21 @@ int demo_condition_launch_plan(const DevCfg& c, int B, int num_cu, int* blocks_o
     return MPK_OK;
 }
 
-template <int MP>
+template <int MP, bool PHASE>
 static int launch_demo_condition_mp(const DemoCondArgs& la, int ns, int blocks, size_t lds, void* stream) {
     auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(64 * la.waves), lds, stream, la); };
     switch (ns) {
-        case 1: return go(k_demo_condition<MP, 1>);
-        case 2: return go(k_demo_condition<MP, 2>);
-        case 3: return go(k_demo_condition<MP, 3>);
-        default: return go(k_demo_condition<MP, 4>);
+        case 1: return go(k_demo_condition<MP, 1, PHASE>);
+        case 2: return go(k_demo_condition<MP, 2, PHASE>);
+        case 3: return go(k_demo_condition<MP, 3, PHASE>);
+        default:
+            // (Pl > 192 passes neither route's LDS limit; the per-episode route does not carry the instantiation)
+            if constexpr (PHASE) {
+                set_error("mpk_demonstration_phase_condition: internal: more than 192 non-phase parameters passed the LDS limit");
+                return MPK_ENOTIMPL;
+            } else {
+                return go(k_demo_condition<MP, 4, PHASE>);
+            }
     }
 }
 
@@ -276,18 +298,25 @@ int launch_demo_condition(const DevCfg& c, const SharedTables& st, const DemoCon
     DemoCondArgs la{};
     size_t lds = 0;
     int blocks = 0;
-    const int rc = demo_condition_plan(c, q.B, num_cu, &la, &lds, &blocks);
+    const int rc = demo_condition_plan(c, q.phase, q.phase ? "mpk_demonstration_phase_condition" : "mpk_demonstration_condition", q.B,
+                                       num_cu, &la, &lds, &blocks);
     if (rc != MPK_OK) return rc;
     const bool promp = c.mp_type == MPK_MP_PROMP;
+    la.flag = q.range_flag;
     la.c = c; la.A = st.A; la.aux = st.aux; la.TS = st.TS; la.init_time = q.init_time;
     la.params = q.params; la.L = q.params_L; la.init_pos = q.init_pos; la.init_vel = q.init_vel;
     la.pos = q.pos; la.sd = q.obs_std;
     la.params_out = q.params_out; la.L_out = q.params_L_out;
     la.B = q.B; la.Pl = c.D * c.Kloc; la.ld = la.Pl | 1;
     const int ns = (la.Pl + 63) / 64;
+    if (q.phase) {
+        *kernel_name = promp ? "k_demo_condition<promp, phase>" : "k_demo_condition<prodmp, phase>";
+        return promp ? launch_demo_condition_mp<MPK_MP_PROMP, true>(la, ns, blocks, lds, stream)
+                     : launch_demo_condition_mp<MPK_MP_PRODMP, true>(la, ns, blocks, lds, stream);
+    }
     *kernel_name = promp ? "k_demo_condition<promp>" : "k_demo_condition<prodmp>";
-    return promp ? launch_demo_condition_mp<MPK_MP_PROMP>(la, ns, blocks, lds, stream)
-                 : launch_demo_condition_mp<MPK_MP_PRODMP>(la, ns, blocks, lds, stream);
+    return promp ? launch_demo_condition_mp<MPK_MP_PROMP, false>(la, ns, blocks, lds, stream)
+                 : launch_demo_condition_mp<MPK_MP_PRODMP, false>(la, ns, blocks, lds, stream);
 }
 #endif  // MPK_DEVICE_ONLY
 

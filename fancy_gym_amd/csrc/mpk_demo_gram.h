@@ -3,10 +3,18 @@
 // the position rows, the accumulation of w, r, G_d, q and the per-DoF counts over the steps, and the packed lower triangle of
 // M = I + tril(L)^T blockdiag(G_d) tril(L) with v = tril(L)^T q.  Both kernels compile this text, so what they accumulate is the same
 // bits.  Notation and the LDS formula: mpk_demo_log_prob.hip.
+// Two row sources, a template flag PHASE on the accumulation and on both kernels.  PHASE = false: the phase all episodes share, the T rows
+// [T][KT] staged once per workgroup from the launch's table.  PHASE = true: a per-episode phase (tau / delay given at the front of the
+// episode's params row): no workgroup-wide row image; for each chunk of tc steps the wave evaluates its own episode's rows, lane <-> step,
+// with the forward's device functions (mpk_phase_rows.h, what k_phase_fit evaluates) into a per-wave float64 chunk image [tc][sl]:
+// Kloc entries regrouped by local parameter, then ca | cb | cc of the step's given part c[t, d] = ca init_pos[d] + cb init_vel[d] + cc.
+// The accumulation reads the chunk image where it reads rows + t KT otherwise; after G_d, q, the counts and the sums nothing knows where
+// the rows came from.
 #pragma once
 #include "mpk_tile.h"
 #include "mpk_vjp_row.h"
 #include "mpk_cond_rows.h"
+#include "mpk_phase_rows.h"
 
 namespace mpk {
 
@@ -30,7 +38,16 @@ struct DemoGramArgs {
     int scratch;           // float64 words of the X image / the chunk's w and r images: max(Kloc ld, 2 tc D)
     int waves;             // per workgroup
     int wave_doubles;      // float64 words of LDS per wave
+    // PHASE only (0 / nullptr otherwise)
+    int sl;                // words between the rows of the chunk image: Kloc + 3, odd
+    int chunk;             // float64 words of the chunk image: tc sl
+    int c_pad;             // floats of the workgroup's row constants (phase_rows_const_floats)
+    int32_t* flag;         // prodmp: raised beyond the pre-computed range (k_phase_fit's)
 };
+
+#ifndef MPK_DEVICE_ONLY
+void demo_plan_args(const DemoPlan& plan, DemoGramArgs* la);    // mpk_demo_log_prob.hip
+#endif
 
 // the LDS images of one wave, and the two the workgroup shares
 struct DemoImages {
@@ -43,12 +60,16 @@ struct DemoImages {
     int* snd;              // [D] kept observations per DoF
     double* rows;          // [T][KT] the position rows (per workgroup)
     int* kof;              // [Kloc] the table column read from local parameter l, or -1 (per workgroup)
+    double* sE;            // PHASE: [tc][sl] the chunk's rows by local parameter | ca cb cc (per wave)
+    float* sK;             // PHASE: the row constants (per workgroup; 8-byte aligned), then
+    float* sBT;            // PHASE: [T] the base times (per workgroup)
 };
 
 __device__ __forceinline__ DemoImages demo_images(const DemoGramArgs& a, double* smem, int wave) {
     const DevCfg& c = a.c;
     DemoImages im;
-    im.sC = smem + (size_t)wave * a.wave_doubles;
+    im.sE = smem + (size_t)wave * a.wave_doubles;
+    im.sC = im.sE + a.chunk;
     im.sG = im.sC + a.Pl * (a.Pl + 1) / 2;
     im.sq = im.sG + c.D * c.Kloc * c.Kloc;
     im.sy = im.sq + a.Pl;
@@ -57,6 +78,8 @@ __device__ __forceinline__ DemoImages demo_images(const DemoGramArgs& a, double*
     im.snd = (int*)(im.sL + ((c.Kloc * a.ld + 1) & ~1));
     im.rows = smem + (size_t)a.waves * a.wave_doubles;
     im.kof = (int*)(im.rows + c.T * c.KT);
+    im.sK = (float*)im.rows;
+    im.sBT = im.sK + a.c_pad;
     return im;
 }
 
@@ -134,7 +157,7 @@ struct DemoSums {
 };
 
 // episode b: mu to sy; w, r, then G_d, q and the per-DoF counts over the steps, a chunk at a time
-template <int MP, bool SUMS>
+template <int MP, bool SUMS, bool PHASE>
 __device__ __forceinline__ DemoSums demo_accumulate(const DemoGramArgs& a, const DemoImages& im, int b, int lane) {
     const DevCfg& c = a.c;
     const int D = c.D, Kloc = c.Kloc, Pl = a.Pl, T = c.T, KT = c.KT, tc = a.tc;
@@ -157,17 +180,41 @@ __device__ __forceinline__ DemoSums demo_accumulate(const DemoGramArgs& a, const
     bool zero_l = false;
     double* sw = im.sX;
     double* sr = im.sX + tc * D;
+    double* sE = im.sE;
+    const int sl = a.sl;
+    PhaseEpisode ep{};
+    if (PHASE) ep = phase_rows_episode<MP>(c, a.params + (size_t)b * c.P, a.init_time);
+    // (PHASE) which of the given columns exist: a ProDMP's init_pos / init_vel, a zero-padded ProMP's init_pos
+    const bool use_ip = a.init_pos && (MP == MPK_MP_PRODMP || KT > c.nb), use_iv = a.init_vel && MP == MPK_MP_PRODMP;
     for (int t0 = 0; t0 < T; t0 += tc) {
         const int nt = T - t0 < tc ? T - t0 : tc;
+        if (PHASE) {                                            // lane <-> step: this episode's rows of the chunk
+            for (int tt = lane; tt < nt; tt += 64) {
+                double e[kPhaseRowSlots], ca, cb, cg;
+                phase_rows_eval<MP>(c, ep, im.sK, im.sBT[t0 + tt], a.flag, e, ca, cb, cg);
+                double* er = sE + tt * sl;
+#pragma unroll
+                for (int k = 0; k < kPhaseRowSlots; ++k)
+                    if (k < Kloc) er[k] = e[k];
+                er[Kloc] = ca; er[Kloc + 1] = cb; er[Kloc + 2] = cg;
+            }
+            cond_wave_sync();
+        }
         for (int e = lane; e < nt * D; e += 64) {               // lane <-> (t, d): coalesced
             const int tt = e / D, d = e - tt * D;
             const size_t at = ((size_t)b * T + t0) * D + e;
             const double sig = (double)a.sd[at], yv = (double)a.pos[at];
             const bool keep = sig > 0.0 && sig != __builtin_inf();   // +inf, NaN, negative: not observed
             zero_l = zero_l || sig == 0.0;
-            const double* hr = rows + (t0 + tt) * KT;
+            const double* hr = PHASE ? sE + tt * sl : rows + (t0 + tt) * KT;
             double cc = 0.0, hmu = 0.0;
-            for (int k = 0; k < KT; ++k) {
+            if (PHASE) {
+                for (int l = 0; l < Kloc; ++l) hmu = __builtin_fma(hr[l], sy[d * Kloc + l], hmu);
+                cc = hr[Kloc + 2];
+                if (use_iv) cc = __builtin_fma(hr[Kloc + 1], (double)a.init_vel[(size_t)b * D + d], cc);
+                if (use_ip) cc = __builtin_fma(hr[Kloc], (double)a.init_pos[(size_t)b * D + d], cc);
+            }
+            for (int k = 0; !PHASE && k < KT; ++k) {
                 int loc;
                 const int kind = x_kind<MP>(c, k, &loc);
                 const double hk = hr[k];
@@ -199,11 +246,11 @@ __device__ __forceinline__ DemoSums demo_accumulate(const DemoGramArgs& a, const
             int k = 0;
             while ((k + 1) * (k + 2) / 2 <= rem) ++k;
             const int l = rem - k * (k + 1) / 2;
-            const int ck = kof[k], cl = kof[l];
+            const int ck = PHASE ? k : kof[k], cl = PHASE ? l : kof[l];
             double acc = sG[d * KK + k * Kloc + l];
             if (ck >= 0 && cl >= 0) {
                 for (int tt = 0; tt < nt; ++tt) {
-                    const double* hr = rows + (t0 + tt) * KT;
+                    const double* hr = PHASE ? sE + tt * sl : rows + (t0 + tt) * KT;
                     acc = __builtin_fma(sw[tt * D + d] * hr[ck], hr[cl], acc);
                 }
             }
@@ -211,10 +258,11 @@ __device__ __forceinline__ DemoSums demo_accumulate(const DemoGramArgs& a, const
             sG[d * KK + l * Kloc + k] = acc;
         }
         for (int row = lane; row < Pl; row += 64) {             // lane <-> row of q
-            const int d = row / Kloc, ck = kof[row - d * Kloc];
+            const int d = row / Kloc, ck = PHASE ? row - d * Kloc : kof[row - d * Kloc];
             double acc = sq[row];
             if (ck >= 0) {
-                for (int tt = 0; tt < nt; ++tt) acc = __builtin_fma(sw[tt * D + d] * sr[tt * D + d], rows[(t0 + tt) * KT + ck], acc);
+                for (int tt = 0; tt < nt; ++tt)
+                    acc = __builtin_fma(sw[tt * D + d] * sr[tt * D + d], PHASE ? sE[tt * sl + ck] : rows[(t0 + tt) * KT + ck], acc);
             }
             sq[row] = acc;
         }

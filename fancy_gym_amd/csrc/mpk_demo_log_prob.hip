@@ -48,7 +48,7 @@ struct DemoLogProbArgs : DemoGramArgs {
     float* g_L;            // [B, Pl, Pl] out or nullptr (GRAD)
 };
 
-template <int MP, int NS, bool GRAD>
+template <int MP, int NS, bool GRAD, bool PHASE>
 __global__ void __launch_bounds__(256) k_demo_log_prob(const DemoLogProbArgs a) {
     extern __shared__ __attribute__((aligned(16))) double demo_smem[];
     const DevCfg& c = a.c;
@@ -64,12 +64,17 @@ __global__ void __launch_bounds__(256) k_demo_log_prob(const DemoLogProbArgs a) 
     double* sX = im.sX;                                             // [Kloc][ld] X_d, then X_d M^-1; the accumulation's w | r [tc][D]
     float* sL = im.sL;                                              // [Kloc][ld] the rows of tril(L)'s block d
     int* snd = im.snd;                                              // [D] kept observations per DoF
-    demo_stage_tables<MP>(a, im, tid);                              // rows [T][KT], kof [Kloc]
+    if (PHASE) {                                                    // row constants, base times [T]
+        phase_rows_stage<MP>(c, im.sK, im.sBT, tid, (int)blockDim.x);
+        __syncthreads();
+    } else {
+        demo_stage_tables<MP>(a, im, tid);                          // rows [T][KT], kof [Kloc]
+    }
     const double nan = __builtin_nan("");
     for (int b = blockIdx.x * a.waves + wave; b < a.B; b += gridDim.x * a.waves) {
         const float* Lb = a.L + (size_t)b * Pl * Pl;
         // ---- w, r, then G, q over the steps, a chunk at a time (mpk_demo_gram.h)
-        const DemoSums sm = demo_accumulate<MP, true>(a, im, b, lane);
+        const DemoSums sm = demo_accumulate<MP, true, PHASE>(a, im, b, lane);
         const double ssum = sm.s, lsig = sm.lsig;
         const int n = sm.n;
         bool bad = sm.zero;                                         // (wave-uniform) a sigma == 0, or a pivot that was not > 0
@@ -278,8 +283,7 @@ __global__ void __launch_bounds__(256) k_demo_log_prob(const DemoLogProbArgs a) 
 #ifndef MPK_DEVICE_ONLY
 // the shapes the kernels of the information form take; MPK_ENOTIMPL with the limit in the message, under the entry's name fn, otherwise
 // (no HIP call)
-int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* wave_doubles_out, int* tc_out, int* scratch_out,
-                         const char* fn) {
+static int demo_limits(const DevCfg& c, bool phase, DemoPlan* plan, const char* fn) {
     const std::string name(fn);
     if (c.mp_type == MPK_MP_DMP || c.dmp_resp) {
         set_error(name + ": a DMP has no probabilistic interface (promp / prodmp only)");
@@ -297,14 +301,28 @@ int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* 
                   std::to_string(c.D) + " DoF x " + std::to_string(c.Kloc) + " = " + std::to_string(Pl) + ")");
         return MPK_ENOTIMPL;
     }
+    if (phase) {
+        // the row evaluation of mpk_phase_rows.h: 16 slots (a ProDMP: weights, goal and the two boundary columns, as k_traj_phase)
+        const bool prodmp = c.mp_type == MPK_MP_PRODMP;
+        const int need = prodmp ? c.nb + 3 : c.KT;
+        if (need > kPhaseRowSlots || c.Kloc > kPhaseRowSlots || c.D < 1 || !c.tab) {
+            set_error(name + ": at most " + std::to_string(kMaxD) + " DoF and " + std::to_string(kMaxKP) +
+                      " table columns (this handle: " + std::to_string(c.D) + " DoF, " + std::to_string(need) +
+                      " columns); the per-episode rows are those of the wave kernel k_traj_phase");
+            return MPK_ENOTIMPL;
+        }
+    }
     const size_t ld = Pl | 1;
     size_t tc = (size_t)c.Kloc * ld / (2 * (size_t)(c.D > 0 ? c.D : 1));
     if (tc < 32) tc = 32;
     if (tc > (size_t)c.T) tc = c.T > 0 ? c.T : 1;
     const size_t xw = (size_t)c.Kloc * ld, ch = 2 * tc * c.D;
     const size_t scratch = xw > ch ? xw : ch;
-    const size_t wave_doubles = Pl * (Pl + 1) / 2 + (size_t)c.D * c.Kloc * c.Kloc + 2 * Pl + scratch + (xw + 1) / 2 + 8;
-    const size_t shared = (size_t)c.T * c.KT * sizeof(double) + 64;
+    // the per-episode route: a chunk image [tc][sl] per wave; the workgroup keeps row constants and base times, no [T][KT] image
+    const size_t sl = phase ? (size_t)(c.Kloc + 3) | 1 : 0, chunk = tc * sl;
+    const size_t c_pad = phase ? (size_t)phase_rows_const_floats(c) : 0, t_pad = ((size_t)c.T + 3) / 4 * 4;
+    const size_t wave_doubles = Pl * (Pl + 1) / 2 + (size_t)c.D * c.Kloc * c.Kloc + 2 * Pl + scratch + (xw + 1) / 2 + 8 + chunk;
+    const size_t shared = phase ? (c_pad + t_pad) * sizeof(float) + 64 : (size_t)c.T * c.KT * sizeof(double) + 64;
     if (wave_doubles * sizeof(double) + shared > kLdsPerCu) {
         set_error(name + ": the float64 images of " + std::to_string(Pl) + " parameters and " + std::to_string(c.T) +
                   " steps (" + std::to_string(wave_doubles * sizeof(double) + shared) + " bytes with one wave per workgroup) do not "
@@ -320,32 +338,64 @@ int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* 
         const size_t on_cu = w * (kLdsPerCu / bytes);
         if (on_cu >= best_on_cu) { best = w; best_on_cu = on_cu; }
     }
-    if (lds_out) *lds_out = best * wave_doubles * sizeof(double) + shared;
-    if (waves_out) *waves_out = best;
-    if (wave_doubles_out) *wave_doubles_out = (int)wave_doubles;
-    if (tc_out) *tc_out = (int)tc;
-    if (scratch_out) *scratch_out = (int)scratch;
+    if (plan) {
+        plan->lds = best * wave_doubles * sizeof(double) + shared;
+        plan->waves = best; plan->wave_doubles = (int)wave_doubles; plan->tc = (int)tc; plan->scratch = (int)scratch;
+        plan->sl = (int)sl; plan->chunk = (int)chunk; plan->c_pad = (int)c_pad;
+    }
     return MPK_OK;
 }
 
-template <int MP, bool GRAD>
+int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* wave_doubles_out, int* tc_out, int* scratch_out,
+                         const char* fn) {
+    DemoPlan plan;
+    const int rc = demo_limits(c, false, &plan, fn);
+    if (rc != MPK_OK) return rc;
+    if (lds_out) *lds_out = plan.lds;
+    if (waves_out) *waves_out = plan.waves;
+    if (wave_doubles_out) *wave_doubles_out = plan.wave_doubles;
+    if (tc_out) *tc_out = plan.tc;
+    if (scratch_out) *scratch_out = plan.scratch;
+    return MPK_OK;
+}
+
+// the per-episode-phase route's limits: the same images plus the chunk image per wave, row constants and base times per workgroup
+int demo_phase_limits(const DevCfg& c, DemoPlan* plan, const char* fn) { return demo_limits(c, true, plan, fn); }
+
+void demo_plan_args(const DemoPlan& plan, DemoGramArgs* la) {
+    la->waves = plan.waves; la->wave_doubles = plan.wave_doubles; la->tc = plan.tc; la->scratch = plan.scratch;
+    la->sl = plan.sl; la->chunk = plan.chunk; la->c_pad = plan.c_pad;
+}
+
+template <int MP, bool GRAD, bool PHASE>
 static int launch_demo_log_prob_mp(const DemoLogProbArgs& la, int ns, int blocks, size_t lds, void* stream) {
     auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(64 * la.waves), lds, stream, la); };
     switch (ns) {
-        case 1: return go(k_demo_log_prob<MP, 1, GRAD>);
-        case 2: return go(k_demo_log_prob<MP, 2, GRAD>);
-        case 3: return go(k_demo_log_prob<MP, 3, GRAD>);
-        default: return go(k_demo_log_prob<MP, 4, GRAD>);
+        case 1: return go(k_demo_log_prob<MP, 1, GRAD, PHASE>);
+        case 2: return go(k_demo_log_prob<MP, 2, GRAD, PHASE>);
+        case 3: return go(k_demo_log_prob<MP, 3, GRAD, PHASE>);
+        default:
+            // (Pl > 192 passes neither route's LDS limit; the per-episode route does not carry the instantiation)
+            if constexpr (PHASE) {
+                set_error("mpk_demonstration_phase_log_prob: internal: more than 192 non-phase parameters passed the LDS limit");
+                return MPK_ENOTIMPL;
+            } else {
+                return go(k_demo_log_prob<MP, 4, GRAD, PHASE>);
+            }
     }
 }
 
 int launch_demo_log_prob(const DevCfg& c, const SharedTables& st, const DemoLogProbLaunch& q, int num_cu, void* stream,
                          const char** kernel_name) {
     DemoLogProbArgs la{};
-    size_t lds = 0;
-    const int rc = demo_log_prob_limits(c, &lds, &la.waves, &la.wave_doubles, &la.tc, &la.scratch);
+    DemoPlan plan;
+    const int rc = q.phase ? demo_phase_limits(c, &plan, q.grad ? "mpk_demonstration_phase_log_prob_vjp" : "mpk_demonstration_phase_log_prob")
+                           : demo_limits(c, false, &plan, "mpk_demonstration_log_prob");
     if (rc != MPK_OK) return rc;
+    demo_plan_args(plan, &la);
+    const size_t lds = plan.lds;
     const bool promp = c.mp_type == MPK_MP_PROMP;
+    la.flag = q.range_flag;
     la.c = c; la.A = st.A; la.aux = st.aux; la.TS = st.TS; la.init_time = q.init_time;
     la.params = q.params; la.L = q.params_L; la.init_pos = q.init_pos; la.init_vel = q.init_vel;
     la.pos = q.pos; la.sd = q.obs_std;
@@ -355,14 +405,24 @@ int launch_demo_log_prob(const DevCfg& c, const SharedTables& st, const DemoLogP
     const long units = ((long)q.B + la.waves - 1) / la.waves;
     const int blocks = (int)(units < (long)num_cu * per_cu ? units : (long)num_cu * per_cu);
     const int ns = (la.Pl + 63) / 64;
+    if (q.phase) {
+        if (q.grad) {
+            *kernel_name = promp ? "k_demo_log_prob<promp, phase, grad>" : "k_demo_log_prob<prodmp, phase, grad>";
+            return promp ? launch_demo_log_prob_mp<MPK_MP_PROMP, true, true>(la, ns, blocks, lds, stream)
+                         : launch_demo_log_prob_mp<MPK_MP_PRODMP, true, true>(la, ns, blocks, lds, stream);
+        }
+        *kernel_name = promp ? "k_demo_log_prob<promp, phase>" : "k_demo_log_prob<prodmp, phase>";
+        return promp ? launch_demo_log_prob_mp<MPK_MP_PROMP, false, true>(la, ns, blocks, lds, stream)
+                     : launch_demo_log_prob_mp<MPK_MP_PRODMP, false, true>(la, ns, blocks, lds, stream);
+    }
     if (q.grad) {
         *kernel_name = promp ? "k_demo_log_prob<promp, grad>" : "k_demo_log_prob<prodmp, grad>";
-        return promp ? launch_demo_log_prob_mp<MPK_MP_PROMP, true>(la, ns, blocks, lds, stream)
-                     : launch_demo_log_prob_mp<MPK_MP_PRODMP, true>(la, ns, blocks, lds, stream);
+        return promp ? launch_demo_log_prob_mp<MPK_MP_PROMP, true, false>(la, ns, blocks, lds, stream)
+                     : launch_demo_log_prob_mp<MPK_MP_PRODMP, true, false>(la, ns, blocks, lds, stream);
     }
     *kernel_name = promp ? "k_demo_log_prob<promp>" : "k_demo_log_prob<prodmp>";
-    return promp ? launch_demo_log_prob_mp<MPK_MP_PROMP, false>(la, ns, blocks, lds, stream)
-                 : launch_demo_log_prob_mp<MPK_MP_PRODMP, false>(la, ns, blocks, lds, stream);
+    return promp ? launch_demo_log_prob_mp<MPK_MP_PROMP, false, false>(la, ns, blocks, lds, stream)
+                 : launch_demo_log_prob_mp<MPK_MP_PRODMP, false, false>(la, ns, blocks, lds, stream);
 }
 #endif  // MPK_DEVICE_ONLY
 

@@ -655,6 +655,13 @@ int mpk_create(const mpk_config* cfg, mpk_handle* out) {
             if (cfg->auto_scale_basis) sc = (float)t.scale[k] * sc;
             packed.push_back((double)sc);
         }
+        // the same scales as FLOAT64 products (appended: nothing before them moves): the per-episode-phase likelihood kernels
+        // (mpk_phase_rows.h) read these -- a column scale that is 4e-8 off moves every row of that column the same way, which a
+        // likelihood at small sigma turns into the prior precision times that shift
+        for (int k = 0; k <= cfg->num_basis; ++k) {
+            const double sc = (double)(k < cfg->num_basis ? (float)cfg->weights_scale : (float)cfg->goal_scale);
+            packed.push_back(cfg->auto_scale_basis ? t.scale[k] * sc : sc);
+        }
         // row table for the per-episode-phase kernel, one table index per row of 2*KS + 4 floats (KS = 8 or 16):
         //   [(Psi_0, dPsi_0) (Psi_1, dPsi_1) .. (Psi_{KS-3}, dPsi_{KS-3}) | y1 y2 dy1 dy2]
         // the position / velocity basis values as fp32 PAIRS (columns past nb are 0) -- the operand pairs of the packed fp32
@@ -1488,6 +1495,103 @@ int mpk_demonstration_condition_plan(mpk_handle hh, int32_t B, int32_t* blocks, 
     int nb = 0, nw = 0;
     size_t lds = 0;
     const int rc = demo_condition_launch_plan(h->dev, B, h->num_cu, &nb, &nw, &lds);
+    if (rc != MPK_OK) return rc;
+    if (blocks) *blocks = nb;
+    if (waves) *waves = nw;
+    if (lds_bytes) *lds_bytes = (int32_t)lds;
+    return MPK_OK;
+}
+
+// ---- the demonstration entries with a per-episode phase: tau / delay given at the front of every params row
+// what the three launches refuse, before any launch: a shared-phase handle, then demo_phase_limits (a DMP, the shapes), no non-phase
+// parameters, a ProDMP without init_pos / init_vel
+static int demonstration_phase_checks(const std::string& name, Handle* h, const float* init_pos, const float* init_vel) {
+    if (!h->cfg.learn_tau && !h->cfg.learn_delay) {
+        set_error(name + ": this handle learns neither tau nor delay: every episode has the handle's phase, which is what the shared-phase "
+                  "entry (without _phase) evaluates");
+        return MPK_ENOTIMPL;
+    }
+    const int rc = demo_phase_limits(h->dev, nullptr, name.c_str());
+    if (rc != MPK_OK) return rc;
+    if (h->dev.D * h->dev.Kloc < 1) { set_error(name + ": the handle has no non-phase parameters"); return MPK_EINVAL; }
+    if ((!init_pos || !init_vel) && h->cfg.mp_type != MPK_MP_PROMP) {
+        set_error(name + ": init_pos and init_vel are required (only a ProMP may pass NULL: zeros)");
+        return MPK_EINVAL;
+    }
+    return MPK_OK;
+}
+
+static int demonstration_phase_log_prob_entry(const char* fn, mpk_handle hh, const float* params, const float* params_L,
+                                              const float* init_pos, const float* init_vel, double init_time_shared, const float* pos,
+                                              const float* obs_std, bool grad, double* log_prob, const double* g, float* g_params,
+                                              float* g_params_L, int32_t B, void* stream) {
+    const std::string name(fn);
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!params || !params_L) { set_error(name + ": NULL params or params_L"); return MPK_EINVAL; }
+    if (!pos || !obs_std) { set_error(name + ": NULL pos or obs_std"); return MPK_EINVAL; }
+    if (!grad && !log_prob) { set_error(name + ": NULL log_prob"); return MPK_EINVAL; }
+    if (grad && !g) { set_error(name + ": NULL g"); return MPK_EINVAL; }
+    if (grad && !g_params && !g_params_L) { set_error(name + ": g_params and g_params_L are both NULL: nothing to compute"); return MPK_EINVAL; }
+    if (B < 1) { set_error(name + ": B must be >= 1"); return MPK_EINVAL; }
+    const int rc = demonstration_phase_checks(name, h, init_pos, init_vel);
+    if (rc != MPK_OK) return rc;
+    MPK_ON_DEVICE(h->cfg.device);
+    DemoLogProbLaunch q;
+    q.params = params; q.params_L = params_L; q.init_pos = init_pos; q.init_vel = init_vel; q.init_time = (float)init_time_shared;
+    q.pos = pos; q.obs_std = obs_std;
+    q.grad = grad; q.log_prob = log_prob; q.g = g; q.g_params = g_params; q.g_params_L = g_params_L; q.B = B;
+    q.phase = true; q.range_flag = h->d_flag;
+    return launch_demo_log_prob(h->dev, SharedTables{}, q, h->num_cu, stream, &h->last_kernel);
+}
+
+int mpk_demonstration_phase_log_prob(mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
+                                     const float* init_vel, double init_time_shared, const float* pos, const float* obs_std,
+                                     double* log_prob, int32_t B, void* stream) {
+    return demonstration_phase_log_prob_entry("mpk_demonstration_phase_log_prob", hh, params, params_L, init_pos, init_vel,
+                                              init_time_shared, pos, obs_std, false, log_prob, nullptr, nullptr, nullptr, B, stream);
+}
+
+int mpk_demonstration_phase_log_prob_vjp(mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
+                                         const float* init_vel, double init_time_shared, const float* pos, const float* obs_std,
+                                         const double* g, float* g_params, float* g_params_L, int32_t B, void* stream) {
+    return demonstration_phase_log_prob_entry("mpk_demonstration_phase_log_prob_vjp", hh, params, params_L, init_pos, init_vel,
+                                              init_time_shared, pos, obs_std, true, nullptr, g, g_params, g_params_L, B, stream);
+}
+
+int mpk_demonstration_phase_condition(mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
+                                      const float* init_vel, double init_time_shared, const float* pos, const float* obs_std,
+                                      float* params_out, float* params_L_out, int32_t B, void* stream) {
+    const std::string name("mpk_demonstration_phase_condition");
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!params || !params_L || !params_out || !params_L_out) { set_error(name + ": NULL params or params_L, in or out"); return MPK_EINVAL; }
+    if (!pos || !obs_std) { set_error(name + ": NULL pos or obs_std"); return MPK_EINVAL; }
+    if (B < 1) { set_error(name + ": B must be >= 1"); return MPK_EINVAL; }
+    const int rc = demonstration_phase_checks(name, h, init_pos, init_vel);
+    if (rc != MPK_OK) return rc;
+    MPK_ON_DEVICE(h->cfg.device);
+    DemoCondLaunch q;
+    q.params = params; q.params_L = params_L; q.init_pos = init_pos; q.init_vel = init_vel; q.init_time = (float)init_time_shared;
+    q.pos = pos; q.obs_std = obs_std; q.params_out = params_out; q.params_L_out = params_L_out; q.B = B;
+    q.phase = true; q.range_flag = h->d_flag;
+    return launch_demo_condition(h->dev, SharedTables{}, q, h->num_cu, stream, &h->last_kernel);
+}
+
+// the launch plan of the three entries above for B episodes on this handle's device: no HIP call
+int mpk_demonstration_phase_plan(mpk_handle hh, int32_t B, int32_t* blocks, int32_t* waves, int32_t* lds_bytes) {
+    const std::string name("mpk_demonstration_phase_plan");
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (B < 1) { set_error(name + ": B must be >= 1"); return MPK_EINVAL; }
+    if (!h->cfg.learn_tau && !h->cfg.learn_delay) {
+        set_error(name + ": this handle learns neither tau nor delay: every episode has the handle's phase, which is what the shared-phase "
+                  "entry (without _phase) evaluates");
+        return MPK_ENOTIMPL;
+    }
+    int nb = 0, nw = 0;
+    size_t lds = 0;
+    const int rc = demo_condition_launch_plan(h->dev, B, h->num_cu, &nb, &nw, &lds, true);
     if (rc != MPK_OK) return rc;
     if (blocks) *blocks = nb;
     if (waves) *waves = nw;

@@ -367,11 +367,24 @@ struct DemoLogProbLaunch {
     const double* g = nullptr;                                          // [B]
     float *g_params = nullptr, *g_params_L = nullptr;
     int B = 0;
+    bool phase = false;                                                 // the per-episode-phase route (below)
+    int32_t* range_flag = nullptr;                                      // phase, ProDMP: raised beyond the pre-computed range
 };
 int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* wave_doubles_out, int* tc_out, int* scratch_out,
                          const char* fn = "mpk_demonstration_log_prob");
 int launch_demo_log_prob(const DevCfg& c, const SharedTables& st, const DemoLogProbLaunch& q, int num_cu, void* stream,
                          const char** kernel_name);
+// mpk_demonstration_phase_* : the same two kernels with a PER-EPISODE row source (template flag PHASE) for handles that learn tau / delay:
+// the tau / delay of episode b are given at the front of params[b], clipped as the forward clips them; the wave evaluates its episode's
+// rows a chunk of steps at a time (mpk_phase_rows.h, k_phase_fit's row evaluation) into a chunk image of its own, and no shared table is
+// read (st is ignored).  demo_phase_limits: demo_log_prob_limits' refusals in the same words -- with the chunk image [tc][(Kloc + 3) | 1]
+// added per wave and [T][KT] replaced by row constants and base times per workgroup -- plus rows beyond k_traj_phase's 16 slots.
+struct DemoPlan {
+    size_t lds = 0;                                                     // bytes per workgroup
+    int waves = 0, wave_doubles = 0, tc = 0, scratch = 0;
+    int sl = 0, chunk = 0, c_pad = 0;                                   // the phase route's (0 otherwise)
+};
+int demo_phase_limits(const DevCfg& c, DemoPlan* plan, const char* fn);
 // mpk_demonstration_condition (mpk_demo_condition.hip): N(params, L L^T) conditioned on the kept entries of whole demonstrations, in the
 // same information form -- M = K^T K from the last row (the reverse Cholesky), L' = tril(L) K^-1, mu' = mu + L' K^-T v: one launch of
 // k_demo_condition, one wave per episode, k_demo_log_prob's images and workgroups (demo_log_prob_limits refuses under this entry's name).
@@ -383,8 +396,10 @@ struct DemoCondLaunch {
     const float *pos = nullptr, *obs_std = nullptr;                     // [B, T, D]
     float *params_out = nullptr, *params_L_out = nullptr;
     int B = 0;
+    bool phase = false;                                                 // the per-episode-phase route
+    int32_t* range_flag = nullptr;
 };
-int demo_condition_launch_plan(const DevCfg& c, int B, int num_cu, int* blocks_out, int* waves_out, size_t* lds_out);
+int demo_condition_launch_plan(const DevCfg& c, int B, int num_cu, int* blocks_out, int* waves_out, size_t* lds_out, bool phase = false);
 int launch_demo_condition(const DevCfg& c, const SharedTables& st, const DemoCondLaunch& q, int num_cu, void* stream,
                           const char** kernel_name);
 int launch_episode_reset(const double* init_q, const double* init_qd, double* q, double* qd, float* cond_pos,

@@ -146,20 +146,22 @@ class _TrajectoryLogProbFn(torch.autograd.Function):
 class _DemonstrationLogProbFn(torch.autograd.Function):
     """``TrajectoryEngine.demonstration_log_prob`` with a backward: forward = the mpk_demonstration_log_prob launch as without autograd,
     backward = one mpk_demonstration_log_prob_vjp launch, which recomputes the Gram matrices and the factorisation from the forward's
-    inputs; the demonstrations, their standard deviations and the initial conditions get no gradient"""
+    inputs; the demonstrations, their standard deviations and the initial conditions get no gradient.  ``phase``: the per-episode-phase
+    route (``timing="given"``: mpk_demonstration_phase_log_prob / _vjp), whose backward leaves exact zeros in the phase columns"""
 
     @staticmethod
-    def forward(ctx, engine, inputs, init_time, params, params_L):
-        ctx.engine, ctx.inputs, ctx.init_time = engine, inputs, init_time
+    def forward(ctx, engine, inputs, init_time, params, params_L, phase=False):
+        ctx.engine, ctx.inputs, ctx.init_time, ctx.phase = engine, inputs, init_time, phase
         ctx.save_for_backward(params, params_L)
-        return engine._demo_log_prob_launch(params, params_L, inputs, init_time)
+        return engine._demo_log_prob_launch(params, params_L, inputs, init_time, phase)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         params, params_L = ctx.saved_tensors
-        g_params, g_L = ctx.engine._demo_log_prob_vjp_launch(g, params, params_L, ctx.inputs, ctx.init_time, ctx.needs_input_grad[3:5])
-        return None, None, None, g_params, g_L
+        g_params, g_L = ctx.engine._demo_log_prob_vjp_launch(g, params, params_L, ctx.inputs, ctx.init_time, ctx.needs_input_grad[3:5],
+                                                             ctx.phase)
+        return None, None, None, g_params, g_L, None
 
 
 class _ReacherRolloutFn(torch.autograd.Function):
@@ -1004,12 +1006,48 @@ class TrajectoryEngine:
             L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
             return self._log_prob_vjp_launch(g, mean, L, steps, inputs, init_time, need)
 
-    def _demo_checks(self, fn, params, params_L, pos, obs_std, init_pos, init_vel):
+    def _timing_given(self, fn, timing) -> bool:
+        """``timing=None | "given"`` of the demonstration entry points: True for the per-episode-phase route"""
+        if timing is None:
+            return False
+        if timing != "given":
+            raise ValueError(f"{fn}: timing must be None or \"given\" (the tau / delay at the front of every params row are that "
+                             f"episode's own), got {timing!r}")
+        if not (self.config.learn_tau or self.config.learn_delay):
+            raise ValueError(f"{fn}: timing=\"given\" on a handle that learns neither tau nor delay: every episode has the handle's phase "
+                             "already; call without timing")
+        return True
+
+    def _demo_phase_checks(self, fn, params, params_L, init_pos, init_vel):
+        """``_obs_checks`` for ``timing="given"``: the Gaussian is over the Pl = P - n_phase non-phase parameters; returns B"""
+        if self.mp_type == "dmp":
+            raise NotImplementedError(f"{fn}: a DMP has no probabilistic interface (promp / prodmp only)")
+        D, P = self.num_dof, self.num_params
+        Pl = P - self._num_phase_params()
+        if D > 16:
+            raise NotImplementedError(f"{fn}: at most 16 DoF and 16 table columns (this handle: {D} DoF)")
+        pshape = tuple(params.shape) if hasattr(params, "shape") else np.shape(params)
+        if len(pshape) != 2 or pshape[0] < 1 or pshape[1] != P:
+            raise ValueError(f"{fn}: params must be [B, {P}] (tau / delay in front, then the mean), got {pshape}")
+        B = pshape[0]
+        lshape = tuple(params_L.shape) if hasattr(params_L, "shape") else np.shape(params_L)
+        if lshape != (B, Pl, Pl):
+            raise ValueError(f"{fn}: params_L must be [{B}, Pl, Pl] with Pl = {Pl} (the factor of the {Pl} non-phase parameters' "
+                             f"covariance; the timing is given, not distributed), got {lshape}")
+        if (init_pos is None or init_vel is None) and self.mp_type != "promp":
+            raise ValueError(f"{fn}: init_pos / init_vel may be None only for a ProMP, which ignores them; a {self.mp_type} starts from "
+                             "them")
+        return B
+
+    def _demo_checks(self, fn, params, params_L, pos, obs_std, init_pos, init_vel, phase=False):
         """the refusals of ``demonstration_log_prob`` / ``demonstration_log_prob_vjp`` -- ``trajectory_log_prob``'s (``_obs_checks``)
         plus the demonstrations' shape and the inputs that have no gradient, all before anything touches the device; returns B"""
         if pos is None or obs_std is None:
             raise ValueError(f"{fn}: pos and obs_std are both required (the demonstrations with their standard deviations)")
-        B, _ = self._obs_checks(fn, "a likelihood kernel", params, params_L, (), pos, obs_std, init_pos, init_vel, None, None)
+        if phase:
+            B = self._demo_phase_checks(fn, params, params_L, init_pos, init_vel)
+        else:
+            B, _ = self._obs_checks(fn, "a likelihood kernel", params, params_L, (), pos, obs_std, init_pos, init_vel, None, None)
         T, D = self.num_steps, self.num_dof
         shape = tuple(pos.shape) if hasattr(pos, "shape") else np.shape(pos)
         if shape != (B, T, D):
@@ -1030,26 +1068,29 @@ class TrajectoryEngine:
                     None if init_vel is None else self._f32(init_vel, (B, D)).detach(),
                     self._f32(pos, (B, T, D)).detach(), self._obs_bcast(fn, obs_std, "obs_std", B, T))
 
-    def _demo_log_prob_launch(self, mean, L, inputs, init_time):
+    def _demo_log_prob_launch(self, mean, L, inputs, init_time, phase=False):
         ip, iv, y, sd = inputs
         out = torch.empty((mean.shape[0],), dtype=torch.float64, device=self.device)
-        _lib.check(self._lib.mpk_demonstration_log_prob(
+        entry = self._lib.mpk_demonstration_phase_log_prob if phase else self._lib.mpk_demonstration_log_prob
+        _lib.check(entry(
             self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time), y.data_ptr(), sd.data_ptr(), out.data_ptr(),
             mean.shape[0], self._stream()))
         return out
 
-    def _demo_log_prob_vjp_launch(self, g, mean, L, inputs, init_time, need):
+    def _demo_log_prob_vjp_launch(self, g, mean, L, inputs, init_time, need, phase=False):
         ip, iv, y, sd = inputs
         B, P = mean.shape
+        Pl = L.shape[1]
         g = torch.as_tensor(g, dtype=torch.float64, device=self.device).detach()
         if tuple(g.shape) != (B,):
             raise ValueError(f"demonstration_log_prob_vjp: g must be [{B}], got {tuple(g.shape)}")
         g = g.contiguous()
         g_mean = torch.empty((B, P), dtype=torch.float32, device=self.device) if need[0] else None
-        g_L = torch.empty((B, P, P), dtype=torch.float32, device=self.device) if need[1] else None
+        g_L = torch.empty((B, Pl, Pl), dtype=torch.float32, device=self.device) if need[1] else None
         if g_mean is None and g_L is None:
             return None, None
-        _lib.check(self._lib.mpk_demonstration_log_prob_vjp(
+        entry = self._lib.mpk_demonstration_phase_log_prob_vjp if phase else self._lib.mpk_demonstration_log_prob_vjp
+        _lib.check(entry(
             self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time), y.data_ptr(), sd.data_ptr(), g.data_ptr(),
             _dptr(g_mean), _dptr(g_L), B, self._stream()))
         return g_mean, g_L
@@ -1071,14 +1112,37 @@ class TrajectoryEngine:
         them that requires grad is a NotImplementedError, not a silent cut.  ``params_L``'s strict upper triangle is never read.
         Refusals are ``trajectory_log_prob``'s, raised before any launch (shapes, a learned tau / delay, a DMP, more than 16 DoF,
         ``init_pos`` / ``init_vel`` None on a ProDMP), plus ValueError for a ``pos`` that is not [B, T, D] with T the handle's steps.
+        A handle that learns tau / delay refuses here; ``demonstration_log_prob_given_timing`` is its entry point.
         """
-        B = self._demo_checks("demonstration_log_prob", params, params_L, pos, obs_std, init_pos, init_vel)
-        inputs = self._demo_inputs("demonstration_log_prob", B, pos, obs_std, init_pos, init_vel)
+        return self._demonstration_log_prob("demonstration_log_prob", None, params, params_L, pos, obs_std, init_pos, init_vel, init_time)
+
+    def demonstration_log_prob_given_timing(self, params, params_L, pos, obs_std, init_pos=None, init_vel=None,
+                                            init_time: float = 0.0) -> torch.Tensor:
+        """
+        ``demonstration_log_prob`` with every episode's timing GIVEN (mpk.h: mpk_demonstration_phase_log_prob), for a handle that
+        learns tau and / or delay, one launch: the tau / delay of episode b are the values at the front of its ``params`` row,
+        exactly where ``trajectory`` reads them and clipped to the handle's bounds as it clips them -- demonstrations of different
+        durations, each scored at its own timing.  They are given, not distributed: the Gaussian is over the ``Pl = P - n_phase``
+        non-phase parameters, ``params[b, n_phase:]`` its mean and ``params_L`` [B, Pl, Pl] its factor.  Everything else is
+        ``demonstration_log_prob``'s: the rule for kept entries, 0.0 for nothing kept, NaN for a ``sigma == 0``, autograd with ONE
+        backward launch (mpk_demonstration_phase_log_prob_vjp).  Timing is an input, not a random variable: the phase columns of
+        ``params.grad`` are exact zeros (no gradient w.r.t. tau / delay is built).  ``init_time`` stays one float for the batch.  A
+        ProDMP timing beyond the pre-computed range makes ``check_range`` raise.  A shared-phase handle is a ValueError (it has
+        ``demonstration_log_prob``); a ``params_L`` that is not [B, Pl, Pl] is a ValueError that names Pl; the other refusals are
+        ``demonstration_log_prob``'s, all before any launch.
+        """
+        return self._demonstration_log_prob("demonstration_log_prob_given_timing", "given", params, params_L, pos, obs_std, init_pos,
+                                            init_vel, init_time)
+
+    def _demonstration_log_prob(self, fn, timing, params, params_L, pos, obs_std, init_pos, init_vel, init_time):
+        phase = self._timing_given(fn, timing)
+        B = self._demo_checks(fn, params, params_L, pos, obs_std, init_pos, init_vel, phase)
+        inputs = self._demo_inputs(fn, B, pos, obs_std, init_pos, init_vel)
         mean = torch.as_tensor(params, dtype=torch.float32, device=self.device)
         L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device)
         if torch.is_grad_enabled() and (mean.requires_grad or L.requires_grad):
-            return _DemonstrationLogProbFn.apply(self, inputs, float(init_time), mean.contiguous(), L.contiguous())
-        return self._demo_log_prob_launch(mean.detach().contiguous(), L.detach().contiguous(), inputs, init_time)
+            return _DemonstrationLogProbFn.apply(self, inputs, float(init_time), mean.contiguous(), L.contiguous(), phase)
+        return self._demo_log_prob_launch(mean.detach().contiguous(), L.detach().contiguous(), inputs, init_time, phase)
 
     def demonstration_log_prob_vjp(self, g, params, params_L, pos, obs_std, init_pos=None, init_vel=None, init_time: float = 0.0, *,
                                    need: Sequence[bool] = (True, True)) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
@@ -1089,12 +1153,28 @@ class TrajectoryEngine:
         triangle is exact zeros, and so are the rows of a DoF none of whose entries remain; an episode with a ``sigma == 0`` gets NaN
         rows (use ``trajectory_log_prob`` for exact observations).  ``need[i]`` False: that output is not computed (None in its place).
         """
-        B = self._demo_checks("demonstration_log_prob_vjp", params, params_L, pos, obs_std, init_pos, init_vel)
-        inputs = self._demo_inputs("demonstration_log_prob_vjp", B, pos, obs_std, init_pos, init_vel)
+        return self._demonstration_log_prob_vjp("demonstration_log_prob_vjp", None, g, params, params_L, pos, obs_std, init_pos, init_vel,
+                                                init_time, need)
+
+    def demonstration_log_prob_vjp_given_timing(self, g, params, params_L, pos, obs_std, init_pos=None, init_vel=None,
+                                                init_time: float = 0.0, *, need: Sequence[bool] = (True, True)
+                                                ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """
+        The vector-Jacobian product of ``demonstration_log_prob_given_timing`` (mpk.h: mpk_demonstration_phase_log_prob_vjp), one
+        launch: ``(g_params [B, P], g_params_L [B, Pl, Pl])`` as ``demonstration_log_prob_vjp`` returns them, with ``Pl = P - n_phase``.
+        The phase columns of ``g_params`` are exact zeros: the likelihood is differentiated at the given timing.
+        """
+        return self._demonstration_log_prob_vjp("demonstration_log_prob_vjp_given_timing", "given", g, params, params_L, pos, obs_std,
+                                                init_pos, init_vel, init_time, need)
+
+    def _demonstration_log_prob_vjp(self, fn, timing, g, params, params_L, pos, obs_std, init_pos, init_vel, init_time, need):
+        phase = self._timing_given(fn, timing)
+        B = self._demo_checks(fn, params, params_L, pos, obs_std, init_pos, init_vel, phase)
+        inputs = self._demo_inputs(fn, B, pos, obs_std, init_pos, init_vel)
         with torch.no_grad():
             mean = torch.as_tensor(params, dtype=torch.float32, device=self.device).detach().contiguous()
             L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
-            return self._demo_log_prob_vjp_launch(g, mean, L, inputs, init_time, need)
+            return self._demo_log_prob_vjp_launch(g, mean, L, inputs, init_time, need, phase)
 
     def condition_on_demonstration(self, params, params_L, pos, obs_std, init_pos=None, init_vel=None, init_time: float = 0.0, *,
                                    out: Optional[Sequence[torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -1111,16 +1191,37 @@ class TrajectoryEngine:
         the lower triangle of its factor are NaN (``condition`` takes exact observations); non-finite inputs do the same and stay
         inside their episode.  ``out=(params, params_L)`` gives the in-place form, validated as ``condition`` validates it.  A
         ``params`` or ``params_L`` that requires grad is detached: there is no gradient through the posterior.  Refusals are
-        ``demonstration_log_prob``'s, raised before any launch.
+        ``demonstration_log_prob``'s, raised before any launch.  A handle that learns tau / delay refuses here;
+        ``condition_on_demonstration_given_timing`` is its entry point.
         """
-        fn = "condition_on_demonstration"
+        return self._condition_on_demonstration("condition_on_demonstration", None, params, params_L, pos, obs_std, init_pos, init_vel,
+                                                init_time, out)
+
+    def condition_on_demonstration_given_timing(self, params, params_L, pos, obs_std, init_pos=None, init_vel=None,
+                                                init_time: float = 0.0, *,
+                                                out: Optional[Sequence[torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """
+        ``condition_on_demonstration`` with every episode's timing GIVEN (mpk.h: mpk_demonstration_phase_condition), for a handle that
+        learns tau and / or delay, one launch: every episode is conditioned at its own tau / delay, the values at the front of its
+        ``params`` row (clipped to the handle's bounds as ``trajectory`` clips them) -- the E-step of EM over demonstrations of
+        different durations, prediction from a prefix at the movement's own speed.  The Gaussian is over the ``Pl = P - n_phase``
+        non-phase parameters: ``params_L`` and the returned factor are [B, Pl, Pl]; the phase columns of the posterior ``params``
+        are the inputs' bits, unclipped.  ``out=(params, params_L)`` gives the in-place form.  Refusals are
+        ``demonstration_log_prob_given_timing``'s, raised before any launch.
+        """
+        return self._condition_on_demonstration("condition_on_demonstration_given_timing", "given", params, params_L, pos, obs_std,
+                                                init_pos, init_vel, init_time, out)
+
+    def _condition_on_demonstration(self, fn, timing, params, params_L, pos, obs_std, init_pos, init_vel, init_time, out):
+        phase = self._timing_given(fn, timing)
         with torch.no_grad():                                       # (nothing here has a gradient: _demo_checks need not refuse one)
-            B = self._demo_checks(fn, params, params_L, pos, obs_std, init_pos, init_vel)
+            B = self._demo_checks(fn, params, params_L, pos, obs_std, init_pos, init_vel, phase)
         P = self.num_params
+        Pl = P - self._num_phase_params() if phase else P
         if out is not None:
             if len(out) != 2:
                 raise ValueError(f"{fn}: out must be a pair (params, params_L) of tensors")
-            for i, (buf, shape) in enumerate(zip(out, ((B, P), (B, P, P)))):
+            for i, (buf, shape) in enumerate(zip(out, ((B, P), (B, Pl, Pl)))):
                 if (not isinstance(buf, torch.Tensor) or tuple(buf.shape) != shape or buf.dtype != torch.float32
                         or not buf.is_contiguous() or buf.device != self.device):
                     raise ValueError(f"{fn}: out[{i}] must be a contiguous float32 tensor of shape {shape} on {self.device}")
@@ -1132,18 +1233,21 @@ class TrajectoryEngine:
                 mean_out, L_out = out
             else:
                 mean_out = torch.empty((B, P), dtype=torch.float32, device=self.device)
-                L_out = torch.empty((B, P, P), dtype=torch.float32, device=self.device)
-            _lib.check(self._lib.mpk_demonstration_condition(
+                L_out = torch.empty((B, Pl, Pl), dtype=torch.float32, device=self.device)
+            entry = self._lib.mpk_demonstration_phase_condition if phase else self._lib.mpk_demonstration_condition
+            _lib.check(entry(
                 self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time), y.data_ptr(), sd.data_ptr(),
                 mean_out.data_ptr(), L_out.data_ptr(), B, self._stream()))
         return mean_out, L_out
 
-    def condition_on_demonstration_plan(self, B: int) -> Tuple[int, int, int]:
+    def condition_on_demonstration_plan(self, B: int, *, timing: Optional[str] = None) -> Tuple[int, int, int]:
         """``(workgroups, waves per workgroup, LDS bytes per workgroup)`` of a ``condition_on_demonstration`` launch of ``B`` episodes
         (mpk.h: mpk_demonstration_condition_plan; nothing is launched): wave w of workgroup g takes the episodes ``g waves + w``,
-        ``+ workgroups waves``, ..."""
+        ``+ workgroups waves``, ...  ``timing="given"``: the plan of the per-episode-phase launches (mpk_demonstration_phase_plan)"""
         nb, nw, lds = C.c_int32(), C.c_int32(), C.c_int32()
-        _lib.check(self._lib.mpk_demonstration_condition_plan(self._h, int(B), C.byref(nb), C.byref(nw), C.byref(lds)))
+        entry = (self._lib.mpk_demonstration_phase_plan if self._timing_given("condition_on_demonstration_plan", timing)
+                 else self._lib.mpk_demonstration_condition_plan)
+        _lib.check(entry(self._h, int(B), C.byref(nb), C.byref(nw), C.byref(lds)))
         return nb.value, nw.value, lds.value
 
     def sample_trajectories(self, params, params_L, init_pos, init_vel, init_time: float = 0.0, *, num_samples: int,

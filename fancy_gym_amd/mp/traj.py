@@ -404,9 +404,10 @@ class MPInterface:
                                                obs_vel_std=sv)
         return float(lp[0])
 
-    def _demonstrations_on_grid(self, fn, kernel, pos, std):
+    def _demonstrations_on_grid(self, fn, kernel, pos, std, timing=None, phase_params=None):
         """what ``log_prob_of_trajectories`` and ``condition_on_trajectories`` hand to the engine after their common refusals: the stored
-        mean and factor repeated per demonstration, ``pos`` as float32 [N, T, D], ``std``, the initial conditions repeated, init_time"""
+        mean and factor repeated per demonstration, ``pos`` as float32 [N, T, D], ``std``, the initial conditions repeated, init_time.
+        ``timing`` not None: the rows are ``[tau?, delay?, mean]`` -- the stored tau / delay, or row n of ``phase_params`` [N, n_phase]"""
         if self.mp_type == "dmp":
             raise NotImplementedError("a DMP has no probabilistic interface (ProMP / ProDMP only)")
         assert self.params is not None, "set_params() first"
@@ -414,9 +415,12 @@ class MPInterface:
             raise RuntimeError("set_mp_params_variances(params_L) first")
         if self.duration is None or self.dt is None:
             raise RuntimeError("set_duration(duration, dt) must be called before demonstrations can be placed on its grid")
-        if self.learn_tau or self.learn_delay:
+        if (self.learn_tau or self.learn_delay) and timing is None:
             raise NotImplementedError(f"{fn}: this generator learns tau / delay, so the grid's phase is not shared; "
                                       f"only shared-phase generators have {kernel}")
+        if timing is not None and not (self.learn_tau or self.learn_delay):
+            raise ValueError(f"{fn}: this generator learns neither tau nor delay: every demonstration has its phase already; call "
+                             "without _given_timing")
         D = self.num_dof
         y = pos.detach().cpu().numpy() if isinstance(pos, torch.Tensor) else np.asarray(pos)
         y = np.asarray(y, np.float32)
@@ -430,7 +434,16 @@ class MPInterface:
         ip = self.init_pos if self.init_pos is not None else np.zeros(D, np.float32)
         iv = self.init_vel if self.init_vel is not None else np.zeros(D, np.float32)
         it = self.init_time if self.init_time is not None else 0.0
-        return (np.repeat(self.params.reshape(1, -1), N, 0), np.repeat(self.params_L[None], N, 0), np.ascontiguousarray(y), sd,
+        rows = np.repeat(self.params.reshape(1, -1), N, 0)
+        if timing is not None:
+            rows = np.repeat(self._full_params()[None], N, 0)
+            if phase_params is not None:
+                ph = phase_params.detach().cpu().numpy() if isinstance(phase_params, torch.Tensor) else np.asarray(phase_params)
+                n_phase = rows.shape[1] - self.params.size
+                if ph.shape != (N, n_phase):
+                    raise ValueError(f"{fn}: phase_params must be [{N}, {n_phase}] (tau / delay per demonstration), got {ph.shape}")
+                rows[:, :n_phase] = np.asarray(ph, np.float32)
+        return (rows, np.repeat(self.params_L[None], N, 0), np.ascontiguousarray(y), sd,
                 np.repeat(np.asarray(ip, np.float32)[None], N, 0), np.repeat(np.asarray(iv, np.float32)[None], N, 0), float(it))
 
     def log_prob_of_trajectories(self, pos, std) -> torch.Tensor:
@@ -439,10 +452,23 @@ class MPInterface:
         (``TrajectoryEngine.demonstration_log_prob``, one launch for all of them): ``pos`` [N, T, D] (or [T, D]: one demonstration) on
         the current grid's T steps, ``std`` a scalar, [D], [T, D] or [N, T, D] (``inf`` removes an entry: missing samples, a prefix;
         0 is not expressible here -- ``log_prob_of_observations`` takes exact observations).  Returns [N] float64 on the CPU; nothing
-        stored changes.  Needs ``set_params`` and ``set_mp_params_variances`` first.
+        stored changes.  Needs ``set_params`` and ``set_mp_params_variances`` first.  A generator that learns tau / delay refuses
+        here: ``log_prob_of_trajectories_given_timing`` is its entry point.
         """
         args = self._demonstrations_on_grid("log_prob_of_trajectories", "a likelihood kernel", pos, std)      # (refusals before the engine)
         lp = self.engine().demonstration_log_prob(*args)
+        return lp.detach().cpu()
+
+    def log_prob_of_trajectories_given_timing(self, pos, std, phase_params=None) -> torch.Tensor:
+        """
+        ``log_prob_of_trajectories`` for a generator that learns tau / delay
+        (``TrajectoryEngine.demonstration_log_prob_given_timing``, one launch): demonstration n is scored at the tau / delay of row n
+        of ``phase_params`` [N, n_phase] -- demonstrations of different durations, each at its own timing -- or, without
+        ``phase_params``, every one at the stored tau / delay.  The stored Gaussian is over the non-phase parameters.
+        """
+        args = self._demonstrations_on_grid("log_prob_of_trajectories_given_timing", "a likelihood kernel", pos, std, "given",
+                                            phase_params)                                                     # (refusals before the engine)
+        lp = self.engine().demonstration_log_prob_given_timing(*args)
         return lp.detach().cpu()
 
     def condition_on_trajectories(self, pos, std):
@@ -453,10 +479,23 @@ class MPInterface:
         0 is not expressible here -- ``condition_on_observations`` takes exact observations).  Returns ``(params [N, P], params_L
         [N, Pl, Pl])`` float32 on the CPU, one posterior per demonstration, each from the stored prior -- the E-step of EM over N
         demonstrations; ``set_params`` / ``set_mp_params_variances`` with row n make posterior n the stored one.  Needs ``set_params``
-        and ``set_mp_params_variances`` first.
+        and ``set_mp_params_variances`` first.  A generator that learns tau / delay refuses here:
+        ``condition_on_trajectories_given_timing`` is its entry point.
         """
         args = self._demonstrations_on_grid("condition_on_trajectories", "a conditioning kernel", pos, std)    # (refusals before the engine)
         mean, L = self.engine().condition_on_demonstration(*args)
+        return mean.detach().cpu(), L.detach().cpu()
+
+    def condition_on_trajectories_given_timing(self, pos, std, phase_params=None):
+        """
+        ``condition_on_trajectories`` for a generator that learns tau / delay
+        (``TrajectoryEngine.condition_on_demonstration_given_timing``, one launch): demonstration n is conditioned at the tau / delay
+        of row n of ``phase_params`` [N, n_phase], or, without ``phase_params``, every one at the stored tau / delay.  Returns
+        ``(params [N, P], params_L [N, Pl, Pl])``: the rows of ``params`` carry those timings in front, as ``set_params`` takes them.
+        """
+        args = self._demonstrations_on_grid("condition_on_trajectories_given_timing", "a conditioning kernel", pos, std, "given",
+                                            phase_params)                                                      # (refusals before the engine)
+        mean, L = self.engine().condition_on_demonstration_given_timing(*args)
         return mean.detach().cpu(), L.detach().cpu()
 
     def sample_trajectories(self, num_smp: int = 1, generator: Optional[torch.Generator] = None):

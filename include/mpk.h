@@ -1204,6 +1204,61 @@ int mpk_demonstration_condition(mpk_handle h, const float* params, const float* 
 int mpk_demonstration_condition_plan(mpk_handle h, int32_t B, int32_t* blocks, int32_t* waves, int32_t* lds_bytes);
 
 /*
+ * The three demonstration entries above for a handle that LEARNS tau and / or delay (ProMP, ProDMP), with every episode's timing GIVEN
+ * (added within ABI 4; no existing prototype changes): demonstrations that do not all last equally long, each scored or conditioned at its
+ * own tau / delay -- maximum likelihood of a shared mean and scale_tril over time-aligned demonstrations, the E-step of EM, prediction
+ * from a prefix at the movement's own speed.  They stand in for the reference's ProMP / ProDMP with learn_tau / learn_delay evaluated at
+ * one (tau, delay) per episode: mp_pytorch's set_params + get_traj_pos design at that episode's phase, with torch.distributions'
+ * MultivariateNormal(log_prob) and the Gaussian conditioning formula above it.
+ *   params      dev float [B, P]        the tau / delay of episode b in front, params[b, :n_phase], exactly where mpk_trajectory reads
+ *                                       them; then the mean of the Gaussian over the Pl = P - n_phase non-phase parameters
+ *   params_L    dev float [B, Pl, Pl]   its factor; the lower triangle is read
+ * The timing is given, not distributed: the Gaussian is over the Pl non-phase parameters only.  Clipping: the row of step t is evaluated
+ * at tau = min(max(params[b, 0], tau_lo), tau_hi) and delay clipped likewise, the handle's bounds, exactly as mpk_trajectory and
+ * mpk_trajectory_phase_fit clip them (np.clip(action, low, high)); a NaN clips to the lower bound.  Where the values leave -- the front
+ * of mpk_demonstration_phase_condition's params_out -- they leave as given, unclipped and bit for bit.  init_time_shared is one value for
+ * the batch.  Every other argument, the rule that an entry is kept when 0 < sigma < +inf, and every formula are those of the
+ * shared-phase entry of the same name without _phase:
+ *     y_td = psi_t(tau_b, delay_b) . w_d + c_td + eps     c_td = ca_t init_pos_d + cb_t init_vel_d + cc_t
+ *     log_prob = -1/2 (s - z.z) - 1/2 (lsig + 2 sum log C_ii) - (n / 2) log 2 pi          (mpk_demonstration_log_prob)
+ *     g_params[off + .] = g gm      g_params_L = g tril(gm (tril(L)^T gm)^T - X M^-1)     (mpk_demonstration_log_prob_vjp)
+ *     L' = tril(L) K^-1             mu' = mu + L' (K^-T v)                                (mpk_demonstration_condition)
+ * with psi_t the episode's own position row regrouped by parameter: for a ProMP the normalised RBFs at the episode's phase times
+ * weights_scale (a zero-padded basis adds init_pos: ca = 1); for a ProDMP Psi_k - xi1 Psi_k(t_b) - xi2 dPsi_k(t_b) times the column's
+ * scale at the pre-computed row nearest to the scaled time, ca = xi1 (plus the goal's row under relative_goal), cb = tau xi2, cc the
+ * goal offset times the goal's row -- the row evaluation of mpk_trajectory_phase_fit at the same table index, but from the float64
+ * tables with float64 column scales (a likelihood at small sigma multiplies a float32 scale's 4e-8 by the prior precision).  The
+ * likelihood is differentiated AT the given
+ * timing: the phase columns of g_params are exact zeros (there is no gradient w.r.t. tau / delay).
+ * n = 0 gives exactly 0.0, zero gradients, and params / tril(params_L) back bit for bit; sigma == 0 or a non-finite input makes that
+ * episode NaN and no other; the strict upper triangle of params_L is never read and leaves as exact zeros; params_out / params_L_out may
+ * be the inputs.  One launch of k_demo_log_prob<promp | prodmp, phase[, grad]> or k_demo_condition<promp | prodmp, phase>
+ * (mpk_last_kernel) on `stream`: no table is built or read, nothing is allocated or synchronised.  One wave per episode; the wave
+ * evaluates its episode's rows a chunk of steps at a time into an LDS image of its own.  No atomics on results, fixed summation orders:
+ * the same bits from run to run, for any alignment, alone or in a batch.  A ProDMP step whose scaled time lies beyond the pre-computed
+ * range raises the handle's range flag (mpk_check_range) as mpk_trajectory_phase_fit does.
+ * mpk_demonstration_phase_plan: the launch plan for B episodes without any HIP call -- workgroups, waves (episodes in flight) per
+ * workgroup, LDS bytes per workgroup; any output may be NULL.
+ * MPK_EINVAL: a NULL handle, params, params_L, pos, obs_std, log_prob, g, an output, or both gradient outputs; B < 1; init_pos /
+ * init_vel NULL for a ProDMP.  MPK_ENOTIMPL, before any launch: a handle that learns neither tau nor delay (use the shared-phase entry);
+ * a DMP; more than 16 DoF or 16 table columns; Pl > 256 (64 x 4); float64 images that exceed a CU's LDS with one wave per workgroup --
+ * per wave 8 (Pl (Pl + 1) / 2 + D Kloc^2 + 2 Pl + max(Kloc (Pl | 1), 2 tc D) + tc ((Kloc + 3) | 1)) + 4 Kloc (Pl | 1) + 64, per workgroup
+ * the row constants and 4 T bytes of base times: Pl = 160 (16 DoF x 10) runs with one wave on a CU, Pl = 224 does not.
+ * Not built: gradients w.r.t. tau / delay, per-episode init_time, velocities as observations, a learned phase in the via-point entries
+ * (mpk_trajectory_condition / _log_prob / _std), DMP.
+ */
+int mpk_demonstration_phase_log_prob(mpk_handle h, const float* params, const float* params_L, const float* init_pos,
+                                     const float* init_vel, double init_time_shared, const float* pos, const float* obs_std,
+                                     double* log_prob, int32_t B, void* stream);
+int mpk_demonstration_phase_log_prob_vjp(mpk_handle h, const float* params, const float* params_L, const float* init_pos,
+                                         const float* init_vel, double init_time_shared, const float* pos, const float* obs_std,
+                                         const double* g, float* g_params, float* g_params_L, int32_t B, void* stream);
+int mpk_demonstration_phase_condition(mpk_handle h, const float* params, const float* params_L, const float* init_pos,
+                                      const float* init_vel, double init_time_shared, const float* pos, const float* obs_std,
+                                      float* params_out, float* params_L_out, int32_t B, void* stream);
+int mpk_demonstration_phase_plan(mpk_handle h, int32_t B, int32_t* blocks, int32_t* waves, int32_t* lds_bytes);
+
+/*
  * The vector-Jacobian product of mpk_reacher_rollout (appended under ABI 4): controller, clip, torque double integrator and
  * SimpleReacher's reward transposed -- the gradient of any scalar loss of the step rewards and the final state w.r.t. the desired
  * trajectory, the plan-start state and the goal, one launch.  The forward it transposes (mpk_reacher_rollout above), per executed step
