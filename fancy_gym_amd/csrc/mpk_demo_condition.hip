@@ -1,6 +1,7 @@
 // k_demo_condition: the Gaussian N(mu, L L^T) over the MP parameters conditioned on WHOLE demonstrations [B, T, D]
 // (mpk_demonstration_condition) -- the information (Pl x Pl) form of mpk_demo_log_prob.hip, leaving as a valid scale_tril
 #include "mpk_demo_gram.h"
+#include "mpk_gauss_launch.h"
 
 namespace mpk {
 
@@ -241,82 +242,61 @@ __global__ void __launch_bounds__(256) k_demo_condition(const DemoCondArgs a) {
 }
 
 #ifndef MPK_DEVICE_ONLY
-// the launch plan: k_demo_log_prob's images and workgroups (demo_log_prob_limits), refusals under this entry's name
-static int demo_condition_plan(const DevCfg& c, bool phase, const char* fn, int B, int num_cu, DemoCondArgs* la, size_t* lds_out,
-                               int* blocks_out) {
-    size_t lds = 0;
-    if (phase) {
-        DemoPlan plan;
-        const int rc = demo_phase_limits(c, &plan, fn);
-        if (rc != MPK_OK) return rc;
-        demo_plan_args(plan, la);
-        lds = plan.lds;
-    } else {
-        const int rc = demo_log_prob_limits(c, &lds, &la->waves, &la->wave_doubles, &la->tc, &la->scratch, fn);
-        if (rc != MPK_OK) return rc;
-    }
-    const int per_cu = (int)(kLdsPerCu / lds) < 1 ? 1 : ((int)(kLdsPerCu / lds) > 8 ? 8 : (int)(kLdsPerCu / lds));
-    const long units = ((long)B + la->waves - 1) / la->waves;
-    *blocks_out = (int)(units < (long)num_cu * per_cu ? units : (long)num_cu * per_cu);
-    *lds_out = lds;
+// the launch plan: k_demo_log_prob's images (its limits, refusing under the entry's name fn) and workgroups
+static int demo_condition_plan(const DevCfg& c, bool phase, const char* fn, int B, int num_cu, DemoPlan* plan, int* blocks_out) {
+    const int rc = phase ? demo_phase_limits(c, plan, fn) : demo_log_prob_limits(c, plan, fn);
+    if (rc != MPK_OK) return rc;
+    *blocks_out = gauss_blocks(B, plan->waves, plan->lds, num_cu);
     return MPK_OK;
 }
 
-int demo_condition_launch_plan(const DevCfg& c, int B, int num_cu, int* blocks_out, int* waves_out, size_t* lds_out, bool phase) {
-    DemoCondArgs la{};
-    size_t lds = 0;
+int demo_condition_launch_plan(const DevCfg& c, int B, int num_cu, bool phase, int32_t* blocks_out, int32_t* waves_out,
+                               int32_t* lds_bytes_out) {
+    DemoPlan plan;
     int blocks = 0;
-    const int rc = demo_condition_plan(c, phase, phase ? "mpk_demonstration_phase_plan" : "mpk_demonstration_condition", B, num_cu, &la,
-                                       &lds, &blocks);
+    const int rc = demo_condition_plan(c, phase, phase ? "mpk_demonstration_phase_plan" : "mpk_demonstration_condition", B, num_cu, &plan,
+                                       &blocks);
     if (rc != MPK_OK) return rc;
     if (blocks_out) *blocks_out = blocks;
-    if (waves_out) *waves_out = la.waves;
-    if (lds_out) *lds_out = lds;
+    if (waves_out) *waves_out = plan.waves;
+    if (lds_bytes_out) *lds_bytes_out = (int32_t)plan.lds;
     return MPK_OK;
-}
-
-template <int MP, bool PHASE>
-static int launch_demo_condition_mp(const DemoCondArgs& la, int ns, int blocks, size_t lds, void* stream) {
-    auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(64 * la.waves), lds, stream, la); };
-    switch (ns) {
-        case 1: return go(k_demo_condition<MP, 1, PHASE>);
-        case 2: return go(k_demo_condition<MP, 2, PHASE>);
-        case 3: return go(k_demo_condition<MP, 3, PHASE>);
-        default:
-            // (Pl > 192 passes neither route's LDS limit; the per-episode route does not carry the instantiation)
-            if constexpr (PHASE) {
-                set_error("mpk_demonstration_phase_condition: internal: more than 192 non-phase parameters passed the LDS limit");
-                return MPK_ENOTIMPL;
-            } else {
-                return go(k_demo_condition<MP, 4, PHASE>);
-            }
-    }
 }
 
 int launch_demo_condition(const DevCfg& c, const SharedTables& st, const DemoCondLaunch& q, int num_cu, void* stream,
                           const char** kernel_name) {
     DemoCondArgs la{};
-    size_t lds = 0;
+    DemoPlan plan;
     int blocks = 0;
-    const int rc = demo_condition_plan(c, q.phase, q.phase ? "mpk_demonstration_phase_condition" : "mpk_demonstration_condition", q.B,
-                                       num_cu, &la, &lds, &blocks);
+    const bool phase = q.obs.phase;
+    const int rc = demo_condition_plan(c, phase, phase ? "mpk_demonstration_phase_condition" : "mpk_demonstration_condition", q.in.B, num_cu,
+                                       &plan, &blocks);
     if (rc != MPK_OK) return rc;
+    demo_plan_args(plan, &la);
+    const size_t lds = plan.lds;
     const bool promp = c.mp_type == MPK_MP_PROMP;
-    la.flag = q.range_flag;
-    la.c = c; la.A = st.A; la.aux = st.aux; la.TS = st.TS; la.init_time = q.init_time;
-    la.params = q.params; la.L = q.params_L; la.init_pos = q.init_pos; la.init_vel = q.init_vel;
-    la.pos = q.pos; la.sd = q.obs_std;
-    la.params_out = q.params_out; la.L_out = q.params_L_out;
-    la.B = q.B; la.Pl = c.D * c.Kloc; la.ld = la.Pl | 1;
-    const int ns = (la.Pl + 63) / 64;
-    if (q.phase) {
-        *kernel_name = promp ? "k_demo_condition<promp, phase>" : "k_demo_condition<prodmp, phase>";
-        return promp ? launch_demo_condition_mp<MPK_MP_PROMP, true>(la, ns, blocks, lds, stream)
-                     : launch_demo_condition_mp<MPK_MP_PRODMP, true>(la, ns, blocks, lds, stream);
-    }
-    *kernel_name = promp ? "k_demo_condition<promp>" : "k_demo_condition<prodmp>";
-    return promp ? launch_demo_condition_mp<MPK_MP_PROMP, false>(la, ns, blocks, lds, stream)
-                 : launch_demo_condition_mp<MPK_MP_PRODMP, false>(la, ns, blocks, lds, stream);
+    la.flag = q.obs.range_flag;
+    la.c = c; la.A = st.A; la.aux = st.aux; la.TS = st.TS; la.init_time = q.in.init_time;
+    la.params = q.in.params; la.L = q.in.params_L; la.init_pos = q.in.init_pos; la.init_vel = q.in.init_vel;
+    la.pos = q.obs.pos; la.sd = q.obs.obs_std;
+    la.params_out = q.out.params_out; la.L_out = q.out.params_L_out;
+    la.B = q.in.B; la.Pl = c.D * c.Kloc; la.ld = la.Pl | 1;
+    static const char* const names[2][2] = {{"k_demo_condition<prodmp>", "k_demo_condition<promp>"},
+                                            {"k_demo_condition<prodmp, phase>", "k_demo_condition<promp, phase>"}};
+    *kernel_name = names[phase][promp];
+    return dispatch_flag(phase, [&](auto ph) {
+        return dispatch_mp(promp, [&](auto mp) {
+            return dispatch_ns((la.Pl + 63) / 64, [&](auto ns) {
+                // (Pl > 192 passes neither route's LDS limit; the per-episode route does not carry the instantiation)
+                if constexpr (ph.value && ns.value == 4) {
+                    set_error("mpk_demonstration_phase_condition: internal: more than 192 non-phase parameters passed the LDS limit");
+                    return (int)MPK_ENOTIMPL;
+                } else {
+                    return launch_kernel(k_demo_condition<mp.value, ns.value, ph.value>, dim3(blocks), dim3(64 * la.waves), lds, stream, la);
+                }
+            });
+        });
+    });
 }
 #endif  // MPK_DEVICE_ONLY
 

@@ -1,6 +1,7 @@
 // k_demo_log_prob: the log-likelihood of WHOLE demonstrations [B, T, D] under a Gaussian over the MP parameters, and its gradient
 // (mpk_demonstration_log_prob, mpk_demonstration_log_prob_vjp) -- the information (Pl x Pl) form, for n >> Pl
 #include "mpk_demo_gram.h"
+#include "mpk_gauss_launch.h"
 
 namespace mpk {
 
@@ -284,17 +285,8 @@ __global__ void __launch_bounds__(256) k_demo_log_prob(const DemoLogProbArgs a) 
 // the shapes the kernels of the information form take; MPK_ENOTIMPL with the limit in the message, under the entry's name fn, otherwise
 // (no HIP call)
 static int demo_limits(const DevCfg& c, bool phase, DemoPlan* plan, const char* fn) {
+    if (const int rc = gauss_common_limits(c, fn)) return rc;
     const std::string name(fn);
-    if (c.mp_type == MPK_MP_DMP || c.dmp_resp) {
-        set_error(name + ": a DMP has no probabilistic interface (promp / prodmp only)");
-        return MPK_ENOTIMPL;
-    }
-    if (c.D > kMaxD || c.KP > kMaxKP) {
-        set_error(name + ": at most " + std::to_string(kMaxD) + " DoF and " + std::to_string(kMaxKP) +
-                  " table columns (this handle: " + std::to_string(c.D) + " DoF, " + std::to_string(c.KT) +
-                  " columns); the k_traj_wide shapes have no kernel here");
-        return MPK_ENOTIMPL;
-    }
     const size_t Pl = (size_t)c.D * c.Kloc;
     if (Pl > (size_t)64 * kDemoSlots) {
         set_error(name + ": at most " + std::to_string(64 * kDemoSlots) + " non-phase parameters (this handle: " +
@@ -329,35 +321,16 @@ static int demo_limits(const DevCfg& c, bool phase, DemoPlan* plan, const char* 
                   "fit the CU's " + std::to_string(kLdsPerCu) + " bytes of LDS");
         return MPK_ENOTIMPL;
     }
-    // the waves per workgroup (<= 4) that put the most waves on a CU; the larger workgroup on a tie (the tables are staged once each)
-    int best = 1;
-    size_t best_on_cu = 0;
-    for (int w = 1; w <= 4; ++w) {
-        const size_t bytes = w * wave_doubles * sizeof(double) + shared;
-        if (bytes > kLdsPerCu) break;
-        const size_t on_cu = w * (kLdsPerCu / bytes);
-        if (on_cu >= best_on_cu) { best = w; best_on_cu = on_cu; }
-    }
     if (plan) {
-        plan->lds = best * wave_doubles * sizeof(double) + shared;
-        plan->waves = best; plan->wave_doubles = (int)wave_doubles; plan->tc = (int)tc; plan->scratch = (int)scratch;
+        const WavePlan wp = gauss_wave_plan(wave_doubles, shared);
+        plan->lds = wp.lds;
+        plan->waves = wp.waves; plan->wave_doubles = (int)wave_doubles; plan->tc = (int)tc; plan->scratch = (int)scratch;
         plan->sl = (int)sl; plan->chunk = (int)chunk; plan->c_pad = (int)c_pad;
     }
     return MPK_OK;
 }
 
-int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* wave_doubles_out, int* tc_out, int* scratch_out,
-                         const char* fn) {
-    DemoPlan plan;
-    const int rc = demo_limits(c, false, &plan, fn);
-    if (rc != MPK_OK) return rc;
-    if (lds_out) *lds_out = plan.lds;
-    if (waves_out) *waves_out = plan.waves;
-    if (wave_doubles_out) *wave_doubles_out = plan.wave_doubles;
-    if (tc_out) *tc_out = plan.tc;
-    if (scratch_out) *scratch_out = plan.scratch;
-    return MPK_OK;
-}
+int demo_log_prob_limits(const DevCfg& c, DemoPlan* plan, const char* fn) { return demo_limits(c, false, plan, fn); }
 
 // the per-episode-phase route's limits: the same images plus the chunk image per wave, row constants and base times per workgroup
 int demo_phase_limits(const DevCfg& c, DemoPlan* plan, const char* fn) { return demo_limits(c, true, plan, fn); }
@@ -367,62 +340,45 @@ void demo_plan_args(const DemoPlan& plan, DemoGramArgs* la) {
     la->sl = plan.sl; la->chunk = plan.chunk; la->c_pad = plan.c_pad;
 }
 
-template <int MP, bool GRAD, bool PHASE>
-static int launch_demo_log_prob_mp(const DemoLogProbArgs& la, int ns, int blocks, size_t lds, void* stream) {
-    auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(64 * la.waves), lds, stream, la); };
-    switch (ns) {
-        case 1: return go(k_demo_log_prob<MP, 1, GRAD, PHASE>);
-        case 2: return go(k_demo_log_prob<MP, 2, GRAD, PHASE>);
-        case 3: return go(k_demo_log_prob<MP, 3, GRAD, PHASE>);
-        default:
-            // (Pl > 192 passes neither route's LDS limit; the per-episode route does not carry the instantiation)
-            if constexpr (PHASE) {
-                set_error("mpk_demonstration_phase_log_prob: internal: more than 192 non-phase parameters passed the LDS limit");
-                return MPK_ENOTIMPL;
-            } else {
-                return go(k_demo_log_prob<MP, 4, GRAD, PHASE>);
-            }
-    }
-}
-
 int launch_demo_log_prob(const DevCfg& c, const SharedTables& st, const DemoLogProbLaunch& q, int num_cu, void* stream,
                          const char** kernel_name) {
     DemoLogProbArgs la{};
     DemoPlan plan;
-    const int rc = q.phase ? demo_phase_limits(c, &plan, q.grad ? "mpk_demonstration_phase_log_prob_vjp" : "mpk_demonstration_phase_log_prob")
-                           : demo_limits(c, false, &plan, "mpk_demonstration_log_prob");
+    const bool phase = q.obs.phase, grad = q.out.grad;
+    const int rc = phase ? demo_phase_limits(c, &plan, grad ? "mpk_demonstration_phase_log_prob_vjp" : "mpk_demonstration_phase_log_prob")
+                         : demo_log_prob_limits(c, &plan);
     if (rc != MPK_OK) return rc;
     demo_plan_args(plan, &la);
     const size_t lds = plan.lds;
     const bool promp = c.mp_type == MPK_MP_PROMP;
-    la.flag = q.range_flag;
-    la.c = c; la.A = st.A; la.aux = st.aux; la.TS = st.TS; la.init_time = q.init_time;
-    la.params = q.params; la.L = q.params_L; la.init_pos = q.init_pos; la.init_vel = q.init_vel;
-    la.pos = q.pos; la.sd = q.obs_std;
-    la.log_prob = q.log_prob; la.g = q.g; la.g_params = q.g_params; la.g_L = q.g_params_L;
-    la.B = q.B; la.Pl = c.D * c.Kloc; la.ld = la.Pl | 1;
-    const int per_cu = (int)(kLdsPerCu / lds) < 1 ? 1 : ((int)(kLdsPerCu / lds) > 8 ? 8 : (int)(kLdsPerCu / lds));
-    const long units = ((long)q.B + la.waves - 1) / la.waves;
-    const int blocks = (int)(units < (long)num_cu * per_cu ? units : (long)num_cu * per_cu);
-    const int ns = (la.Pl + 63) / 64;
-    if (q.phase) {
-        if (q.grad) {
-            *kernel_name = promp ? "k_demo_log_prob<promp, phase, grad>" : "k_demo_log_prob<prodmp, phase, grad>";
-            return promp ? launch_demo_log_prob_mp<MPK_MP_PROMP, true, true>(la, ns, blocks, lds, stream)
-                         : launch_demo_log_prob_mp<MPK_MP_PRODMP, true, true>(la, ns, blocks, lds, stream);
-        }
-        *kernel_name = promp ? "k_demo_log_prob<promp, phase>" : "k_demo_log_prob<prodmp, phase>";
-        return promp ? launch_demo_log_prob_mp<MPK_MP_PROMP, false, true>(la, ns, blocks, lds, stream)
-                     : launch_demo_log_prob_mp<MPK_MP_PRODMP, false, true>(la, ns, blocks, lds, stream);
-    }
-    if (q.grad) {
-        *kernel_name = promp ? "k_demo_log_prob<promp, grad>" : "k_demo_log_prob<prodmp, grad>";
-        return promp ? launch_demo_log_prob_mp<MPK_MP_PROMP, true, false>(la, ns, blocks, lds, stream)
-                     : launch_demo_log_prob_mp<MPK_MP_PRODMP, true, false>(la, ns, blocks, lds, stream);
-    }
-    *kernel_name = promp ? "k_demo_log_prob<promp>" : "k_demo_log_prob<prodmp>";
-    return promp ? launch_demo_log_prob_mp<MPK_MP_PROMP, false, false>(la, ns, blocks, lds, stream)
-                 : launch_demo_log_prob_mp<MPK_MP_PRODMP, false, false>(la, ns, blocks, lds, stream);
+    la.flag = q.obs.range_flag;
+    la.c = c; la.A = st.A; la.aux = st.aux; la.TS = st.TS; la.init_time = q.in.init_time;
+    la.params = q.in.params; la.L = q.in.params_L; la.init_pos = q.in.init_pos; la.init_vel = q.in.init_vel;
+    la.pos = q.obs.pos; la.sd = q.obs.obs_std;
+    la.log_prob = q.out.log_prob; la.g = q.out.g; la.g_params = q.out.g_params; la.g_L = q.out.g_params_L;
+    la.B = q.in.B; la.Pl = c.D * c.Kloc; la.ld = la.Pl | 1;
+    const int blocks = gauss_blocks(q.in.B, la.waves, lds, num_cu);
+    static const char* const names[2][2][2] = {
+        {{"k_demo_log_prob<prodmp>", "k_demo_log_prob<promp>"}, {"k_demo_log_prob<prodmp, grad>", "k_demo_log_prob<promp, grad>"}},
+        {{"k_demo_log_prob<prodmp, phase>", "k_demo_log_prob<promp, phase>"},
+         {"k_demo_log_prob<prodmp, phase, grad>", "k_demo_log_prob<promp, phase, grad>"}}};
+    *kernel_name = names[phase][grad][promp];
+    return dispatch_flag(phase, [&](auto ph) {
+        return dispatch_flag(grad, [&](auto gr) {
+            return dispatch_mp(promp, [&](auto mp) {
+                return dispatch_ns((la.Pl + 63) / 64, [&](auto ns) {
+                    // (Pl > 192 passes neither route's LDS limit; the per-episode route does not carry the instantiation)
+                    if constexpr (ph.value && ns.value == 4) {
+                        set_error("mpk_demonstration_phase_log_prob: internal: more than 192 non-phase parameters passed the LDS limit");
+                        return (int)MPK_ENOTIMPL;
+                    } else {
+                        return launch_kernel(k_demo_log_prob<mp.value, ns.value, gr.value, ph.value>, dim3(blocks), dim3(64 * la.waves), lds,
+                                             stream, la);
+                    }
+                });
+            });
+        });
+    });
 }
 #endif  // MPK_DEVICE_ONLY
 

@@ -1232,371 +1232,284 @@ int mpk_fit_status(mpk_handle hh, int32_t* not_positive_definite, void* stream) 
     return MPK_OK;
 }
 
-// the trajectory's standard deviation under a Gaussian over the non-phase parameters: the tables of (init_time_shared, T) as
-// mpk_trajectory_vjp builds or reuses them, one launch
+// ---- the probabilistic entry points: a Gaussian N(params, L L^T) over the non-phase parameters.  Every refusal exists once, below, and
+// carries the name of the entry that calls it; an entry is its own NULL checks, these in its order, the tables, the request, the launch
+static int refuse(int code, const std::string& msg) {
+    set_error(msg);
+    return code;
+}
+
+static int batch_check(const std::string& name, int32_t B) {
+    return B < 1 ? refuse(MPK_EINVAL, name + ": B must be >= 1") : MPK_OK;
+}
+
+// the M observed steps: a host array of strictly increasing step indices in [0, T)
+static int steps_check(const std::string& name, const Handle* h, const int32_t* obs_steps, int32_t M) {
+    if (M < 1 || M > MPK_COND_MAX_STEPS || !obs_steps)
+        return refuse(MPK_EINVAL, name + ": M must be 1.." + std::to_string(MPK_COND_MAX_STEPS) + " observed steps (obs_steps: a host array of "
+                                  "M step indices), got " + std::to_string(M));
+    for (int m = 0; m < M; ++m)
+        if (obs_steps[m] < 0 || obs_steps[m] >= h->dev.T || (m > 0 && obs_steps[m] <= obs_steps[m - 1]))
+            return refuse(MPK_EINVAL, name + ": obs_steps must be strictly increasing step indices in [0, " + std::to_string(h->dev.T) +
+                                      "); obs_steps[" + std::to_string(m) + "] = " + std::to_string(obs_steps[m]));
+    return MPK_OK;
+}
+
+static int observed_check(const std::string& name, const float* obs_pos, const float* obs_pos_std, const float* obs_vel,
+                          const float* obs_vel_std) {
+    if (!obs_pos && !obs_pos_std && !obs_vel && !obs_vel_std)
+        return refuse(MPK_EINVAL, name + ": obs_pos and obs_vel are both NULL: nothing is observed");
+    if (!obs_pos != !obs_pos_std || !obs_vel != !obs_vel_std)
+        return refuse(MPK_EINVAL, name + ": observed values and their standard deviations come in pairs (obs_pos with obs_pos_std, obs_vel "
+                                  "with obs_vel_std)");
+    return MPK_OK;
+}
+
+// kernel: the family's word -- "a standard-deviation kernel", "a conditioning kernel", "a likelihood kernel"
+static int shared_phase_check(const std::string& name, const Handle* h, const char* kernel) {
+    if (h->cfg.learn_tau || h->cfg.learn_delay)
+        return refuse(MPK_ENOTIMPL, name + ": a learned tau / delay gives every episode its own phase and its own table: only shared-phase "
+                                    "handles have " + kernel);
+    return MPK_OK;
+}
+
+static int episode_phase_check(const std::string& name, const Handle* h) {
+    if (!h->cfg.learn_tau && !h->cfg.learn_delay)
+        return refuse(MPK_ENOTIMPL, name + ": this handle learns neither tau nor delay: every episode has the handle's phase, which is what "
+                                    "the shared-phase entry (without _phase) evaluates");
+    return MPK_OK;
+}
+
+static int has_params_check(const std::string& name, const Handle* h) {
+    return h->dev.D * h->dev.Kloc < 1 ? refuse(MPK_EINVAL, name + ": the handle has no non-phase parameters") : MPK_OK;
+}
+
+static int promp_velocity_check(const Handle* h, const float* obs_vel) {
+    if (obs_vel && h->cfg.mp_type == MPK_MP_PROMP && h->dev.T < 2)
+        return refuse(MPK_EINVAL, "promp needs at least two time steps for the finite-difference velocity");
+    return MPK_OK;
+}
+
+static int start_check(const std::string& name, const Handle* h, const float* init_pos, const float* init_vel) {
+    if ((!init_pos || !init_vel) && h->cfg.mp_type != MPK_MP_PROMP)
+        return refuse(MPK_EINVAL, name + ": init_pos and init_vel are required (only a ProMP may pass NULL: zeros)");
+    return MPK_OK;
+}
+
+static int likelihood_out_check(const std::string& name, const LikelihoodOut& out) {
+    if (!out.grad && !out.log_prob) return refuse(MPK_EINVAL, name + ": NULL log_prob");
+    if (out.grad && !out.g) return refuse(MPK_EINVAL, name + ": NULL g");
+    if (out.grad && !out.g_params && !out.g_params_L)
+        return refuse(MPK_EINVAL, name + ": g_params and g_params_L are both NULL: nothing to compute");
+    return MPK_OK;
+}
+
+// the trajectory's standard deviation: the tables of (init_time_shared, T) as mpk_trajectory_vjp builds or reuses them, one launch
 int mpk_trajectory_std(mpk_handle hh, const float* params_L, double init_time_shared, float* pos_std, float* vel_std, int32_t B,
                        void* stream) {
+    const std::string name("mpk_trajectory_std");
     if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
     Handle* h = reinterpret_cast<Handle*>(hh);
-    if (!params_L) { set_error("mpk_trajectory_std: NULL params_L"); return MPK_EINVAL; }
-    if (B < 1) { set_error("mpk_trajectory_std: B must be >= 1"); return MPK_EINVAL; }
-    if (!pos_std && !vel_std) { set_error("mpk_trajectory_std: pos_std and vel_std are both NULL: nothing to compute"); return MPK_EINVAL; }
-    if (h->cfg.learn_tau || h->cfg.learn_delay) {
-        set_error("mpk_trajectory_std: a learned tau / delay gives every episode its own phase and its own table: only shared-phase "
-                  "handles have a standard-deviation kernel");
-        return MPK_ENOTIMPL;
-    }
-    int rc = traj_std_limits(h->dev, nullptr, nullptr, nullptr);
-    if (rc != MPK_OK) return rc;
+    if (!params_L) return refuse(MPK_EINVAL, name + ": NULL params_L");
+    if (const int rc = batch_check(name, B)) return rc;
+    if (!pos_std && !vel_std) return refuse(MPK_EINVAL, name + ": pos_std and vel_std are both NULL: nothing to compute");
+    if (const int rc = shared_phase_check(name, h, "a standard-deviation kernel")) return rc;
+    if (const int rc = traj_std_limits(h->dev, nullptr, nullptr, nullptr)) return rc;
     if (h->dev.D == 0) return MPK_OK;
     MPK_ON_DEVICE(h->cfg.device);
     SharedTables st;
-    rc = get_shared(h, (float)init_time_shared, stream, &st);
-    if (rc != MPK_OK) return rc;
+    if (const int rc = get_shared(h, (float)init_time_shared, stream, &st)) return rc;
     return launch_traj_std(h->dev, st, params_L, pos_std, vel_std, B, h->num_cu, stream, &h->last_kernel);
 }
 
-// the Gaussian over the non-phase parameters conditioned on observed trajectory points: every refusal before any launch, the tables of
-// (init_time_shared, T) as mpk_trajectory_std builds or reuses them, one launch; obs_steps is copied into the launch arguments
+// what the point-observation entries refuse between their NULL checks and their limits
+static int point_checks(const std::string& name, const Handle* h, const char* kernel, const GaussIn& in, const PointObs& obs) {
+    if (const int rc = batch_check(name, in.B)) return rc;
+    if (const int rc = steps_check(name, h, obs.steps, obs.M)) return rc;
+    if (const int rc = observed_check(name, obs.obs_pos, obs.obs_pos_std, obs.obs_vel, obs.obs_vel_std)) return rc;
+    return shared_phase_check(name, h, kernel);
+}
+
+// ... and behind their limits, before the tables
+static int point_handle_checks(const std::string& name, const Handle* h, const GaussIn& in, const PointObs& obs) {
+    if (const int rc = has_params_check(name, h)) return rc;
+    if (const int rc = promp_velocity_check(h, obs.obs_vel)) return rc;
+    return start_check(name, h, in.init_pos, in.init_vel);
+}
+
+// the Gaussian conditioned on observed trajectory points: every refusal before any launch, the tables as mpk_trajectory_std builds or
+// reuses them, one launch; obs_steps is copied into the launch arguments
 int mpk_trajectory_condition(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
                              double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
                              const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, float* params_out,
                              float* params_L_out, int32_t B, void* stream) {
+    const std::string name("mpk_trajectory_condition");
     if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
     Handle* h = reinterpret_cast<Handle*>(hh);
-    if (!params || !params_L || !params_out || !params_L_out) {
-        set_error("mpk_trajectory_condition: NULL params, params_L, params_out or params_L_out");
-        return MPK_EINVAL;
-    }
-    if (B < 1) { set_error("mpk_trajectory_condition: B must be >= 1"); return MPK_EINVAL; }
-    if (M < 1 || M > MPK_COND_MAX_STEPS || !obs_steps) {
-        set_error("mpk_trajectory_condition: M must be 1.." + std::to_string(MPK_COND_MAX_STEPS) + " observed steps (obs_steps: a host "
-                  "array of M step indices), got " + std::to_string(M));
-        return MPK_EINVAL;
-    }
-    for (int m = 0; m < M; ++m) {
-        if (obs_steps[m] < 0 || obs_steps[m] >= h->dev.T || (m > 0 && obs_steps[m] <= obs_steps[m - 1])) {
-            set_error("mpk_trajectory_condition: obs_steps must be strictly increasing step indices in [0, " + std::to_string(h->dev.T) +
-                      "); obs_steps[" + std::to_string(m) + "] = " + std::to_string(obs_steps[m]));
-            return MPK_EINVAL;
-        }
-    }
-    if (!obs_pos && !obs_pos_std && !obs_vel && !obs_vel_std) {
-        set_error("mpk_trajectory_condition: obs_pos and obs_vel are both NULL: nothing is observed");
-        return MPK_EINVAL;
-    }
-    if (!obs_pos != !obs_pos_std || !obs_vel != !obs_vel_std) {
-        set_error("mpk_trajectory_condition: observed values and their standard deviations come in pairs (obs_pos with obs_pos_std, "
-                  "obs_vel with obs_vel_std)");
-        return MPK_EINVAL;
-    }
-    if (h->cfg.learn_tau || h->cfg.learn_delay) {
-        set_error("mpk_trajectory_condition: a learned tau / delay gives every episode its own phase and its own table: only shared-phase "
-                  "handles have a conditioning kernel");
-        return MPK_ENOTIMPL;
-    }
-    int rc = traj_cond_limits(h->dev, M, nullptr, nullptr, nullptr);
-    if (rc != MPK_OK) return rc;
-    if (h->dev.D * h->dev.Kloc < 1) { set_error("mpk_trajectory_condition: the handle has no non-phase parameters"); return MPK_EINVAL; }
-    if (obs_vel && h->cfg.mp_type == MPK_MP_PROMP && h->dev.T < 2) {
-        set_error("promp needs at least two time steps for the finite-difference velocity");
-        return MPK_EINVAL;
-    }
-    if ((!init_pos || !init_vel) && h->cfg.mp_type != MPK_MP_PROMP) {
-        set_error("mpk_trajectory_condition: init_pos and init_vel are required (only a ProMP may pass NULL: zeros)");
-        return MPK_EINVAL;
-    }
+    if (!params || !params_L || !params_out || !params_L_out)
+        return refuse(MPK_EINVAL, name + ": NULL params, params_L, params_out or params_L_out");
+    const CondLaunch q{{params, params_L, init_pos, init_vel, (float)init_time_shared, B},
+                       {obs_steps, M, obs_pos, obs_pos_std, obs_vel, obs_vel_std}, {params_out, params_L_out}};
+    if (const int rc = point_checks(name, h, "a conditioning kernel", q.in, q.obs)) return rc;
+    if (const int rc = traj_cond_limits(h->dev, M, nullptr, nullptr, nullptr)) return rc;
+    if (const int rc = point_handle_checks(name, h, q.in, q.obs)) return rc;
     MPK_ON_DEVICE(h->cfg.device);
     SharedTables st;
-    rc = get_shared(h, (float)init_time_shared, stream, &st);
-    if (rc != MPK_OK) return rc;
-    CondLaunch q;
-    q.params = params; q.params_L = params_L; q.init_pos = init_pos; q.init_vel = init_vel;
-    q.steps = obs_steps; q.M = M; q.init_time = (float)init_time_shared;
-    q.obs_pos = obs_pos; q.obs_pos_std = obs_pos_std; q.obs_vel = obs_vel; q.obs_vel_std = obs_vel_std;
-    q.params_out = params_out; q.params_L_out = params_L_out; q.B = B;
+    if (const int rc = get_shared(h, (float)init_time_shared, stream, &st)) return rc;
     return launch_traj_condition(h->dev, st, q, h->num_cu, stream, &h->last_kernel);
 }
 
-// the log-likelihood of conditioning's observations under N(params, L L^T) and its gradient: the refusals of mpk_trajectory_condition
-// plus the observation count, every one before any launch; the tables as above; one launch.  grad: the _vjp entry
-static int trajectory_log_prob_entry(const char* fn, mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
-                                     const float* init_vel, double init_time_shared, const int32_t* obs_steps, int32_t M,
-                                     const float* obs_pos, const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std,
-                                     bool grad, double* log_prob, const double* g, float* g_params, float* g_params_L, int32_t B,
-                                     void* stream) {
-    const std::string name(fn);
+// the log-likelihood of conditioning's observations and its gradient (out.grad: the _vjp entry): the refusals of
+// mpk_trajectory_condition plus the observation count, every one before any launch; the tables as above; one launch
+static int trajectory_log_prob_entry(const std::string& name, mpk_handle hh, const GaussIn& in, double init_time_shared,
+                                     const PointObs& obs, const LikelihoodOut& out, void* stream) {
     if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
     Handle* h = reinterpret_cast<Handle*>(hh);
-    if (!params || !params_L) { set_error(name + ": NULL params or params_L"); return MPK_EINVAL; }
-    if (!grad && !log_prob) { set_error(name + ": NULL log_prob"); return MPK_EINVAL; }
-    if (grad && !g) { set_error(name + ": NULL g"); return MPK_EINVAL; }
-    if (grad && !g_params && !g_params_L) { set_error(name + ": g_params and g_params_L are both NULL: nothing to compute"); return MPK_EINVAL; }
-    if (B < 1) { set_error(name + ": B must be >= 1"); return MPK_EINVAL; }
-    if (M < 1 || M > MPK_COND_MAX_STEPS || !obs_steps) {
-        set_error(name + ": M must be 1.." + std::to_string(MPK_COND_MAX_STEPS) + " observed steps (obs_steps: a host array of M step "
-                  "indices), got " + std::to_string(M));
-        return MPK_EINVAL;
-    }
-    for (int m = 0; m < M; ++m) {
-        if (obs_steps[m] < 0 || obs_steps[m] >= h->dev.T || (m > 0 && obs_steps[m] <= obs_steps[m - 1])) {
-            set_error(name + ": obs_steps must be strictly increasing step indices in [0, " + std::to_string(h->dev.T) + "); obs_steps[" +
-                      std::to_string(m) + "] = " + std::to_string(obs_steps[m]));
-            return MPK_EINVAL;
-        }
-    }
-    if (!obs_pos && !obs_pos_std && !obs_vel && !obs_vel_std) {
-        set_error(name + ": obs_pos and obs_vel are both NULL: nothing is observed");
-        return MPK_EINVAL;
-    }
-    if (!obs_pos != !obs_pos_std || !obs_vel != !obs_vel_std) {
-        set_error(name + ": observed values and their standard deviations come in pairs (obs_pos with obs_pos_std, obs_vel with "
-                  "obs_vel_std)");
-        return MPK_EINVAL;
-    }
-    if (h->cfg.learn_tau || h->cfg.learn_delay) {
-        set_error(name + ": a learned tau / delay gives every episode its own phase and its own table: only shared-phase handles have a "
-                  "likelihood kernel");
-        return MPK_ENOTIMPL;
-    }
-    int rc = traj_log_prob_limits(h->dev, M, (obs_pos ? 1 : 0) + (obs_vel ? 1 : 0), nullptr, nullptr, nullptr);
-    if (rc != MPK_OK) return rc;
-    if (h->dev.D * h->dev.Kloc < 1) { set_error(name + ": the handle has no non-phase parameters"); return MPK_EINVAL; }
-    if (obs_vel && h->cfg.mp_type == MPK_MP_PROMP && h->dev.T < 2) {
-        set_error("promp needs at least two time steps for the finite-difference velocity");
-        return MPK_EINVAL;
-    }
-    if ((!init_pos || !init_vel) && h->cfg.mp_type != MPK_MP_PROMP) {
-        set_error(name + ": init_pos and init_vel are required (only a ProMP may pass NULL: zeros)");
-        return MPK_EINVAL;
-    }
+    if (!in.params || !in.params_L) return refuse(MPK_EINVAL, name + ": NULL params or params_L");
+    if (const int rc = likelihood_out_check(name, out)) return rc;
+    if (const int rc = point_checks(name, h, "a likelihood kernel", in, obs)) return rc;
+    if (const int rc = traj_log_prob_limits(h->dev, obs.M, (obs.obs_pos ? 1 : 0) + (obs.obs_vel ? 1 : 0), nullptr, nullptr, nullptr)) return rc;
+    if (const int rc = point_handle_checks(name, h, in, obs)) return rc;
     MPK_ON_DEVICE(h->cfg.device);
     SharedTables st;
-    rc = get_shared(h, (float)init_time_shared, stream, &st);
-    if (rc != MPK_OK) return rc;
-    LogProbLaunch q;
-    q.params = params; q.params_L = params_L; q.init_pos = init_pos; q.init_vel = init_vel;
-    q.steps = obs_steps; q.M = M; q.init_time = (float)init_time_shared;
-    q.obs_pos = obs_pos; q.obs_pos_std = obs_pos_std; q.obs_vel = obs_vel; q.obs_vel_std = obs_vel_std;
-    q.grad = grad; q.log_prob = log_prob; q.g = g; q.g_params = g_params; q.g_params_L = g_params_L; q.B = B;
-    return launch_traj_log_prob(h->dev, st, q, h->num_cu, stream, &h->last_kernel);
+    if (const int rc = get_shared(h, (float)init_time_shared, stream, &st)) return rc;
+    return launch_traj_log_prob(h->dev, st, LogProbLaunch{in, obs, out}, h->num_cu, stream, &h->last_kernel);
 }
 
 int mpk_trajectory_log_prob(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
                             double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
                             const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, double* log_prob, int32_t B,
                             void* stream) {
-    return trajectory_log_prob_entry("mpk_trajectory_log_prob", hh, params, params_L, init_pos, init_vel, init_time_shared, obs_steps, M,
-                                     obs_pos, obs_pos_std, obs_vel, obs_vel_std, false, log_prob, nullptr, nullptr, nullptr, B, stream);
+    return trajectory_log_prob_entry("mpk_trajectory_log_prob", hh, {params, params_L, init_pos, init_vel, (float)init_time_shared, B},
+                                     init_time_shared, {obs_steps, M, obs_pos, obs_pos_std, obs_vel, obs_vel_std},
+                                     {false, log_prob, nullptr, nullptr, nullptr}, stream);
 }
 
 int mpk_trajectory_log_prob_vjp(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
                                 double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
                                 const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, const double* g, float* g_params,
                                 float* g_params_L, int32_t B, void* stream) {
-    return trajectory_log_prob_entry("mpk_trajectory_log_prob_vjp", hh, params, params_L, init_pos, init_vel, init_time_shared, obs_steps,
-                                     M, obs_pos, obs_pos_std, obs_vel, obs_vel_std, true, nullptr, g, g_params, g_params_L, B, stream);
+    return trajectory_log_prob_entry("mpk_trajectory_log_prob_vjp", hh, {params, params_L, init_pos, init_vel, (float)init_time_shared, B},
+                                     init_time_shared, {obs_steps, M, obs_pos, obs_pos_std, obs_vel, obs_vel_std},
+                                     {true, nullptr, g, g_params, g_params_L}, stream);
 }
 
-// the log-likelihood of whole demonstrations under N(params, L L^T) in the information form, and its gradient: every refusal before any
-// launch; the tables as above; one launch.  grad: the _vjp entry
-static int demonstration_log_prob_entry(const char* fn, mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
-                                        const float* init_vel, double init_time_shared, const float* pos, const float* obs_std, bool grad,
-                                        double* log_prob, const double* g, float* g_params, float* g_params_L, int32_t B, void* stream) {
-    const std::string name(fn);
+// ---- whole demonstrations, in the information form.  phase: the mpk_demonstration_phase_* entries, tau / delay given at the front of
+// every params row.  What both routes refuse behind their NULL checks and B, before any launch: the wrong kind of handle (kernel: the
+// shared-phase route's word), the route's limits (a DMP, the shapes; limits_fn: the name the shared-phase route's refuse under), no
+// non-phase parameters, a ProDMP without init_pos / init_vel
+static int demonstration_checks(const std::string& name, const Handle* h, bool phase, const char* kernel, const char* limits_fn,
+                                const GaussIn& in) {
+    if (const int rc = phase ? episode_phase_check(name, h) : shared_phase_check(name, h, kernel)) return rc;
+    if (const int rc = phase ? demo_phase_limits(h->dev, nullptr, name.c_str()) : demo_log_prob_limits(h->dev, nullptr, limits_fn)) return rc;
+    if (const int rc = has_params_check(name, h)) return rc;
+    return start_check(name, h, in.init_pos, in.init_vel);
+}
+
+// the shared-phase route's tables as above (the per-episode route reads none)
+static int demonstration_tables(Handle* h, bool phase, double init_time_shared, void* stream, SharedTables* st) {
+    return phase ? MPK_OK : get_shared(h, (float)init_time_shared, stream, st);
+}
+
+// the log-likelihood of whole demonstrations and its gradient (out.grad: the _vjp entry); one launch
+static int demonstration_log_prob_entry(const std::string& name, bool phase, mpk_handle hh, const GaussIn& in, double init_time_shared,
+                                        const float* pos, const float* obs_std, const LikelihoodOut& out, void* stream) {
     if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
     Handle* h = reinterpret_cast<Handle*>(hh);
-    if (!params || !params_L) { set_error(name + ": NULL params or params_L"); return MPK_EINVAL; }
-    if (!pos || !obs_std) { set_error(name + ": NULL pos or obs_std"); return MPK_EINVAL; }
-    if (!grad && !log_prob) { set_error(name + ": NULL log_prob"); return MPK_EINVAL; }
-    if (grad && !g) { set_error(name + ": NULL g"); return MPK_EINVAL; }
-    if (grad && !g_params && !g_params_L) { set_error(name + ": g_params and g_params_L are both NULL: nothing to compute"); return MPK_EINVAL; }
-    if (B < 1) { set_error(name + ": B must be >= 1"); return MPK_EINVAL; }
-    if (h->cfg.learn_tau || h->cfg.learn_delay) {
-        set_error(name + ": a learned tau / delay gives every episode its own phase and its own table: only shared-phase handles have a "
-                  "likelihood kernel");
-        return MPK_ENOTIMPL;
-    }
-    int rc = demo_log_prob_limits(h->dev, nullptr, nullptr, nullptr, nullptr, nullptr);
-    if (rc != MPK_OK) return rc;
-    if (h->dev.D * h->dev.Kloc < 1) { set_error(name + ": the handle has no non-phase parameters"); return MPK_EINVAL; }
-    if ((!init_pos || !init_vel) && h->cfg.mp_type != MPK_MP_PROMP) {
-        set_error(name + ": init_pos and init_vel are required (only a ProMP may pass NULL: zeros)");
-        return MPK_EINVAL;
-    }
+    if (!in.params || !in.params_L) return refuse(MPK_EINVAL, name + ": NULL params or params_L");
+    if (!pos || !obs_std) return refuse(MPK_EINVAL, name + ": NULL pos or obs_std");
+    if (const int rc = likelihood_out_check(name, out)) return rc;
+    if (const int rc = batch_check(name, in.B)) return rc;
+    if (const int rc = demonstration_checks(name, h, phase, "a likelihood kernel", "mpk_demonstration_log_prob", in)) return rc;
     MPK_ON_DEVICE(h->cfg.device);
     SharedTables st;
-    rc = get_shared(h, (float)init_time_shared, stream, &st);
-    if (rc != MPK_OK) return rc;
-    DemoLogProbLaunch q;
-    q.params = params; q.params_L = params_L; q.init_pos = init_pos; q.init_vel = init_vel; q.init_time = (float)init_time_shared;
-    q.pos = pos; q.obs_std = obs_std;
-    q.grad = grad; q.log_prob = log_prob; q.g = g; q.g_params = g_params; q.g_params_L = g_params_L; q.B = B;
+    if (const int rc = demonstration_tables(h, phase, init_time_shared, stream, &st)) return rc;
+    const DemoLogProbLaunch q{in, {pos, obs_std, phase, phase ? h->d_flag : nullptr}, out};
     return launch_demo_log_prob(h->dev, st, q, h->num_cu, stream, &h->last_kernel);
 }
 
 int mpk_demonstration_log_prob(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
                                double init_time_shared, const float* pos, const float* obs_std, double* log_prob, int32_t B,
                                void* stream) {
-    return demonstration_log_prob_entry("mpk_demonstration_log_prob", hh, params, params_L, init_pos, init_vel, init_time_shared, pos,
-                                        obs_std, false, log_prob, nullptr, nullptr, nullptr, B, stream);
+    return demonstration_log_prob_entry("mpk_demonstration_log_prob", false, hh,
+                                        {params, params_L, init_pos, init_vel, (float)init_time_shared, B}, init_time_shared, pos, obs_std,
+                                        {false, log_prob, nullptr, nullptr, nullptr}, stream);
 }
 
 int mpk_demonstration_log_prob_vjp(mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
                                    const float* init_vel, double init_time_shared, const float* pos, const float* obs_std, const double* g,
                                    float* g_params, float* g_params_L, int32_t B, void* stream) {
-    return demonstration_log_prob_entry("mpk_demonstration_log_prob_vjp", hh, params, params_L, init_pos, init_vel, init_time_shared, pos,
-                                        obs_std, true, nullptr, g, g_params, g_params_L, B, stream);
-}
-
-// N(params, L L^T) conditioned on whole demonstrations in the information form: mpk_demonstration_log_prob's validation, refusals and
-// tables; one launch
-int mpk_demonstration_condition(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
-                                double init_time_shared, const float* pos, const float* obs_std, float* params_out,
-                                float* params_L_out, int32_t B, void* stream) {
-    const std::string name("mpk_demonstration_condition");
-    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
-    Handle* h = reinterpret_cast<Handle*>(hh);
-    if (!params || !params_L || !params_out || !params_L_out) { set_error(name + ": NULL params or params_L, in or out"); return MPK_EINVAL; }
-    if (!pos || !obs_std) { set_error(name + ": NULL pos or obs_std"); return MPK_EINVAL; }
-    if (B < 1) { set_error(name + ": B must be >= 1"); return MPK_EINVAL; }
-    if (h->cfg.learn_tau || h->cfg.learn_delay) {
-        set_error(name + ": a learned tau / delay gives every episode its own phase and its own table: only shared-phase handles have a "
-                  "conditioning kernel");
-        return MPK_ENOTIMPL;
-    }
-    int rc = demo_log_prob_limits(h->dev, nullptr, nullptr, nullptr, nullptr, nullptr, name.c_str());
-    if (rc != MPK_OK) return rc;
-    if (h->dev.D * h->dev.Kloc < 1) { set_error(name + ": the handle has no non-phase parameters"); return MPK_EINVAL; }
-    if ((!init_pos || !init_vel) && h->cfg.mp_type != MPK_MP_PROMP) {
-        set_error(name + ": init_pos and init_vel are required (only a ProMP may pass NULL: zeros)");
-        return MPK_EINVAL;
-    }
-    MPK_ON_DEVICE(h->cfg.device);
-    SharedTables st;
-    rc = get_shared(h, (float)init_time_shared, stream, &st);
-    if (rc != MPK_OK) return rc;
-    DemoCondLaunch q;
-    q.params = params; q.params_L = params_L; q.init_pos = init_pos; q.init_vel = init_vel; q.init_time = (float)init_time_shared;
-    q.pos = pos; q.obs_std = obs_std; q.params_out = params_out; q.params_L_out = params_L_out; q.B = B;
-    return launch_demo_condition(h->dev, st, q, h->num_cu, stream, &h->last_kernel);
-}
-
-// the launch plan of mpk_demonstration_condition for B episodes on this handle's device: no HIP call
-int mpk_demonstration_condition_plan(mpk_handle hh, int32_t B, int32_t* blocks, int32_t* waves, int32_t* lds_bytes) {
-    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
-    Handle* h = reinterpret_cast<Handle*>(hh);
-    if (B < 1) { set_error("mpk_demonstration_condition_plan: B must be >= 1"); return MPK_EINVAL; }
-    if (h->cfg.learn_tau || h->cfg.learn_delay) {
-        set_error("mpk_demonstration_condition_plan: a learned tau / delay gives every episode its own phase and its own table: only "
-                  "shared-phase handles have a conditioning kernel");
-        return MPK_ENOTIMPL;
-    }
-    int nb = 0, nw = 0;
-    size_t lds = 0;
-    const int rc = demo_condition_launch_plan(h->dev, B, h->num_cu, &nb, &nw, &lds);
-    if (rc != MPK_OK) return rc;
-    if (blocks) *blocks = nb;
-    if (waves) *waves = nw;
-    if (lds_bytes) *lds_bytes = (int32_t)lds;
-    return MPK_OK;
-}
-
-// ---- the demonstration entries with a per-episode phase: tau / delay given at the front of every params row
-// what the three launches refuse, before any launch: a shared-phase handle, then demo_phase_limits (a DMP, the shapes), no non-phase
-// parameters, a ProDMP without init_pos / init_vel
-static int demonstration_phase_checks(const std::string& name, Handle* h, const float* init_pos, const float* init_vel) {
-    if (!h->cfg.learn_tau && !h->cfg.learn_delay) {
-        set_error(name + ": this handle learns neither tau nor delay: every episode has the handle's phase, which is what the shared-phase "
-                  "entry (without _phase) evaluates");
-        return MPK_ENOTIMPL;
-    }
-    const int rc = demo_phase_limits(h->dev, nullptr, name.c_str());
-    if (rc != MPK_OK) return rc;
-    if (h->dev.D * h->dev.Kloc < 1) { set_error(name + ": the handle has no non-phase parameters"); return MPK_EINVAL; }
-    if ((!init_pos || !init_vel) && h->cfg.mp_type != MPK_MP_PROMP) {
-        set_error(name + ": init_pos and init_vel are required (only a ProMP may pass NULL: zeros)");
-        return MPK_EINVAL;
-    }
-    return MPK_OK;
-}
-
-static int demonstration_phase_log_prob_entry(const char* fn, mpk_handle hh, const float* params, const float* params_L,
-                                              const float* init_pos, const float* init_vel, double init_time_shared, const float* pos,
-                                              const float* obs_std, bool grad, double* log_prob, const double* g, float* g_params,
-                                              float* g_params_L, int32_t B, void* stream) {
-    const std::string name(fn);
-    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
-    Handle* h = reinterpret_cast<Handle*>(hh);
-    if (!params || !params_L) { set_error(name + ": NULL params or params_L"); return MPK_EINVAL; }
-    if (!pos || !obs_std) { set_error(name + ": NULL pos or obs_std"); return MPK_EINVAL; }
-    if (!grad && !log_prob) { set_error(name + ": NULL log_prob"); return MPK_EINVAL; }
-    if (grad && !g) { set_error(name + ": NULL g"); return MPK_EINVAL; }
-    if (grad && !g_params && !g_params_L) { set_error(name + ": g_params and g_params_L are both NULL: nothing to compute"); return MPK_EINVAL; }
-    if (B < 1) { set_error(name + ": B must be >= 1"); return MPK_EINVAL; }
-    const int rc = demonstration_phase_checks(name, h, init_pos, init_vel);
-    if (rc != MPK_OK) return rc;
-    MPK_ON_DEVICE(h->cfg.device);
-    DemoLogProbLaunch q;
-    q.params = params; q.params_L = params_L; q.init_pos = init_pos; q.init_vel = init_vel; q.init_time = (float)init_time_shared;
-    q.pos = pos; q.obs_std = obs_std;
-    q.grad = grad; q.log_prob = log_prob; q.g = g; q.g_params = g_params; q.g_params_L = g_params_L; q.B = B;
-    q.phase = true; q.range_flag = h->d_flag;
-    return launch_demo_log_prob(h->dev, SharedTables{}, q, h->num_cu, stream, &h->last_kernel);
+    return demonstration_log_prob_entry("mpk_demonstration_log_prob_vjp", false, hh,
+                                        {params, params_L, init_pos, init_vel, (float)init_time_shared, B}, init_time_shared, pos, obs_std,
+                                        {true, nullptr, g, g_params, g_params_L}, stream);
 }
 
 int mpk_demonstration_phase_log_prob(mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
                                      const float* init_vel, double init_time_shared, const float* pos, const float* obs_std,
                                      double* log_prob, int32_t B, void* stream) {
-    return demonstration_phase_log_prob_entry("mpk_demonstration_phase_log_prob", hh, params, params_L, init_pos, init_vel,
-                                              init_time_shared, pos, obs_std, false, log_prob, nullptr, nullptr, nullptr, B, stream);
+    return demonstration_log_prob_entry("mpk_demonstration_phase_log_prob", true, hh,
+                                        {params, params_L, init_pos, init_vel, (float)init_time_shared, B}, init_time_shared, pos, obs_std,
+                                        {false, log_prob, nullptr, nullptr, nullptr}, stream);
 }
 
 int mpk_demonstration_phase_log_prob_vjp(mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
                                          const float* init_vel, double init_time_shared, const float* pos, const float* obs_std,
                                          const double* g, float* g_params, float* g_params_L, int32_t B, void* stream) {
-    return demonstration_phase_log_prob_entry("mpk_demonstration_phase_log_prob_vjp", hh, params, params_L, init_pos, init_vel,
-                                              init_time_shared, pos, obs_std, true, nullptr, g, g_params, g_params_L, B, stream);
+    return demonstration_log_prob_entry("mpk_demonstration_phase_log_prob_vjp", true, hh,
+                                        {params, params_L, init_pos, init_vel, (float)init_time_shared, B}, init_time_shared, pos, obs_std,
+                                        {true, nullptr, g, g_params, g_params_L}, stream);
+}
+
+// N(params, L L^T) conditioned on whole demonstrations: the log-likelihood's validation, refusals and tables; one launch
+static int demonstration_condition_entry(const std::string& name, bool phase, mpk_handle hh, const GaussIn& in, double init_time_shared,
+                                         const float* pos, const float* obs_std, const PosteriorOut& out, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!in.params || !in.params_L || !out.params_out || !out.params_L_out)
+        return refuse(MPK_EINVAL, name + ": NULL params or params_L, in or out");
+    if (!pos || !obs_std) return refuse(MPK_EINVAL, name + ": NULL pos or obs_std");
+    if (const int rc = batch_check(name, in.B)) return rc;
+    if (const int rc = demonstration_checks(name, h, phase, "a conditioning kernel", name.c_str(), in)) return rc;
+    MPK_ON_DEVICE(h->cfg.device);
+    SharedTables st;
+    if (const int rc = demonstration_tables(h, phase, init_time_shared, stream, &st)) return rc;
+    const DemoCondLaunch q{in, {pos, obs_std, phase, phase ? h->d_flag : nullptr}, out};
+    return launch_demo_condition(h->dev, st, q, h->num_cu, stream, &h->last_kernel);
+}
+
+int mpk_demonstration_condition(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                                double init_time_shared, const float* pos, const float* obs_std, float* params_out,
+                                float* params_L_out, int32_t B, void* stream) {
+    return demonstration_condition_entry("mpk_demonstration_condition", false, hh,
+                                         {params, params_L, init_pos, init_vel, (float)init_time_shared, B}, init_time_shared, pos, obs_std,
+                                         {params_out, params_L_out}, stream);
 }
 
 int mpk_demonstration_phase_condition(mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
                                       const float* init_vel, double init_time_shared, const float* pos, const float* obs_std,
                                       float* params_out, float* params_L_out, int32_t B, void* stream) {
-    const std::string name("mpk_demonstration_phase_condition");
-    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
-    Handle* h = reinterpret_cast<Handle*>(hh);
-    if (!params || !params_L || !params_out || !params_L_out) { set_error(name + ": NULL params or params_L, in or out"); return MPK_EINVAL; }
-    if (!pos || !obs_std) { set_error(name + ": NULL pos or obs_std"); return MPK_EINVAL; }
-    if (B < 1) { set_error(name + ": B must be >= 1"); return MPK_EINVAL; }
-    const int rc = demonstration_phase_checks(name, h, init_pos, init_vel);
-    if (rc != MPK_OK) return rc;
-    MPK_ON_DEVICE(h->cfg.device);
-    DemoCondLaunch q;
-    q.params = params; q.params_L = params_L; q.init_pos = init_pos; q.init_vel = init_vel; q.init_time = (float)init_time_shared;
-    q.pos = pos; q.obs_std = obs_std; q.params_out = params_out; q.params_L_out = params_L_out; q.B = B;
-    q.phase = true; q.range_flag = h->d_flag;
-    return launch_demo_condition(h->dev, SharedTables{}, q, h->num_cu, stream, &h->last_kernel);
+    return demonstration_condition_entry("mpk_demonstration_phase_condition", true, hh,
+                                         {params, params_L, init_pos, init_vel, (float)init_time_shared, B}, init_time_shared, pos, obs_std,
+                                         {params_out, params_L_out}, stream);
 }
 
-// the launch plan of the three entries above for B episodes on this handle's device: no HIP call
-int mpk_demonstration_phase_plan(mpk_handle hh, int32_t B, int32_t* blocks, int32_t* waves, int32_t* lds_bytes) {
-    const std::string name("mpk_demonstration_phase_plan");
+// the launch plan of the conditioning entries (phase: of the three mpk_demonstration_phase_* entries) for B episodes on this handle's
+// device: no HIP call
+static int demonstration_plan_entry(const std::string& name, bool phase, mpk_handle hh, int32_t B, int32_t* blocks, int32_t* waves,
+                                    int32_t* lds_bytes) {
     if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
     Handle* h = reinterpret_cast<Handle*>(hh);
-    if (B < 1) { set_error(name + ": B must be >= 1"); return MPK_EINVAL; }
-    if (!h->cfg.learn_tau && !h->cfg.learn_delay) {
-        set_error(name + ": this handle learns neither tau nor delay: every episode has the handle's phase, which is what the shared-phase "
-                  "entry (without _phase) evaluates");
-        return MPK_ENOTIMPL;
-    }
-    int nb = 0, nw = 0;
-    size_t lds = 0;
-    const int rc = demo_condition_launch_plan(h->dev, B, h->num_cu, &nb, &nw, &lds, true);
-    if (rc != MPK_OK) return rc;
-    if (blocks) *blocks = nb;
-    if (waves) *waves = nw;
-    if (lds_bytes) *lds_bytes = (int32_t)lds;
-    return MPK_OK;
+    if (const int rc = batch_check(name, B)) return rc;
+    if (const int rc = phase ? episode_phase_check(name, h) : shared_phase_check(name, h, "a conditioning kernel")) return rc;
+    return demo_condition_launch_plan(h->dev, B, h->num_cu, phase, blocks, waves, lds_bytes);
+}
+
+int mpk_demonstration_condition_plan(mpk_handle hh, int32_t B, int32_t* blocks, int32_t* waves, int32_t* lds_bytes) {
+    return demonstration_plan_entry("mpk_demonstration_condition_plan", false, hh, B, blocks, waves, lds_bytes);
+}
+
+int mpk_demonstration_phase_plan(mpk_handle hh, int32_t B, int32_t* blocks, int32_t* waves, int32_t* lds_bytes) {
+    return demonstration_plan_entry("mpk_demonstration_phase_plan", true, hh, B, blocks, waves, lds_bytes);
 }
 
 int mpk_trajectory_actions(mpk_handle hh, const float* params, const float* init_pos, const float* init_vel,

@@ -312,94 +312,95 @@ int launch_traj_fit(const DevCfg& c, const SharedTables& st, const double* fac, 
 int traj_std_limits(const DevCfg& c, size_t* lds_out, int* pitch_out, int* image_out);
 int launch_traj_std(const DevCfg& c, const SharedTables& st, const float* params_L, float* pos_std, float* vel_std, int B, int num_cu,
                     void* stream, const char** kernel_name);
-// mpk_trajectory_condition (mpk_traj_condition.hip): the Gaussian N(params, L L^T) over the non-phase parameters conditioned on observed
-// positions / velocities at M shared steps -- a sequential square-root measurement update of the factor in float64, one launch of
-// k_traj_condition, one wave per episode.  steps: HOST, validated by the caller (strictly increasing, in [0, T)); either observation
-// pair may be nullptr; the outputs may be the inputs.  traj_cond_limits: MPK_OK, or MPK_ENOTIMPL with the reason in the message -- a DMP,
-// more than kMaxD DoF or kMaxKP columns, a Pl whose float64 triangle and work vectors exceed the LDS with one wave per workgroup (no HIP
-// call; the outputs may be nullptr).
-struct CondLaunch {
+// ---- the probabilistic entry points: a launch request is {in, obs, out}, composed from these parts (mpk_gauss_launch.h has the launch
+// plumbing the four wave-per-episode units share)
+struct GaussIn {                                                        // the Gaussian N(params, L L^T) and the movement's start
     const float *params = nullptr, *params_L = nullptr, *init_pos = nullptr, *init_vel = nullptr;
-    const int32_t* steps = nullptr;                                     // HOST [M]
-    int M = 0;
     float init_time = 0.f;                                              // the tables' (init_time_shared)
-    const float *obs_pos = nullptr, *obs_pos_std = nullptr, *obs_vel = nullptr, *obs_vel_std = nullptr;   // [B, M, D]
-    float *params_out = nullptr, *params_L_out = nullptr;
     int B = 0;
+};
+struct PointObs {                                                       // positions / velocities at M shared steps; either pair may be nullptr
+    const int32_t* steps = nullptr;                                     // HOST [M], validated by the caller (strictly increasing, in [0, T))
+    int M = 0;
+    const float *obs_pos = nullptr, *obs_pos_std = nullptr, *obs_vel = nullptr, *obs_vel_std = nullptr;   // [B, M, D]
+};
+struct DemoObs {                                                        // whole demonstrations
+    const float *pos = nullptr, *obs_std = nullptr;                     // [B, T, D]
+    bool phase = false;                                                 // the per-episode-phase route (mpk_demonstration_phase_*)
+    int32_t* range_flag = nullptr;                                      // phase, ProDMP: raised beyond the pre-computed range
+};
+struct LikelihoodOut {                                                  // grad = false: log_prob is written; grad = true: g is read and
+    bool grad = false;                                                  // g_params / g_params_L (either may be nullptr) are written
+    double* log_prob = nullptr;                                         // [B]
+    const double* g = nullptr;                                          // [B]
+    float *g_params = nullptr, *g_params_L = nullptr;
+};
+struct PosteriorOut {                                                   // may be the inputs
+    float *params_out = nullptr, *params_L_out = nullptr;
+};
+// mpk_trajectory_condition (mpk_traj_condition.hip): the Gaussian over the non-phase parameters conditioned on point observations -- a
+// sequential square-root measurement update of the factor in float64, one launch of k_traj_condition, one wave per episode.
+// traj_cond_limits: MPK_OK, or MPK_ENOTIMPL with the reason in the message -- a DMP, more than kMaxD DoF or kMaxKP columns, a Pl whose
+// float64 triangle and work vectors exceed the LDS with one wave per workgroup (no HIP call; the outputs may be nullptr).
+struct CondLaunch {
+    GaussIn in;
+    PointObs obs;
+    PosteriorOut out;
 };
 int traj_cond_limits(const DevCfg& c, int M, size_t* lds_out, int* waves_out, int* wave_doubles_out);
 int launch_traj_condition(const DevCfg& c, const SharedTables& st, const CondLaunch& q, int num_cu, void* stream, const char** kernel_name);
 // mpk_trajectory_log_prob / _vjp (mpk_traj_log_prob.hip): the log-likelihood of conditioning's scalar observations under N(params, L L^T)
 // by a dense float64 Cholesky factorisation of their n x n covariance, and its gradient w.r.t. params and params_L -- one launch of
-// k_traj_log_prob each, one wave per episode, the gradient launch recomputing everything from the inputs.  steps: HOST, validated by the
-// caller; either observation pair may be nullptr.  grad = false: log_prob [B] is written; grad = true: g [B] is read and g_params /
-// g_params_L (either may be nullptr) are written.  traj_log_prob_limits: MPK_OK, or MPK_ENOTIMPL with the reason in the message -- a DMP,
-// more than kMaxD DoF or kMaxKP columns, more than MPK_LOGPROB_MAX_OBS candidate observations (M D narr, narr the observation arrays
-// given), float64 images that exceed the LDS with one wave per workgroup (no HIP call; the outputs may be nullptr).
+// k_traj_log_prob each, one wave per episode, the gradient launch recomputing everything from the inputs.  traj_log_prob_limits: MPK_OK,
+// or MPK_ENOTIMPL with the reason in the message -- a DMP, more than kMaxD DoF or kMaxKP columns, more than MPK_LOGPROB_MAX_OBS candidate
+// observations (M D narr, narr the observation arrays given), float64 images that exceed the LDS with one wave per workgroup (no HIP
+// call; the outputs may be nullptr).
 struct LogProbLaunch {
-    const float *params = nullptr, *params_L = nullptr, *init_pos = nullptr, *init_vel = nullptr;
-    const int32_t* steps = nullptr;                                     // HOST [M]
-    int M = 0;
-    float init_time = 0.f;                                              // the tables' (init_time_shared)
-    const float *obs_pos = nullptr, *obs_pos_std = nullptr, *obs_vel = nullptr, *obs_vel_std = nullptr;   // [B, M, D]
-    bool grad = false;
-    double* log_prob = nullptr;                                         // [B]
-    const double* g = nullptr;                                          // [B]
-    float *g_params = nullptr, *g_params_L = nullptr;
-    int B = 0;
+    GaussIn in;
+    PointObs obs;
+    LikelihoodOut out;
 };
 int traj_log_prob_limits(const DevCfg& c, int M, int narr, size_t* lds_out, int* waves_out, int* wave_doubles_out);
 int launch_traj_log_prob(const DevCfg& c, const SharedTables& st, const LogProbLaunch& q, int num_cu, void* stream,
                          const char** kernel_name);
-// mpk_demonstration_log_prob / _vjp (mpk_demo_log_prob.hip): the log-likelihood of whole demonstrations pos [B, T, D] with standard
-// deviations obs_std [B, T, D] under N(params, L L^T) in the information form -- the Gram matrices G_d, M = I + tril(L)^T G tril(L)
-// = C C^T [Pl x Pl] -- and its gradient w.r.t. params and params_L: one launch of k_demo_log_prob each, one wave per episode, the
-// gradient launch recomputing everything from the inputs.  grad = false: log_prob [B] is written; grad = true: g [B] is read and
-// g_params / g_params_L (either may be nullptr) are written.  demo_log_prob_limits: MPK_OK, or MPK_ENOTIMPL with the limit in the
-// message -- a DMP, more than kMaxD DoF or kMaxKP columns, Pl > 64 x 4, float64 images that exceed the LDS with one wave per workgroup
-// (no HIP call; the outputs may be nullptr).
+// mpk_demonstration_log_prob / _vjp (mpk_demo_log_prob.hip): the log-likelihood of whole demonstrations under N(params, L L^T) in the
+// information form -- the Gram matrices G_d, M = I + tril(L)^T G tril(L) = C C^T [Pl x Pl] -- and its gradient w.r.t. params and
+// params_L: one launch of k_demo_log_prob each, one wave per episode, the gradient launch recomputing everything from the inputs.
+// demo_log_prob_limits: MPK_OK and the launch's plan (plan may be nullptr), or MPK_ENOTIMPL with the limit in the message, under the
+// entry's name fn -- a DMP, more than kMaxD DoF or kMaxKP columns, Pl > 64 x 4, float64 images that exceed the LDS with one wave per
+// workgroup (no HIP call).
+// mpk_demonstration_phase_* : the same two kernels with a PER-EPISODE row source (template flag PHASE, obs.phase) for handles that learn
+// tau / delay: the tau / delay of episode b are given at the front of params[b], clipped as the forward clips them; the wave evaluates
+// its episode's rows a chunk of steps at a time (mpk_phase_rows.h, k_phase_fit's row evaluation) into a chunk image of its own, and no
+// shared table is read (st is ignored).  demo_phase_limits: demo_log_prob_limits' refusals in the same words -- with the chunk image
+// [tc][(Kloc + 3) | 1] added per wave and [T][KT] replaced by row constants and base times per workgroup -- plus rows beyond
+// k_traj_phase's 16 slots.
 struct DemoLogProbLaunch {
-    const float *params = nullptr, *params_L = nullptr, *init_pos = nullptr, *init_vel = nullptr;
-    float init_time = 0.f;                                              // the tables' (init_time_shared)
-    const float *pos = nullptr, *obs_std = nullptr;                     // [B, T, D]
-    bool grad = false;
-    double* log_prob = nullptr;                                         // [B]
-    const double* g = nullptr;                                          // [B]
-    float *g_params = nullptr, *g_params_L = nullptr;
-    int B = 0;
-    bool phase = false;                                                 // the per-episode-phase route (below)
-    int32_t* range_flag = nullptr;                                      // phase, ProDMP: raised beyond the pre-computed range
+    GaussIn in;
+    DemoObs obs;
+    LikelihoodOut out;
 };
-int demo_log_prob_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* wave_doubles_out, int* tc_out, int* scratch_out,
-                         const char* fn = "mpk_demonstration_log_prob");
-int launch_demo_log_prob(const DevCfg& c, const SharedTables& st, const DemoLogProbLaunch& q, int num_cu, void* stream,
-                         const char** kernel_name);
-// mpk_demonstration_phase_* : the same two kernels with a PER-EPISODE row source (template flag PHASE) for handles that learn tau / delay:
-// the tau / delay of episode b are given at the front of params[b], clipped as the forward clips them; the wave evaluates its episode's
-// rows a chunk of steps at a time (mpk_phase_rows.h, k_phase_fit's row evaluation) into a chunk image of its own, and no shared table is
-// read (st is ignored).  demo_phase_limits: demo_log_prob_limits' refusals in the same words -- with the chunk image [tc][(Kloc + 3) | 1]
-// added per wave and [T][KT] replaced by row constants and base times per workgroup -- plus rows beyond k_traj_phase's 16 slots.
 struct DemoPlan {
     size_t lds = 0;                                                     // bytes per workgroup
     int waves = 0, wave_doubles = 0, tc = 0, scratch = 0;
     int sl = 0, chunk = 0, c_pad = 0;                                   // the phase route's (0 otherwise)
 };
+int demo_log_prob_limits(const DevCfg& c, DemoPlan* plan, const char* fn = "mpk_demonstration_log_prob");
 int demo_phase_limits(const DevCfg& c, DemoPlan* plan, const char* fn);
+int launch_demo_log_prob(const DevCfg& c, const SharedTables& st, const DemoLogProbLaunch& q, int num_cu, void* stream,
+                         const char** kernel_name);
 // mpk_demonstration_condition (mpk_demo_condition.hip): N(params, L L^T) conditioned on the kept entries of whole demonstrations, in the
 // same information form -- M = K^T K from the last row (the reverse Cholesky), L' = tril(L) K^-1, mu' = mu + L' K^-T v: one launch of
-// k_demo_condition, one wave per episode, k_demo_log_prob's images and workgroups (demo_log_prob_limits refuses under this entry's name).
-// The outputs may be the inputs.  demo_condition_launch_plan: the workgroups, waves per workgroup and LDS bytes a launch of B episodes
-// takes (no HIP call; any output may be nullptr).
+// k_demo_condition, one wave per episode, k_demo_log_prob's images and workgroups (its limits refuse under this entry's name).
+// demo_condition_launch_plan: the workgroups, waves per workgroup and LDS bytes a launch of B episodes takes, on either route (no HIP
+// call; any output may be nullptr).
 struct DemoCondLaunch {
-    const float *params = nullptr, *params_L = nullptr, *init_pos = nullptr, *init_vel = nullptr;
-    float init_time = 0.f;                                              // the tables' (init_time_shared)
-    const float *pos = nullptr, *obs_std = nullptr;                     // [B, T, D]
-    float *params_out = nullptr, *params_L_out = nullptr;
-    int B = 0;
-    bool phase = false;                                                 // the per-episode-phase route
-    int32_t* range_flag = nullptr;
+    GaussIn in;
+    DemoObs obs;
+    PosteriorOut out;
 };
-int demo_condition_launch_plan(const DevCfg& c, int B, int num_cu, int* blocks_out, int* waves_out, size_t* lds_out, bool phase = false);
+int demo_condition_launch_plan(const DevCfg& c, int B, int num_cu, bool phase, int32_t* blocks_out, int32_t* waves_out,
+                               int32_t* lds_bytes_out);
 int launch_demo_condition(const DevCfg& c, const SharedTables& st, const DemoCondLaunch& q, int num_cu, void* stream,
                           const char** kernel_name);
 int launch_episode_reset(const double* init_q, const double* init_qd, double* q, double* qd, float* cond_pos,

@@ -2,6 +2,7 @@
 #include "mpk_tile.h"
 #include "mpk_vjp_row.h"
 #include "mpk_cond_rows.h"
+#include "mpk_gauss_launch.h"
 
 namespace mpk {
 
@@ -245,16 +246,7 @@ __global__ void __launch_bounds__(256) k_traj_condition(const CondArgs a) {
 #ifndef MPK_DEVICE_ONLY
 // the shapes the kernel takes; MPK_ENOTIMPL with the limit in the message otherwise (no HIP call).  M: the observed steps of the call.
 int traj_cond_limits(const DevCfg& c, int M, size_t* lds_out, int* waves_out, int* wave_doubles_out) {
-    if (c.mp_type == MPK_MP_DMP || c.dmp_resp) {
-        set_error("mpk_trajectory_condition: a DMP has no probabilistic interface (promp / prodmp only)");
-        return MPK_ENOTIMPL;
-    }
-    if (c.D > kMaxD || c.KP > kMaxKP) {
-        set_error("mpk_trajectory_condition: at most " + std::to_string(kMaxD) + " DoF and " + std::to_string(kMaxKP) +
-                  " table columns (this handle: " + std::to_string(c.D) + " DoF, " + std::to_string(c.KT) +
-                  " columns); the k_traj_wide shapes have no kernel here");
-        return MPK_ENOTIMPL;
-    }
+    if (const int rc = gauss_common_limits(c, "mpk_trajectory_condition")) return rc;
     const size_t Pl = (size_t)c.D * c.Kloc;
     const size_t wave_doubles = Pl * (Pl + 1) / 2 + 4 * Pl;
     const size_t shared = (size_t)2 * M * c.KT * sizeof(double);
@@ -264,58 +256,41 @@ int traj_cond_limits(const DevCfg& c, int M, size_t* lds_out, int* waves_out, in
                   std::to_string(kLdsPerCu) + " bytes of LDS");
         return MPK_ENOTIMPL;
     }
-    // the waves per workgroup (<= 4) that put the most waves on a CU; the larger workgroup on a tie (the tables are staged once each)
-    int best = 1;
-    size_t best_on_cu = 0;
-    for (int w = 1; w <= 4; ++w) {
-        const size_t bytes = w * wave_doubles * sizeof(double) + shared;
-        if (bytes > kLdsPerCu) break;
-        const size_t on_cu = w * (kLdsPerCu / bytes);
-        if (on_cu >= best_on_cu) { best = w; best_on_cu = on_cu; }
-    }
-    if (lds_out) *lds_out = best * wave_doubles * sizeof(double) + shared;
-    if (waves_out) *waves_out = best;
+    const WavePlan plan = gauss_wave_plan(wave_doubles, shared);
+    if (lds_out) *lds_out = plan.lds;
+    if (waves_out) *waves_out = plan.waves;
     if (wave_doubles_out) *wave_doubles_out = (int)wave_doubles;
     return MPK_OK;
-}
-
-template <int MP>
-static int launch_traj_condition_mp(const CondArgs& ca, int ns, int blocks, size_t lds, void* stream) {
-    auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(64 * ca.waves), lds, stream, ca); };
-    switch (ns) {
-        case 1: return go(k_traj_condition<MP, 1>);
-        case 2: return go(k_traj_condition<MP, 2>);
-        case 3: return go(k_traj_condition<MP, 3>);
-        default: return go(k_traj_condition<MP, 4>);
-    }
 }
 
 int launch_traj_condition(const DevCfg& c, const SharedTables& st, const CondLaunch& q, int num_cu, void* stream, const char** kernel_name) {
     CondArgs ca{};
     size_t lds = 0;
-    const int rc = traj_cond_limits(c, q.M, &lds, &ca.waves, &ca.wave_doubles);
+    const int M = q.obs.M;
+    const int rc = traj_cond_limits(c, M, &lds, &ca.waves, &ca.wave_doubles);
     if (rc != MPK_OK) return rc;
     const bool promp = c.mp_type == MPK_MP_PROMP;
-    if (promp && q.obs_vel && c.T < 2) {
+    if (promp && q.obs.obs_vel && c.T < 2) {
         set_error("promp needs at least two time steps for the finite-difference velocity");
         return MPK_EINVAL;
     }
-    if (q.M < 1 || q.M > kCondMaxObs) {
+    if (M < 1 || M > kCondMaxObs) {
         set_error("mpk_trajectory_condition: internal: the number of observed steps is outside 1.." + std::to_string(kCondMaxObs));
         return MPK_EINVAL;
     }
-    ca.c = c; ca.A = st.A; ca.aux = st.aux; ca.TS = st.TS; ca.init_time = q.init_time;
-    ca.params = q.params; ca.L = q.params_L; ca.init_pos = q.init_pos; ca.init_vel = q.init_vel;
-    ca.obs[0] = q.obs_pos; ca.sd[0] = q.obs_pos_std; ca.obs[1] = q.obs_vel; ca.sd[1] = q.obs_vel_std;
-    ca.params_out = q.params_out; ca.L_out = q.params_L_out;
-    ca.B = q.B; ca.Pl = c.D * c.Kloc; ca.M = q.M;
-    for (int m = 0; m < q.M; ++m) ca.steps[m] = q.steps[m];
-    const int per_cu = (int)(kLdsPerCu / lds) < 1 ? 1 : ((int)(kLdsPerCu / lds) > 8 ? 8 : (int)(kLdsPerCu / lds));
-    const long units = ((long)q.B + ca.waves - 1) / ca.waves;
-    const int blocks = (int)(units < (long)num_cu * per_cu ? units : (long)num_cu * per_cu);
+    ca.c = c; ca.A = st.A; ca.aux = st.aux; ca.TS = st.TS; ca.init_time = q.in.init_time;
+    ca.params = q.in.params; ca.L = q.in.params_L; ca.init_pos = q.in.init_pos; ca.init_vel = q.in.init_vel;
+    ca.obs[0] = q.obs.obs_pos; ca.sd[0] = q.obs.obs_pos_std; ca.obs[1] = q.obs.obs_vel; ca.sd[1] = q.obs.obs_vel_std;
+    ca.params_out = q.out.params_out; ca.L_out = q.out.params_L_out;
+    ca.B = q.in.B; ca.Pl = c.D * c.Kloc; ca.M = M;
+    for (int m = 0; m < M; ++m) ca.steps[m] = q.obs.steps[m];
+    const int blocks = gauss_blocks(q.in.B, ca.waves, lds, num_cu);
     *kernel_name = promp ? "k_traj_condition<promp>" : "k_traj_condition<prodmp>";
-    return promp ? launch_traj_condition_mp<MPK_MP_PROMP>(ca, (ca.Pl + 63) / 64, blocks, lds, stream)
-                 : launch_traj_condition_mp<MPK_MP_PRODMP>(ca, (ca.Pl + 63) / 64, blocks, lds, stream);
+    return dispatch_mp(promp, [&](auto mp) {
+        return dispatch_ns((ca.Pl + 63) / 64, [&](auto ns) {
+            return launch_kernel(k_traj_condition<mp.value, ns.value>, dim3(blocks), dim3(64 * ca.waves), lds, stream, ca);
+        });
+    });
 }
 #endif  // MPK_DEVICE_ONLY
 

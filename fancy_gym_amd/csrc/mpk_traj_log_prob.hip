@@ -3,6 +3,7 @@
 #include "mpk_tile.h"
 #include "mpk_vjp_row.h"
 #include "mpk_cond_rows.h"
+#include "mpk_gauss_launch.h"
 
 namespace mpk {
 
@@ -338,16 +339,7 @@ __global__ void __launch_bounds__(256) k_traj_log_prob(const LogProbArgs a) {
 // the shapes the kernel takes; MPK_ENOTIMPL with the limit in the message otherwise (no HIP call).  M: the observed steps of the call,
 // narr: the observation arrays given (1 or 2)
 int traj_log_prob_limits(const DevCfg& c, int M, int narr, size_t* lds_out, int* waves_out, int* wave_doubles_out) {
-    if (c.mp_type == MPK_MP_DMP || c.dmp_resp) {
-        set_error("mpk_trajectory_log_prob: a DMP has no probabilistic interface (promp / prodmp only)");
-        return MPK_ENOTIMPL;
-    }
-    if (c.D > kMaxD || c.KP > kMaxKP) {
-        set_error("mpk_trajectory_log_prob: at most " + std::to_string(kMaxD) + " DoF and " + std::to_string(kMaxKP) +
-                  " table columns (this handle: " + std::to_string(c.D) + " DoF, " + std::to_string(c.KT) +
-                  " columns); the k_traj_wide shapes have no kernel here");
-        return MPK_ENOTIMPL;
-    }
+    if (const int rc = gauss_common_limits(c, "mpk_trajectory_log_prob")) return rc;
     const size_t nmax = (size_t)M * c.D * narr;
     if (nmax > (size_t)kLpMaxObs) {
         set_error("mpk_trajectory_log_prob: at most " + std::to_string(kLpMaxObs) + " scalar observations per episode (M x D x the "
@@ -364,67 +356,47 @@ int traj_log_prob_limits(const DevCfg& c, int M, int narr, size_t* lds_out, int*
                   "fit the CU's " + std::to_string(kLdsPerCu) + " bytes of LDS");
         return MPK_ENOTIMPL;
     }
-    // the waves per workgroup (<= 4) that put the most waves on a CU; the larger workgroup on a tie (the tables are staged once each)
-    int best = 1;
-    size_t best_on_cu = 0;
-    for (int w = 1; w <= 4; ++w) {
-        const size_t bytes = w * wave_doubles * sizeof(double) + shared;
-        if (bytes > kLdsPerCu) break;
-        const size_t on_cu = w * (kLdsPerCu / bytes);
-        if (on_cu >= best_on_cu) { best = w; best_on_cu = on_cu; }
-    }
-    if (lds_out) *lds_out = best * wave_doubles * sizeof(double) + shared;
-    if (waves_out) *waves_out = best;
+    const WavePlan plan = gauss_wave_plan(wave_doubles, shared);
+    if (lds_out) *lds_out = plan.lds;
+    if (waves_out) *waves_out = plan.waves;
     if (wave_doubles_out) *wave_doubles_out = (int)wave_doubles;
     return MPK_OK;
-}
-
-template <int MP, bool GRAD>
-static int launch_traj_log_prob_mp(const LogProbArgs& la, int ns, int blocks, size_t lds, void* stream) {
-    auto go = [&](auto kern) { return launch_kernel(kern, dim3(blocks), dim3(64 * la.waves), lds, stream, la); };
-    switch (ns) {
-        case 1: return go(k_traj_log_prob<MP, 1, GRAD>);
-        case 2: return go(k_traj_log_prob<MP, 2, GRAD>);
-        case 3: return go(k_traj_log_prob<MP, 3, GRAD>);
-        default: return go(k_traj_log_prob<MP, 4, GRAD>);
-    }
 }
 
 int launch_traj_log_prob(const DevCfg& c, const SharedTables& st, const LogProbLaunch& q, int num_cu, void* stream,
                          const char** kernel_name) {
     LogProbArgs la{};
     size_t lds = 0;
-    const int narr = (q.obs_pos ? 1 : 0) + (q.obs_vel ? 1 : 0);
-    if (q.M < 1 || q.M > MPK_COND_MAX_STEPS || narr < 1) {
+    const int M = q.obs.M, narr = (q.obs.obs_pos ? 1 : 0) + (q.obs.obs_vel ? 1 : 0);
+    if (M < 1 || M > MPK_COND_MAX_STEPS || narr < 1) {
         set_error("mpk_trajectory_log_prob: internal: the observed steps are outside 1.." + std::to_string(MPK_COND_MAX_STEPS) +
                   " or no observation array is given");
         return MPK_EINVAL;
     }
-    const int rc = traj_log_prob_limits(c, q.M, narr, &lds, &la.waves, &la.wave_doubles);
+    const int rc = traj_log_prob_limits(c, M, narr, &lds, &la.waves, &la.wave_doubles);
     if (rc != MPK_OK) return rc;
     const bool promp = c.mp_type == MPK_MP_PROMP;
-    if (promp && q.obs_vel && c.T < 2) {
+    if (promp && q.obs.obs_vel && c.T < 2) {
         set_error("promp needs at least two time steps for the finite-difference velocity");
         return MPK_EINVAL;
     }
-    la.c = c; la.A = st.A; la.aux = st.aux; la.TS = st.TS; la.init_time = q.init_time;
-    la.params = q.params; la.L = q.params_L; la.init_pos = q.init_pos; la.init_vel = q.init_vel;
-    la.obs[0] = q.obs_pos; la.sd[0] = q.obs_pos_std; la.obs[1] = q.obs_vel; la.sd[1] = q.obs_vel_std;
-    la.log_prob = q.log_prob; la.g = q.g; la.g_params = q.g_params; la.g_L = q.g_params_L;
-    la.B = q.B; la.Pl = c.D * c.Kloc; la.M = q.M; la.narr = narr; la.nmax = q.M * c.D * narr; la.ld = la.Pl | 1;
-    for (int m = 0; m < q.M; ++m) la.steps[m] = q.steps[m];
-    const int per_cu = (int)(kLdsPerCu / lds) < 1 ? 1 : ((int)(kLdsPerCu / lds) > 8 ? 8 : (int)(kLdsPerCu / lds));
-    const long units = ((long)q.B + la.waves - 1) / la.waves;
-    const int blocks = (int)(units < (long)num_cu * per_cu ? units : (long)num_cu * per_cu);
-    const int ns = (la.Pl + 63) / 64;
-    if (q.grad) {
-        *kernel_name = promp ? "k_traj_log_prob<promp, grad>" : "k_traj_log_prob<prodmp, grad>";
-        return promp ? launch_traj_log_prob_mp<MPK_MP_PROMP, true>(la, ns, blocks, lds, stream)
-                     : launch_traj_log_prob_mp<MPK_MP_PRODMP, true>(la, ns, blocks, lds, stream);
-    }
-    *kernel_name = promp ? "k_traj_log_prob<promp>" : "k_traj_log_prob<prodmp>";
-    return promp ? launch_traj_log_prob_mp<MPK_MP_PROMP, false>(la, ns, blocks, lds, stream)
-                 : launch_traj_log_prob_mp<MPK_MP_PRODMP, false>(la, ns, blocks, lds, stream);
+    la.c = c; la.A = st.A; la.aux = st.aux; la.TS = st.TS; la.init_time = q.in.init_time;
+    la.params = q.in.params; la.L = q.in.params_L; la.init_pos = q.in.init_pos; la.init_vel = q.in.init_vel;
+    la.obs[0] = q.obs.obs_pos; la.sd[0] = q.obs.obs_pos_std; la.obs[1] = q.obs.obs_vel; la.sd[1] = q.obs.obs_vel_std;
+    la.log_prob = q.out.log_prob; la.g = q.out.g; la.g_params = q.out.g_params; la.g_L = q.out.g_params_L;
+    la.B = q.in.B; la.Pl = c.D * c.Kloc; la.M = M; la.narr = narr; la.nmax = M * c.D * narr; la.ld = la.Pl | 1;
+    for (int m = 0; m < M; ++m) la.steps[m] = q.obs.steps[m];
+    const int blocks = gauss_blocks(q.in.B, la.waves, lds, num_cu);
+    static const char* const names[2][2] = {{"k_traj_log_prob<prodmp>", "k_traj_log_prob<promp>"},
+                                            {"k_traj_log_prob<prodmp, grad>", "k_traj_log_prob<promp, grad>"}};
+    *kernel_name = names[q.out.grad][promp];
+    return dispatch_flag(q.out.grad, [&](auto grad) {
+        return dispatch_mp(promp, [&](auto mp) {
+            return dispatch_ns((la.Pl + 63) / 64, [&](auto ns) {
+                return launch_kernel(k_traj_log_prob<mp.value, ns.value, grad.value>, dim3(blocks), dim3(64 * la.waves), lds, stream, la);
+            });
+        });
+    });
 }
 #endif  // MPK_DEVICE_ONLY
 

@@ -2,6 +2,7 @@
 #include "mpk_tile.h"
 #include "mpk_run_stage.h"
 #include "mpk_vjp_row.h"
+#include "mpk_gauss_launch.h"
 
 namespace mpk {
 
@@ -185,15 +186,7 @@ __global__ void __launch_bounds__(256) k_traj_std_tile(const StdArgs a) {
 #ifndef MPK_DEVICE_ONLY
 // the shapes the kernel takes; MPK_ENOTIMPL with the limit in the message otherwise (no HIP call)
 int traj_std_limits(const DevCfg& c, size_t* lds_out, int* pitch_out, int* image_out) {
-    if (c.mp_type == MPK_MP_DMP || c.dmp_resp) {
-        set_error("mpk_trajectory_std: a DMP has no probabilistic interface (promp / prodmp only)");
-        return MPK_ENOTIMPL;
-    }
-    if (c.D > kMaxD || c.KP > kMaxKP) {
-        set_error("mpk_trajectory_std: at most " + std::to_string(kMaxD) + " DoF and " + std::to_string(kMaxKP) + " table columns (this handle: " +
-                  std::to_string(c.D) + " DoF, " + std::to_string(c.KT) + " columns); the k_traj_wide shapes have no kernel here");
-        return MPK_ENOTIMPL;
-    }
+    if (const int rc = gauss_common_limits(c, "mpk_trajectory_std")) return rc;
     const int T16 = (c.T + 15) / 16 * 16;
     const int pitch = T16 % 32 == 16 ? T16 : T16 + 16;
     const int image = (c.T * c.D + 3 + 3) / 4 * 4;                  // the run shifted by up to three floats, whole 16-byte chunks

@@ -825,31 +825,12 @@ class TrajectoryEngine:
         """
         B, steps = self._obs_checks("condition", "a conditioning kernel", params, params_L, obs_steps, obs_pos, obs_std, init_pos,
                                     init_vel, obs_vel, obs_vel_std)
-        D, P, M = self.num_dof, self.num_params, int(steps.size)
-        if out is not None:
-            if len(out) != 2:
-                raise ValueError("condition: out must be a pair (params, params_L) of tensors")
-            for i, (buf, shape) in enumerate(zip(out, ((B, P), (B, P, P)))):
-                if (not isinstance(buf, torch.Tensor) or tuple(buf.shape) != shape or buf.dtype != torch.float32
-                        or not buf.is_contiguous() or buf.device != self.device):
-                    raise ValueError(f"condition: out[{i}] must be a contiguous float32 tensor of shape {shape} on {self.device}")
-
-        def bcast(x, name):
-            return self._obs_bcast("condition", x, name, B, M)
+        P, M = self.num_params, int(steps.size)
+        self._out_pair_check("condition", out, B, P, P)
+        ip, iv, yp, sp, yv, sv = self._log_prob_inputs("condition", B, M, obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std)
         with torch.no_grad():
-            mean = torch.as_tensor(params, dtype=torch.float32, device=self.device).detach().contiguous()
-            L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
-            ip = None if init_pos is None else self._f32(init_pos, (B, D)).detach()
-            iv = None if init_vel is None else self._f32(init_vel, (B, D)).detach()
-            yp = None if obs_pos is None else bcast(obs_pos, "obs_pos")
-            sp = None if obs_pos is None else bcast(obs_std, "obs_std")
-            yv = None if obs_vel is None else bcast(obs_vel, "obs_vel")
-            sv = None if obs_vel is None else bcast(obs_vel_std, "obs_vel_std")
-            if out is not None:
-                mean_out, L_out = out
-            else:
-                mean_out = torch.empty((B, P), dtype=torch.float32, device=self.device)
-                L_out = torch.empty((B, P, P), dtype=torch.float32, device=self.device)
+            mean, L = self._mean_and_factor(params, params_L)
+            mean_out, L_out = out if out is not None else self._posterior_buffers(B, P, P)
             _lib.check(self._lib.mpk_trajectory_condition(
                 self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time),
                 steps.ctypes.data_as(C.POINTER(C.c_int32)), M, _dptr(yp), _dptr(sp), _dptr(yv), _dptr(sv), mean_out.data_ptr(),
@@ -860,22 +841,7 @@ class TrajectoryEngine:
         """the refusals ``condition`` and ``trajectory_log_prob`` / ``_vjp`` share, all before anything touches the device (what only
         the library can judge -- the steps' range and order -- is refused by the launch's own checks, still before any launch);
         returns (B, steps int32 [M])"""
-        if self.config.learn_tau or self.config.learn_delay:
-            raise NotImplementedError(f"{fn}: a learned tau / delay gives every episode its own phase; only shared-phase handles have "
-                                      f"{kernel}")
-        if self.mp_type == "dmp":
-            raise NotImplementedError(f"{fn}: a DMP has no probabilistic interface (promp / prodmp only)")
-        D, P = self.num_dof, self.num_params
-        if D > 16:
-            raise NotImplementedError(f"{fn}: at most 16 DoF and 16 table columns (this handle: {D} DoF)")
-        pshape = tuple(params.shape) if hasattr(params, "shape") else np.shape(params)
-        if len(pshape) != 2 or pshape[0] < 1 or pshape[1] != P:
-            raise ValueError(f"{fn}: params must be [B, {P}], got {pshape}")
-        B = pshape[0]
-        lshape = tuple(params_L.shape) if hasattr(params_L, "shape") else np.shape(params_L)
-        if lshape != (B, P, P):
-            raise ValueError(f"{fn}: params_L must be [{B}, {P}, {P}] (the factor of the {P} non-phase parameters' covariance), "
-                             f"got {lshape}")
+        B = self._gaussian_checks(fn, kernel, params, params_L, 0)
         steps = np.asarray(list(obs_steps))
         if steps.ndim != 1 or (steps.size and not np.issubdtype(steps.dtype, np.integer)):
             raise ValueError(f"{fn}: obs_steps must be a sequence of ints, got {obs_steps!r}")
@@ -885,10 +851,79 @@ class TrajectoryEngine:
         for val, sd, names in ((obs_pos, obs_std, ("obs_pos", "obs_std")), (obs_vel, obs_vel_std, ("obs_vel", "obs_vel_std"))):
             if (val is None) != (sd is None):
                 raise ValueError(f"{fn}: {names[0]} and {names[1]} come in pairs (observed values with their standard deviations)")
+        self._start_check(fn, init_pos, init_vel)
+        return B, steps
+
+    def _gaussian_checks(self, fn, kernel, params, params_L, n_phase):
+        """what every entry point that takes ``N(params, L L^T)`` refuses about the handle and the Gaussian's shape; returns B.
+        ``n_phase`` = 0: the shared-phase route, a Gaussian over all P parameters (a learned tau / delay is refused; ``kernel``: the
+        family's word); otherwise ``timing="given"``: over the Pl = P - n_phase non-phase parameters"""
+        if not n_phase and (self.config.learn_tau or self.config.learn_delay):
+            raise NotImplementedError(f"{fn}: a learned tau / delay gives every episode its own phase; only shared-phase handles have "
+                                      f"{kernel}")
+        if self.mp_type == "dmp":
+            raise NotImplementedError(f"{fn}: a DMP has no probabilistic interface (promp / prodmp only)")
+        D, P = self.num_dof, self.num_params
+        Pl = P - n_phase
+        if D > 16:
+            raise NotImplementedError(f"{fn}: at most 16 DoF and 16 table columns (this handle: {D} DoF)")
+        pshape = tuple(params.shape) if hasattr(params, "shape") else np.shape(params)
+        if len(pshape) != 2 or pshape[0] < 1 or pshape[1] != P:
+            raise ValueError(f"{fn}: params must be [B, {P}]" + (" (tau / delay in front, then the mean)" if n_phase else "") +
+                             f", got {pshape}")
+        B = pshape[0]
+        lshape = tuple(params_L.shape) if hasattr(params_L, "shape") else np.shape(params_L)
+        if lshape != (B, Pl, Pl):
+            if n_phase:
+                raise ValueError(f"{fn}: params_L must be [{B}, Pl, Pl] with Pl = {Pl} (the factor of the {Pl} non-phase parameters' "
+                                 f"covariance; the timing is given, not distributed), got {lshape}")
+            raise ValueError(f"{fn}: params_L must be [{B}, {P}, {P}] (the factor of the {P} non-phase parameters' covariance), "
+                             f"got {lshape}")
+        return B
+
+    def _start_check(self, fn, init_pos, init_vel):
         if (init_pos is None or init_vel is None) and self.mp_type != "promp":
             raise ValueError(f"{fn}: init_pos / init_vel may be None only for a ProMP, which ignores them; a {self.mp_type} starts from "
                              "them")
-        return B, steps
+
+    def _no_grad_check(self, fn, named):
+        """the likelihood's inputs that have no gradient: (name, value) pairs, refused where a tensor among them requires grad"""
+        if torch.is_grad_enabled():
+            for name, t in named:
+                if isinstance(t, torch.Tensor) and t.requires_grad:
+                    raise NotImplementedError(f"{fn}: {name} requires grad, but the likelihood has a gradient w.r.t. params and params_L "
+                                              "only; detach it")
+
+    def _out_pair_check(self, fn, out, B, P, Pl):
+        """``out=(params, params_L)`` of the conditioning entry points: None, or contiguous float32 [B, P] and [B, Pl, Pl] on the device"""
+        if out is None:
+            return
+        if len(out) != 2:
+            raise ValueError(f"{fn}: out must be a pair (params, params_L) of tensors")
+        for i, (buf, shape) in enumerate(zip(out, ((B, P), (B, Pl, Pl)))):
+            if (not isinstance(buf, torch.Tensor) or tuple(buf.shape) != shape or buf.dtype != torch.float32
+                    or not buf.is_contiguous() or buf.device != self.device):
+                raise ValueError(f"{fn}: out[{i}] must be a contiguous float32 tensor of shape {shape} on {self.device}")
+
+    def _posterior_buffers(self, B, P, Pl):
+        return (torch.empty((B, P), dtype=torch.float32, device=self.device),
+                torch.empty((B, Pl, Pl), dtype=torch.float32, device=self.device))
+
+    def _mean_and_factor(self, params, params_L):
+        """the Gaussian's mean and factor as detached contiguous float32 device tensors"""
+        return (torch.as_tensor(params, dtype=torch.float32, device=self.device).detach().contiguous(),
+                torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous())
+
+    def _vjp_outputs(self, fn, g, mean, L, need):
+        """the gradient launches' ``g`` as contiguous float64 [B] and their output buffers (None where ``need[i]`` is False), or None
+        when no output is asked for"""
+        B = mean.shape[0]
+        g = torch.as_tensor(g, dtype=torch.float64, device=self.device).detach()
+        if tuple(g.shape) != (B,):
+            raise ValueError(f"{fn}: g must be [{B}], got {tuple(g.shape)}")
+        g_mean = torch.empty_like(mean) if need[0] else None
+        g_L = torch.empty_like(L) if need[1] else None
+        return None if g_mean is None and g_L is None else (g.contiguous(), g_mean, g_L)
 
     def _log_prob_checks(self, fn, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std):
         """the refusals of ``trajectory_log_prob`` / ``trajectory_log_prob_vjp`` -- ``condition``'s, plus the steps (here, so that no
@@ -905,12 +940,8 @@ class TrajectoryEngine:
         if n_obs > _lib.MPK_LOGPROB_MAX_OBS:
             raise NotImplementedError(f"{fn}: at most {_lib.MPK_LOGPROB_MAX_OBS} scalar observations per episode (steps x DoF x the "
                                       f"observation arrays given = {n_obs}); the whole-trajectory likelihood has no kernel here")
-        if torch.is_grad_enabled():
-            for name, t in (("init_pos", init_pos), ("init_vel", init_vel), ("obs_pos", obs_pos), ("obs_std", obs_std),
-                            ("obs_vel", obs_vel), ("obs_vel_std", obs_vel_std)):
-                if isinstance(t, torch.Tensor) and t.requires_grad:
-                    raise NotImplementedError(f"{fn}: {name} requires grad, but the likelihood has a gradient w.r.t. params and params_L "
-                                              "only; detach it")
+        self._no_grad_check(fn, (("init_pos", init_pos), ("init_vel", init_vel), ("obs_pos", obs_pos), ("obs_std", obs_std),
+                                 ("obs_vel", obs_vel), ("obs_vel_std", obs_vel_std)))
         return B, steps
 
     def _obs_bcast(self, fn, x, name, B, M):
@@ -947,18 +978,14 @@ class TrajectoryEngine:
 
     def _log_prob_vjp_launch(self, g, mean, L, steps, inputs, init_time, need):
         ip, iv, yp, sp, yv, sv = inputs
-        B, P = mean.shape
-        g = torch.as_tensor(g, dtype=torch.float64, device=self.device).detach()
-        if tuple(g.shape) != (B,):
-            raise ValueError(f"trajectory_log_prob_vjp: g must be [{B}], got {tuple(g.shape)}")
-        g = g.contiguous()
-        g_mean = torch.empty((B, P), dtype=torch.float32, device=self.device) if need[0] else None
-        g_L = torch.empty((B, P, P), dtype=torch.float32, device=self.device) if need[1] else None
-        if g_mean is None and g_L is None:
+        outs = self._vjp_outputs("trajectory_log_prob_vjp", g, mean, L, need)
+        if outs is None:
             return None, None
+        g, g_mean, g_L = outs
         _lib.check(self._lib.mpk_trajectory_log_prob_vjp(
             self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time), steps.ctypes.data_as(C.POINTER(C.c_int32)),
-            int(steps.size), _dptr(yp), _dptr(sp), _dptr(yv), _dptr(sv), g.data_ptr(), _dptr(g_mean), _dptr(g_L), B, self._stream()))
+            int(steps.size), _dptr(yp), _dptr(sp), _dptr(yv), _dptr(sv), g.data_ptr(), _dptr(g_mean), _dptr(g_L), mean.shape[0],
+            self._stream()))
         return g_mean, g_L
 
     def trajectory_log_prob(self, params, params_L, obs_steps, obs_pos=None, obs_std=None, init_pos=None, init_vel=None,
@@ -1002,8 +1029,7 @@ class TrajectoryEngine:
         inputs = self._log_prob_inputs("trajectory_log_prob_vjp", B, int(steps.size), obs_pos, obs_std, init_pos, init_vel, obs_vel,
                                        obs_vel_std)
         with torch.no_grad():
-            mean = torch.as_tensor(params, dtype=torch.float32, device=self.device).detach().contiguous()
-            L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
+            mean, L = self._mean_and_factor(params, params_L)
             return self._log_prob_vjp_launch(g, mean, L, steps, inputs, init_time, need)
 
     def _timing_given(self, fn, timing) -> bool:
@@ -1018,45 +1044,19 @@ class TrajectoryEngine:
                              "already; call without timing")
         return True
 
-    def _demo_phase_checks(self, fn, params, params_L, init_pos, init_vel):
-        """``_obs_checks`` for ``timing="given"``: the Gaussian is over the Pl = P - n_phase non-phase parameters; returns B"""
-        if self.mp_type == "dmp":
-            raise NotImplementedError(f"{fn}: a DMP has no probabilistic interface (promp / prodmp only)")
-        D, P = self.num_dof, self.num_params
-        Pl = P - self._num_phase_params()
-        if D > 16:
-            raise NotImplementedError(f"{fn}: at most 16 DoF and 16 table columns (this handle: {D} DoF)")
-        pshape = tuple(params.shape) if hasattr(params, "shape") else np.shape(params)
-        if len(pshape) != 2 or pshape[0] < 1 or pshape[1] != P:
-            raise ValueError(f"{fn}: params must be [B, {P}] (tau / delay in front, then the mean), got {pshape}")
-        B = pshape[0]
-        lshape = tuple(params_L.shape) if hasattr(params_L, "shape") else np.shape(params_L)
-        if lshape != (B, Pl, Pl):
-            raise ValueError(f"{fn}: params_L must be [{B}, Pl, Pl] with Pl = {Pl} (the factor of the {Pl} non-phase parameters' "
-                             f"covariance; the timing is given, not distributed), got {lshape}")
-        if (init_pos is None or init_vel is None) and self.mp_type != "promp":
-            raise ValueError(f"{fn}: init_pos / init_vel may be None only for a ProMP, which ignores them; a {self.mp_type} starts from "
-                             "them")
-        return B
-
     def _demo_checks(self, fn, params, params_L, pos, obs_std, init_pos, init_vel, phase=False):
-        """the refusals of ``demonstration_log_prob`` / ``demonstration_log_prob_vjp`` -- ``trajectory_log_prob``'s (``_obs_checks``)
-        plus the demonstrations' shape and the inputs that have no gradient, all before anything touches the device; returns B"""
+        """the refusals of ``demonstration_log_prob`` / ``demonstration_log_prob_vjp`` -- ``trajectory_log_prob``'s (for
+        ``timing="given"`` with the Gaussian over the Pl = P - n_phase non-phase parameters) plus the demonstrations' shape and the
+        inputs that have no gradient, all before anything touches the device; returns B"""
         if pos is None or obs_std is None:
             raise ValueError(f"{fn}: pos and obs_std are both required (the demonstrations with their standard deviations)")
-        if phase:
-            B = self._demo_phase_checks(fn, params, params_L, init_pos, init_vel)
-        else:
-            B, _ = self._obs_checks(fn, "a likelihood kernel", params, params_L, (), pos, obs_std, init_pos, init_vel, None, None)
+        B = self._gaussian_checks(fn, "a likelihood kernel", params, params_L, self._num_phase_params() if phase else 0)
+        self._start_check(fn, init_pos, init_vel)
         T, D = self.num_steps, self.num_dof
         shape = tuple(pos.shape) if hasattr(pos, "shape") else np.shape(pos)
         if shape != (B, T, D):
             raise ValueError(f"{fn}: pos must be [{B}, {T}, {D}] (whole demonstrations on the handle's {T} steps), got {shape}")
-        if torch.is_grad_enabled():
-            for name, t in (("init_pos", init_pos), ("init_vel", init_vel), ("pos", pos), ("obs_std", obs_std)):
-                if isinstance(t, torch.Tensor) and t.requires_grad:
-                    raise NotImplementedError(f"{fn}: {name} requires grad, but the likelihood has a gradient w.r.t. params and params_L "
-                                              "only; detach it")
+        self._no_grad_check(fn, (("init_pos", init_pos), ("init_vel", init_vel), ("pos", pos), ("obs_std", obs_std)))
         return B
 
     def _demo_inputs(self, fn, B, pos, obs_std, init_pos, init_vel):
@@ -1079,20 +1079,14 @@ class TrajectoryEngine:
 
     def _demo_log_prob_vjp_launch(self, g, mean, L, inputs, init_time, need, phase=False):
         ip, iv, y, sd = inputs
-        B, P = mean.shape
-        Pl = L.shape[1]
-        g = torch.as_tensor(g, dtype=torch.float64, device=self.device).detach()
-        if tuple(g.shape) != (B,):
-            raise ValueError(f"demonstration_log_prob_vjp: g must be [{B}], got {tuple(g.shape)}")
-        g = g.contiguous()
-        g_mean = torch.empty((B, P), dtype=torch.float32, device=self.device) if need[0] else None
-        g_L = torch.empty((B, Pl, Pl), dtype=torch.float32, device=self.device) if need[1] else None
-        if g_mean is None and g_L is None:
+        outs = self._vjp_outputs("demonstration_log_prob_vjp", g, mean, L, need)
+        if outs is None:
             return None, None
+        g, g_mean, g_L = outs
         entry = self._lib.mpk_demonstration_phase_log_prob_vjp if phase else self._lib.mpk_demonstration_log_prob_vjp
         _lib.check(entry(
             self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time), y.data_ptr(), sd.data_ptr(), g.data_ptr(),
-            _dptr(g_mean), _dptr(g_L), B, self._stream()))
+            _dptr(g_mean), _dptr(g_L), mean.shape[0], self._stream()))
         return g_mean, g_L
 
     def demonstration_log_prob(self, params, params_L, pos, obs_std, init_pos=None, init_vel=None,
@@ -1172,8 +1166,7 @@ class TrajectoryEngine:
         B = self._demo_checks(fn, params, params_L, pos, obs_std, init_pos, init_vel, phase)
         inputs = self._demo_inputs(fn, B, pos, obs_std, init_pos, init_vel)
         with torch.no_grad():
-            mean = torch.as_tensor(params, dtype=torch.float32, device=self.device).detach().contiguous()
-            L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
+            mean, L = self._mean_and_factor(params, params_L)
             return self._demo_log_prob_vjp_launch(g, mean, L, inputs, init_time, need, phase)
 
     def condition_on_demonstration(self, params, params_L, pos, obs_std, init_pos=None, init_vel=None, init_time: float = 0.0, *,
@@ -1218,22 +1211,11 @@ class TrajectoryEngine:
             B = self._demo_checks(fn, params, params_L, pos, obs_std, init_pos, init_vel, phase)
         P = self.num_params
         Pl = P - self._num_phase_params() if phase else P
-        if out is not None:
-            if len(out) != 2:
-                raise ValueError(f"{fn}: out must be a pair (params, params_L) of tensors")
-            for i, (buf, shape) in enumerate(zip(out, ((B, P), (B, Pl, Pl)))):
-                if (not isinstance(buf, torch.Tensor) or tuple(buf.shape) != shape or buf.dtype != torch.float32
-                        or not buf.is_contiguous() or buf.device != self.device):
-                    raise ValueError(f"{fn}: out[{i}] must be a contiguous float32 tensor of shape {shape} on {self.device}")
+        self._out_pair_check(fn, out, B, P, Pl)
         ip, iv, y, sd = self._demo_inputs(fn, B, pos, obs_std, init_pos, init_vel)
         with torch.no_grad():
-            mean = torch.as_tensor(params, dtype=torch.float32, device=self.device).detach().contiguous()
-            L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
-            if out is not None:
-                mean_out, L_out = out
-            else:
-                mean_out = torch.empty((B, P), dtype=torch.float32, device=self.device)
-                L_out = torch.empty((B, Pl, Pl), dtype=torch.float32, device=self.device)
+            mean, L = self._mean_and_factor(params, params_L)
+            mean_out, L_out = out if out is not None else self._posterior_buffers(B, P, Pl)
             entry = self._lib.mpk_demonstration_phase_condition if phase else self._lib.mpk_demonstration_condition
             _lib.check(entry(
                 self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time), y.data_ptr(), sd.data_ptr(),
