@@ -378,6 +378,13 @@ __device__ __forceinline__ void flush_span2(const float* __restrict__ s0, const 
     if (lane < end - tail) { store4<WT>(o0 - sh + tail + lane, s0[tail + lane]); store4<WT>(o1 - sh + tail + lane, s1[tail + lane]); }
 }
 
+// an episode's learned tau / delay from the front of its parameter row `prm` (else they stay the handle's)
+__device__ __forceinline__ void episode_tau_delay(const DevCfg& c, const float* prm, float& tau, float& delay) {
+    // np.clip(action, low, high): only tau / delay carry finite bounds (black_box_wrapper.py:104-105)
+    if (c.learn_tau) tau = fminf(fmaxf(prm[0], c.tau_lo), c.tau_hi);
+    if (c.learn_delay) delay = fminf(fmaxf(prm[c.learn_tau ? 1 : 0], c.delay_lo), c.delay_hi);
+}
+
 
 // TL (prodmp): the fp32 row table is staged in the workgroup's LDS (row stride 2*KS + 4 floats: 16-byte aligned rows
 // spread over the banks) and the workgroup is up to 16 waves, so row and boundary gathers never enter the memory queue
@@ -660,14 +667,12 @@ __global__ void __launch_bounds__(TL ? 1024 : 256) k_traj_phase(const PhaseArgs 
             const float* prm = img + e * P;
             const float* ipe = img + E * P + e * D;
             const float* ive = ipe + E * D;
-            // np.clip(action, low, high): only tau / delay carry finite bounds (black_box_wrapper.py:104-105)
             float tau = c.tau, delay = c.delay, it;
             if (MP == MPK_MP_PRODMP) {                  // clipped per chunk above
                 const float* sc3 = img + E * a.x_pad + 3 * e;
                 tau = sc3[0]; delay = sc3[1]; it = sc3[2];
             } else {
-                if (c.learn_tau) tau = fminf(fmaxf(prm[0], c.tau_lo), c.tau_hi);
-                if (c.learn_delay) delay = fminf(fmaxf(prm[c.learn_tau ? 1 : 0], c.delay_lo), c.delay_hi);
+                episode_tau_delay(c, prm, tau, delay);
                 it = img[E * P + 2 * E * D + e];
             }
             float inv_tau = 0.0f;
@@ -799,6 +804,228 @@ __global__ void __launch_bounds__(TL ? 1024 : 256) k_traj_phase(const PhaseArgs 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// The per-episode-phase DMP kernels below -- k_traj_phase_dmp (a wave per chunk), k_traj_phase_dmp_wg (a workgroup per chunk) and
+// k_traj_phase_dmp_pipe (the same as a pipeline) -- are three SCHEDULES over the item functions here: what an episode, an
+// (episode, step) item, a forcing value, an Euler step and a stored run are is written once, so the three leave the same bits by
+// construction.  A kernel owns its loops, barriers, wave roles and LDS layout, and passes the slots that differ.
+// ------------------------------------------------------------------------------------------------------------
+// the workgroup's tables: base times, RBF centres | bandwidths (| recurrence constants) and, where the launch has one (h_pad > 0), the
+// interpolation table of the forcing rows
+__device__ __forceinline__ void stage_phase_tables(const PhaseArgs& a, double* sCen, float* sFast, float* sBT) {
+    const DevCfg& c = a.c;
+    // (first elements of the small tables requested before the row table's copy waits for its loads)
+    const int tid_ = (int)threadIdx.x, bd_ = (int)blockDim.x, T = c.T;
+    const float bt0 = tid_ < T ? c.base_times[tid_] : 0.0f;
+    const double cen0 = tid_ < 2 * c.n_total + 3 ? c.tab[tid_] : 0.0;
+    if (a.h_pad > 0) fast_rows_stage(c.rows32, sFast, a.h_pad, tid_, bd_);
+    if (tid_ < T) sBT[tid_] = bt0;
+    for (int t = tid_ + bd_; t < T; t += bd_) sBT[t] = c.base_times[t];
+    if (tid_ < 2 * c.n_total + 3) sCen[tid_] = cen0;
+    for (int k = tid_ + bd_; k < 2 * c.n_total + 3; k += bd_) sCen[k] = c.tab[k];
+}
+
+// episode b's timing: tau / delay (episode_tau_delay) and its init_time where the launch has one per episode (else `it` stays the shared value)
+__device__ __forceinline__ void episode_timing(const PhaseArgs& a, const int b, float& tau, float& delay, float& it) {
+    episode_tau_delay(a.c, a.params + (size_t)b * a.c.P, tau, delay);
+    if (a.init_time) it = a.init_time[b];
+}
+// sPhe = sPh + 8 e: tau, delay, init_time (clipped), -, 1 / tau refined (float64), -
+__device__ __forceinline__ void publish_timing(float* sPhe, const float tau, const float delay, const float it) {
+    sPhe[0] = tau; sPhe[1] = delay; sPhe[2] = it;
+    *reinterpret_cast<double*>(sPhe + 4) = make_pos_div((double)tau).y;
+}
+
+// value idx of a chunk's [E][D][KS] columns (weights .., goal, y0, ydot0); b0: the chunk's first episode, inv_d = 1 / D
+template <int KS>
+__device__ __forceinline__ float dmp_x_value(const PhaseArgs& a, const int b0, const int idx, const int D, const float inv_d) {
+    const int pi = idx / KS, k = idx - pi * KS;             // pi = e * D + dd
+    const int e = (int)(((float)pi + 0.5f) * inv_d), dd = pi - e * D;
+    const size_t bb = (size_t)(b0 + e);
+    return phase_x_value<MPK_MP_DMP>(a.c, a.params + bb * a.c.P, a.init_pos + bb * D, a.init_vel + bb * D, dd, k, KS);
+}
+
+// The workgroup kernels' FIRST chunk (blockIdx.x): its inputs are requested before the tables are staged (one memory round trip under
+// the other: behind the table copy they were 1 700 of a workgroup's 40 000 cycles at 4 096 episodes, where a workgroup has one chunk)
+// and handed over where the chunk loop starts.  Thread <-> column value; the timing on the Euler wave's lanes (le: the lane's episode).
+template <int KS>
+struct DmpFirstChunk {
+    float xf, tau, delay, it;
+    __device__ __forceinline__ DmpFirstChunk(const PhaseArgs& a, const int nchunks, const int D, const float inv_d, const bool euler_wave,
+                                             const int lane, const int le)
+        : xf(0.0f), tau(a.c.tau), delay(a.c.delay), it(a.init_time_shared) {
+        const int ch0 = (int)blockIdx.x, E = a.chunk;
+        if (ch0 < nchunks) {
+            const int b0 = ch0 * E, ne = min(E, a.B - b0);
+            if ((int)threadIdx.x < ne * D * KS) xf = dmp_x_value<KS>(a, b0, (int)threadIdx.x, D, inv_d);
+            if (euler_wave && lane < ne * D) episode_timing(a, b0 + le, tau, delay, it);
+        }
+    }
+};
+// a chunk's inputs of the workgroup kernels: the columns into sX over all threads, and on the Euler wave's lanes (`on`; lane <->
+// (le, ld) = (episode, DoF)) the episode's timing, which the DoF-0 lane publishes to sPh.  Returns the lane's tau.
+template <int KS>
+__device__ __forceinline__ float dmp_wg_chunk_inputs(const PhaseArgs& a, const DmpFirstChunk<KS>& f0, const bool first, const int b0,
+                                                     const int ne, const int D, const float inv_d, const bool on, const int le,
+                                                     const int ld, float* sX, float* sPh) {
+    int idx = (int)threadIdx.x;
+    if (first) {
+        if (idx < ne * D * KS) sX[idx] = f0.xf;
+        idx += (int)blockDim.x;
+    }
+    for (; idx < ne * D * KS; idx += blockDim.x) sX[idx] = dmp_x_value<KS>(a, b0, idx, D, inv_d);
+    float tau = a.c.tau, delay = a.c.delay, it = a.init_time_shared;
+    if (on) {
+        if (first) {
+            tau = f0.tau; delay = f0.delay; it = f0.it;
+        } else {
+            episode_timing(a, b0 + le, tau, delay, it);
+        }
+        if (ld == 0) publish_timing(sPh + 8 * le, tau, delay, it);
+    }
+    return tau;
+}
+
+// The row of one (episode, step) item, in registers (round 4 wrote it to LDS and read it back once per DoF): phase and RBF row in
+// float64 with the builders' functions (same bits as every other DMP kernel), or from the interpolation table where the launch
+// staged one and the item's scaled time is inside it; the step's ds to *ds.  sPhe = sPh + 8 e, t: the step (< T).
+template <int KS>
+__device__ __forceinline__ void dmp_item_row(const DevCfg& c, const float* sPhe, const float* sBT, const double* sCen, const float* sFast,
+                                             const bool fast, const int t, float (&h)[KS], float* ds) {
+#pragma unroll
+    for (int k = 0; k < KS; ++k) h[k] = 0.0f;
+    const float taue = sPhe[0], delaye = sPhe[1], ite = sPhe[2];
+    const float time = sBT[t] + ite;
+    const float s_item = scaled_time(time, delaye, taue);
+    if (KS == 8 && fast && fast_rows_arg(c, s_item) < kFastS) {
+        if constexpr (KS == 8) fast_rows_eval<KS>(sFast, fast_rows_arg(c, s_item), h);
+    } else {
+        const PosDiv taud{(double)taue, *reinterpret_cast<const double*>(sPhe + 4)};
+        const double x = phase_f64(c, time, taud, delaye, ExpLiteral());
+        // every RBF once, in registers (rbf_cols evaluates them for the sum and again for the values; same bits)
+        rbf_row<KS>(c, sCen, sCen + c.n_total, x, x * (double)c.ws, h, ExpLiteral());
+    }
+    if (t < c.T - 1) *ds = scaled_time(sBT[t + 1] + ite, delaye, taue) - s_item;
+}
+
+// An item's forcing values: row_chain's fmaf chain in ascending k over the weight columns (the last three columns carry goal, y0,
+// ydot0: not weights -- the chain multiplied them by 0, which leaves the accumulator's bits alone).  sXe: the episode's columns,
+// dst: the item's slot of DoF 0, slots DS floats apart (1: an image of floats, 2: (pos, tau x vel) pairs).
+// DC DoF, the count compiled in: the DC chains side by side, offsets as constants (same chain order per DoF: same bits)
+template <int KQ, int DC, int DS>
+__device__ __forceinline__ void dmp_forcing_dc(const float* sXe, const float (&h)[KQ * 4], float* dst) {
+    constexpr int KS = KQ * 4;
+    float x[DC][KS];
+#pragma unroll
+    for (int d = 0; d < DC; ++d)
+#pragma unroll
+        for (int j = 0; j < KQ; ++j) {
+            const float4 v = *reinterpret_cast<const float4*>(sXe + d * KS + 4 * j);
+            x[d][4 * j + 0] = v.x; x[d][4 * j + 1] = v.y; x[d][4 * j + 2] = v.z; x[d][4 * j + 3] = v.w;
+        }
+    float acc[DC];
+#pragma unroll
+    for (int d = 0; d < DC; ++d) acc[d] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < KS - 3; ++k)
+#pragma unroll
+        for (int d = 0; d < DC; ++d) acc[d] = fmaf(h[k], x[d][k], acc[d]);
+#pragma unroll
+    for (int d = 0; d < DC; ++d) dst[DS * d] = acc[d];
+}
+// D DoF at run time, four side by side (one after the other: two LDS reads, KS - 3 dependent FMAs and an LDS write, D times in a row):
+// episode e of the chunk's columns sX, into the pairs slot .. slot + D - 1 of sPV.  (The indices are formed per DoF on purpose: with
+// the episode's and the item's base hoisted into the arguments, the KQ = 4 workgroup kernels spilled one more register.)
+template <int KQ>
+__device__ __forceinline__ void dmp_forcing_by_four(const float* sX, const int e, const int D, const float (&h)[KQ * 4], float* sPV,
+                                                    const int slot) {
+    constexpr int KS = KQ * 4;
+    for (int d0 = 0; d0 < D; d0 += 4) {
+        float x[4][KS];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int d = min(d0 + i, D - 1);
+#pragma unroll
+            for (int j = 0; j < KQ; ++j) {
+                const float4 v = *reinterpret_cast<const float4*>(sX + (e * D + d) * KS + 4 * j);
+                x[i][4 * j + 0] = v.x; x[i][4 * j + 1] = v.y; x[i][4 * j + 2] = v.z; x[i][4 * j + 3] = v.w;
+            }
+        }
+        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int k = 0; k < KS - 3; ++k)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i] = fmaf(h[k], x[i][k], acc[i]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (d0 + i < D) sPV[2 * (slot + d0 + i)] = acc[i];
+    }
+}
+
+// A block's Euler steps of one (episode, DoF) lane on (pos, tau x vel) pairs (one rounding per operation): pq = the lane's
+// pairs, 2 D floats apart per step, each holding the step's forcing value until its results replace it with ONE 8-byte LDS write (a write
+// costs the lone wave ~18 cycles whatever its width; the division by tau is the storing waves'); pds = the block's ds; steps t0 .. t0 + rows.
+__device__ __forceinline__ void dmp_euler_pairs(const DevCfg& c, float* pq, const float* pds, const int D, const int t0, const int rows,
+                                                float& y, float& z, const float g) {
+    const int T = c.T;
+    // round 5: 8-step pieces every step of which advances the state take their forcing values and step sizes into
+    // registers first (the loop form reads each forcing value behind the previous step's write to the same image: an LDS
+    // round trip inside every one of a chunk's 200 dependent steps -- most of the workgroup kernel's time at 4 096 episodes)
+    constexpr int PC = 8;               // (16 at a time spill: four workgroups per CU leave 128 registers)
+    int tl0 = 0;
+    for (; tl0 + PC <= rows && t0 + tl0 + PC < T; tl0 += PC) {
+        float fr[PC], dsr[PC];
+#pragma unroll
+        for (int j = 0; j < PC / 4; ++j) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(pds + tl0 + 4 * j);
+            dsr[4 * j] = v[0]; dsr[4 * j + 1] = v[1]; dsr[4 * j + 2] = v[2]; dsr[4 * j + 3] = v[3];
+        }
+#pragma unroll
+        for (int i = 0; i < PC; ++i) fr[i] = pq[2 * (tl0 + i) * D];
+#pragma unroll
+        // (what a step costs the lone Euler wave, round 5 trace at one workgroup per CU: 98 cycles -- 61 for the five dependent
+        // operations and the reads, 37 for the two LDS writes it then had; a lone wave issues one instruction per 5.6 - 9 cycles)
+        for (int i = 0; i < PC; ++i) {
+            *reinterpret_cast<f32x2*>(pq + 2 * (tl0 + i) * D) = f32x2{y, z};
+            dmp_phase_step(y, z, g, fr[i], dsr[i], c.dmp_alpha, c.dmp_beta);
+        }
+    }
+#pragma unroll 1
+    for (int tl = tl0; tl < rows; ++tl) {
+        const float f = pq[2 * tl * D];
+        *reinterpret_cast<f32x2*>(pq + 2 * tl * D) = f32x2{y, z};
+        if (t0 + tl < T - 1) {
+            const float ds = pds[tl];
+            dmp_phase_step(y, z, g, f, ds, c.dmp_alpha, c.dmp_beta);
+        }
+    }
+}
+
+// values of pos / vel at offset go of the outputs: write-through stores while the outputs are cache resident (PhaseArgs::wt)
+__device__ __forceinline__ void store_pos_vel(const PhaseArgs& a, const size_t go, const f32x4& vp, const f32x4& vv) {
+    if (a.wt) { store16<true>(a.pos + go, vp); store16<true>(a.vel + go, vv); }
+    else { store16<false>(a.pos + go, vp); store16<false>(a.vel + go, vv); }
+}
+__device__ __forceinline__ void store_pos_vel(const PhaseArgs& a, const size_t go, const float p, const float v) {
+    if (a.wt) { store4<true>(a.pos + go, p); store4<true>(a.vel + go, v); }
+    else { store4<false>(a.pos + go, p); store4<false>(a.vel + go, v); }
+}
+// four (pos, tau x vel) pairs at src / one pair, parted and stored: the velocity divided by the episode's tau (sPhe[0])
+__device__ __forceinline__ void dmp_store_pairs4(const PhaseArgs& a, const float* src, const float* sPhe, const size_t go) {
+    const f32x4 pa = *reinterpret_cast<const f32x4*>(src);
+    const f32x4 pb = *reinterpret_cast<const f32x4*>(src + 4);
+    const f32x4 vp = {pa[0], pa[2], pb[0], pb[2]};
+    f32x4 vv = {pa[1], pa[3], pb[1], pb[3]};
+    const TauDiv tde = make_tau_div(sPhe[0]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) vv[q] = div_tau(vv[q], tde);
+    store_pos_vel(a, go, vp, vv);
+}
+__device__ __forceinline__ void dmp_store_pair(const PhaseArgs& a, const float* src, const float* sPhe, const size_t go) {
+    const f32x2 pr = *reinterpret_cast<const f32x2*>(src);
+    store_pos_vel(a, go, pr[0], div_tau(pr[1], make_tau_div(sPhe[0])));
+}
+
 template <int KQ, int DC = 0>       // DC: the DoF count at compile time (0: c.D), as k_traj_phase_dmp_pipe
 __global__ void __launch_bounds__(512) k_traj_phase_dmp(const PhaseArgs a) {      // (four or eight waves: the launcher, by the waves a CU's LDS then holds)
     // DMP with a per-episode phase.  The Euler recurrence is serial in t and needs one lane per (episode, DoF); run per
@@ -811,11 +1038,10 @@ __global__ void __launch_bounds__(512) k_traj_phase_dmp(const PhaseArgs a) {    
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const DevCfg& c = a.c;
     constexpr int KS = KQ * 4, TT = 16;
-    constexpr int MP = MPK_MP_DMP;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int wpb = (int)(blockDim.x >> 6);
-    const int D = DC > 0 ? DC : c.D, T = c.T, E = a.chunk, P = c.P;
+    const int D = DC > 0 ? DC : c.D, T = c.T, E = a.chunk;
     const int seg = TT * D;                             // floats of one episode's tile
     double* sCen = reinterpret_cast<double*>(smem);     // [c_pad / 2] RBF centres | bandwidths (| recurrence constants)
     float* sFast = smem + a.c_pad;                      // [h_pad] interpolation table of the forcing rows (fast_rows_build)
@@ -825,16 +1051,8 @@ __global__ void __launch_bounds__(512) k_traj_phase_dmp(const PhaseArgs a) {    
     float* sDs = sPh + 8 * E;                           // [E][TT] ds of the tile's steps
     float* sP = sDs + E * TT;                           // [E][TT * D] forcing -> pos   (round 5: the rows stay in registers, no row buffer)
     float* sV = sP + a.o_pad;                           // [E][TT * D] vel
-    // (first elements of the small tables requested before the row table's copy waits for its loads)
-    const int tid_ = (int)threadIdx.x, bd_ = (int)blockDim.x;
-    const float bt0 = tid_ < T ? c.base_times[tid_] : 0.0f;
-    const double cen0 = tid_ < 2 * c.n_total + 3 ? c.tab[tid_] : 0.0;
     const bool fast = a.h_pad > 0;
-    if (fast) fast_rows_stage(c.rows32, sFast, a.h_pad, tid_, bd_);
-    if (tid_ < T) sBT[tid_] = bt0;
-    for (int t = tid_ + bd_; t < T; t += bd_) sBT[t] = c.base_times[t];
-    if (tid_ < 2 * c.n_total + 3) sCen[tid_] = cen0;
-    for (int k = tid_ + bd_; k < 2 * c.n_total + 3; k += bd_) sCen[k] = c.tab[k];
+    stage_phase_tables(a, sCen, sFast, sBT);
     __syncthreads();
     const float inv_d = 1.0f / (float)D;
     const int le = (int)(((float)lane + 0.5f) * inv_d), ld = lane - le * D;        // lane <-> (episode, DoF)
@@ -845,24 +1063,12 @@ __global__ void __launch_bounds__(512) k_traj_phase_dmp(const PhaseArgs a) {    
     for (int ch = (int)blockIdx.x * wpb + wave; ch < nchunks; ch += cstride) {
         const int b0 = ch * E, ne = min(E, a.B - b0);
         // ---- the chunk's inputs: columns of every (episode, DoF), phase values per episode
-        for (int idx = lane; idx < ne * D * KS; idx += 64) {
-            const int pi = idx / KS, k = idx - pi * KS;             // pi = e * D + dd
-            const int e = (int)(((float)pi + 0.5f) * inv_d), dd = pi - e * D;
-            const size_t bb = (size_t)(b0 + e);
-            sX[idx] = phase_x_value<MP>(c, a.params + bb * P, a.init_pos + bb * D, a.init_vel + bb * D, dd, k, KS);
-        }
+        for (int idx = lane; idx < ne * D * KS; idx += 64) sX[idx] = dmp_x_value<KS>(a, b0, idx, D, inv_d);
         float tau = c.tau, delay = c.delay, it = a.init_time_shared;
         const bool on = lane < ne * D;
         if (on) {
-            const float* prm = a.params + (size_t)(b0 + le) * P;
-            // np.clip(action, low, high): only tau / delay carry finite bounds (black_box_wrapper.py:104-105)
-            if (c.learn_tau) tau = fminf(fmaxf(prm[0], c.tau_lo), c.tau_hi);
-            if (c.learn_delay) delay = fminf(fmaxf(prm[c.learn_tau ? 1 : 0], c.delay_lo), c.delay_hi);
-            if (a.init_time) it = a.init_time[b0 + le];
-            if (ld == 0) {
-                sPh[8 * le] = tau; sPh[8 * le + 1] = delay; sPh[8 * le + 2] = it;
-                *reinterpret_cast<double*>(sPh + 8 * le + 4) = make_pos_div((double)tau).y;
-            }
+            episode_timing(a, b0 + le, tau, delay, it);
+            if (ld == 0) publish_timing(sPh + 8 * le, tau, delay, it);
         }
         __builtin_amdgcn_wave_barrier();
         float y = 0.0f, z = 0.0f, g = 0.0f;
@@ -879,56 +1085,20 @@ __global__ void __launch_bounds__(512) k_traj_phase_dmp(const PhaseArgs a) {    
             for (int i0 = 0; i0 < ne * TT; i0 += 64) {
                 const int idx = i0 + lane, e = idx >> 4, tl = idx & (TT - 1), t = t0 + tl;
                 const bool live = idx < ne * TT && t < T;
-                // (the item's row stays in registers: round 4 wrote it to LDS and read it back once per DoF)
                 float h[KS];
-#pragma unroll
-                for (int k = 0; k < KS; ++k) h[k] = 0.0f;
-                if (live) {
-                    const float taue = sPh[8 * e], delaye = sPh[8 * e + 1], ite = sPh[8 * e + 2];
-                    const float time = sBT[t] + ite;
-                    const float s_item = scaled_time(time, delaye, taue);
-                    if (KS == 8 && fast && fast_rows_arg(c, s_item) < kFastS) {
-                        if constexpr (KS == 8) fast_rows_eval<KS>(sFast, fast_rows_arg(c, s_item), h);
-                    } else {
-                        const PosDiv taud{(double)taue, *reinterpret_cast<const double*>(sPh + 8 * e + 4)};
-                        const double x = phase_f64(c, time, taud, delaye, ExpLiteral());
-                        // every RBF once, in registers (rbf_cols evaluates them for the sum and again for the values; same bits)
-                        rbf_row<KS>(c, sCen, sCen + c.n_total, x, x * (double)c.ws, h, ExpLiteral());
-                    }
-                    if (t < T - 1) sDs[idx] = scaled_time(sBT[t + 1] + ite, delaye, taue) - s_item;
-                }
+                if (live) dmp_item_row<KS>(c, sPh + 8 * e, sBT, sCen, sFast, fast, t, h, sDs + idx);
                 if (ti_ < 8 && i0 == 0) MPK_STAMP(11 + 5 * ti_);
                 if constexpr (DC > 0) {
-                    if (live) {                             // the DC chains side by side, offsets as constants (same chain order per DoF: same bits)
-                        float x[DC][KS];
-#pragma unroll
-                        for (int d = 0; d < DC; ++d)
-#pragma unroll
-                            for (int j = 0; j < KQ; ++j) {
-                                const float4 v = *reinterpret_cast<const float4*>(sX + (e * DC + d) * KS + 4 * j);
-                                x[d][4 * j + 0] = v.x; x[d][4 * j + 1] = v.y; x[d][4 * j + 2] = v.z; x[d][4 * j + 3] = v.w;
-                            }
-                        float acc[DC];
-#pragma unroll
-                        for (int d = 0; d < DC; ++d) acc[d] = 0.0f;
-#pragma unroll
-                        for (int k = 0; k < KS - 3; ++k)
-#pragma unroll
-                            for (int d = 0; d < DC; ++d) acc[d] = fmaf(h[k], x[d][k], acc[d]);
-#pragma unroll
-                        for (int d = 0; d < DC; ++d) sP[e * seg + tl * DC + d] = acc[d];
-                    }
+                    if (live) dmp_forcing_dc<KQ, DC, 1>(sX + e * DC * KS, h, sP + e * seg + tl * DC);
                 } else
                 if (live) {
-                    for (int d = 0; d < D; ++d) {
+                    for (int d = 0; d < D; ++d) {             // (one DoF at a time: dmp_forcing_by_four's chain, DoF for DoF)
                         float x[KS];
 #pragma unroll
                         for (int j = 0; j < KQ; ++j) {
                             const float4 v = *reinterpret_cast<const float4*>(sX + (e * D + d) * KS + 4 * j);
                             x[4 * j + 0] = v.x; x[4 * j + 1] = v.y; x[4 * j + 2] = v.z; x[4 * j + 3] = v.w;
                         }
-                        // row_chain's fmaf chain in ascending k over the weight columns (the last three columns carry goal, y0, ydot0:
-                        // not weights -- the chain multiplied them by 0, which leaves the accumulator's bits alone)
                         float acc = 0.0f;
 #pragma unroll
                         for (int k = 0; k < KS - 3; ++k) acc = fmaf(h[k], x[k], acc);
@@ -986,8 +1156,7 @@ __global__ void __launch_bounds__(512) k_traj_phase_dmp(const PhaseArgs a) {    
                         const size_t go = ((size_t)(b0 + e) * T + t0) * D + 4 * q;
                         const f32x4 vp = *reinterpret_cast<const f32x4*>(sP + e * seg + 4 * q);
                         const f32x4 vv = *reinterpret_cast<const f32x4*>(sV + e * seg + 4 * q);
-                        if (a.wt) { store16<true>(a.pos + go, vp); store16<true>(a.vel + go, vv); }
-                        else { store16<false>(a.pos + go, vp); store16<false>(a.vel + go, vv); }
+                        store_pos_vel(a, go, vp, vv);
                     }
                 }
                 if (tail) {                             // the last tile of a horizon whose rows * D is no multiple of 4
@@ -995,8 +1164,7 @@ __global__ void __launch_bounds__(512) k_traj_phase_dmp(const PhaseArgs a) {    
                         const int idx = i0 + lane, e = idx >> 2, r = idx & 3;
                         if (e < ne && r < tail) {
                             const size_t go = ((size_t)(b0 + e) * T + t0) * D + 4 * n4 + r;
-                            if (a.wt) { store4<true>(a.pos + go, sP[e * seg + 4 * n4 + r]); store4<true>(a.vel + go, sV[e * seg + 4 * n4 + r]); }
-                            else { store4<false>(a.pos + go, sP[e * seg + 4 * n4 + r]); store4<false>(a.vel + go, sV[e * seg + 4 * n4 + r]); }
+                            store_pos_vel(a, go, sP[e * seg + 4 * n4 + r], sV[e * seg + 4 * n4 + r]);
                         }
                     }
                 }
@@ -1006,8 +1174,7 @@ __global__ void __launch_bounds__(512) k_traj_phase_dmp(const PhaseArgs a) {    
                     const int e = (int)(((float)idx + 0.5f) * inv_seg), w = idx - e * seg;
                     if (e < ne && w < n) {
                         const size_t go = ((size_t)(b0 + e) * T + t0) * D + w;
-                        if (a.wt) { store4<true>(a.pos + go, sP[e * seg + w]); store4<true>(a.vel + go, sV[e * seg + w]); }
-                        else { store4<false>(a.pos + go, sP[e * seg + w]); store4<false>(a.vel + go, sV[e * seg + w]); }
+                        store_pos_vel(a, go, sP[e * seg + w], sV[e * seg + w]);
                     }
                 }
             }
@@ -1038,10 +1205,9 @@ __global__ void __launch_bounds__(NTB == 5 ? 320 : 256, 4) k_traj_phase_dmp_wg(c
     // of 80 steps where that saves a block (a block costs its rows + two barriers whatever its length: T = 200 is 80 + 80 + 40 instead
     // of 64 + 64 + 64 + 8 -- 17.5 -> 16.1 us at 2 048 episodes of cfg3 + learned tau; up to two workgroups per CU: the launcher)
     constexpr int KS = KQ * 4, TT = 16, TB = TT * NTB;     // steps per block
-    constexpr int MP = MPK_MP_DMP;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int D = c.D, T = c.T, E = a.chunk, P = c.P;
+    const int D = c.D, T = c.T, E = a.chunk;
     const int bseg = TB * D;                            // floats of one episode's block
     MPK_STAMP(0);                                       // (trace builds, tools/dev/trace_phase_dmp.py wg: kernel entry)
     double* sCen = reinterpret_cast<double*>(smem);     // [c_pad / 2] RBF centres | bandwidths
@@ -1056,71 +1222,21 @@ __global__ void __launch_bounds__(NTB == 5 ? 320 : 256, 4) k_traj_phase_dmp_wg(c
     const float inv_d = 1.0f / (float)D;
     const int le = (int)(((float)lane + 0.5f) * inv_d), ld = lane - le * D;        // lane <-> (episode, DoF)  (wave 0)
     const int nchunks = (a.B + E - 1) / E;
-    // the FIRST chunk's inputs are requested before the tables are staged (one memory round trip under the other: behind the table copy
-    // they were 1 700 of a workgroup's 40 000 cycles at 4 096 episodes, where a workgroup has one chunk)
     const int ch0 = (int)blockIdx.x;
-    float xf0 = 0.0f, tau0 = c.tau, delay0 = c.delay, it0 = a.init_time_shared;
-    if (ch0 < nchunks) {
-        const int b0 = ch0 * E, ne = min(E, a.B - b0);
-        if ((int)threadIdx.x < ne * D * KS) {
-            const int idx = (int)threadIdx.x, pi = idx / KS, kk = idx - pi * KS;
-            const int e = (int)(((float)pi + 0.5f) * inv_d), dd = pi - e * D;
-            const size_t bb = (size_t)(b0 + e);
-            xf0 = phase_x_value<MP>(c, a.params + bb * P, a.init_pos + bb * D, a.init_vel + bb * D, dd, kk, KS);
-        }
-        if (wave == 0 && lane < ne * D) {
-            const float* prm = a.params + (size_t)(b0 + le) * P;
-            if (c.learn_tau) tau0 = fminf(fmaxf(prm[0], c.tau_lo), c.tau_hi);
-            if (c.learn_delay) delay0 = fminf(fmaxf(prm[c.learn_tau ? 1 : 0], c.delay_lo), c.delay_hi);
-            if (a.init_time) it0 = a.init_time[b0 + le];
-        }
-    }
-    // (first elements of the small tables requested before the row table's copy waits for its loads)
-    const int tid_ = (int)threadIdx.x, bd_ = (int)blockDim.x;
-    const float bt0 = tid_ < T ? c.base_times[tid_] : 0.0f;
-    const double cen0 = tid_ < 2 * c.n_total + 3 ? c.tab[tid_] : 0.0;
+    const DmpFirstChunk<KS> first(a, nchunks, D, inv_d, wave == 0, lane, le);
     const bool fast = a.h_pad > 0;
-    if (fast) fast_rows_stage(c.rows32, sFast, a.h_pad, tid_, bd_);
-    if (tid_ < T) sBT[tid_] = bt0;
-    for (int t = tid_ + bd_; t < T; t += bd_) sBT[t] = c.base_times[t];
-    if (tid_ < 2 * c.n_total + 3) sCen[tid_] = cen0;
-    for (int k = tid_ + bd_; k < 2 * c.n_total + 3; k += bd_) sCen[k] = c.tab[k];
+    stage_phase_tables(a, sCen, sFast, sBT);
     const bool vec = a.vec_ok != 0;
     for (int ch = ch0; ch < nchunks; ch += (int)gridDim.x) {
         const int b0 = ch * E, ne = min(E, a.B - b0);
         // (no barrier here: the previous chunk's last block ended with one, and the tables are only read behind the next one -- the
         // chunk's input loads travel together with the table copy: 1 800 of a workgroup's 42 000 cycles at 4 096 episodes)
         MPK_STAMP(1);
-        int idx = (int)threadIdx.x;
-        if (ch == ch0) {
-            if (idx < ne * D * KS) sX[idx] = xf0;
-            idx += (int)blockDim.x;
-        }
-        for (; idx < ne * D * KS; idx += blockDim.x) {
-            const int pi = idx / KS, k = idx - pi * KS;             // pi = e * D + dd
-            const int e = (int)(((float)pi + 0.5f) * inv_d), dd = pi - e * D;
-            const size_t bb = (size_t)(b0 + e);
-            sX[idx] = phase_x_value<MP>(c, a.params + bb * P, a.init_pos + bb * D, a.init_vel + bb * D, dd, k, KS);
-        }
-        float tau = c.tau, delay = c.delay, it = a.init_time_shared;
         // (the Euler wave is wave 0 of EVERY workgroup: the serial chains of a CU's resident workgroups then share one SIMD, where they
         // interleave at no cost to each other -- a chain issues one instruction per ~9 cycles -- and leave the other three SIMDs to the
         // row / store phases; rotating the Euler wave over the SIMDs put every chain behind three busy waves: 21.9 -> 23.5 us at 4 096)
         const bool on = wave == 0 && lane < ne * D;
-        if (on) {
-            if (ch == ch0) {
-                tau = tau0; delay = delay0; it = it0;
-            } else {
-                const float* prm = a.params + (size_t)(b0 + le) * P;
-                if (c.learn_tau) tau = fminf(fmaxf(prm[0], c.tau_lo), c.tau_hi);
-                if (c.learn_delay) delay = fminf(fmaxf(prm[c.learn_tau ? 1 : 0], c.delay_lo), c.delay_hi);
-                if (a.init_time) it = a.init_time[b0 + le];
-            }
-            if (ld == 0) {
-                sPh[8 * le] = tau; sPh[8 * le + 1] = delay; sPh[8 * le + 2] = it;
-                *reinterpret_cast<double*>(sPh + 8 * le + 4) = make_pos_div((double)tau).y;
-            }
-        }
+        const float tau = dmp_wg_chunk_inputs<KS>(a, first, ch == ch0, b0, ne, D, inv_d, on, le, ld, sX, sPh);
         __syncthreads();
         MPK_STAMP(2);
         float y = 0.0f, z = 0.0f, g = 0.0f;
@@ -1135,85 +1251,17 @@ __global__ void __launch_bounds__(NTB == 5 ? 320 : 256, 4) k_traj_phase_dmp_wg(c
             {
                 const int e = (wave / NTB) * 4 + (lane >> 4), tl = lane & (TT - 1), tb = (wave % NTB) * TT + tl, t = t0 + tb;
                 const bool live = e < ne && t < T;
-                float h[KS];                        // (the item's row stays in registers, as in k_traj_phase_dmp)
-#pragma unroll
-                for (int k = 0; k < KS; ++k) h[k] = 0.0f;
                 if (live) {
-                    const float taue = sPh[8 * e], delaye = sPh[8 * e + 1], ite = sPh[8 * e + 2];
-                    const float time = sBT[t] + ite;
-                    const float s_item = scaled_time(time, delaye, taue);
-                    if (KS == 8 && fast && fast_rows_arg(c, s_item) < kFastS) {
-                        if constexpr (KS == 8) fast_rows_eval<KS>(sFast, fast_rows_arg(c, s_item), h);
-                    } else {
-                        const PosDiv taud{(double)taue, *reinterpret_cast<const double*>(sPh + 8 * e + 4)};
-                        const double x = phase_f64(c, time, taud, delaye, ExpLiteral());
-                        rbf_row<KS>(c, sCen, sCen + c.n_total, x, x * (double)c.ws, h, ExpLiteral());
-                    }
-                    if (t < T - 1) sDs[e * TB + tb] = scaled_time(sBT[t + 1] + ite, delaye, taue) - s_item;
-                }
-                if (live) {
-                    // four DoF side by side (one after the other: two LDS reads, KS - 3 dependent FMAs and an LDS write, D times in a row)
-                    for (int d0 = 0; d0 < D; d0 += 4) {
-                        float x[4][KS];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const int d = min(d0 + i, D - 1);
-#pragma unroll
-                            for (int j = 0; j < KQ; ++j) {
-                                const float4 v = *reinterpret_cast<const float4*>(sX + (e * D + d) * KS + 4 * j);
-                                x[i][4 * j + 0] = v.x; x[i][4 * j + 1] = v.y; x[i][4 * j + 2] = v.z; x[i][4 * j + 3] = v.w;
-                            }
-                        }
-                        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};    // (row_chain's chain over the weight columns: k_traj_phase_dmp)
-#pragma unroll
-                        for (int k = 0; k < KS - 3; ++k)
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) acc[i] = fmaf(h[k], x[i][k], acc[i]);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            if (d0 + i < D) sPV[2 * (e * bseg + tb * D + d0 + i)] = acc[i];
-                    }
+                    float h[KS];
+                    dmp_item_row<KS>(c, sPh + 8 * e, sBT, sCen, sFast, fast, t, h, sDs + e * TB + tb);
+                    dmp_forcing_by_four<KQ>(sX, e, D, h, sPV, e * bseg + tb * D);
                 }
             }
             if (bi_ < 8) MPK_STAMP(10 + 4 * bi_);
             __syncthreads();
             if (bi_ < 8) MPK_STAMP(11 + 4 * bi_);
             // ---- B: wave 0: the block's Euler steps of every (episode, DoF) of the chunk (one rounding per operation)
-            if (on) {
-                float* pq = sPV + 2 * (le * bseg + ld);          // the lane's (pos, tau x vel) pairs, 2 D floats apart per step
-                const float* pds = sDs + le * TB;
-                // round 5: 8-step pieces every step of which advances the state take their forcing values and step sizes into
-                // registers first (the loop form reads each forcing value behind the previous step's write to the same image: an LDS
-                // round trip inside every one of a chunk's 200 dependent steps -- most of this kernel's time at 4 096 episodes)
-                constexpr int PC = 8;               // (16 at a time spill: four workgroups per CU leave 128 registers)
-                int tl0 = 0;
-                for (; tl0 + PC <= rows && t0 + tl0 + PC < T; tl0 += PC) {
-                    float fr[PC], dsr[PC];
-#pragma unroll
-                    for (int j = 0; j < PC / 4; ++j) {
-                        const f32x4 v = *reinterpret_cast<const f32x4*>(pds + tl0 + 4 * j);
-                        dsr[4 * j] = v[0]; dsr[4 * j + 1] = v[1]; dsr[4 * j + 2] = v[2]; dsr[4 * j + 3] = v[3];
-                    }
-#pragma unroll
-                    for (int i = 0; i < PC; ++i) fr[i] = pq[2 * (tl0 + i) * D];
-#pragma unroll
-                    // (what a step costs the lone Euler wave, round 5 trace at one workgroup per CU: 98 cycles -- 61 for the five dependent
-                    // operations and the reads, 37 for the two LDS writes; a lone wave issues one instruction per 5.6 - 9 cycles)
-                    for (int i = 0; i < PC; ++i) {
-                        *reinterpret_cast<f32x2*>(pq + 2 * (tl0 + i) * D) = f32x2{y, z};      // (tau x velocity: the division by tau is the storing waves')
-                        dmp_phase_step(y, z, g, fr[i], dsr[i], c.dmp_alpha, c.dmp_beta);
-                    }
-                }
-#pragma unroll 1
-                for (int tl = tl0; tl < rows; ++tl) {
-                    const float f = pq[2 * tl * D];
-                    *reinterpret_cast<f32x2*>(pq + 2 * tl * D) = f32x2{y, z};
-                    if (t0 + tl < T - 1) {
-                        const float ds = pds[tl];
-                        dmp_phase_step(y, z, g, f, ds, c.dmp_alpha, c.dmp_beta);
-                    }
-                }
-            }
+            if (on) dmp_euler_pairs(c, sPV + 2 * (le * bseg + ld), sDs + le * TB, D, t0, rows, y, z, g);
             if (bi_ < 8) MPK_STAMP(12 + 4 * bi_);
             __syncthreads();
             // ---- C: the block's runs, rows * D contiguous floats per episode and array
@@ -1222,25 +1270,12 @@ __global__ void __launch_bounds__(NTB == 5 ? 320 : 256, 4) k_traj_phase_dmp_wg(c
                 const int n4 = n >> 2;
                 for (int idx = threadIdx.x; idx < ne * n4; idx += blockDim.x) {
                     const int e = idx / n4, q4 = idx - e * n4;
-                    const size_t go = ((size_t)(b0 + e) * T + t0) * D + 4 * q4;
-                    const f32x4 pa = *reinterpret_cast<const f32x4*>(sPV + 2 * (e * bseg + 4 * q4));
-                    const f32x4 pb = *reinterpret_cast<const f32x4*>(sPV + 2 * (e * bseg + 4 * q4) + 4);
-                    const f32x4 vp = {pa[0], pa[2], pb[0], pb[2]};
-                    f32x4 vv = {pa[1], pa[3], pb[1], pb[3]};
-                    const TauDiv tde = make_tau_div(sPh[8 * e]);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) vv[q] = div_tau(vv[q], tde);
-                    if (a.wt) { store16<true>(a.pos + go, vp); store16<true>(a.vel + go, vv); }
-                    else { store16<false>(a.pos + go, vp); store16<false>(a.vel + go, vv); }
+                    dmp_store_pairs4(a, sPV + 2 * (e * bseg + 4 * q4), sPh + 8 * e, ((size_t)(b0 + e) * T + t0) * D + 4 * q4);
                 }
             } else {
                 for (int idx = threadIdx.x; idx < ne * n; idx += blockDim.x) {
                     const int e = idx / n, w = idx - e * n;
-                    const size_t go = ((size_t)(b0 + e) * T + t0) * D + w;
-                    const f32x2 pr = *reinterpret_cast<const f32x2*>(sPV + 2 * (e * bseg + w));
-                    const float vel = div_tau(pr[1], make_tau_div(sPh[8 * e]));
-                    if (a.wt) { store4<true>(a.pos + go, pr[0]); store4<true>(a.vel + go, vel); }
-                    else { store4<false>(a.pos + go, pr[0]); store4<false>(a.vel + go, vel); }
+                    dmp_store_pair(a, sPV + 2 * (e * bseg + w), sPh + 8 * e, ((size_t)(b0 + e) * T + t0) * D + w);
                 }
             }
             if (bi_ < 8) MPK_STAMP(13 + 4 * bi_);
@@ -1266,10 +1301,9 @@ __global__ void __launch_bounds__(256, 4) k_traj_phase_dmp_pipe(const PhaseArgs 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const DevCfg& c = a.c;
     constexpr int KS = KQ * 4, TT = 16, NH = 3, TB = TT * NH;     // 48 steps per block: a tile per helper wave
-    constexpr int MP = MPK_MP_DMP;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int D = DC > 0 ? DC : c.D, T = c.T, E = a.chunk, P = c.P;
+    const int D = DC > 0 ? DC : c.D, T = c.T, E = a.chunk;
     const int bseg = TB * D;                            // (pos, tau x vel) pairs of one episode's block
     MPK_STAMP(0);
     double* sCen = reinterpret_cast<double*>(smem);     // [c_pad / 2] RBF centres | bandwidths
@@ -1283,63 +1317,16 @@ __global__ void __launch_bounds__(256, 4) k_traj_phase_dmp_pipe(const PhaseArgs 
     const int le = (int)(((float)lane + 0.5f) * inv_d), ld = lane - le * D;        // lane <-> (episode, DoF)  (wave 0)
     const int nchunks = (a.B + E - 1) / E;
     const int ch0 = (int)blockIdx.x;
-    float xf0 = 0.0f, tau0 = c.tau, delay0 = c.delay, it0 = a.init_time_shared;
-    if (ch0 < nchunks) {                                // the first chunk's inputs: requested before the tables are staged
-        const int b0 = ch0 * E, ne = min(E, a.B - b0);
-        if ((int)threadIdx.x < ne * D * KS) {
-            const int idx = (int)threadIdx.x, pi = idx / KS, kk = idx - pi * KS;
-            const int e = (int)(((float)pi + 0.5f) * inv_d), dd = pi - e * D;
-            const size_t bb = (size_t)(b0 + e);
-            xf0 = phase_x_value<MP>(c, a.params + bb * P, a.init_pos + bb * D, a.init_vel + bb * D, dd, kk, KS);
-        }
-        if (wave == 0 && lane < ne * D) {
-            const float* prm = a.params + (size_t)(b0 + le) * P;
-            if (c.learn_tau) tau0 = fminf(fmaxf(prm[0], c.tau_lo), c.tau_hi);
-            if (c.learn_delay) delay0 = fminf(fmaxf(prm[c.learn_tau ? 1 : 0], c.delay_lo), c.delay_hi);
-            if (a.init_time) it0 = a.init_time[b0 + le];
-        }
-    }
-    const int tid_ = (int)threadIdx.x, bd_ = (int)blockDim.x;
-    const float bt0 = tid_ < T ? c.base_times[tid_] : 0.0f;
-    const double cen0 = tid_ < 2 * c.n_total + 3 ? c.tab[tid_] : 0.0;
+    const DmpFirstChunk<KS> first(a, nchunks, D, inv_d, wave == 0, lane, le);
     const bool fast = a.h_pad > 0;
-    if (fast) fast_rows_stage(c.rows32, sFast, a.h_pad, tid_, bd_);
-    if (tid_ < T) sBT[tid_] = bt0;
-    for (int t = tid_ + bd_; t < T; t += bd_) sBT[t] = c.base_times[t];
-    if (tid_ < 2 * c.n_total + 3) sCen[tid_] = cen0;
-    for (int k = tid_ + bd_; k < 2 * c.n_total + 3; k += bd_) sCen[k] = c.tab[k];
+    stage_phase_tables(a, sCen, sFast, sBT);
     const bool vec = a.vec_ok != 0;
     const int NB = (T + TB - 1) / TB;
     for (int ch = ch0; ch < nchunks; ch += (int)gridDim.x) {
         const int b0 = ch * E, ne = min(E, a.B - b0);
         MPK_STAMP(1);
-        int idx = (int)threadIdx.x;
-        if (ch == ch0) {
-            if (idx < ne * D * KS) sX[idx] = xf0;
-            idx += (int)blockDim.x;
-        }
-        for (; idx < ne * D * KS; idx += blockDim.x) {
-            const int pi = idx / KS, k = idx - pi * KS;             // pi = e * D + dd
-            const int e = (int)(((float)pi + 0.5f) * inv_d), dd = pi - e * D;
-            const size_t bb = (size_t)(b0 + e);
-            sX[idx] = phase_x_value<MP>(c, a.params + bb * P, a.init_pos + bb * D, a.init_vel + bb * D, dd, k, KS);
-        }
-        float tau = c.tau, delay = c.delay, it = a.init_time_shared;
         const bool on = wave == 0 && lane < ne * D;
-        if (on) {
-            if (ch == ch0) {
-                tau = tau0; delay = delay0; it = it0;
-            } else {
-                const float* prm = a.params + (size_t)(b0 + le) * P;
-                if (c.learn_tau) tau = fminf(fmaxf(prm[0], c.tau_lo), c.tau_hi);
-                if (c.learn_delay) delay = fminf(fmaxf(prm[c.learn_tau ? 1 : 0], c.delay_lo), c.delay_hi);
-                if (a.init_time) it = a.init_time[b0 + le];
-            }
-            if (ld == 0) {
-                sPh[8 * le] = tau; sPh[8 * le + 1] = delay; sPh[8 * le + 2] = it;
-                *reinterpret_cast<double*>(sPh + 8 * le + 4) = make_pos_div((double)tau).y;
-            }
-        }
+        const float tau = dmp_wg_chunk_inputs<KS>(a, first, ch == ch0, b0, ne, D, inv_d, on, le, ld, sX, sPh);
         __syncthreads();
         MPK_STAMP(2);
         float y = 0.0f, z = 0.0f, g = 0.0f;
@@ -1352,34 +1339,7 @@ __global__ void __launch_bounds__(256, 4) k_traj_phase_dmp_pipe(const PhaseArgs 
                 // ---- B: the Euler steps of block s - 1 (the workgroup kernel's, step for step)
                 if (on && s >= 1 && s <= NB) {
                     const int t0 = (s - 1) * TB, rows = min(TB, T - t0), bi = (s - 1) & 1;
-                    float* pq = sPV + (size_t)bi * 2 * E * bseg + 2 * (le * bseg + ld);
-                    const float* pds = sDs + bi * E * TB + le * TB;
-                    constexpr int PC = 8;
-                    int tl0 = 0;
-                    for (; tl0 + PC <= rows && t0 + tl0 + PC < T; tl0 += PC) {
-                        float fr[PC], dsr[PC];
-#pragma unroll
-                        for (int j = 0; j < PC / 4; ++j) {
-                            const f32x4 v = *reinterpret_cast<const f32x4*>(pds + tl0 + 4 * j);
-                            dsr[4 * j] = v[0]; dsr[4 * j + 1] = v[1]; dsr[4 * j + 2] = v[2]; dsr[4 * j + 3] = v[3];
-                        }
-#pragma unroll
-                        for (int i = 0; i < PC; ++i) fr[i] = pq[2 * (tl0 + i) * D];
-#pragma unroll
-                        for (int i = 0; i < PC; ++i) {
-                            *reinterpret_cast<f32x2*>(pq + 2 * (tl0 + i) * D) = f32x2{y, z};
-                            dmp_phase_step(y, z, g, fr[i], dsr[i], c.dmp_alpha, c.dmp_beta);
-                        }
-                    }
-#pragma unroll 1
-                    for (int tl = tl0; tl < rows; ++tl) {
-                        const float f = pq[2 * tl * D];
-                        *reinterpret_cast<f32x2*>(pq + 2 * tl * D) = f32x2{y, z};
-                        if (t0 + tl < T - 1) {
-                            const float ds = pds[tl];
-                            dmp_phase_step(y, z, g, f, ds, c.dmp_alpha, c.dmp_beta);
-                        }
-                    }
+                    dmp_euler_pairs(c, sPV + (size_t)bi * 2 * E * bseg + 2 * (le * bseg + ld), sDs + bi * E * TB + le * TB, D, t0, rows, y, z, g);
                 }
                 if (s < 8) MPK_STAMP(10 + 2 * s);
             } else {
@@ -1395,25 +1355,12 @@ __global__ void __launch_bounds__(256, 4) k_traj_phase_dmp_pipe(const PhaseArgs 
                             const float inv_n4 = 1.0f / (float)n4;      // (i + 0.5) / n4: the exact floor for these few hundred indices
                             for (int i = lane; i < ne * n4; i += 64) {
                                 const int e = (int)(((float)i + 0.5f) * inv_n4), q4 = i - e * n4;
-                                const size_t go = ((size_t)(b0 + e) * T + t0) * D + 4 * q4;
-                                const f32x4 pa = *reinterpret_cast<const f32x4*>(src + 2 * (e * bseg + 4 * q4));
-                                const f32x4 pb = *reinterpret_cast<const f32x4*>(src + 2 * (e * bseg + 4 * q4) + 4);
-                                const f32x4 vp = {pa[0], pa[2], pb[0], pb[2]};
-                                f32x4 vv = {pa[1], pa[3], pb[1], pb[3]};
-                                const TauDiv tde = make_tau_div(sPh[8 * e]);
-#pragma unroll
-                                for (int q = 0; q < 4; ++q) vv[q] = div_tau(vv[q], tde);
-                                if (a.wt) { store16<true>(a.pos + go, vp); store16<true>(a.vel + go, vv); }
-                                else { store16<false>(a.pos + go, vp); store16<false>(a.vel + go, vv); }
+                                dmp_store_pairs4(a, src + 2 * (e * bseg + 4 * q4), sPh + 8 * e, ((size_t)(b0 + e) * T + t0) * D + 4 * q4);
                             }
                         } else {
                             for (int i = lane; i < ne * n; i += 64) {
                                 const int e = i / n, w = i - e * n;
-                                const size_t go = ((size_t)(b0 + e) * T + t0) * D + w;
-                                const f32x2 pr = *reinterpret_cast<const f32x2*>(src + 2 * (e * bseg + w));
-                                const float vel = div_tau(pr[1], make_tau_div(sPh[8 * e]));
-                                if (a.wt) { store4<true>(a.pos + go, pr[0]); store4<true>(a.vel + go, vel); }
-                                else { store4<false>(a.pos + go, pr[0]); store4<false>(a.vel + go, vel); }
+                                dmp_store_pair(a, src + 2 * (e * bseg + w), sPh + 8 * e, ((size_t)(b0 + e) * T + t0) * D + w);
                             }
                         }
                     }
@@ -1423,60 +1370,11 @@ __global__ void __launch_bounds__(256, 4) k_traj_phase_dmp_pipe(const PhaseArgs 
                 if (s < NB) {
                     const int e = lane >> 4, tl = lane & (TT - 1), tb = hw * TT + tl, t = s * TB + tb;
                     const bool live = e < ne && t < T;
-                    float h[KS];
-#pragma unroll
-                    for (int k = 0; k < KS; ++k) h[k] = 0.0f;
                     if (live) {
-                        const float taue = sPh[8 * e], delaye = sPh[8 * e + 1], ite = sPh[8 * e + 2];
-                        const float time = sBT[t] + ite;
-                        const float s_item = scaled_time(time, delaye, taue);
-                        if (KS == 8 && fast && fast_rows_arg(c, s_item) < kFastS) {
-                            if constexpr (KS == 8) fast_rows_eval<KS>(sFast, fast_rows_arg(c, s_item), h);
-                        } else {
-                            const PosDiv taud{(double)taue, *reinterpret_cast<const double*>(sPh + 8 * e + 4)};
-                            const double x = phase_f64(c, time, taud, delaye, ExpLiteral());
-                            rbf_row<KS>(c, sCen, sCen + c.n_total, x, x * (double)c.ws, h, ExpLiteral());
-                        }
-                        if (t < T - 1) sDs[bi * E * TB + e * TB + tb] = scaled_time(sBT[t + 1] + ite, delaye, taue) - s_item;
-                        if constexpr (DC > 0) {
-                            float x[DC][KS];
-#pragma unroll
-                            for (int d = 0; d < DC; ++d)
-#pragma unroll
-                                for (int j = 0; j < KQ; ++j) {
-                                    const float4 v = *reinterpret_cast<const float4*>(sX + (e * DC + d) * KS + 4 * j);
-                                    x[d][4 * j + 0] = v.x; x[d][4 * j + 1] = v.y; x[d][4 * j + 2] = v.z; x[d][4 * j + 3] = v.w;
-                                }
-                            float acc[DC];
-#pragma unroll
-                            for (int d = 0; d < DC; ++d) acc[d] = 0.0f;
-#pragma unroll
-                            for (int k = 0; k < KS - 3; ++k)
-#pragma unroll
-                                for (int d = 0; d < DC; ++d) acc[d] = fmaf(h[k], x[d][k], acc[d]);
-#pragma unroll
-                            for (int d = 0; d < DC; ++d) pvb[2 * (e * bseg + tb * DC + d)] = acc[d];
-                        } else
-                        for (int d0 = 0; d0 < D; d0 += 4) {
-                            float x[4][KS];
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int d = min(d0 + i, D - 1);
-#pragma unroll
-                                for (int j = 0; j < KQ; ++j) {
-                                    const float4 v = *reinterpret_cast<const float4*>(sX + (e * D + d) * KS + 4 * j);
-                                    x[i][4 * j + 0] = v.x; x[i][4 * j + 1] = v.y; x[i][4 * j + 2] = v.z; x[i][4 * j + 3] = v.w;
-                                }
-                            }
-                            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                            for (int k = 0; k < KS - 3; ++k)
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) acc[i] = fmaf(h[k], x[i][k], acc[i]);
-#pragma unroll
-                            for (int i = 0; i < 4; ++i)
-                                if (d0 + i < D) pvb[2 * (e * bseg + tb * D + d0 + i)] = acc[i];
-                        }
+                        float h[KS];
+                        dmp_item_row<KS>(c, sPh + 8 * e, sBT, sCen, sFast, fast, t, h, sDs + bi * E * TB + e * TB + tb);
+                        if constexpr (DC > 0) dmp_forcing_dc<KQ, DC, 2>(sX + e * DC * KS, h, pvb + 2 * (e * bseg + tb * DC));
+                        else dmp_forcing_by_four<KQ>(sX, e, D, h, pvb, e * bseg + tb * D);
                     }
                 }
             }

@@ -1024,6 +1024,45 @@ def test_per_episode_dmp_workgroup_and_wave_kernels_agree_bitwise(D, nb, T, B, m
     close(p2.cpu().numpy(), rp, "pos (automatic)"); close(v2.cpu().numpy(), rv, "vel (automatic)")
 
 
+@pytest.mark.parametrize("D,nb,T,B", [(7, 5, 200, 37),        # seven DoF compiled in, a pipeline with a ragged last block, five-wave workgroups
+                                      (3, 4, 70, 9),          # T * D no multiple of 4: the scalar stores; a partial last chunk
+                                      (16, 9, 33, 50),        # sixteen columns: no pipeline
+                                      (5, 5, 100, 7000),      # chunks of eight episodes, two tiles per block
+                                      # a workgroup's second chunk reloads its timing where the chunks (of eight) outnumber the launch's
+                                      # workgroups: CUs x resident workgroups, at most five by the registers, fewer by the LDS.  On 256 CUs
+                                      # 1 280 chunks do so only with the interpolation table staged (four resident), 1 288 with both settings
+                                      (7, 5, 200, 10240), (7, 5, 200, 10300)])
+def test_per_episode_dmp_routes_agree_with_delay_and_own_init_time(D, nb, T, B, mpk_option):
+    """learned tau AND delay with an init_time per episode: the wave, workgroup and pipeline kernels share one text for an episode's
+    timing (both clips, the init_time array), and leave the same bits; the first 64 episodes follow the oracle at their own init_time"""
+    pc, bc, tc, dt, dur = cfg_for("dmp", D, nb, T)
+    pc = dataclasses.replace(pc, learn_tau=True, learn_delay=True, tau_bound=(0.5 * dur, 1.5 * dur), delay_bound=(0.0, 0.2 * dur))
+    eng = make_engine(pc, bc, tc, dt, dur)
+    params, ip, iv = inputs(pc, bc, tc, B, seed=B + T)
+    it = (np.random.default_rng(B + T).integers(0, 4, B) * dt).astype(np.float32)         # multiples of dt in [0, 3 dt]
+    n = min(B, 64)
+    rp, rv = O.get_trajectory(pc, bc, tc, params[:n], dur, dt, it[:n], ip[:n], iv[:n], dtype=np.float64)
+    params, ip, iv, it = (torch.tensor(x, device="cuda") for x in (params, ip, iv, it))
+    for table in (0, 1):
+        mpk_option("phase_table", table)
+        mpk_option("phase_flat", 1)
+        mpk_option("pipe", 0)
+        p1, v1 = [x.clone() for x in eng.trajectory(params, ip, iv, it)]
+        assert eng.last_kernel() == "k_traj_phase<dmp,wg>", eng.last_kernel()
+        mpk_option("pipe", -1)
+        p2, v2 = [x.clone() for x in eng.trajectory(params, ip, iv, it)]
+        if (D, nb, T, B) == (7, 5, 200, 37):
+            assert eng.last_kernel() == "k_traj_phase<dmp,wg,pipe>", eng.last_kernel()
+        if nb + 3 > 8:
+            assert eng.last_kernel() == "k_traj_phase<dmp,wg>", eng.last_kernel()
+        assert torch.equal(p1, p2) and torch.equal(v1, v2), (table, eng.last_kernel())
+        mpk_option("phase_flat", 0)
+        p0, v0 = eng.trajectory(params, ip, iv, it)
+        assert eng.last_kernel() == "k_traj_phase<dmp>", eng.last_kernel()
+        assert torch.equal(p1, p0) and torch.equal(v1, v0), table
+        close(p1[:n].cpu().numpy(), rp, "pos"); close(v1[:n].cpu().numpy(), rv, "vel")
+
+
 def test_dmp_horizon_beyond_the_lds_of_the_shared_phase_kernels_runs_time_tiled():
     """T = 8000: the forcing / state rows of a whole horizon no longer fit any kernel's LDS (round 1 refused this
     shape); the per-episode DMP kernel walks the horizon in 16-step tiles and takes it"""
