@@ -363,6 +363,84 @@ def test_oracle_solves_the_ode_for_every_baseline_prodmp_and_dmp_configuration()
     G.check_cfg3_dmp(factory=OracleEngine)
 
 
+def test_oracle_solves_the_ode_for_the_prodmp_cases_with_own_init_time_and_the_remaining_flags():
+    """learned tau / delay with an init_time per episode, init_vel, an enabled scaled relative goal in both relative_goal_mode
+    settings; disable_weights with goal_scale 0.5; goal_offset_mode = add; cfg2 with an init_time array -- at the bounds of _check"""
+    from tests import test_gpu_ode as G
+    from tests.oracle_engine import OracleEngine
+    for mode in ("before_scale", "after_scale"):
+        G.check_tabletennis_prodmp_own_init_time(mode, factory=OracleEngine)
+    for which in ("disable_weights", "goal_offset", "own_init_time"):
+        G.check_prodmp_flags(which, factory=OracleEngine)
+
+
+@pytest.mark.parametrize("name", ["shared", "learned", "offgrid", "linear", "step_shared", "step_learned"])
+def test_oracle_dmp_extrapolation_solves_the_ode_and_gives_the_recorded_residuals(name):
+    """the Richardson-extrapolated Euler recurrence of the float64 oracle against SciPy, positions and velocities: the check
+    the GPU suite applies to every DMP route (its conditions included: a tenth of the plain error, second order with the delay
+    on the grid) -- and the residuals the GPU bounds are derived from (tests/test_gpu_ode.py DMP_MEASURED) are what the oracle
+    gives"""
+    from tests import test_gpu_ode as G
+    from tests.oracle_engine import OracleEngine
+    fig = G.check_dmp_extrapolated(name, factory=OracleEngine)
+    for dt, (rp, rv) in G.DMP_MEASURED[name].items():
+        assert abs(fig[dt][0] / rp - 1) < 0.02 and abs(fig[dt][1] / rv - 1) < 0.02, (name, dt, fig[dt], (rp, rv))
+
+
+def _misreading(kind):
+    """OracleEngine with ONE thing of the DMP semantics read differently"""
+    import dataclasses
+    import torch
+    from tests.oracle_engine import OracleEngine
+
+    class Misread(OracleEngine):
+        def __init__(self, pc, bc, tc, dt, duration):
+            super().__init__(pc, bc, tc, dt, duration)          # (the construction-time constants stay the handle's)
+            self.delay_bound = pc.delay_bound
+            if kind == "goal_scale_ignored":
+                self.tc = dataclasses.replace(tc, goal_scale=1.0)
+            if kind == "tau_unclipped":
+                self.pc = dataclasses.replace(pc, tau_bound=(1e-5, np.inf))
+            if kind == "delay_hold_one_step_late":
+                self.pc = dataclasses.replace(pc, delay_bound=(pc.delay_bound[0], np.inf))
+
+        def trajectory(self, params, init_pos, init_vel, init_time=0.0):
+            pc = self.pc
+            params = np.array(params, np.float32)
+            tau = np.float32(pc.tau)
+            if pc.learn_tau:
+                tau = np.clip(params[:, 0], *np.float32(pc.tau_bound))[:, None]
+            if kind == "init_vel_not_times_tau":
+                init_vel = np.asarray(init_vel) / tau
+            if kind == "delay_hold_one_step_late" and pc.learn_delay:
+                c = int(pc.learn_tau)
+                params[:, c] = np.clip(params[:, c], *np.float32(self.delay_bound)) + np.float32(self.dt)
+            pos, vel = super().trajectory(params, init_pos, init_vel, init_time)
+            if kind == "vel_not_divided_by_tau":
+                vel = vel * torch.as_tensor(np.asarray(tau, np.float64))[..., None]
+            return pos, vel
+
+    return Misread
+
+
+@pytest.mark.parametrize("kind", ["vel_not_divided_by_tau", "init_vel_not_times_tau", "goal_scale_ignored",
+                                  "delay_hold_one_step_late", "tau_unclipped"])
+def test_the_extrapolated_dmp_checks_reject_misreadings_the_first_order_check_accepts(kind):
+    """why the extrapolated checks exist: each of these one-line misreadings of the DMP semantics passes check_cfg3_dmp (shared
+    phase, init_vel 0, unit scales, no delay, positions only, 5 %) and fails the learned-phase or the shared-phase check"""
+    from tests import test_gpu_ode as G
+    factory = _misreading(kind)
+    G.check_cfg3_dmp(factory=factory)                      # let through
+    caught = []
+    for name in ("learned", "shared"):
+        try:
+            G.check_dmp_extrapolated(name, factory=factory)
+        except AssertionError:
+            caught.append(name)
+    print(kind, "caught by", caught)
+    assert "learned" in caught, (kind, caught)
+
+
 def test_golden_fixtures_record_their_provenance():
     """every fixture names the numpy / torch versions it was produced with and carries the hash of the generator script
     and of the oracle it came from; the committed generator AND the committed oracle are the ones that produced the
