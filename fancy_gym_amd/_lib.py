@@ -241,6 +241,14 @@ SIGNATURES = {
     "mpk_demonstration_phase_log_prob_vjp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mpk_demonstration_phase_condition": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mpk_demonstration_phase_plan": (C.c_int, [_vp, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    # the point-wise entries with a per-episode phase (tau / delay given at the front of params)
+    "mpk_trajectory_phase_condition": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _dbl, C.POINTER(C.c_int32), _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 _i32, _vp]),
+    "mpk_trajectory_phase_log_prob": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _dbl, C.POINTER(C.c_int32), _i32, _vp, _vp, _vp, _vp, _vp, _i32,
+                                                _vp]),
+    "mpk_trajectory_phase_log_prob_vjp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _dbl, C.POINTER(C.c_int32), _i32, _vp, _vp, _vp, _vp, _vp,
+                                                    _vp, _vp, _i32, _vp]),
+    "mpk_trajectory_phase_std": (C.c_int, [_vp, _vp, _vp, _dbl, _vp, _vp, _i32, _vp]),
     "mpk_trajectory_phase_vjp": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
 }
 
@@ -248,7 +256,7 @@ _lib: Optional[C.CDLL] = None
 
 # the files libmpk.so is built from, in the order mpk_source_hash() is defined over (include/mpk.h)
 _ROOT = os.path.dirname(_HERE)
-KERNEL_UNITS = ("mpk_traj_family.hip", "mpk_traj_ring.hip", "mpk_episode.hip", "mpk_episode_vjp.hip", "mpk_traj_launch.hip", "mpk_traj_wide.hip", "mpk_traj_vjp.hip", "mpk_traj_fit.hip", "mpk_traj_std.hip", "mpk_traj_condition.hip", "mpk_traj_log_prob.hip", "mpk_demo_log_prob.hip", "mpk_demo_condition.hip", "mpk_traj_phase.hip",
+KERNEL_UNITS = ("mpk_traj_family.hip", "mpk_traj_ring.hip", "mpk_episode.hip", "mpk_episode_vjp.hip", "mpk_traj_launch.hip", "mpk_traj_wide.hip", "mpk_traj_vjp.hip", "mpk_traj_fit.hip", "mpk_traj_std.hip", "mpk_traj_phase_std.hip", "mpk_traj_condition.hip", "mpk_traj_log_prob.hip", "mpk_demo_log_prob.hip", "mpk_demo_condition.hip", "mpk_traj_phase.hip",
                 "mpk_phase_fused.hip", "mpk_rollout.hip", "mpk_rollout_vjp.hip", "mpk_hole.hip", "mpk_hole_vjp.hip", "mpk_phase_vjp.hip", "mpk_reset.hip", "mpk_obs.hip", "mpk_autoreset.hip", "mpk_env_step.hip", "mpk_misc.hip")          # translation units of the device code (mpk_traj_family.hip: once per MP type)
 KERNEL_HEADERS = ("mpk_dev.h", "mpk_tile.h", "mpk_traj_tiles.h", "mpk_traj_stream.h", "mpk_traj_flat.h", "mpk_traj_ring.h", "mpk_traj_quad.h",
                   "mpk_traj_pipe.h", "mpk_traj_route.h", "mpk_reward.h", "mpk_vjp_row.h", "mpk_cond_rows.h", "mpk_demo_gram.h", "mpk_gauss_launch.h", "mpk_phase_rows.h", "mpk_run_stage.h", "mpk_phase.h", "mpk_trace_reader.h", "mpk_nprng.h", "mpk_plant.h", "mpk_reacher_env.h", "mpk_hole_geom.h")

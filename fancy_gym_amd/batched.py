@@ -630,6 +630,25 @@ class BatchedBlackBox:
         return self.engine.trajectory_log_prob(params, params_L, obs_steps, obs_pos, obs_std, cond_pos.detach(), cond_vel.detach(),
                                                self._plan_time(), obs_vel=obs_vel, obs_vel_std=obs_vel_std)
 
+    def condition_given_timing(self, params, params_L, obs_steps, obs_pos=None, obs_std=None, *, obs_vel=None, obs_vel_std=None, out=None):
+        """``condition`` for a learned tau / delay (``TrajectoryEngine.condition_given_timing``, one launch): every episode at the tau /
+        delay in front of its ``params`` row, which come back as given; the Gaussian over the non-phase parameters"""
+        cond_pos = self.condition_pos if self.condition_pos is not None else self.q.float()
+        cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
+        return self.engine.condition_given_timing(params, params_L, obs_steps, obs_pos, obs_std, cond_pos.detach(), cond_vel.detach(),
+                                                  self._plan_time(), obs_vel=obs_vel, obs_vel_std=obs_vel_std, out=out)
+
+    def trajectory_log_prob_given_timing(self, params, params_L, obs_steps, obs_pos=None, obs_std=None, *, obs_vel=None,
+                                         obs_vel_std=None):
+        """``trajectory_log_prob`` for a learned tau / delay (``TrajectoryEngine.trajectory_log_prob_given_timing``, one launch;
+        differentiable w.r.t. ``params`` and ``params_L``, exact zeros in the phase columns): every episode at the tau / delay in
+        front of its ``params`` row"""
+        cond_pos = self.condition_pos if self.condition_pos is not None else self.q.float()
+        cond_vel = self.condition_vel if self.condition_vel is not None else self.qd.float()
+        return self.engine.trajectory_log_prob_given_timing(params, params_L, obs_steps, obs_pos, obs_std, cond_pos.detach(),
+                                                            cond_vel.detach(), self._plan_time(), obs_vel=obs_vel,
+                                                            obs_vel_std=obs_vel_std)
+
     def demonstration_log_prob(self, params, params_L, pos, obs_std):
         """the log-likelihood [B] float64 of whole demonstrations ``pos`` [B, T, D] of the plan under the Gaussian ``N(params, L L^T)``
         (``TrajectoryEngine.demonstration_log_prob``, one launch; differentiable w.r.t. ``params`` and ``params_L``) from the

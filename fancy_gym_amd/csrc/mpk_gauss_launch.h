@@ -1,5 +1,5 @@
 // the launch plumbing the probabilistic units share (mpk_traj_condition.hip, mpk_traj_log_prob.hip, mpk_demo_log_prob.hip,
-// mpk_demo_condition.hip; mpk_traj_std.hip takes the two refusals only): host code, no kernel
+// mpk_demo_condition.hip, mpk_traj_phase_std.hip; mpk_traj_std.hip takes the two refusals only): host code, no kernel
 #pragma once
 
 #include "mpk_dev.h"
@@ -18,6 +18,18 @@ inline int gauss_common_limits(const DevCfg& c, const char* fn) {
         set_error(name + ": at most " + std::to_string(kMaxD) + " DoF and " + std::to_string(kMaxKP) +
                   " table columns (this handle: " + std::to_string(c.D) + " DoF, " + std::to_string(c.KT) +
                   " columns); the k_traj_wide shapes have no kernel here");
+        return MPK_ENOTIMPL;
+    }
+    return MPK_OK;
+}
+
+// ... and what a per-episode row source (mpk_phase_rows.h, `slots` row slots) refuses on top, in demo_phase_limits' words
+inline int gauss_phase_row_limits(const DevCfg& c, int slots, const char* fn) {
+    const int need = c.mp_type == MPK_MP_PRODMP ? c.nb + 3 : c.KT;
+    if (need > slots || c.Kloc > slots || c.D < 1 || !c.tab) {
+        set_error(std::string(fn) + ": at most " + std::to_string(kMaxD) + " DoF and " + std::to_string(kMaxKP) +
+                  " table columns (this handle: " + std::to_string(c.D) + " DoF, " + std::to_string(need) +
+                  " columns); the per-episode rows are those of the wave kernel k_traj_phase");
         return MPK_ENOTIMPL;
     }
     return MPK_OK;

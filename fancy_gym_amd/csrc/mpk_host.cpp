@@ -1234,6 +1234,7 @@ int mpk_fit_status(mpk_handle hh, int32_t* not_positive_definite, void* stream) 
 
 // ---- the probabilistic entry points: a Gaussian N(params, L L^T) over the non-phase parameters.  Every refusal exists once, below, and
 // carries the name of the entry that calls it; an entry is its own NULL checks, these in its order, the tables, the request, the launch
+static int demonstration_tables(Handle* h, bool phase, double init_time_shared, void* stream, SharedTables* st);
 static int refuse(int code, const std::string& msg) {
     set_error(msg);
     return code;
@@ -1322,12 +1323,30 @@ int mpk_trajectory_std(mpk_handle hh, const float* params_L, double init_time_sh
     return launch_traj_std(h->dev, st, params_L, pos_std, vel_std, B, h->num_cu, stream, &h->last_kernel);
 }
 
-// what the point-observation entries refuse between their NULL checks and their limits
-static int point_checks(const std::string& name, const Handle* h, const char* kernel, const GaussIn& in, const PointObs& obs) {
+// the trajectory's standard deviation at a per-episode tau / delay (the front of every params row): no table, one launch
+int mpk_trajectory_phase_std(mpk_handle hh, const float* params, const float* params_L, double init_time_shared, float* pos_std,
+                             float* vel_std, int32_t B, void* stream) {
+    const std::string name("mpk_trajectory_phase_std");
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!params || !params_L) return refuse(MPK_EINVAL, name + ": NULL params or params_L");
+    if (const int rc = batch_check(name, B)) return rc;
+    if (!pos_std && !vel_std) return refuse(MPK_EINVAL, name + ": pos_std and vel_std are both NULL: nothing to compute");
+    if (const int rc = episode_phase_check(name, h)) return rc;
+    if (const int rc = traj_phase_std_limits(h->dev, nullptr, nullptr, nullptr)) return rc;
+    if (const int rc = has_params_check(name, h)) return rc;
+    MPK_ON_DEVICE(h->cfg.device);
+    return launch_traj_phase_std(h->dev, params, params_L, (float)init_time_shared, pos_std, vel_std, h->d_flag, B, h->num_cu, stream,
+                                 &h->last_kernel);
+}
+
+// what the point-observation entries refuse between their NULL checks and their limits.  phase: the mpk_trajectory_phase_* entries, tau /
+// delay given at the front of every params row
+static int point_checks(const std::string& name, const Handle* h, bool phase, const char* kernel, const GaussIn& in, const PointObs& obs) {
     if (const int rc = batch_check(name, in.B)) return rc;
     if (const int rc = steps_check(name, h, obs.steps, obs.M)) return rc;
     if (const int rc = observed_check(name, obs.obs_pos, obs.obs_pos_std, obs.obs_vel, obs.obs_vel_std)) return rc;
-    return shared_phase_check(name, h, kernel);
+    return phase ? episode_phase_check(name, h) : shared_phase_check(name, h, kernel);
 }
 
 // ... and behind their limits, before the tables
@@ -1339,48 +1358,66 @@ static int point_handle_checks(const std::string& name, const Handle* h, const G
 
 // the Gaussian conditioned on observed trajectory points: every refusal before any launch, the tables as mpk_trajectory_std builds or
 // reuses them, one launch; obs_steps is copied into the launch arguments
+static int trajectory_condition_entry(const std::string& name, bool phase, mpk_handle hh, const GaussIn& in, double init_time_shared,
+                                      const PointObs& obs, const PosteriorOut& out, void* stream) {
+    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
+    Handle* h = reinterpret_cast<Handle*>(hh);
+    if (!in.params || !in.params_L || !out.params_out || !out.params_L_out)
+        return refuse(MPK_EINVAL, name + ": NULL params, params_L, params_out or params_L_out");
+    const CondLaunch q{in, obs, out, phase, phase ? h->d_flag : nullptr};
+    if (const int rc = point_checks(name, h, phase, "a conditioning kernel", q.in, q.obs)) return rc;
+    if (const int rc = phase ? traj_cond_phase_limits(h->dev, obs.M, nullptr, nullptr, nullptr)
+                             : traj_cond_limits(h->dev, obs.M, nullptr, nullptr, nullptr)) return rc;
+    if (const int rc = point_handle_checks(name, h, q.in, q.obs)) return rc;
+    MPK_ON_DEVICE(h->cfg.device);
+    SharedTables st;
+    if (const int rc = demonstration_tables(h, phase, init_time_shared, stream, &st)) return rc;
+    return launch_traj_condition(h->dev, st, q, h->num_cu, stream, &h->last_kernel);
+}
+
 int mpk_trajectory_condition(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
                              double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
                              const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, float* params_out,
                              float* params_L_out, int32_t B, void* stream) {
-    const std::string name("mpk_trajectory_condition");
-    if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
-    Handle* h = reinterpret_cast<Handle*>(hh);
-    if (!params || !params_L || !params_out || !params_L_out)
-        return refuse(MPK_EINVAL, name + ": NULL params, params_L, params_out or params_L_out");
-    const CondLaunch q{{params, params_L, init_pos, init_vel, (float)init_time_shared, B},
-                       {obs_steps, M, obs_pos, obs_pos_std, obs_vel, obs_vel_std}, {params_out, params_L_out}};
-    if (const int rc = point_checks(name, h, "a conditioning kernel", q.in, q.obs)) return rc;
-    if (const int rc = traj_cond_limits(h->dev, M, nullptr, nullptr, nullptr)) return rc;
-    if (const int rc = point_handle_checks(name, h, q.in, q.obs)) return rc;
-    MPK_ON_DEVICE(h->cfg.device);
-    SharedTables st;
-    if (const int rc = get_shared(h, (float)init_time_shared, stream, &st)) return rc;
-    return launch_traj_condition(h->dev, st, q, h->num_cu, stream, &h->last_kernel);
+    return trajectory_condition_entry("mpk_trajectory_condition", false, hh, {params, params_L, init_pos, init_vel, (float)init_time_shared, B},
+                                      init_time_shared, {obs_steps, M, obs_pos, obs_pos_std, obs_vel, obs_vel_std},
+                                      {params_out, params_L_out}, stream);
+}
+
+int mpk_trajectory_phase_condition(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                                   double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
+                                   const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, float* params_out,
+                                   float* params_L_out, int32_t B, void* stream) {
+    return trajectory_condition_entry("mpk_trajectory_phase_condition", true, hh,
+                                      {params, params_L, init_pos, init_vel, (float)init_time_shared, B}, init_time_shared,
+                                      {obs_steps, M, obs_pos, obs_pos_std, obs_vel, obs_vel_std}, {params_out, params_L_out}, stream);
 }
 
 // the log-likelihood of conditioning's observations and its gradient (out.grad: the _vjp entry): the refusals of
 // mpk_trajectory_condition plus the observation count, every one before any launch; the tables as above; one launch
-static int trajectory_log_prob_entry(const std::string& name, mpk_handle hh, const GaussIn& in, double init_time_shared,
+static int trajectory_log_prob_entry(const std::string& name, bool phase, mpk_handle hh, const GaussIn& in, double init_time_shared,
                                      const PointObs& obs, const LikelihoodOut& out, void* stream) {
     if (!hh) { set_error("NULL handle"); return MPK_EINVAL; }
     Handle* h = reinterpret_cast<Handle*>(hh);
     if (!in.params || !in.params_L) return refuse(MPK_EINVAL, name + ": NULL params or params_L");
     if (const int rc = likelihood_out_check(name, out)) return rc;
-    if (const int rc = point_checks(name, h, "a likelihood kernel", in, obs)) return rc;
-    if (const int rc = traj_log_prob_limits(h->dev, obs.M, (obs.obs_pos ? 1 : 0) + (obs.obs_vel ? 1 : 0), nullptr, nullptr, nullptr)) return rc;
+    if (const int rc = point_checks(name, h, phase, "a likelihood kernel", in, obs)) return rc;
+    const int narr = (obs.obs_pos ? 1 : 0) + (obs.obs_vel ? 1 : 0);
+    if (const int rc = phase ? traj_log_prob_phase_limits(h->dev, obs.M, narr, name.c_str(), nullptr, nullptr, nullptr)
+                             : traj_log_prob_limits(h->dev, obs.M, narr, nullptr, nullptr, nullptr)) return rc;
     if (const int rc = point_handle_checks(name, h, in, obs)) return rc;
     MPK_ON_DEVICE(h->cfg.device);
     SharedTables st;
-    if (const int rc = get_shared(h, (float)init_time_shared, stream, &st)) return rc;
-    return launch_traj_log_prob(h->dev, st, LogProbLaunch{in, obs, out}, h->num_cu, stream, &h->last_kernel);
+    if (const int rc = demonstration_tables(h, phase, init_time_shared, stream, &st)) return rc;
+    return launch_traj_log_prob(h->dev, st, LogProbLaunch{in, obs, out, phase, phase ? h->d_flag : nullptr}, h->num_cu, stream,
+                                &h->last_kernel);
 }
 
 int mpk_trajectory_log_prob(mpk_handle hh, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
                             double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
                             const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, double* log_prob, int32_t B,
                             void* stream) {
-    return trajectory_log_prob_entry("mpk_trajectory_log_prob", hh, {params, params_L, init_pos, init_vel, (float)init_time_shared, B},
+    return trajectory_log_prob_entry("mpk_trajectory_log_prob", false, hh, {params, params_L, init_pos, init_vel, (float)init_time_shared, B},
                                      init_time_shared, {obs_steps, M, obs_pos, obs_pos_std, obs_vel, obs_vel_std},
                                      {false, log_prob, nullptr, nullptr, nullptr}, stream);
 }
@@ -1389,9 +1426,29 @@ int mpk_trajectory_log_prob_vjp(mpk_handle hh, const float* params, const float*
                                 double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
                                 const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, const double* g, float* g_params,
                                 float* g_params_L, int32_t B, void* stream) {
-    return trajectory_log_prob_entry("mpk_trajectory_log_prob_vjp", hh, {params, params_L, init_pos, init_vel, (float)init_time_shared, B},
+    return trajectory_log_prob_entry("mpk_trajectory_log_prob_vjp", false, hh, {params, params_L, init_pos, init_vel, (float)init_time_shared, B},
                                      init_time_shared, {obs_steps, M, obs_pos, obs_pos_std, obs_vel, obs_vel_std},
                                      {true, nullptr, g, g_params, g_params_L}, stream);
+}
+
+int mpk_trajectory_phase_log_prob(mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
+                                  const float* init_vel, double init_time_shared, const int32_t* obs_steps, int32_t M,
+                                  const float* obs_pos, const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std,
+                                  double* log_prob, int32_t B, void* stream) {
+    return trajectory_log_prob_entry("mpk_trajectory_phase_log_prob", true, hh,
+                                     {params, params_L, init_pos, init_vel, (float)init_time_shared, B}, init_time_shared,
+                                     {obs_steps, M, obs_pos, obs_pos_std, obs_vel, obs_vel_std}, {false, log_prob, nullptr, nullptr, nullptr},
+                                     stream);
+}
+
+int mpk_trajectory_phase_log_prob_vjp(mpk_handle hh, const float* params, const float* params_L, const float* init_pos,
+                                      const float* init_vel, double init_time_shared, const int32_t* obs_steps, int32_t M,
+                                      const float* obs_pos, const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std,
+                                      const double* g, float* g_params, float* g_params_L, int32_t B, void* stream) {
+    return trajectory_log_prob_entry("mpk_trajectory_phase_log_prob_vjp", true, hh,
+                                     {params, params_L, init_pos, init_vel, (float)init_time_shared, B}, init_time_shared,
+                                     {obs_steps, M, obs_pos, obs_pos_std, obs_vel, obs_vel_std}, {true, nullptr, g, g_params, g_params_L},
+                                     stream);
 }
 
 // ---- whole demonstrations, in the information form.  phase: the mpk_demonstration_phase_* entries, tau / delay given at the front of

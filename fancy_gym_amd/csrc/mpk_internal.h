@@ -342,12 +342,20 @@ struct PosteriorOut {                                                   // may b
 // sequential square-root measurement update of the factor in float64, one launch of k_traj_condition, one wave per episode.
 // traj_cond_limits: MPK_OK, or MPK_ENOTIMPL with the reason in the message -- a DMP, more than kMaxD DoF or kMaxKP columns, a Pl whose
 // float64 triangle and work vectors exceed the LDS with one wave per workgroup (no HIP call; the outputs may be nullptr).
+// mpk_trajectory_phase_* : the point-observation kernels with a PER-EPISODE row source (phase = true) for handles that learn tau /
+// delay: every wave evaluates its own episode's rows at the tau / delay in front of its params row (mpk_phase_rows.h, float64; the
+// velocity row included) into an image of its own, [2][M][Kloc + 3] float64 more per wave; no shared table is read (st is ignored).
+// traj_cond_phase_limits / traj_log_prob_phase_limits: the shared route's refusals in the same words, under the _phase_ entry's name,
+// plus rows beyond the 16 slots.  range_flag: raised by a ProDMP timing beyond the pre-computed range.
 struct CondLaunch {
     GaussIn in;
     PointObs obs;
     PosteriorOut out;
+    bool phase = false;
+    int32_t* range_flag = nullptr;
 };
 int traj_cond_limits(const DevCfg& c, int M, size_t* lds_out, int* waves_out, int* wave_doubles_out);
+int traj_cond_phase_limits(const DevCfg& c, int M, size_t* lds_out, int* waves_out, int* wave_doubles_out);
 int launch_traj_condition(const DevCfg& c, const SharedTables& st, const CondLaunch& q, int num_cu, void* stream, const char** kernel_name);
 // mpk_trajectory_log_prob / _vjp (mpk_traj_log_prob.hip): the log-likelihood of conditioning's scalar observations under N(params, L L^T)
 // by a dense float64 Cholesky factorisation of their n x n covariance, and its gradient w.r.t. params and params_L -- one launch of
@@ -359,8 +367,17 @@ struct LogProbLaunch {
     GaussIn in;
     PointObs obs;
     LikelihoodOut out;
+    bool phase = false;
+    int32_t* range_flag = nullptr;
 };
 int traj_log_prob_limits(const DevCfg& c, int M, int narr, size_t* lds_out, int* waves_out, int* wave_doubles_out);
+int traj_log_prob_phase_limits(const DevCfg& c, int M, int narr, const char* fn, size_t* lds_out, int* waves_out, int* wave_doubles_out);
+// mpk_trajectory_phase_std (mpk_traj_phase_std.hip): the trajectory's standard deviation at a per-episode tau / delay, one launch of
+// k_traj_phase_std, one wave per episode, the factor form on float64 rows.  traj_phase_std_limits: MPK_OK, or MPK_ENOTIMPL with the
+// reason in the message -- a DMP, more than kMaxD DoF or kMaxKP columns, rows beyond the 16 slots, a factor one wave's LDS cannot hold.
+int traj_phase_std_limits(const DevCfg& c, size_t* lds_out, int* waves_out, int* wave_floats_out);
+int launch_traj_phase_std(const DevCfg& c, const float* params, const float* params_L, float init_time, float* pos_std, float* vel_std,
+                          int32_t* range_flag, int B, int num_cu, void* stream, const char** kernel_name);
 int launch_traj_log_prob(const DevCfg& c, const SharedTables& st, const LogProbLaunch& q, int num_cu, void* stream,
                          const char** kernel_name);
 // mpk_demonstration_log_prob / _vjp (mpk_demo_log_prob.hip): the log-likelihood of whole demonstrations under N(params, L L^T) in the

@@ -16,6 +16,7 @@
 //                        (and the way back, LDS image -> HBM: mpk_traj_std.hip)
 //   mpk_traj_fit.hip     k_traj_fit_tile: the least-squares fit of the shared-phase map to demonstrations (mpk_trajectory_fit)
 //   mpk_traj_std.hip     k_traj_std_tile: the trajectory's standard deviation from the factor of a weight covariance (mpk_trajectory_std)
+//   mpk_traj_phase_std.hip   k_traj_phase_std: the same at a per-episode tau / delay, on float64 rows (mpk_trajectory_phase_std)
 //   mpk_traj_condition.hip   k_traj_condition: a Gaussian over the parameters conditioned on observed points (mpk_trajectory_condition)
 //   mpk_traj_log_prob.hip    k_traj_log_prob: the log-likelihood of observed points under that Gaussian and its gradient (mpk_trajectory_log_prob)
 //   mpk_demo_log_prob.hip    k_demo_log_prob: the log-likelihood of whole demonstrations in the Pl x Pl form and its gradient (mpk_demonstration_log_prob)
@@ -47,6 +48,7 @@
 #include "mpk_traj_vjp.hip"
 #include "mpk_traj_fit.hip"
 #include "mpk_traj_std.hip"
+#include "mpk_traj_phase_std.hip"
 #include "mpk_traj_condition.hip"
 #include "mpk_traj_log_prob.hip"
 #include "mpk_demo_log_prob.hip"

@@ -131,4 +131,81 @@ __device__ __forceinline__ void phase_rows_eval(const DevCfg& c, const PhaseEpis
     }
 }
 
+// a ProMP's normalised RBF row at phase x in float64 (weights_scale folded in; exact 0 beyond nb): rbf_row's direct-exponential
+// arithmetic without its rounding to float32 -- for rows that are DIFFERENCED (cond_promp_vel_row says why)
+__device__ __forceinline__ void phase_rows_rbf64(const DevCfg& c, const double* cen, const double* bw, double x,
+                                                 double (&e)[kPhaseRowSlots]) {
+    double sum = 0.0;
+    for (int i = 0; i < c.n_total; ++i) {
+        const double dx = x - cen[i];
+        sum += exp_nonpos(-(dx * dx * bw[i]) * 0.5);
+    }
+    const double scale = c.n_total > 1 ? div_pos((double)c.ws, sum) : (double)c.ws;
+#pragma unroll
+    for (int k = 0; k < kPhaseRowSlots; ++k) {
+        e[k] = 0.0;
+        if (k < c.nb) {
+            const double dx = x - cen[c.zs + k];
+            e[k] = exp_nonpos(-(dx * dx * bw[c.zs + k]) * 0.5) * scale;
+        }
+    }
+}
+
+// the VELOCITY row of step t (sBT: the base times phase_rows_stage staged), regrouped as phase_rows_eval regroups the position row:
+// ev[k] the entry of local parameter k, and the given part cv[t, d] = cva init_pos[d] + cvb init_vel[d] + cvc -- the row of the
+// velocity the forward returns for this episode at this step.
+//   promp   the forward difference of the position rows of steps (t, t + 1) -- (T - 2, T - 1) at the last step, which repeats the
+//           difference before it -- times the forward's float32 reciprocal time step.  Two FLOAT64 rows are differenced
+//           (phase_rows_rbf64): the difference of two float32-rounded rows carries their rounding amplified by |row| / |difference|
+//           (profiles/r20_traj_condition.md).  A zero-padded basis' init_pos is constant over the steps: cva = 0.
+//   prodmp  phase_rows_eval's regrouping on the derivative tables: dPsi_k (vel_basis) for Psi_k and (dy1, dy2) for (y1, y2) at the
+//           step, the boundary row and the column scales as they are, everything times the forward's float32 1 / tau.
+template <int MP>
+__device__ __forceinline__ void phase_rows_eval_vel(const DevCfg& c, const PhaseEpisode& ep, const float* consts, const float* sBT, int t,
+                                                    int32_t* flag, double (&ev)[kPhaseRowSlots], double& cva, double& cvb, double& cvc) {
+    constexpr int KS = kPhaseRowSlots;
+    cva = 0.0; cvb = 0.0; cvc = 0.0;
+    if (MP == MPK_MP_PRODMP) {
+        const double* sc = reinterpret_cast<const double*>(consts);
+        const size_t n_pc = (size_t)c.n_pc, K = (size_t)c.nb + 1;
+        const float time = sBT[t] + ep.it;
+        const float s = fmaxf(div_exact(time - ep.delay, ep.dtau), 0.0f);
+        if (s > (float)c.len_factor) atomicOr(flag, 1);
+        const size_t idx = (size_t)max(min((int)rintf(div_exact(s, ep.dsdt)), c.n_pc - 1), 0);
+        const double* row = c.tab + 4 * n_pc + n_pc * K + idx * K;          // dPsi_k at the step
+        const double dy1 = c.tab[2 * n_pc + idx], dy2 = c.tab[3 * n_pc + idx];
+        const double xi3 = fma(ep.bca, dy1, -(ep.bcb * dy2)), xi4 = fma(ep.bcc, dy2, -(ep.bcd * dy1));
+        const double itau = (double)ep.dtau.r;
+        const int nw = c.disable_weights ? 0 : c.nb;
+        double eg = 0.0, egs = 0.0;
+#pragma unroll
+        for (int k = 0; k < KS; ++k) {
+            ev[k] = 0.0;
+            if (k <= c.nb) {
+                const double raw = (row[k] - xi3 * ep.pb[k] - xi4 * ep.vb[k]) * itau;
+                const double scaled = raw * sc[k];
+                if (k == c.nb) { eg = raw; egs = scaled; }
+                else if (k < nw) ev[k] = scaled;
+            }
+        }
+        if (!c.disable_goal) {
+#pragma unroll
+            for (int k = 0; k < KS; ++k)
+                if (k == nw) ev[k] = egs;
+        }
+        cva = xi3 * itau + (c.relative_goal ? (c.relgoal_before_scale ? eg * sc[KS] : eg) : 0.0);
+        cvb = xi4 * (double)ep.tau * itau;
+        cvc = c.goal_off_on ? eg * (double)c.goal_offset : 0.0;
+    } else {
+        const double* sCen = reinterpret_cast<const double*>(consts);
+        const int th = t < c.T - 1 ? t + 1 : c.T - 1, tl = t < c.T - 1 ? t : c.T - 2;
+        const float rdt = 1.0f / ((sBT[th] + ep.it) - (sBT[tl] + ep.it));
+        double lo[KS];
+        phase_rows_rbf64(c, sCen, sCen + c.n_total, phase_f64(c, sBT[th] + ep.it, ep.taud, ep.delay, ExpLiteral()), ev);
+        phase_rows_rbf64(c, sCen, sCen + c.n_total, phase_f64(c, sBT[tl] + ep.it, ep.taud, ep.delay, ExpLiteral()), lo);
+#pragma unroll
+        for (int k = 0; k < KS; ++k) ev[k] = (ev[k] - lo[k]) * (double)rdt;
+    }
+}
+
 }  // namespace mpk

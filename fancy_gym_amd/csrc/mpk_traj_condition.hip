@@ -2,6 +2,7 @@
 #include "mpk_tile.h"
 #include "mpk_vjp_row.h"
 #include "mpk_cond_rows.h"
+#include "mpk_phase_rows.h"
 #include "mpk_gauss_launch.h"
 
 namespace mpk {
@@ -43,6 +44,12 @@ namespace mpk {
 // No atomics, an episode never leaves its wave, and nothing depends on an address: the same bits from run to run, for any alignment of
 // the pointers, alone or in a batch.  A skipped observation touches nothing: float32 -> float64 -> float32 is the identity.
 // LDS: waves x 8 (Pl (Pl + 1) / 2 + 4 Pl) bytes + 16 M KT; traj_cond_limits refuses a Pl that one wave cannot hold (Pl = 160: 108 KB).
+// k_traj_condition<MP, NS, PHASE = true> (mpk_trajectory_phase_condition; last_kernel "k_traj_condition<.., phase>"): the same text with a
+// PER-EPISODE row source, for handles that learn tau / delay -- the tau / delay of episode b stand at the front of its params row
+// (phase_rows_episode reads and clips them as the forward does).  No workgroup-wide row image: before the sweep every wave evaluates its
+// own episode's [2][M] rows, lane <-> (array, step), with mpk_phase_rows.h in float64 into an image of its own, [2][M][Kloc + 3]: the
+// entries regrouped by local parameter, then ca | cb | cc of the given part c = ca init_pos + cb init_vel + cc.  The workgroup shares
+// the row constants and the base times.  The phase columns leave as they came, unclipped.  LDS: 16 M (Kloc + 3) more per wave.
 // ------------------------------------------------------------------------------------------------------------
 constexpr int kCondMaxObs = MPK_COND_MAX_STEPS;                     // observed steps per call (mpk.h)
 constexpr int kCondSlots = 4;                                       // rows per lane at most (NS = ceil(Pl / 64)): Pl <= 256 whatever the LDS allows
@@ -76,9 +83,16 @@ __device__ __forceinline__ void cond_unpack(int p, int* i_out, int* j_out) {
     *i_out = i; *j_out = p - i * (i + 1) / 2;
 }
 
-// NS: rows per lane, ceil(Pl / 64)
-template <int MP, int NS>
-__global__ void __launch_bounds__(256) k_traj_condition(const CondArgs a) {
+// the per-episode row source's arguments behind the shared ones (A, aux, TS are not read)
+struct CondPhaseArgs : CondArgs {
+    int sl;                // words between the rows of a wave's row image: Kloc + 3
+    int c_pad;             // floats of the workgroup's row constants (phase_rows_const_floats)
+    int32_t* flag;         // prodmp: raised beyond the pre-computed range (k_phase_fit's)
+};
+
+// NS: rows per lane, ceil(Pl / 64); PHASE: the per-episode row source ("k_traj_condition<.., phase>")
+template <int MP, int NS, bool PHASE = false>
+__global__ void __launch_bounds__(256) k_traj_condition(const std::conditional_t<PHASE, CondPhaseArgs, CondArgs> a) {
     extern __shared__ __attribute__((aligned(16))) double cond_smem[];
     const DevCfg& c = a.c;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -91,7 +105,20 @@ __global__ void __launch_bounds__(256) k_traj_condition(const CondArgs a) {
     double* sa = sv + Pl;                                           // [Pl] sqrt(b_{j+1} / b_j)
     double* sb = sa + Pl;                                           // [Pl] v_j / sqrt(b_{j+1} b_j)
     double* rows = cond_smem + (size_t)a.waves * a.wave_doubles;    // [2][M][KT]
-    for (int i = tid; i < 2 * M * KT; i += blockDim.x) {
+    double* prow = sb + Pl;                                         // PHASE: [2][M][sl] this episode's rows
+    float* sK = (float*)rows;                                       // PHASE: the row constants, then the base times [T]
+    int sl = 0;
+    const float* sBT = nullptr;
+    bool use_ip = false, use_iv = false;
+    if constexpr (PHASE) {
+        sl = a.sl;
+        sBT = sK + a.c_pad;
+        phase_rows_stage<MP>(c, sK, sK + a.c_pad, tid, blockDim.x);
+        // which of the given columns exist: a ProDMP's init_pos / init_vel, a zero-padded ProMP's init_pos
+        use_ip = a.init_pos && (MP == MPK_MP_PRODMP || KT > c.nb);
+        use_iv = a.init_vel && MP == MPK_MP_PRODMP;
+    }
+    for (int i = tid; !PHASE && i < 2 * M * KT; i += blockDim.x) {
         const int o = i / (M * KT), r = i - o * M * KT;
         const int m = r / KT, k = r - m * KT;
         double x = 0.0;
@@ -115,6 +142,20 @@ __global__ void __launch_bounds__(256) k_traj_condition(const CondArgs a) {
             tri[p] = (double)Lb[(size_t)i * Pl + j];
         }
         for (int i = lane; i < Pl; i += 64) smu[i] = (double)a.params[(size_t)b * c.P + c.off + i];
+        if constexpr (PHASE) {                                      // lane <-> (array, step): this episode's rows
+            const PhaseEpisode ep = phase_rows_episode<MP>(c, a.params + (size_t)b * c.P, a.init_time);
+            const int o = lane >= M ? 1 : 0, m = lane - o * M;
+            if (lane < 2 * M && a.obs[o]) {
+                double e[kPhaseRowSlots], ca, cb, cg;
+                if (o) phase_rows_eval_vel<MP>(c, ep, sK, sBT, a.steps[m], a.flag, e, ca, cb, cg);
+                else phase_rows_eval<MP>(c, ep, sK, sBT[a.steps[m]], a.flag, e, ca, cb, cg);
+                double* er = prow + (o * M + m) * sl;
+#pragma unroll
+                for (int k = 0; k < kPhaseRowSlots; ++k)
+                    if (k < Kloc) er[k] = e[k];
+                er[Kloc] = ca; er[Kloc + 1] = cb; er[Kloc + 2] = cg;
+            }
+        }
         cond_wave_sync();
         for (int m = 0; m < M; ++m) {
             for (int od = 0; od < 2 * D; ++od) {
@@ -123,14 +164,30 @@ __global__ void __launch_bounds__(256) k_traj_condition(const CondArgs a) {
                 const size_t at = ((size_t)b * M + m) * D + d;
                 const double sigma = (double)__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(a.sd[o][at])));
                 if (!(sigma >= 0.0) || sigma == __builtin_inf()) continue;    // +inf, NaN, negative: not observed (wave-uniform)
-                const double* hr = rows + (o * M + m) * KT;
+                const double* hr = PHASE ? prow + (o * M + m) * sl : rows + (o * M + m) * KT;
                 const int n = (d + 1) * Kloc;
                 // ---- c and h . mu (every lane, table order), v (lane <-> column)
                 double cc = 0.0, hmu = 0.0;
                 double vj[NS];
 #pragma unroll
                 for (int s = 0; s < NS; ++s) vj[s] = 0.0;
-                for (int k = 0; k < KT; ++k) {
+                if constexpr (PHASE) {
+                    for (int l = 0; l < Kloc; ++l) {
+                        const int row = d * Kloc + l;
+                        const double hk = hr[l];
+                        hmu = __builtin_fma(hk, smu[row], hmu);
+                        const double* lr = tri + row * (row + 1) / 2;
+#pragma unroll
+                        for (int s = 0; s < NS; ++s) {
+                            const int j = lane + 64 * s;
+                            if (j <= row) vj[s] = __builtin_fma(hk, lr[j], vj[s]);
+                        }
+                    }
+                    cc = hr[Kloc + 2];
+                    if (use_iv) cc = __builtin_fma(hr[Kloc + 1], (double)a.init_vel[(size_t)b * D + d], cc);
+                    if (use_ip) cc = __builtin_fma(hr[Kloc], (double)a.init_pos[(size_t)b * D + d], cc);
+                }
+                for (int k = 0; !PHASE && k < KT; ++k) {
                     int loc;
                     const int kind = x_kind<MP>(c, k, &loc);
                     const double hk = hr[k];
@@ -244,14 +301,19 @@ __global__ void __launch_bounds__(256) k_traj_condition(const CondArgs a) {
 }
 
 #ifndef MPK_DEVICE_ONLY
-// the shapes the kernel takes; MPK_ENOTIMPL with the limit in the message otherwise (no HIP call).  M: the observed steps of the call.
-int traj_cond_limits(const DevCfg& c, int M, size_t* lds_out, int* waves_out, int* wave_doubles_out) {
-    if (const int rc = gauss_common_limits(c, "mpk_trajectory_condition")) return rc;
+// the shapes the kernels take; MPK_ENOTIMPL with the limit in the message, under the entry's name fn, otherwise (no HIP call).  M: the
+// observed steps of the call.  phase: the per-episode row source -- [2][M][Kloc + 3] more per wave, and the row constants and base times
+// per workgroup where the shared route has [2][M][KT]; rows beyond mpk_phase_rows.h's 16 slots are refused
+static int cond_limits(const DevCfg& c, int M, bool phase, const char* fn, size_t* lds_out, int* waves_out, int* wave_doubles_out) {
+    if (const int rc = gauss_common_limits(c, fn)) return rc;
+    const std::string name(fn);
+    if (phase)
+        if (const int rc = gauss_phase_row_limits(c, kPhaseRowSlots, fn)) return rc;
     const size_t Pl = (size_t)c.D * c.Kloc;
-    const size_t wave_doubles = Pl * (Pl + 1) / 2 + 4 * Pl;
-    const size_t shared = (size_t)2 * M * c.KT * sizeof(double);
+    const size_t wave_doubles = Pl * (Pl + 1) / 2 + 4 * Pl + (phase ? (size_t)2 * M * (c.Kloc + 3) : 0);
+    const size_t shared = phase ? ((size_t)phase_rows_const_floats(c) + c.T + 1) / 2 * 2 * sizeof(float) : (size_t)2 * M * c.KT * sizeof(double);
     if (wave_doubles * sizeof(double) + shared > kLdsPerCu || Pl > 64 * kCondSlots) {
-        set_error("mpk_trajectory_condition: the float64 triangle and work vectors of " + std::to_string(Pl) + " parameters (" +
+        set_error(name + ": the float64 triangle and work vectors of " + std::to_string(Pl) + " parameters (" +
                   std::to_string(wave_doubles * sizeof(double) + shared) + " bytes with one wave per workgroup) do not fit the CU's " +
                   std::to_string(kLdsPerCu) + " bytes of LDS");
         return MPK_ENOTIMPL;
@@ -263,11 +325,22 @@ int traj_cond_limits(const DevCfg& c, int M, size_t* lds_out, int* waves_out, in
     return MPK_OK;
 }
 
+int traj_cond_limits(const DevCfg& c, int M, size_t* lds_out, int* waves_out, int* wave_doubles_out) {
+    return cond_limits(c, M, false, "mpk_trajectory_condition", lds_out, waves_out, wave_doubles_out);
+}
+
+int traj_cond_phase_limits(const DevCfg& c, int M, size_t* lds_out, int* waves_out, int* wave_doubles_out) {
+    return cond_limits(c, M, true, "mpk_trajectory_phase_condition", lds_out, waves_out, wave_doubles_out);
+}
+
 int launch_traj_condition(const DevCfg& c, const SharedTables& st, const CondLaunch& q, int num_cu, void* stream, const char** kernel_name) {
-    CondArgs ca{};
+    CondPhaseArgs ca{};
     size_t lds = 0;
     const int M = q.obs.M;
-    const int rc = traj_cond_limits(c, M, &lds, &ca.waves, &ca.wave_doubles);
+    const bool phase = q.phase;
+    const std::string name(phase ? "mpk_trajectory_phase_condition" : "mpk_trajectory_condition");
+    const int rc = phase ? traj_cond_phase_limits(c, M, &lds, &ca.waves, &ca.wave_doubles)
+                         : traj_cond_limits(c, M, &lds, &ca.waves, &ca.wave_doubles);
     if (rc != MPK_OK) return rc;
     const bool promp = c.mp_type == MPK_MP_PROMP;
     if (promp && q.obs.obs_vel && c.T < 2) {
@@ -275,7 +348,7 @@ int launch_traj_condition(const DevCfg& c, const SharedTables& st, const CondLau
         return MPK_EINVAL;
     }
     if (M < 1 || M > kCondMaxObs) {
-        set_error("mpk_trajectory_condition: internal: the number of observed steps is outside 1.." + std::to_string(kCondMaxObs));
+        set_error(name + ": internal: the number of observed steps is outside 1.." + std::to_string(kCondMaxObs));
         return MPK_EINVAL;
     }
     ca.c = c; ca.A = st.A; ca.aux = st.aux; ca.TS = st.TS; ca.init_time = q.in.init_time;
@@ -285,10 +358,20 @@ int launch_traj_condition(const DevCfg& c, const SharedTables& st, const CondLau
     ca.B = q.in.B; ca.Pl = c.D * c.Kloc; ca.M = M;
     for (int m = 0; m < M; ++m) ca.steps[m] = q.obs.steps[m];
     const int blocks = gauss_blocks(q.in.B, ca.waves, lds, num_cu);
+    if (phase) {
+        ca.sl = c.Kloc + 3; ca.c_pad = phase_rows_const_floats(c); ca.flag = q.range_flag;
+        *kernel_name = promp ? "k_traj_condition<promp, phase>" : "k_traj_condition<prodmp, phase>";
+        return dispatch_mp(promp, [&](auto mp) {
+            return dispatch_ns((ca.Pl + 63) / 64, [&](auto ns) {
+                return launch_kernel(k_traj_condition<mp.value, ns.value, true>, dim3(blocks), dim3(64 * ca.waves), lds, stream, ca);
+            });
+        });
+    }
     *kernel_name = promp ? "k_traj_condition<promp>" : "k_traj_condition<prodmp>";
     return dispatch_mp(promp, [&](auto mp) {
         return dispatch_ns((ca.Pl + 63) / 64, [&](auto ns) {
-            return launch_kernel(k_traj_condition<mp.value, ns.value>, dim3(blocks), dim3(64 * ca.waves), lds, stream, ca);
+            return launch_kernel(k_traj_condition<mp.value, ns.value>, dim3(blocks), dim3(64 * ca.waves), lds, stream,
+                                 static_cast<const CondArgs&>(ca));
         });
     });
 }

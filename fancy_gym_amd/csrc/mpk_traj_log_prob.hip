@@ -3,6 +3,7 @@
 #include "mpk_tile.h"
 #include "mpk_vjp_row.h"
 #include "mpk_cond_rows.h"
+#include "mpk_phase_rows.h"
 #include "mpk_gauss_launch.h"
 
 namespace mpk {
@@ -38,6 +39,11 @@ namespace mpk {
 // No atomics, an episode never leaves its wave, and nothing depends on an address: the same bits from run to run, for any alignment of
 // the pointers, alone or in a batch.  No index depends on a value that is read: non-finite inputs give non-finite outputs, never a fault.
 // LDS: waves x 8 (nmax ld + nmax (nmax + 1) / 2 + 3 nmax) + 16 M KT + 64 bytes, nmax = M D narr, ld = Pl | 1 (Pl = 160, n = 64: 101 KB).
+// k_traj_log_prob<MP, NS, GRAD, PHASE = true> (mpk_trajectory_phase_log_prob / _vjp; last_kernel "k_traj_log_prob<.., phase>"): the same text
+// with k_traj_condition's PER-EPISODE row source, for handles that learn tau / delay: every wave evaluates its own episode's [2][M]
+// rows at the tau / delay in front of its params row (mpk_phase_rows.h, float64) into an image of its own, [2][M][Kloc + 3], regrouped
+// by local parameter (kof is the identity) with ca | cb | cc of the given part behind.  The phase columns of g_params are exact zeros:
+// the timing is an input.  LDS: 16 M (Kloc + 3) more per wave; the row constants and base times per workgroup instead of [2][M][KT].
 // ------------------------------------------------------------------------------------------------------------
 constexpr int kLpMaxObs = MPK_LOGPROB_MAX_OBS;                      // scalar observations per episode: one lane each
 constexpr int kLpSlots = 4;                                         // columns per lane at most (NS = ceil(Pl / 64))
@@ -76,8 +82,17 @@ __device__ __forceinline__ double lp_wave_sum(double x) {
     return x;
 }
 
-template <int MP, int NS, bool GRAD>
-__global__ void __launch_bounds__(256) k_traj_log_prob(const LogProbArgs a) {
+// the per-episode row source's arguments behind the shared ones (A, aux, TS are not read)
+struct LogProbPhaseArgs : LogProbArgs {
+    int sl;                // words between the rows of a wave's row image: Kloc + 3
+    int c_pad;             // floats of the workgroup's row constants (phase_rows_const_floats)
+    int32_t* flag;         // prodmp: raised beyond the pre-computed range (k_phase_fit's)
+};
+static_assert(sizeof(LogProbPhaseArgs) <= 4096, "kernel arguments");
+
+// PHASE: the per-episode row source ("k_traj_log_prob<.., phase>")
+template <int MP, int NS, bool GRAD, bool PHASE = false>
+__global__ void __launch_bounds__(256) k_traj_log_prob(const std::conditional_t<PHASE, LogProbPhaseArgs, LogProbArgs> a) {
     extern __shared__ __attribute__((aligned(16))) double lp_smem[];
     const DevCfg& c = a.c;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -90,8 +105,21 @@ __global__ void __launch_bounds__(256) k_traj_log_prob(const LogProbArgs a) {
     int* cidx = (int*)(ssg + nmax);                                 // [nmax] candidate -> its index among the kept ones, or -1
     int* sdof = cidx + nmax;                                        // [nmax] kept -> its DoF
     double* rows = lp_smem + (size_t)a.waves * a.wave_doubles;      // [2][M][KT]
-    int* kof = (int*)(rows + 2 * M * KT);                           // [Kloc] the table column read from local parameter l, or -1
-    for (int i = tid; i < 2 * M * KT; i += blockDim.x) {
+    int* kof = (int*)(rows + (PHASE ? 0 : 2 * M * KT));             // [Kloc] the table column read from local parameter l, or -1
+    double* prow = ssg + 2 * nmax;                                  // PHASE: [2][M][sl] this episode's rows
+    float* sK = (float*)(rows + 8);                                 // PHASE: behind kof the row constants, then the base times [T]
+    int sl = 0;
+    const float* sBT = nullptr;
+    bool use_ip = false, use_iv = false;
+    if constexpr (PHASE) {
+        sl = a.sl;
+        sBT = sK + a.c_pad;
+        phase_rows_stage<MP>(c, sK, sK + a.c_pad, tid, blockDim.x);
+        // which of the given columns exist: a ProDMP's init_pos / init_vel, a zero-padded ProMP's init_pos
+        use_ip = a.init_pos && (MP == MPK_MP_PRODMP || KT > c.nb);
+        use_iv = a.init_vel && MP == MPK_MP_PRODMP;
+    }
+    for (int i = tid; !PHASE && i < 2 * M * KT; i += blockDim.x) {
         const int o = i / (M * KT), r = i - o * M * KT;
         const int m = r / KT, k = r - m * KT;
         rows[i] = a.obs[o] ? cond_obs_row<MP>(c, a.A, a.aux, a.TS, a.init_time, o, k, a.steps[m]) : 0.0;
@@ -102,13 +130,27 @@ __global__ void __launch_bounds__(256) k_traj_log_prob(const LogProbArgs a) {
             int loc;
             if (x_kind<MP>(c, k, &loc) == XK_PARAM && loc == tid) found = k;
         }
-        kof[tid] = found;
+        kof[tid] = PHASE ? tid : found;
     }
     __syncthreads();
     const int o_first = a.obs[0] ? 0 : 1;                           // the array candidate `array 0` belongs to
     const double nan = __builtin_nan("");
     for (int b = blockIdx.x * a.waves + wave; b < a.B; b += gridDim.x * a.waves) {
         const float* Lb = a.L + (size_t)b * Pl * Pl;
+        if constexpr (PHASE) {                                      // lane <-> (array, step): this episode's rows
+            const PhaseEpisode ep = phase_rows_episode<MP>(c, a.params + (size_t)b * c.P, a.init_time);
+            const int o = lane >= M ? 1 : 0, m = lane - o * M;
+            if (lane < 2 * M && a.obs[o]) {
+                double e[kPhaseRowSlots], ca, cb, cg;
+                if (o) phase_rows_eval_vel<MP>(c, ep, sK, sBT, a.steps[m], a.flag, e, ca, cb, cg);
+                else phase_rows_eval<MP>(c, ep, sK, sBT[a.steps[m]], a.flag, e, ca, cb, cg);
+                double* er = prow + (o * M + m) * sl;
+#pragma unroll
+                for (int k = 0; k < kPhaseRowSlots; ++k)
+                    if (k < Kloc) er[k] = e[k];
+                er[Kloc] = ca; er[Kloc + 1] = cb; er[Kloc + 2] = cg;
+            }
+        }
         // ---- which observations count (lane <-> candidate)
         bool keep = false;
         double sig = 0.0, yv = 0.0;
@@ -138,12 +180,28 @@ __global__ void __launch_bounds__(256) k_traj_log_prob(const LogProbArgs a) {
                     const int i = __builtin_amdgcn_readfirstlane(cidx[mo * D + d]);
                     if (i < 0) continue;
                     const int m = mo / narr, o = (mo - m * narr) ? 1 : o_first;
-                    const double* hr = rows + (o * M + m) * KT;
+                    const double* hr = PHASE ? prow + (o * M + m) * sl : rows + (o * M + m) * KT;
                     double cc = 0.0, hmu = 0.0;
                     double acc[NS];
 #pragma unroll
                     for (int s = 0; s < NS; ++s) acc[s] = 0.0;
-                    for (int k = 0; k < KT; ++k) {
+                    if constexpr (PHASE) {
+                        for (int l = 0; l < Kloc; ++l) {
+                            const int row = d * Kloc + l;
+                            const double hk = hr[l];
+                            hmu = __builtin_fma(hk, (double)a.params[(size_t)b * c.P + c.off + row], hmu);
+                            const float* lr = Lb + (size_t)row * Pl;
+#pragma unroll
+                            for (int s = 0; s < NS; ++s) {
+                                const int j = lane + 64 * s;
+                                if (j <= row) acc[s] = __builtin_fma(hk, (double)lr[j], acc[s]);
+                            }
+                        }
+                        cc = hr[Kloc + 2];
+                        if (use_iv) cc = __builtin_fma(hr[Kloc + 1], (double)a.init_vel[(size_t)b * D + d], cc);
+                        if (use_ip) cc = __builtin_fma(hr[Kloc], (double)a.init_pos[(size_t)b * D + d], cc);
+                    }
+                    for (int k = 0; !PHASE && k < KT; ++k) {
                         int loc;
                         const int kind = x_kind<MP>(c, k, &loc);
                         const double hk = hr[k];
@@ -288,7 +346,7 @@ __global__ void __launch_bounds__(256) k_traj_log_prob(const LogProbArgs a) {
                             const int i = __builtin_amdgcn_readfirstlane(cidx[mo * D + d]);
                             if (i < 0) continue;
                             const int m = mo / narr, o = (mo - m * narr) ? 1 : o_first;
-                            const double hk = rows[(o * M + m) * KT + k], al = sal[i];
+                            const double hk = PHASE ? prow[(o * M + m) * sl + k] : rows[(o * M + m) * KT + k], al = sal[i];
                             any = true;
 #pragma unroll
                             for (int s = 0; s < NS; ++s) {
@@ -321,7 +379,7 @@ __global__ void __launch_bounds__(256) k_traj_log_prob(const LogProbArgs a) {
                                 const int i = cidx[mo * D + d];
                                 if (i < 0) continue;
                                 const int m = mo / narr, o = (mo - m * narr) ? 1 : o_first;
-                                acc = __builtin_fma(rows[(o * M + m) * KT + k], sal[i], acc);
+                                acc = __builtin_fma(PHASE ? prow[(o * M + m) * sl + k] : rows[(o * M + m) * KT + k], sal[i], acc);
                                 any = true;
                             }
                         }
@@ -336,22 +394,28 @@ __global__ void __launch_bounds__(256) k_traj_log_prob(const LogProbArgs a) {
 }
 
 #ifndef MPK_DEVICE_ONLY
-// the shapes the kernel takes; MPK_ENOTIMPL with the limit in the message otherwise (no HIP call).  M: the observed steps of the call,
-// narr: the observation arrays given (1 or 2)
-int traj_log_prob_limits(const DevCfg& c, int M, int narr, size_t* lds_out, int* waves_out, int* wave_doubles_out) {
-    if (const int rc = gauss_common_limits(c, "mpk_trajectory_log_prob")) return rc;
+// the shapes the kernels take; MPK_ENOTIMPL with the limit in the message, under the entry's name fn, otherwise (no HIP call).  M: the
+// observed steps of the call, narr: the observation arrays given (1 or 2).  phase: the per-episode row source -- [2][M][Kloc + 3] more
+// per wave, the row constants and base times per workgroup where the shared route has [2][M][KT]; rows beyond the 16 slots are refused
+static int log_prob_limits(const DevCfg& c, int M, int narr, bool phase, const char* fn, size_t* lds_out, int* waves_out,
+                           int* wave_doubles_out) {
+    if (const int rc = gauss_common_limits(c, fn)) return rc;
+    const std::string name(fn);
+    if (phase)
+        if (const int rc = gauss_phase_row_limits(c, kPhaseRowSlots, fn)) return rc;
     const size_t nmax = (size_t)M * c.D * narr;
     if (nmax > (size_t)kLpMaxObs) {
-        set_error("mpk_trajectory_log_prob: at most " + std::to_string(kLpMaxObs) + " scalar observations per episode (M x D x the "
+        set_error(name + ": at most " + std::to_string(kLpMaxObs) + " scalar observations per episode (M x D x the "
                   "observation arrays given = " + std::to_string(M) + " x " + std::to_string(c.D) + " x " + std::to_string(narr) + " = " +
                   std::to_string(nmax) + "); the whole-trajectory likelihood wants the Pl x Pl form, which has no kernel here");
         return MPK_ENOTIMPL;
     }
     const size_t Pl = (size_t)c.D * c.Kloc;
-    const size_t wave_doubles = nmax * (Pl | 1) + nmax * (nmax + 1) / 2 + 3 * nmax;
-    const size_t shared = (size_t)2 * M * c.KT * sizeof(double) + 64;
+    const size_t wave_doubles = nmax * (Pl | 1) + nmax * (nmax + 1) / 2 + 3 * nmax + (phase ? (size_t)2 * M * (c.Kloc + 3) : 0);
+    const size_t shared = phase ? 64 + ((size_t)phase_rows_const_floats(c) + c.T + 1) / 2 * 2 * sizeof(float)
+                                : (size_t)2 * M * c.KT * sizeof(double) + 64;
     if (wave_doubles * sizeof(double) + shared > kLdsPerCu || Pl > 64 * kLpSlots) {
-        set_error("mpk_trajectory_log_prob: the float64 images of " + std::to_string(nmax) + " observations of " + std::to_string(Pl) +
+        set_error(name + ": the float64 images of " + std::to_string(nmax) + " observations of " + std::to_string(Pl) +
                   " parameters (" + std::to_string(wave_doubles * sizeof(double) + shared) + " bytes with one wave per workgroup) do not "
                   "fit the CU's " + std::to_string(kLdsPerCu) + " bytes of LDS");
         return MPK_ENOTIMPL;
@@ -363,17 +427,28 @@ int traj_log_prob_limits(const DevCfg& c, int M, int narr, size_t* lds_out, int*
     return MPK_OK;
 }
 
+int traj_log_prob_limits(const DevCfg& c, int M, int narr, size_t* lds_out, int* waves_out, int* wave_doubles_out) {
+    return log_prob_limits(c, M, narr, false, "mpk_trajectory_log_prob", lds_out, waves_out, wave_doubles_out);
+}
+
+int traj_log_prob_phase_limits(const DevCfg& c, int M, int narr, const char* fn, size_t* lds_out, int* waves_out, int* wave_doubles_out) {
+    return log_prob_limits(c, M, narr, true, fn, lds_out, waves_out, wave_doubles_out);
+}
+
 int launch_traj_log_prob(const DevCfg& c, const SharedTables& st, const LogProbLaunch& q, int num_cu, void* stream,
                          const char** kernel_name) {
-    LogProbArgs la{};
+    LogProbPhaseArgs la{};
     size_t lds = 0;
+    const bool phase = q.phase;
+    const char* fn = !phase ? "mpk_trajectory_log_prob" : (q.out.grad ? "mpk_trajectory_phase_log_prob_vjp" : "mpk_trajectory_phase_log_prob");
     const int M = q.obs.M, narr = (q.obs.obs_pos ? 1 : 0) + (q.obs.obs_vel ? 1 : 0);
     if (M < 1 || M > MPK_COND_MAX_STEPS || narr < 1) {
-        set_error("mpk_trajectory_log_prob: internal: the observed steps are outside 1.." + std::to_string(MPK_COND_MAX_STEPS) +
+        set_error(std::string(fn) + ": internal: the observed steps are outside 1.." + std::to_string(MPK_COND_MAX_STEPS) +
                   " or no observation array is given");
         return MPK_EINVAL;
     }
-    const int rc = traj_log_prob_limits(c, M, narr, &lds, &la.waves, &la.wave_doubles);
+    const int rc = phase ? traj_log_prob_phase_limits(c, M, narr, fn, &lds, &la.waves, &la.wave_doubles)
+                         : traj_log_prob_limits(c, M, narr, &lds, &la.waves, &la.wave_doubles);
     if (rc != MPK_OK) return rc;
     const bool promp = c.mp_type == MPK_MP_PROMP;
     if (promp && q.obs.obs_vel && c.T < 2) {
@@ -387,13 +462,27 @@ int launch_traj_log_prob(const DevCfg& c, const SharedTables& st, const LogProbL
     la.B = q.in.B; la.Pl = c.D * c.Kloc; la.M = M; la.narr = narr; la.nmax = M * c.D * narr; la.ld = la.Pl | 1;
     for (int m = 0; m < M; ++m) la.steps[m] = q.obs.steps[m];
     const int blocks = gauss_blocks(q.in.B, la.waves, lds, num_cu);
-    static const char* const names[2][2] = {{"k_traj_log_prob<prodmp>", "k_traj_log_prob<promp>"},
-                                            {"k_traj_log_prob<prodmp, grad>", "k_traj_log_prob<promp, grad>"}};
-    *kernel_name = names[q.out.grad][promp];
+    static const char* const names[2][2][2] = {
+        {{"k_traj_log_prob<prodmp>", "k_traj_log_prob<promp>"}, {"k_traj_log_prob<prodmp, grad>", "k_traj_log_prob<promp, grad>"}},
+        {{"k_traj_log_prob<prodmp, phase>", "k_traj_log_prob<promp, phase>"},
+         {"k_traj_log_prob<prodmp, phase, grad>", "k_traj_log_prob<promp, phase, grad>"}}};
+    *kernel_name = names[phase][q.out.grad][promp];
+    if (phase) {
+        la.sl = c.Kloc + 3; la.c_pad = phase_rows_const_floats(c); la.flag = q.range_flag;
+        return dispatch_flag(q.out.grad, [&](auto grad) {
+            return dispatch_mp(promp, [&](auto mp) {
+                return dispatch_ns((la.Pl + 63) / 64, [&](auto ns) {
+                    return launch_kernel(k_traj_log_prob<mp.value, ns.value, grad.value, true>, dim3(blocks), dim3(64 * la.waves), lds,
+                                         stream, la);
+                });
+            });
+        });
+    }
     return dispatch_flag(q.out.grad, [&](auto grad) {
         return dispatch_mp(promp, [&](auto mp) {
             return dispatch_ns((la.Pl + 63) / 64, [&](auto ns) {
-                return launch_kernel(k_traj_log_prob<mp.value, ns.value, grad.value>, dim3(blocks), dim3(64 * la.waves), lds, stream, la);
+                return launch_kernel(k_traj_log_prob<mp.value, ns.value, grad.value>, dim3(blocks), dim3(64 * la.waves), lds, stream,
+                                     static_cast<const LogProbArgs&>(la));
             });
         });
     });

@@ -126,21 +126,23 @@ class _TrajectoryPhaseFn(torch.autograd.Function):
 class _TrajectoryLogProbFn(torch.autograd.Function):
     """``TrajectoryEngine.trajectory_log_prob`` with a backward: forward = the mpk_trajectory_log_prob launch as without autograd,
     backward = one mpk_trajectory_log_prob_vjp launch, which recomputes the factorisation from the forward's inputs (nothing of the
-    forward launch is kept but those); the observations and the initial conditions get no gradient"""
+    forward launch is kept but those); the observations and the initial conditions get no gradient.  ``phase``: the per-episode-phase
+    route (``trajectory_log_prob_given_timing``: mpk_trajectory_phase_log_prob / _vjp), whose backward leaves exact zeros in the phase
+    columns"""
 
     @staticmethod
-    def forward(ctx, engine, steps, inputs, init_time, params, params_L):
-        ctx.engine, ctx.steps, ctx.inputs, ctx.init_time = engine, steps, inputs, init_time
+    def forward(ctx, engine, steps, inputs, init_time, params, params_L, phase=False):
+        ctx.engine, ctx.steps, ctx.inputs, ctx.init_time, ctx.phase = engine, steps, inputs, init_time, phase
         ctx.save_for_backward(params, params_L)
-        return engine._log_prob_launch(params, params_L, steps, inputs, init_time)
+        return engine._log_prob_launch(params, params_L, steps, inputs, init_time, phase)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         params, params_L = ctx.saved_tensors
         g_params, g_L = ctx.engine._log_prob_vjp_launch(g, params, params_L, ctx.steps, ctx.inputs, ctx.init_time,
-                                                        ctx.needs_input_grad[4:6])
-        return None, None, None, None, g_params, g_L
+                                                        ctx.needs_input_grad[4:6], ctx.phase)
+        return None, None, None, None, g_params, g_L, None
 
 
 class _DemonstrationLogProbFn(torch.autograd.Function):
@@ -783,8 +785,20 @@ class TrajectoryEngine:
             raise ValueError(f"trajectory_std: params_L must be [B, {Pl}, {Pl}] (the factor of the {Pl} non-phase parameters' covariance), "
                              f"got {shape}")
         B = shape[0]
+        res = self._std_out_check("trajectory_std", out, pos, vel, B)
+        with torch.no_grad():
+            L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
+            res = [torch.empty((B, T, D), dtype=torch.float32, device=self.device) if r is False else r for r in res]
+            _lib.check(self._lib.mpk_trajectory_std(self._h, L.data_ptr(), float(init_time), _dptr(res[0]), _dptr(res[1]), B,
+                                                    self._stream()))
+        return res[0], res[1]
+
+    def _std_out_check(self, fn, out, pos, vel, B):
+        """``out=(pos_std, vel_std)`` of the standard-deviation entry points: per array None (not wanted), the caller's buffer --
+        contiguous float32 [B, T, D] on the device -- or False (to be allocated)"""
+        D, T = self.num_dof, self.num_steps
         if out is not None and len(out) != 2:
-            raise ValueError("trajectory_std: out must be a pair (pos_std, vel_std) of tensors or None")
+            raise ValueError(f"{fn}: out must be a pair (pos_std, vel_std) of tensors or None")
         res = []
         for i, want in enumerate((pos, vel)):
             buf = out[i] if out is not None else None
@@ -792,15 +806,39 @@ class TrajectoryEngine:
                 res.append(None)
             elif buf is not None:
                 if tuple(buf.shape) != (B, T, D) or buf.dtype != torch.float32 or not buf.is_contiguous() or buf.device != self.device:
-                    raise ValueError(f"trajectory_std: out[{i}] must be a contiguous float32 tensor of shape {(B, T, D)} on {self.device}")
+                    raise ValueError(f"{fn}: out[{i}] must be a contiguous float32 tensor of shape {(B, T, D)} on {self.device}")
                 res.append(buf)
             else:
                 res.append(False)
+        return res
+
+    def trajectory_std_given_timing(self, params, params_L, init_time: float = 0.0, *, pos: bool = True, vel: bool = True,
+                                    out: Optional[Sequence[Optional[torch.Tensor]]] = None
+                                    ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """
+        ``trajectory_std`` with every episode's timing GIVEN (mpk.h: mpk_trajectory_phase_std), for a handle that learns tau and / or
+        delay, one launch: ``(pos_std, vel_std)`` [B, T, D] float32, None for a disabled one, each episode's band at its own tau /
+        delay.  Of ``params`` [B, P] only the phase columns at the front are read (where ``trajectory`` reads them, clipped as it
+        clips them); ``params_L`` [B, Pl, Pl] is the factor of the ``Pl = P - n_phase`` non-phase parameters' covariance.  The factor
+        form on the episode's own float64 rows, ``| row tril(L) |``: ``L L^T`` is never formed, ``L = 0`` gives exact zeros, a
+        rank-deficient covariance keeps its zeros, the strict upper triangle is never read.  ``init_time`` stays one float for the
+        batch.  A ProDMP timing beyond the pre-computed range makes ``check_range`` raise.  Every refusal is raised before any
+        launch: ValueError for a shared-phase handle (it has ``trajectory_std``), wrong shapes, a wrong ``out``, ``pos = vel =
+        False``; NotImplementedError for a DMP and more than 16 DoF or 16 table columns.  Not built: gradients w.r.t. tau / delay,
+        per-episode ``init_time`` tensors.
+        """
+        fn = "trajectory_std_given_timing"
+        if not pos and not vel:
+            raise ValueError(f"{fn}: pos and vel are both False: nothing to compute")
+        self._timing_given(fn, "given")
+        B = self._gaussian_checks(fn, "a standard-deviation kernel", params, params_L, self._num_phase_params())
+        res = self._std_out_check(fn, out, pos, vel, B)
         with torch.no_grad():
-            L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device).detach().contiguous()
-            res = [torch.empty((B, T, D), dtype=torch.float32, device=self.device) if r is False else r for r in res]
-            _lib.check(self._lib.mpk_trajectory_std(self._h, L.data_ptr(), float(init_time), _dptr(res[0]), _dptr(res[1]), B,
-                                                    self._stream()))
+            mean, L = self._mean_and_factor(params, params_L)
+            res = [torch.empty((B, self.num_steps, self.num_dof), dtype=torch.float32, device=self.device) if r is False else r
+                   for r in res]
+            _lib.check(self._lib.mpk_trajectory_phase_std(self._h, mean.data_ptr(), L.data_ptr(), float(init_time), _dptr(res[0]),
+                                                          _dptr(res[1]), B, self._stream()))
         return res[0], res[1]
 
     def condition(self, params, params_L, obs_steps, obs_pos=None, obs_std=None, init_pos=None, init_vel=None,
@@ -823,25 +861,56 @@ class TrajectoryEngine:
         observation at all, values without standard deviations, bad steps, ``init_pos=None`` on a ProDMP; NotImplementedError for a
         handle that learns tau / delay, a DMP, more than 16 DoF or 16 table columns, and a Pl whose float64 triangle exceeds a CU's LDS.
         """
-        B, steps = self._obs_checks("condition", "a conditioning kernel", params, params_L, obs_steps, obs_pos, obs_std, init_pos,
-                                    init_vel, obs_vel, obs_vel_std)
+        return self._condition("condition", None, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, init_time, obs_vel,
+                               obs_vel_std, out)
+
+    def condition_given_timing(self, params, params_L, obs_steps, obs_pos=None, obs_std=None, init_pos=None, init_vel=None,
+                               init_time: float = 0.0, *, obs_vel=None, obs_vel_std=None,
+                               out: Optional[Sequence[torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """
+        ``condition`` with every episode's timing GIVEN (mpk.h: mpk_trajectory_phase_condition), for a handle that learns tau and / or
+        delay, one launch: every episode is conditioned on the via-points at its own tau / delay, the values at the front of its
+        ``params`` row (read where ``trajectory`` reads them, clipped to the handle's bounds as it clips them) -- a prior learned from
+        demonstrations of different durations, conditioned at a new movement's speed.  The Gaussian is over the ``Pl = P - n_phase``
+        non-phase parameters: ``params_L`` and the returned factor are [B, Pl, Pl]; the phase columns of the posterior ``params`` are
+        the inputs' bits, unclipped.  Every convention is ``condition``'s: at most 32 shared, strictly increasing steps; the order
+        steps ascending, positions by DoF, then velocities by DoF; ``sigma = 0`` conditions exactly; ``+inf``, NaN or a negative one
+        skips the entry bit for bit; the factor form in float64, rounded once; exact zeros in the strict upper triangle, which is
+        never read on input; ``out=(params, params_L)`` gives the in-place form.  The rows are the episode's own, in float64: an
+        observed velocity is the velocity ``trajectory`` returns for that episode at that step.  ``init_time`` stays one float for the
+        batch.  A ProDMP timing beyond the pre-computed range makes ``check_range`` raise.  A shared-phase handle is a ValueError (it
+        has ``condition``); a ``params_L`` that is not [B, Pl, Pl] is a ValueError that names Pl; the other refusals are
+        ``condition``'s, all before any launch.  Not built: gradients w.r.t. tau / delay, per-episode ``init_time`` tensors, DMP,
+        correlated noise.
+        """
+        return self._condition("condition_given_timing", "given", params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel,
+                               init_time, obs_vel, obs_vel_std, out)
+
+    def _condition(self, fn, timing, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, init_time, obs_vel, obs_vel_std,
+                   out):
+        phase = self._timing_given(fn, timing)
+        n_phase = self._num_phase_params() if phase else 0
+        B, steps = self._obs_checks(fn, "a conditioning kernel", params, params_L, obs_steps, obs_pos, obs_std, init_pos,
+                                    init_vel, obs_vel, obs_vel_std, n_phase)
         P, M = self.num_params, int(steps.size)
-        self._out_pair_check("condition", out, B, P, P)
-        ip, iv, yp, sp, yv, sv = self._log_prob_inputs("condition", B, M, obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std)
+        self._out_pair_check(fn, out, B, P, P - n_phase)
+        ip, iv, yp, sp, yv, sv = self._log_prob_inputs(fn, B, M, obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std)
         with torch.no_grad():
             mean, L = self._mean_and_factor(params, params_L)
-            mean_out, L_out = out if out is not None else self._posterior_buffers(B, P, P)
-            _lib.check(self._lib.mpk_trajectory_condition(
+            mean_out, L_out = out if out is not None else self._posterior_buffers(B, P, P - n_phase)
+            entry = self._lib.mpk_trajectory_phase_condition if phase else self._lib.mpk_trajectory_condition
+            _lib.check(entry(
                 self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time),
                 steps.ctypes.data_as(C.POINTER(C.c_int32)), M, _dptr(yp), _dptr(sp), _dptr(yv), _dptr(sv), mean_out.data_ptr(),
                 L_out.data_ptr(), B, self._stream()))
         return mean_out, L_out
 
-    def _obs_checks(self, fn, kernel, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std):
+    def _obs_checks(self, fn, kernel, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std,
+                    n_phase=0):
         """the refusals ``condition`` and ``trajectory_log_prob`` / ``_vjp`` share, all before anything touches the device (what only
         the library can judge -- the steps' range and order -- is refused by the launch's own checks, still before any launch);
-        returns (B, steps int32 [M])"""
-        B = self._gaussian_checks(fn, kernel, params, params_L, 0)
+        ``n_phase``: of the ``_given_timing`` methods (``_gaussian_checks``); returns (B, steps int32 [M])"""
+        B = self._gaussian_checks(fn, kernel, params, params_L, n_phase)
         steps = np.asarray(list(obs_steps))
         if steps.ndim != 1 or (steps.size and not np.issubdtype(steps.dtype, np.integer)):
             raise ValueError(f"{fn}: obs_steps must be a sequence of ints, got {obs_steps!r}")
@@ -925,11 +994,11 @@ class TrajectoryEngine:
         g_L = torch.empty_like(L) if need[1] else None
         return None if g_mean is None and g_L is None else (g.contiguous(), g_mean, g_L)
 
-    def _log_prob_checks(self, fn, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std):
+    def _log_prob_checks(self, fn, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std, n_phase=0):
         """the refusals of ``trajectory_log_prob`` / ``trajectory_log_prob_vjp`` -- ``condition``'s, plus the steps (here, so that no
         refusal needs the handle), the observation count and the inputs that have no gradient; returns (B, steps int32 [M])"""
         B, steps = self._obs_checks(fn, "a likelihood kernel", params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, obs_vel,
-                                    obs_vel_std)
+                                    obs_vel_std, n_phase)
         D = self.num_dof
         if not 1 <= steps.size <= 32:
             raise ValueError(f"{fn}: M must be 1..32 observed steps, got {steps.size}")
@@ -968,21 +1037,23 @@ class TrajectoryEngine:
                     None if obs_vel is None else bcast(obs_vel, "obs_vel"),
                     None if obs_vel is None else bcast(obs_vel_std, "obs_vel_std"))
 
-    def _log_prob_launch(self, mean, L, steps, inputs, init_time):
+    def _log_prob_launch(self, mean, L, steps, inputs, init_time, phase=False):
         ip, iv, yp, sp, yv, sv = inputs
         out = torch.empty((mean.shape[0],), dtype=torch.float64, device=self.device)
-        _lib.check(self._lib.mpk_trajectory_log_prob(
+        entry = self._lib.mpk_trajectory_phase_log_prob if phase else self._lib.mpk_trajectory_log_prob
+        _lib.check(entry(
             self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time), steps.ctypes.data_as(C.POINTER(C.c_int32)),
             int(steps.size), _dptr(yp), _dptr(sp), _dptr(yv), _dptr(sv), out.data_ptr(), mean.shape[0], self._stream()))
         return out
 
-    def _log_prob_vjp_launch(self, g, mean, L, steps, inputs, init_time, need):
+    def _log_prob_vjp_launch(self, g, mean, L, steps, inputs, init_time, need, phase=False):
         ip, iv, yp, sp, yv, sv = inputs
-        outs = self._vjp_outputs("trajectory_log_prob_vjp", g, mean, L, need)
+        outs = self._vjp_outputs("trajectory_log_prob_vjp_given_timing" if phase else "trajectory_log_prob_vjp", g, mean, L, need)
         if outs is None:
             return None, None
         g, g_mean, g_L = outs
-        _lib.check(self._lib.mpk_trajectory_log_prob_vjp(
+        entry = self._lib.mpk_trajectory_phase_log_prob_vjp if phase else self._lib.mpk_trajectory_log_prob_vjp
+        _lib.check(entry(
             self._h, mean.data_ptr(), L.data_ptr(), _dptr(ip), _dptr(iv), float(init_time), steps.ctypes.data_as(C.POINTER(C.c_int32)),
             int(steps.size), _dptr(yp), _dptr(sp), _dptr(yv), _dptr(sv), g.data_ptr(), _dptr(g_mean), _dptr(g_L), mean.shape[0],
             self._stream()))
@@ -1004,15 +1075,37 @@ class TrajectoryEngine:
         a NotImplementedError, not a silent cut.  ``params_L``'s strict upper triangle is never read.  Refusals are ``condition``'s,
         raised before any launch, plus NotImplementedError for more than 64 observations.
         """
-        B, steps = self._log_prob_checks("trajectory_log_prob", params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel,
-                                         obs_vel, obs_vel_std)
-        inputs = self._log_prob_inputs("trajectory_log_prob", B, int(steps.size), obs_pos, obs_std, init_pos, init_vel, obs_vel,
-                                       obs_vel_std)
+        return self._trajectory_log_prob("trajectory_log_prob", None, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel,
+                                         init_time, obs_vel, obs_vel_std)
+
+    def trajectory_log_prob_given_timing(self, params, params_L, obs_steps, obs_pos=None, obs_std=None, init_pos=None, init_vel=None,
+                                         init_time: float = 0.0, *, obs_vel=None, obs_vel_std=None) -> torch.Tensor:
+        """
+        ``trajectory_log_prob`` with every episode's timing GIVEN (mpk.h: mpk_trajectory_phase_log_prob), for a handle that learns tau
+        and / or delay, one launch: [B] float64, the observed points of episode b scored at its own tau / delay, the values at the
+        front of its ``params`` row (clipped as ``trajectory`` clips them).  The Gaussian is over the ``Pl = P - n_phase`` non-phase
+        parameters, ``params[b, n_phase:]`` its mean and ``params_L`` [B, Pl, Pl] its factor.  Everything else is
+        ``trajectory_log_prob``'s: at most 64 scalar observations per episode, exactly 0.0 for none kept, NaN for a singular
+        covariance in that episode alone, autograd with ONE backward launch (mpk_trajectory_phase_log_prob_vjp), a tensor among the
+        observations or initial conditions that requires grad refused.  Timing is an input, not a random variable: the phase columns
+        of ``params.grad`` are exact zeros (no gradient w.r.t. tau / delay is built).  ``init_time`` stays one float for the batch.  A
+        shared-phase handle is a ValueError (it has ``trajectory_log_prob``); the other refusals are ``trajectory_log_prob``'s, all
+        before any launch.
+        """
+        return self._trajectory_log_prob("trajectory_log_prob_given_timing", "given", params, params_L, obs_steps, obs_pos, obs_std,
+                                         init_pos, init_vel, init_time, obs_vel, obs_vel_std)
+
+    def _trajectory_log_prob(self, fn, timing, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, init_time, obs_vel,
+                             obs_vel_std):
+        phase = self._timing_given(fn, timing)
+        B, steps = self._log_prob_checks(fn, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std,
+                                         self._num_phase_params() if phase else 0)
+        inputs = self._log_prob_inputs(fn, B, int(steps.size), obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std)
         mean = torch.as_tensor(params, dtype=torch.float32, device=self.device)
         L = torch.as_tensor(params_L, dtype=torch.float32, device=self.device)
         if torch.is_grad_enabled() and (mean.requires_grad or L.requires_grad):
-            return _TrajectoryLogProbFn.apply(self, steps, inputs, float(init_time), mean.contiguous(), L.contiguous())
-        return self._log_prob_launch(mean.detach().contiguous(), L.detach().contiguous(), steps, inputs, init_time)
+            return _TrajectoryLogProbFn.apply(self, steps, inputs, float(init_time), mean.contiguous(), L.contiguous(), phase)
+        return self._log_prob_launch(mean.detach().contiguous(), L.detach().contiguous(), steps, inputs, init_time, phase)
 
     def trajectory_log_prob_vjp(self, g, params, params_L, obs_steps, obs_pos=None, obs_std=None, init_pos=None, init_vel=None,
                                 init_time: float = 0.0, *, obs_vel=None, obs_vel_std=None,
@@ -1024,13 +1117,30 @@ class TrajectoryEngine:
         and so are the rows of a DoF none of whose observations remain; an episode whose covariance is singular gets NaN rows.
         ``need[i]`` False: that output is not computed (None in its place).
         """
-        B, steps = self._log_prob_checks("trajectory_log_prob_vjp", params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel,
-                                         obs_vel, obs_vel_std)
-        inputs = self._log_prob_inputs("trajectory_log_prob_vjp", B, int(steps.size), obs_pos, obs_std, init_pos, init_vel, obs_vel,
-                                       obs_vel_std)
+        return self._trajectory_log_prob_vjp("trajectory_log_prob_vjp", None, g, params, params_L, obs_steps, obs_pos, obs_std, init_pos,
+                                             init_vel, init_time, obs_vel, obs_vel_std, need)
+
+    def trajectory_log_prob_vjp_given_timing(self, g, params, params_L, obs_steps, obs_pos=None, obs_std=None, init_pos=None,
+                                             init_vel=None, init_time: float = 0.0, *, obs_vel=None, obs_vel_std=None,
+                                             need: Sequence[bool] = (True, True)
+                                             ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        """
+        The vector-Jacobian product of ``trajectory_log_prob_given_timing`` (mpk.h: mpk_trajectory_phase_log_prob_vjp), one launch:
+        ``(g_params [B, P], g_params_L [B, Pl, Pl])`` as ``trajectory_log_prob_vjp`` returns them, with ``Pl = P - n_phase``.  The
+        phase columns of ``g_params`` are exact zeros: the likelihood is differentiated at the given timing.
+        """
+        return self._trajectory_log_prob_vjp("trajectory_log_prob_vjp_given_timing", "given", g, params, params_L, obs_steps, obs_pos,
+                                             obs_std, init_pos, init_vel, init_time, obs_vel, obs_vel_std, need)
+
+    def _trajectory_log_prob_vjp(self, fn, timing, g, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, init_time,
+                                 obs_vel, obs_vel_std, need):
+        phase = self._timing_given(fn, timing)
+        B, steps = self._log_prob_checks(fn, params, params_L, obs_steps, obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std,
+                                         self._num_phase_params() if phase else 0)
+        inputs = self._log_prob_inputs(fn, B, int(steps.size), obs_pos, obs_std, init_pos, init_vel, obs_vel, obs_vel_std)
         with torch.no_grad():
             mean, L = self._mean_and_factor(params, params_L)
-            return self._log_prob_vjp_launch(g, mean, L, steps, inputs, init_time, need)
+            return self._log_prob_vjp_launch(g, mean, L, steps, inputs, init_time, need, phase)
 
     def _timing_given(self, fn, timing) -> bool:
         """``timing=None | "given"`` of the demonstration entry points: True for the per-episode-phase route"""

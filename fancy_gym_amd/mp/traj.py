@@ -404,6 +404,75 @@ class MPInterface:
                                                obs_vel_std=sv)
         return float(lp[0])
 
+    def _given_timing_row(self, fn, phase_params):
+        """what the point-wise ``_given_timing`` methods hand to the engine as ``params`` [1, P] after their common refusals: the stored
+        ``[tau?, delay?, mean]`` row, its front replaced by ``phase_params`` [1, n_phase] (or [n_phase]) where given -- as
+        ``log_prob_of_trajectories_given_timing`` takes them, for the one movement these methods look at"""
+        if self.mp_type == "dmp":
+            raise NotImplementedError("a DMP has no probabilistic interface (ProMP / ProDMP only)")
+        assert self.params is not None, "set_params() first"
+        if self.params_L is None:
+            raise RuntimeError("set_mp_params_variances(params_L) first")
+        if self.duration is None or self.dt is None:
+            raise RuntimeError("set_duration(duration, dt) must be called before the grid's steps exist")
+        if not (self.learn_tau or self.learn_delay):
+            raise ValueError(f"{fn}: this generator learns neither tau nor delay: the movement has its phase already; call "
+                             "without _given_timing")
+        row = np.array(self._full_params(), np.float32)[None]
+        if phase_params is not None:
+            ph = phase_params.detach().cpu().numpy() if isinstance(phase_params, torch.Tensor) else np.asarray(phase_params)
+            n_phase = row.shape[1] - self.params.size
+            if ph.shape == (n_phase,):
+                ph = ph[None]
+            if ph.shape != (1, n_phase):
+                raise ValueError(f"{fn}: phase_params must be [1, {n_phase}] (the movement's tau / delay), got {ph.shape}")
+            row[:, :n_phase] = np.asarray(ph, np.float32)
+        return row
+
+    def condition_on_observations_given_timing(self, times, pos, std, vel=None, vel_std=None, phase_params=None):
+        """
+        ``condition_on_observations`` for a generator that learns tau / delay (``TrajectoryEngine.condition_given_timing``, one
+        launch): the via-points are observed at the tau / delay of ``phase_params`` [1, n_phase] -- a new movement's own speed -- or,
+        without ``phase_params``, at the stored tau / delay.  The stored Gaussian is over the non-phase parameters; its mean and factor
+        are REPLACED by the posterior, the stored tau / delay stay.  Returns ``(params, params_L)`` as stored.
+        """
+        fn = "condition_on_observations_given_timing"
+        row = self._given_timing_row(fn, phase_params)                                                         # (refusals before the engine)
+        steps, yp, sp, yv, sv, ip, iv, it = self._observations_on_grid(fn, times, pos, std, vel, vel_std)
+        mean, L = self.engine().condition_given_timing(row, self.params_L[None], steps, yp, sp, ip, iv, it, obs_vel=yv, obs_vel_std=sv)
+        n_phase = row.shape[1] - self.params.size
+        self.params = np.ascontiguousarray(mean[0, n_phase:].cpu().numpy().reshape(self.params.shape))
+        self.params_L = np.ascontiguousarray(L[0].cpu().numpy())
+        self._clear()
+        return self.params, self.params_L
+
+    def log_prob_of_observations_given_timing(self, times, pos, std, vel=None, vel_std=None, phase_params=None) -> float:
+        """
+        ``log_prob_of_observations`` for a generator that learns tau / delay (``TrajectoryEngine.trajectory_log_prob_given_timing``,
+        one launch), a float: the points are scored at the tau / delay of ``phase_params`` [1, n_phase] or, without it, at the stored
+        ones.  Nothing stored changes.
+        """
+        fn = "log_prob_of_observations_given_timing"
+        row = self._given_timing_row(fn, phase_params)                                                         # (refusals before the engine)
+        steps, yp, sp, yv, sv, ip, iv, it = self._observations_on_grid(fn, times, pos, std, vel, vel_std)
+        lp = self.engine().trajectory_log_prob_given_timing(row, self.params_L[None], steps, yp, sp, ip, iv, it, obs_vel=yv,
+                                                            obs_vel_std=sv)
+        return float(lp[0])
+
+    def _std_given_timing(self, fn, phase_params):
+        row = self._given_timing_row(fn, phase_params)                                                         # (refusals before the engine)
+        it = self.init_time if self.init_time is not None else 0.0
+        pos_std, vel_std = self.engine().trajectory_std_given_timing(row, self.params_L[None], it)
+        return pos_std[0].cpu(), vel_std[0].cpu()
+
+    def get_traj_pos_std_given_timing(self, phase_params=None) -> torch.Tensor:
+        """[T, D]: ``get_traj_pos_std`` for a generator that learns tau / delay (``TrajectoryEngine.trajectory_std_given_timing``), at
+        the tau / delay of ``phase_params`` [1, n_phase] or, without it, at the stored ones"""
+        return self._std_given_timing("get_traj_pos_std_given_timing", phase_params)[0]
+
+    def get_traj_vel_std_given_timing(self, phase_params=None) -> torch.Tensor:
+        return self._std_given_timing("get_traj_vel_std_given_timing", phase_params)[1]
+
     def _demonstrations_on_grid(self, fn, kernel, pos, std, timing=None, phase_params=None):
         """what ``log_prob_of_trajectories`` and ``condition_on_trajectories`` hand to the engine after their common refusals: the stored
         mean and factor repeated per demonstration, ``pos`` as float32 [N, T, D], ``std``, the initial conditions repeated, init_time.

@@ -1244,8 +1244,8 @@ int mpk_demonstration_condition_plan(mpk_handle h, int32_t B, int32_t* blocks, i
  * a DMP; more than 16 DoF or 16 table columns; Pl > 256 (64 x 4); float64 images that exceed a CU's LDS with one wave per workgroup --
  * per wave 8 (Pl (Pl + 1) / 2 + D Kloc^2 + 2 Pl + max(Kloc (Pl | 1), 2 tc D) + tc ((Kloc + 3) | 1)) + 4 Kloc (Pl | 1) + 64, per workgroup
  * the row constants and 4 T bytes of base times: Pl = 160 (16 DoF x 10) runs with one wave on a CU, Pl = 224 does not.
- * Not built: gradients w.r.t. tau / delay, per-episode init_time, velocities as observations, a learned phase in the via-point entries
- * (mpk_trajectory_condition / _log_prob / _std), DMP.
+ * Not built: gradients w.r.t. tau / delay, per-episode init_time, velocities as observations, DMP.  (The via-point entries at a
+ * per-episode timing are mpk_trajectory_phase_condition / _log_prob / _log_prob_vjp / _std below.)
  */
 int mpk_demonstration_phase_log_prob(mpk_handle h, const float* params, const float* params_L, const float* init_pos,
                                      const float* init_vel, double init_time_shared, const float* pos, const float* obs_std,
@@ -1257,6 +1257,63 @@ int mpk_demonstration_phase_condition(mpk_handle h, const float* params, const f
                                       const float* init_vel, double init_time_shared, const float* pos, const float* obs_std,
                                       float* params_out, float* params_L_out, int32_t B, void* stream);
 int mpk_demonstration_phase_plan(mpk_handle h, int32_t B, int32_t* blocks, int32_t* waves, int32_t* lds_bytes);
+
+/*
+ * The POINT-wise entries -- mpk_trajectory_condition, mpk_trajectory_log_prob, mpk_trajectory_log_prob_vjp, mpk_trajectory_std -- for a
+ * handle that LEARNS tau and / or delay (ProMP, ProDMP), with every episode's timing GIVEN (added within ABI 4; no existing prototype
+ * changes): a prior learned from demonstrations of different durations conditioned on a via-point at a new movement's own speed, a
+ * handful of observed points scored at it, the uncertainty band of the prior or the posterior.  params and params_L are those of the
+ * mpk_demonstration_phase_* entries above: the tau / delay of episode b in front of its params row, read where mpk_trajectory reads them
+ * and clipped to the handle's bounds as it clips them; the Gaussian over the Pl = P - n_phase non-phase parameters, params_L
+ * [B, Pl, Pl].  Every other argument, convention and formula is that of the shared-phase entry of the same name without _phase:
+ *   mpk_trajectory_phase_condition      M <= MPK_COND_MAX_STEPS strictly increasing host steps shared by the batch; the order steps
+ *       ascending, positions by DoF, then velocities by DoF; sigma = 0 conditions exactly; +inf, NaN or a negative sigma skips the entry
+ *       bit for bit; Carlson's sequential square-root update in float64, each output rounded once; the strict upper triangle of params_L
+ *       is never read and leaves as exact zeros; the outputs may be the inputs.  The phase columns of params_out are the inputs' bits,
+ *       unclipped.
+ *   mpk_trajectory_phase_log_prob       at most MPK_LOGPROB_MAX_OBS candidate observations (M x D x arrays given); n = 0 kept gives
+ *       exactly 0.0; a singular S gives NaN for that episode alone.
+ *   mpk_trajectory_phase_log_prob_vjp   the closed-form gradients recomputed from the inputs in ONE launch; exact zeros in the strict
+ *       upper triangle of g_params_L and in the phase columns of g_params: the timing is an input, not a random variable.
+ *   mpk_trajectory_phase_std            std[b, t, d] = | row_{b,t,d} tril(L_b) |, the factor form: L L^T is never formed, L = 0 gives
+ *       exact zeros, a rank-deficient covariance keeps its zeros, the strict upper triangle is never read.  Of params only the phase
+ *       columns are read.  pos_std / vel_std dev float [B, T, D]; either may be NULL (not computed).
+ * The only difference is the row source.  The observation y = h . w + c + eps of episode b at step t reads the episode's OWN rows in
+ * float64: the position row of mpk_demonstration_phase_* (above), and the velocity row -- the row of the velocity mpk_trajectory returns
+ * for that episode at that step.  For a ProMP that is the difference of the float64 position rows of steps (t, t + 1) times the
+ * forward's float32 reciprocal time step, the last step repeating the difference before it (float64 rows are differenced, never
+ * float32-rounded ones; a zero-padded basis' init_pos drops out).  For a ProDMP it is dPsi_k - xi3 Psi_k(t_b) - xi4 dPsi_k(t_b) times
+ * the column's scale over tau, with (xi3, xi4) from (dy1, dy2) as (xi1, xi2) come from (y1, y2); ca = xi3 / tau (plus the goal's row
+ * under relative_goal), cb = xi4, cc the goal offset times the goal's row.
+ * One launch each on `stream` -- k_traj_condition<promp | prodmp, phase>, k_traj_log_prob<promp | prodmp, phase[, grad]>,
+ * k_traj_phase_std<promp | prodmp> (mpk_last_kernel) -- no table is built or read, nothing is allocated or synchronised.  One wave per
+ * episode; before its sweep the wave evaluates its episode's [2][M] rows into an LDS image of its own, 16 M (Kloc + 3) bytes; the
+ * standard-deviation kernel holds the episode's lower triangle as packed float32 in LDS, evaluates 64 steps a round (lane <-> step)
+ * and stores every round as one contiguous run.  No atomics on results, fixed summation orders: the same bits from run to run, for any
+ * alignment, alone or in a batch.  A ProDMP step whose scaled time lies beyond the pre-computed range raises the handle's range flag
+ * (mpk_check_range).
+ * MPK_EINVAL: a NULL handle, params, params_L or output; B < 1; bad steps; no observation, or values without standard deviations;
+ * init_pos / init_vel NULL for a ProDMP; a ProMP's velocities with fewer than two steps.  MPK_ENOTIMPL, before any launch, under the
+ * entry's own name: a handle that learns neither tau nor delay (use the entry without _phase); a DMP; more than 16 DoF or 16 table
+ * columns; more than MPK_LOGPROB_MAX_OBS candidate observations; images that exceed a CU's LDS with one wave per workgroup -- the
+ * shared-phase entries' per-wave bytes plus the row image, so Pl = 160 (16 DoF x 10) runs for conditioning at M = 5 and for the
+ * likelihood at n = 64, as without _phase.
+ * Not built: gradients w.r.t. tau / delay, a per-episode init_time, DMP, correlated noise.
+ */
+int mpk_trajectory_phase_condition(mpk_handle h, const float* params, const float* params_L, const float* init_pos, const float* init_vel,
+                                   double init_time_shared, const int32_t* obs_steps, int32_t M, const float* obs_pos,
+                                   const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std, float* params_out,
+                                   float* params_L_out, int32_t B, void* stream);
+int mpk_trajectory_phase_log_prob(mpk_handle h, const float* params, const float* params_L, const float* init_pos,
+                                  const float* init_vel, double init_time_shared, const int32_t* obs_steps, int32_t M,
+                                  const float* obs_pos, const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std,
+                                  double* log_prob, int32_t B, void* stream);
+int mpk_trajectory_phase_log_prob_vjp(mpk_handle h, const float* params, const float* params_L, const float* init_pos,
+                                      const float* init_vel, double init_time_shared, const int32_t* obs_steps, int32_t M,
+                                      const float* obs_pos, const float* obs_pos_std, const float* obs_vel, const float* obs_vel_std,
+                                      const double* g, float* g_params, float* g_params_L, int32_t B, void* stream);
+int mpk_trajectory_phase_std(mpk_handle h, const float* params, const float* params_L, double init_time_shared, float* pos_std,
+                             float* vel_std, int32_t B, void* stream);
 
 /*
  * The vector-Jacobian product of mpk_reacher_rollout (appended under ABI 4): controller, clip, torque double integrator and
